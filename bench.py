@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: eigenmodes/sec (assembly + solve) on the 7-core hexagonal P2 mesh, 10 modes.
 
-    python bench.py --gpus N --steps K --warmup W [--levels L | --ladder | --sweep]
+    python bench.py --gpus N --steps K --warmup W [--levels L | --ladder | --sweep] [--dump-outputs DIR]
 
 One "step" = one full ``TrueVectorialMaxwellSolver.solve_vectorial_modes(mesh, 10)`` call on the
 north-star cross-section C1 (BASELINE.json configs[1]: 7-core hexagonal_1plus6_7, r = 1.5 um, pitch
@@ -22,6 +22,9 @@ sweep sharded over the ranks with one RCCL all-gather of the result records per 
 ``--ladder``: one line per rung of BASELINE.json configs[2] (L = 0, 1, 2 uniform refinements).
 
 Rank 0 prints ONE JSON line per configuration; see DESIGN.md for how ``roofline`` and ``cpu_baseline`` are measured.
+``ms_per_step`` = wall time of the K timed steps / K.  ``--dump-outputs DIR``: after the timed steps, rank 0 writes what
+the last timed step returned (the mode records of the solve, or the sweep's n_eff table) as ``DIR/<name>.npy``; the
+inputs are fixed (no random mesh, a fixed start vector), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -57,7 +60,66 @@ def parse_args(argv=None):
     ap.add_argument("--ladder", action="store_true", help="BASELINE configs[2]: one line per rung L = 0, 1, 2")
     ap.add_argument("--sweep", action="store_true", help="BASELINE configs[3]: a step = the 64-solve multi-band sweep")
     ap.add_argument("--lanes", type=int, default=0, help="--sweep: solves in flight per GPU (0 = the driver's default)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB in all; rank 0 only)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.ladder:
+        ap.error("--dump-outputs takes one configuration: not with --ladder")
+    return args
+
+
+# ----------------------------------------------------------------------------------------------------
+# --dump-outputs: the arrays the timed path returned in its last step, for output-for-output comparison of two builds
+# ----------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+MODE_SCALARS = ("n_eff", "beta", "P_x", "P_y", "PDL_dB", "confinement", "core_overlap", "div_ratio")
+MODE_FIELDS = ("Ex_dofs", "Ey_dofs")
+
+
+def _write_arrays(out_dir: str, arrays: dict) -> dict:
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT_BYTES, total
+    return {"dir": out_dir, "arrays": sorted(arrays), "bytes": total}
+
+
+def dump_modes(out_dir: str, modes) -> dict:
+    """The mode records of one solve, in the order returned: one (k,) array per numeric scalar of a record
+    (``MODE_SCALARS``; the ``polarization`` label is a function of P_x / P_y) and one (k, N_solve) array per DOF vector
+    (``MODE_FIELDS``).  When the DOF vectors would exceed ``DUMP_LIMIT_BYTES``, the same fixed sample of DOF columns
+    (seed 0, sorted) is taken from each, and its indices are written as ``field_dof_index``."""
+    import numpy as np
+    arrays = {key: np.array([m[key] for m in modes], dtype=np.float64) for key in MODE_SCALARS}
+    fields = {key: (np.stack([np.asarray(m[key]) for m in modes]) if modes else np.zeros((0, 0))) for key in MODE_FIELDS}
+    k, n = fields[MODE_FIELDS[0]].shape
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())
+    if 8 * k * n * len(MODE_FIELDS) > room:
+        cols = room // (8 * (k * len(MODE_FIELDS) + 1))
+        idx = np.sort(np.random.default_rng(0).choice(n, size=cols, replace=False))
+        fields = {key: f[:, idx] for key, f in fields.items()}
+        arrays["field_dof_index"] = idx
+    arrays.update(fields)
+    return _write_arrays(out_dir, arrays)
+
+
+def dump_sweep(out_dir: str, table) -> dict:
+    """The sweep's table: row i = the descending n_eff list of item i, padded with NaN to the longest list."""
+    import numpy as np
+    width = max((len(table[i]) for i in table), default=0)
+    t = np.full((len(table), width), np.nan)
+    for row, i in enumerate(sorted(table)):
+        t[row, :len(table[i])] = table[i]
+    return _write_arrays(out_dir, {"sweep_n_eff": t})
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -487,6 +549,7 @@ def run_solve_config(args, D: Dist, levels: int, with_cpu_baseline: bool):
         phases.append(phase_record(ls, step_ms[-1]))
     D.sync()
     elapsed = D.max_over_ranks(time.perf_counter() - t0)
+    dumped = dump_modes(args.dump_outputs, modes) if (args.dump_outputs and D.rank == 0) else None
     stats = dict(solver.last_stats)
     # the CPU leg sits BETWEEN the timed GPU steps and the GPU extras below (warm steps, concurrent lanes): the device is
     # busy at both ends of the run, whichever way the driver's activity samples fall
@@ -571,6 +634,8 @@ def run_solve_config(args, D: Dist, levels: int, with_cpu_baseline: bool):
                         "workspace_alloc": round(max(h[2] for h in host_ms), 2)},
         "roofline": roof,
     }
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
     if steady is not None:
         out["steady"] = steady
     if conc is not None:
@@ -643,6 +708,7 @@ def run_sweep_config(args, D: Dist):
     D.sync()
     elapsed = D.max_over_ranks(time.perf_counter() - t0)
     host = _host_picture(solve, time.perf_counter() - t0) if hasattr(solve, "timeline") else None
+    dumped = dump_sweep(args.dump_outputs, table) if (args.dump_outputs and D.rank == 0) else None
     # the same sweep with the mesh producer INSIDE the timed region (Delaunay + refinement per cross-section, overlapped
     # with the solves by the sweep's preparer threads): reported beside the headline, which keeps its inputs resident
     elapsed_mesh = host_mesh = None
@@ -672,6 +738,8 @@ def run_sweep_config(args, D: Dist):
                       "host_threads_per_rank": int(os.environ.get("PLFEM_HOST_THREADS", "0")) or None},
            "sweep": {"solves": len(items), "solves_per_s": args.steps * len(items) / elapsed, "solves_rank0": n_local,
                      "n_eff_checksum": float(sum(float(np.sum(table[i])) for i in sorted(table)))}}
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
     if host is not None:
         out["sweep"]["host_timeline_rank0"] = host
     if elapsed_mesh is not None:

@@ -123,3 +123,53 @@ def test_pmc_summaries_are_keyed_by_rung_and_checked_against_the_library(tmp_pat
         else:
             assert fams == {} and isinstance(check, str) and check, (levels, check)
             print(f"rung L = {levels}: committed PMC summary refused ({check}): bench.py reports traffic: null until it is regenerated")
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the sweep's table of the last timed step as float64 .npy, the same on a second run."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        res = _run("--gpus", "1", "--steps", "2", "--warmup", "0", "--sweep", "--dump-outputs", str(d))
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["outputs_dumped"]["arrays"] == ["sweep_n_eff"]
+    a, b = (np.load(d / "sweep_n_eff.npy") for d in dirs)
+    assert a.dtype == np.float64 and a.shape[0] == 64 and np.array_equal(a, b, equal_nan=True)
+    assert np.all(np.diff(a, axis=1)[~np.isnan(np.diff(a, axis=1))] <= 0)          # descending n_eff per row
+
+
+def test_dump_modes_writes_every_numeric_field_and_samples_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    modes = [dict({k: float(rng.random()) for k in bench.MODE_SCALARS}, Ex_dofs=rng.random(1000), Ey_dofs=rng.random(1000),
+                  polarization="x", is_vectorial=True) for _ in range(3)]
+    rec = bench.dump_modes(str(tmp_path / "full"), modes)
+    assert set(rec["arrays"]) == set(bench.MODE_SCALARS) | set(bench.MODE_FIELDS)
+    ex = np.load(tmp_path / "full" / "Ex_dofs.npy")
+    assert ex.dtype == np.float64 and ex.shape == (3, 1000) and np.array_equal(ex[2], modes[2]["Ex_dofs"])
+    assert np.array_equal(np.load(tmp_path / "full" / "n_eff.npy"), [m["n_eff"] for m in modes])
+    # over the limit: the same seeded DOF columns of every field, their indices written beside them, the total within the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 30000)
+    for d in ("s1", "s2"):
+        rec = bench.dump_modes(str(tmp_path / d), modes)
+        assert rec["bytes"] <= 30000
+    idx = np.load(tmp_path / "s1" / "field_dof_index.npy").astype(np.int64)
+    ey = np.load(tmp_path / "s1" / "Ey_dofs.npy")
+    assert 0 < len(idx) < 1000 and np.all(np.diff(idx) > 0) and np.array_equal(ey, np.stack([m["Ey_dofs"][idx] for m in modes]))
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "field_dof_index.npy"))
+
+
+def test_steps_and_warmup_are_checked():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--steps", "3", "--warmup", "0"]).steps == 3
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--ladder", "--dump-outputs", "x"]):
+        try:
+            bench.parse_args(bad)
+        except SystemExit as e:
+            assert e.code != 0
+        else:
+            raise AssertionError(f"{bad} accepted")
