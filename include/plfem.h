@@ -289,6 +289,54 @@ enum { PLFEM_PROF_KFWD = 0, PLFEM_PROF_FWD_SWEEP, PLFEM_PROF_BWD_SWEEP, PLFEM_PR
 int plfem_profile_begin(plfem_ctx* ctx, int32_t max_ranges);
 int plfem_profile_end(plfem_ctx* ctx, double* out_host /* [PLFEM_PROF_COUNT][3] */);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mode fields at arbitrary points and overlaps of modes across meshes (no solve context needed).
+ * Replaces, on the user's side: scikit-fem Basis.probes(points) / Basis.interpolate(x) on the reference's
+ *           Basis(mesh, ElementTriP2()) (reference solver_fem.py:126), and the integral of a field interpolated from
+ *           one basis at the quadrature points of another (skfem Functional over basis_b with basis_a.interpolate);
+ *           the reference itself evaluates no mode field anywhere.
+ * A locator binds a symbolic analysis to a device and a stream: the point-location grid (built on the host on first
+ * request, plfem_symbolic_get "loc_grid" [6] f64 = x0, y0, 1/hx, 1/hy, nx, ny; "loc_cell_ptr" [nx ny + 1] i32;
+ * "loc_cell_elems" i32, ascending per cell; "loc_stats" [4] f64 = cells, mean / max candidates per cell, build seconds),
+ * the vertex coordinates, element_dofs and the DOF -> interior map, uploaded into caller-owned device memory
+ * (256-byte aligned, at least plfem_locator_bytes(sym) bytes; like plfem_create's workspace).  It allocates nothing
+ * else, leaves plfem_workspace_bytes / plfem_create untouched, and the symbolic handle must outlive it.
+ * Containment: a point is in element e when each of its three barycentric coordinates is >= -(PLFEM_LOC_TOL + the
+ * rounding bound of that coordinate: PLFEM_LOC_EPS4 (|j11| (|x| + |x0|) + |j01| (|y| + |y0|)) / |det J| for xi, J = [p1-p0,
+ * p2-p0]); a coordinate within its bound of 0 is set to 0 (the point is evaluated on that edge); among the
+ * elements listed in the point's cell that contain it, the smallest element id wins; a point in none gets element -1
+ * and value 0.
+ * Mode layouts: "staged" = DOF-major, [ncomp][nrows][k] (plfem_stage_modes transposes [ncomp][k][nrows] into it);
+ * indexed = 1: rows are interior DOFs (nrows = nsolve, the 'Ex_dofs' / 'Ey_dofs' layout), the map is int_index (a
+ * boundary DOF contributes 0); indexed = 0: rows are all N DOFs ('field_vector' of the scalar solver).
+ * ------------------------------------------------------------------------------------------- */
+#define PLFEM_LOC_TOL 1e-10
+#define PLFEM_LOC_EPS4 8.881784197001252e-16   /* 4 x DBL_EPSILON */
+typedef struct plfem_locator plfem_locator;
+int plfem_locator_bytes(const plfem_symbolic* sym, int64_t* bytes);
+int plfem_locator_create(const plfem_symbolic* sym, int32_t device, void* hip_stream, void* mem_dev, int64_t mem_bytes,
+                         plfem_locator** out, char* err, int32_t errlen);
+void plfem_locator_destroy(plfem_locator* loc);
+const char* plfem_locator_last_error(const plfem_locator* loc);
+/* dst_dev[c][r][m] = src_dev[c][m][r] for c < ncomp, m < k, r < nrows (device, the locator's stream) */
+int plfem_stage_modes(plfem_locator* loc, int32_t ncomp, int32_t k, int32_t nrows, const double* src_dev, double* dst_dev);
+/* Sample k modes at npts points (device arrays, the locator's stream, no synchronisation).
+ * ncomp = 1: out_dev[0][k][npts] = u; ncomp = 2: out_dev[0] = Hx, out_dev[1] = Hy, and with beta_dev (k doubles, or
+ * NULL) out_dev[2] = Hz_im = -(dHx/dx + dHy/dy) / beta (the imaginary part of Hz under exp(j(wt - beta z))).
+ * points_dev [2][npts] (x row, y row); elem_dev [npts]: the element each point was found in, or -1. */
+int plfem_sample_fields(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                        const double* beta_dev, int32_t npts, const double* points_dev, double* out_dev, int32_t* elem_dev);
+/* O[i][j] = sum over the elements of mesh B, over B's six-point rule (the assembly's), |det J| w_q wt(x_q) ua_i(x_q).ub_j(x_q)
+ * (transverse dot product for ncomp = 2), ua located in mesh A inside the kernel.  wt = 1 when ncore < 0, else 1/eps(x)
+ * with the closed-disc core test of plfem_assemble_hfield (ncore <= 64).  Partial ka x kb blocks per workgroup and a
+ * fixed-order second stage: the same bits on every run.  work_dev: device scratch of plfem_overlap_work_bytes(ka, kb)
+ * bytes; out_host [ka][kb] (synchronises the locators' stream; both locators on one device, loc_a's stream is used). */
+int plfem_overlap_work_bytes(int32_t ka, int32_t kb, int64_t* bytes);
+int plfem_field_overlap(plfem_locator* loc_a, const double* modes_a_dev, int32_t ka, int32_t indexed_a,
+                        plfem_locator* loc_b, const double* modes_b_dev, int32_t kb, int32_t indexed_b, int32_t ncomp,
+                        const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                        void* work_dev, int64_t work_bytes, double* out_host);
+
 #ifdef PLFEM_TEST_HOOKS
 /* ---------------------------------------------------------------------------------------------
  * TEST HOOKS -- NOT exported by libplfem_hip.so.  They live in the add-on libplfem_testhooks.so (csrc/api_debug.hip,

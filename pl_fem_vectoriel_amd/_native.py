@@ -36,6 +36,8 @@ EXPORTS = (
     "plfem_mesh_edge_count", "plfem_mesh_refine",
     "plfem_residuals", "plfem_set_option", "plfem_symbolic_create_ex", "plfem_assemble_scalar", "plfem_cmt_coupling",
     "plfem_solve_modes", "plfem_modes_dev",
+    "plfem_locator_bytes", "plfem_locator_create", "plfem_locator_destroy", "plfem_locator_last_error", "plfem_stage_modes",
+    "plfem_sample_fields", "plfem_overlap_work_bytes", "plfem_field_overlap",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -51,6 +53,7 @@ _ARRAY_DTYPES = {
     "nptr": np.int32, "nadj": np.int32, "nloc": np.uint8, "leaf_of_elem": np.int32, "leaf_elem_ptr": np.int32, "leaf_elems": np.int32, "epos": np.int32, "epos_leaf": np.int32,
     "owner": np.int32, "fs": np.int32, "fb": np.int32, "fs_true": np.int32, "fb_true": np.int32,
     "fnode_ptr": np.int64, "fnodes": np.int32, "cinv0": np.int32, "cinv1": np.int32, "foff": np.int64, "soff": np.int64, "prow": np.int32, "npos": np.int32,
+    "loc_grid": np.float64, "loc_cell_ptr": np.int32, "loc_cell_elems": np.int32, "loc_stats": np.float64,
 }
 
 
@@ -157,6 +160,21 @@ def load_library() -> ctypes.CDLL:
                                       [ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_double,
                                        ctypes.c_double] + [ctypes.c_void_p] * 6)
     lib.plfem_modes_dev.argtypes = [ctypes.c_void_p, c_void_pp, ctypes.POINTER(ctypes.c_int32)]
+    lib.plfem_locator_bytes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+    lib.plfem_locator_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                         c_void_pp, ctypes.c_char_p, ctypes.c_int32]
+    lib.plfem_locator_destroy.argtypes = [ctypes.c_void_p]
+    lib.plfem_locator_destroy.restype = None
+    lib.plfem_locator_last_error.argtypes = [ctypes.c_void_p]
+    lib.plfem_locator_last_error.restype = ctypes.c_char_p
+    lib.plfem_stage_modes.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                      ctypes.c_void_p]
+    lib.plfem_sample_fields.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.plfem_overlap_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
+    lib.plfem_field_overlap.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] * 2 +
+                                        [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p])
     _lib = lib
     return lib
 

@@ -129,6 +129,10 @@ bool lookup(const Symbolic& S, const char* name, ArrayRef& r) {
   else if (n == "soff") r = aref(S.soff);
   else if (n == "prow") r = aref(S.prow);
   else if (n == "npos") r = aref(S.npos);
+  else if (n == "loc_grid") { plfem::ensure_locator(S); r = aref(S.loc_grid); }
+  else if (n == "loc_cell_ptr") { plfem::ensure_locator(S); r = aref(S.loc_cell_ptr); }
+  else if (n == "loc_cell_elems") { plfem::ensure_locator(S); r = aref(S.loc_cell_elems); }
+  else if (n == "loc_stats") { plfem::ensure_locator(S); r = aref(S.loc_stats); }
   else return false;
   return true;
 }

@@ -1,0 +1,523 @@
+// gfx950 kernels and C-ABI of the mode-field calls (include/plfem.h, "Mode fields at arbitrary points"): the point
+// locator bound to a device, P2 evaluation of many modes at many points (k_sample_fields) and the overlap integral of
+// two mode sets living on two meshes (k_field_overlap + k_overlap_reduce).
+//
+// Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
+// (reference solver_fem.py:126): the reference itself turns no mode vector back into a field.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+#include "../../include/plfem.h"
+#include "internal.h"
+#include <hip/hip_runtime.h>
+
+struct plfem_locator {
+  const plfem::Symbolic* S = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  int nv = 0, ne = 0, N = 0, nsolve = 0;
+  double x0 = 0, y0 = 0, inv_hx = 0, inv_hy = 0;
+  int nx = 0, ny = 0;
+  int32_t *d_cell_ptr = nullptr, *d_cell_elems = nullptr, *d_edof = nullptr, *d_int_index = nullptr;
+  double* d_pxy = nullptr;                     // [2][nv] vertex coordinates
+};
+
+namespace plfem {
+namespace {
+
+// 6-point degree-4 rule on the reference triangle: the values of kernels_assembly.hip (k_element_matrices)
+__constant__ double c_fqx[6] = {0.445948490915965, 0.10810301816807, 0.445948490915965,
+                                0.091576213509771, 0.816847572980458, 0.091576213509771};
+__constant__ double c_fqy[6] = {0.445948490915965, 0.445948490915965, 0.10810301816807,
+                                0.091576213509771, 0.091576213509771, 0.816847572980458};
+__constant__ double c_fqw[6] = {0.1116907948390055, 0.1116907948390055, 0.1116907948390055,
+                                0.054975871827661, 0.054975871827661, 0.054975871827661};
+
+struct LocArgs {
+  double x0, y0, inv_hx, inv_hy;
+  int nx, ny, nv, ne;
+  const int32_t* cell_ptr;
+  const int32_t* cell_elems;
+  const double* pxy;
+  const int32_t* edof;      // [6][ne]; rows 0-2 = the sorted vertices
+  const int32_t* map;       // DOF -> row of the staged modes (int_index) or nullptr = identity
+};
+
+struct CoreTable {
+  double c[64 * 3];
+};
+
+LocArgs loc_args(const plfem_locator* L, bool indexed) {
+  return {L->x0, L->y0, L->inv_hx, L->inv_hy, L->nx, L->ny, L->nv, L->ne, L->d_cell_ptr, L->d_cell_elems, L->d_pxy,
+          L->d_edof, indexed ? L->d_int_index : nullptr};
+}
+
+// cell index: the formula of locator.cpp (cell_of), so a point inside an element's bounding box lands in a listed cell
+__device__ __forceinline__ int dev_cell(double v, double v0, double inv_h, int n) {
+  const double f = floor((v - v0) * inv_h);
+  if (!(f >= 0.0)) return 0;
+  return f >= (double)(n - 1) ? n - 1 : (int)f;
+}
+
+// IEEE product kept out of fused multiply-adds (hipcc's default -ffp-contract=fast ignores the contract pragma): the
+// barycentric numerators below must round exactly as the host's (NumPy's) arithmetic does, so that a point on a vertex
+// gets coordinates of exactly 0 / 1 and the emulation in tests/ reproduces every containment decision.
+__device__ __forceinline__ double mul_rn(double a, double b) {
+  double r;
+  asm volatile("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// Smallest element id among the point's cell candidates that contain it (the lists are ascending, so that is the first
+// hit), with the reference coordinates (xi, eta) and the inverse Jacobian.  Containment: every barycentric coordinate
+// >= -(PLFEM_LOC_TOL + its rounding bound s), s = PLFEM_LOC_EPS4 (|j11| (|x| + |x0|) + |j01| (|y| + |y0|)) / |det J| for xi
+// (the same form for eta, s_xi + s_eta for 1 - xi - eta): what the rounding of the point's and the vertex's own
+// coordinates can move the coordinate by.  On a sliver (det J ~ 1e-8 of its edge products) that exceeds 1e-10.  A
+// coordinate within its bound of 0 is set to 0 exactly: the point is then evaluated ON that edge, through the
+// well-conditioned coordinate along it, instead of through the sliver's ill-conditioned width.
+__device__ int dev_locate(const LocArgs& L, double x, double y, double& xi, double& eta, double inv[4]) {
+  const int ix = dev_cell(x, L.x0, L.inv_hx, L.nx), iy = dev_cell(y, L.y0, L.inv_hy, L.ny);
+  const int cell = iy * L.nx + ix;
+  const int q1 = L.cell_ptr[cell + 1];
+  const double* px = L.pxy;
+  const double* py = L.pxy + L.nv;
+  for (int q = L.cell_ptr[cell]; q < q1; ++q) {
+    const int e = L.cell_elems[q];
+    const int v0 = L.edof[e], v1 = L.edof[L.ne + e], v2 = L.edof[2 * L.ne + e];
+    const double ax = px[v0], ay = py[v0];
+    const double j00 = px[v1] - ax, j10 = py[v1] - ay, j01 = px[v2] - ax, j11 = py[v2] - ay;
+    const double det = mul_rn(j00, j11) - mul_rn(j01, j10);
+    const double dx = x - ax, dy = y - ay;
+    double a = (mul_rn(j11, dx) - mul_rn(j01, dy)) / det, b = (mul_rn(j00, dy) - mul_rn(j10, dx)) / det;
+    const double mx = fabs(x) + fabs(ax), my = fabs(y) + fabs(ay);
+    const double sa = PLFEM_LOC_EPS4 * (mul_rn(fabs(j11), mx) + mul_rn(fabs(j01), my)) / fabs(det);
+    const double sb = PLFEM_LOC_EPS4 * (mul_rn(fabs(j00), my) + mul_rn(fabs(j10), mx)) / fabs(det);
+    const double c = 1.0 - a - b;
+    if (a >= -(PLFEM_LOC_TOL + sa) && b >= -(PLFEM_LOC_TOL + sb) && c >= -(PLFEM_LOC_TOL + sa + sb)) {   // (NaN: never)
+      const bool za = fabs(a) <= sa, zb = fabs(b) <= sb;
+      if (za) a = 0.0;
+      if (zb) b = 0.0;
+      if (fabs(c) <= sa + sb) {               // on the edge opposite vertex 0: a + b = 1
+        if (zb) a = 1.0;
+        else if (za) b = 1.0;
+        else if (sa >= sb) a = 1.0 - b;
+        else b = 1.0 - a;
+      }
+      xi = a;
+      eta = b;
+      const double idet = 1.0 / det;
+      inv[0] = j11 * idet; inv[1] = -j01 * idet; inv[2] = -j10 * idet; inv[3] = j00 * idet;
+      return e;
+    }
+  }
+  return -1;
+}
+
+__device__ __forceinline__ void p2_phi(double x, double y, double phi[6]) {
+  phi[0] = 1 - 3 * x - 3 * y + 2 * x * x + 4 * x * y + 2 * y * y;
+  phi[1] = 2 * x * x - x;
+  phi[2] = 2 * y * y - y;
+  phi[3] = 4 * x - 4 * x * x - 4 * x * y;
+  phi[4] = 4 * x * y;
+  phi[5] = 4 * y - 4 * x * y - 4 * y * y;
+}
+
+// staged row of DOF d of element e, -1 = contributes nothing (boundary DOF of an interior-indexed record)
+__device__ __forceinline__ int dev_row(const LocArgs& L, int e, int a) {
+  const int d = L.edof[a * L.ne + e];
+  return L.map ? L.map[d] : d;
+}
+
+// One lane per point.  Modes staged DOF-major ([comp][nrows][k]): the six gathers of a point are six contiguous runs of k
+// doubles, read one mode per iteration; the output is [comp][k][npts], so a wave's stores of one mode are coalesced.
+__global__ __launch_bounds__(256) void k_sample_fields(LocArgs L, int ncomp, int k, int64_t nrows, const double* __restrict__ V,
+                                                       const double* __restrict__ beta, int npts, const double* __restrict__ pts,
+                                                       double* __restrict__ out, int32_t* __restrict__ elem) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npts) return;
+  double xi = 0, eta = 0, inv[4] = {0, 0, 0, 0};
+  const int e = dev_locate(L, pts[p], pts[(int64_t)npts + p], xi, eta, inv);
+  elem[p] = e;
+  const int64_t plane = (int64_t)k * npts;
+  const int nout = ncomp + (ncomp == 2 && beta != nullptr);
+  if (e < 0) {
+    for (int c = 0; c < nout; ++c)
+      for (int m = 0; m < k; ++m) out[c * plane + (int64_t)m * npts + p] = 0.0;
+    return;
+  }
+  double phi[6], gx[6], gy[6];
+  p2_phi(xi, eta, phi);
+  {
+    const double dxh[6] = {-3 + 4 * xi + 4 * eta, 4 * xi - 1, 0.0, 4 - 8 * xi - 4 * eta, 4 * eta, -4 * eta};
+    const double dyh[6] = {-3 + 4 * xi + 4 * eta, 0.0, 4 * eta - 1, -4 * xi, 4 * xi, 4 - 4 * xi - 8 * eta};
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {            // grad = J^-T grad_hat
+      gx[a] = inv[0] * dxh[a] + inv[2] * dyh[a];
+      gy[a] = inv[1] * dxh[a] + inv[3] * dyh[a];
+    }
+  }
+  int64_t row[6];
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const int r = dev_row(L, e, a);
+    row[a] = r < 0 ? -1 : (int64_t)r * k;
+  }
+  const double* V1 = V + nrows * k;
+  for (int m = 0; m < k; ++m) {
+    double u0 = 0.0, u1 = 0.0, dv = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      if (row[a] < 0) continue;
+      const double v0 = V[row[a] + m];
+      u0 += phi[a] * v0;
+      if (ncomp == 2) {
+        const double v1 = V1[row[a] + m];
+        u1 += phi[a] * v1;
+        dv += gx[a] * v0 + gy[a] * v1;
+      }
+    }
+    out[(int64_t)m * npts + p] = u0;
+    if (ncomp == 2) {
+      out[plane + (int64_t)m * npts + p] = u1;
+      if (beta) out[2 * plane + (int64_t)m * npts + p] = -dv / beta[m];
+    }
+  }
+}
+
+// [c][m][r] -> [c][r][m], 32 x 32 tiles through LDS
+__global__ __launch_bounds__(256) void k_stage_modes(int k, int nrows, const double* __restrict__ src, double* __restrict__ dst) {
+  __shared__ double tile[32][33];
+  const int c = blockIdx.z;
+  const int r0 = blockIdx.x * 32, m0 = blockIdx.y * 32;
+  const double* s = src + (int64_t)c * k * nrows;
+  double* d = dst + (int64_t)c * k * nrows;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+  for (int j = ty; j < 32; j += 8) {
+    const int m = m0 + j, r = r0 + tx;
+    if (m < k && r < nrows) tile[j][tx] = s[(int64_t)m * nrows + r];
+  }
+  __syncthreads();
+  for (int j = ty; j < 32; j += 8) {
+    const int r = r0 + j, m = m0 + tx;
+    if (m < k && r < nrows) d[(int64_t)r * k + m] = tile[tx][j];
+  }
+}
+
+// Overlap: one workgroup walks tiles of OT quadrature points of mesh B (element-major, six points per element) for one
+// (32-mode chunk of A, 32-mode chunk of B) pair.  Per tile: OT lanes locate their point in mesh A and stage the basis
+// values and rows; all lanes evaluate ua[c][t][i] and w ub[c][t][j] into LDS; every lane then accumulates a 2 x 2 block
+// of the 32 x 32 chunk product over the tile.  The workgroup's partial goes to its own slot: no atomics.
+constexpr int OT = 64;          // quadrature points per tile
+constexpr int OC = 32;          // modes per chunk
+constexpr int OVL_BLOCKS = 1024;
+
+__global__ __launch_bounds__(256) void k_field_overlap(LocArgs A, LocArgs B, int ncomp, int ka, int64_t nrows_a,
+                                                       const double* __restrict__ Va, int kb, int64_t nrows_b,
+                                                       const double* __restrict__ Vb, CoreTable cores, int ncore,
+                                                       double inv_eps_core, double inv_eps_clad, int nchunk_b,
+                                                       double* __restrict__ partial) {
+  __shared__ double s_phi[6][OT];
+  __shared__ int s_ra[6][OT], s_rb[6][OT];
+  __shared__ double s_w[OT];
+  __shared__ int s_q[OT];
+  __shared__ double s_ua[2][OT][OC];
+  __shared__ double s_ub[2][OT][OC];
+  const int tid = threadIdx.x;
+  const int ca = blockIdx.y / nchunk_b, cb = blockIdx.y % nchunk_b;
+  const int ia0 = ca * OC, jb0 = cb * OC;
+  const int64_t nq = (int64_t)6 * B.ne;
+  const int64_t ntiles = (nq + OT - 1) / OT;
+  const int ti = tid >> 4, tj = tid & 15;
+  double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+  const double* pbx = B.pxy;
+  const double* pby = B.pxy + B.nv;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < OT) {
+      const int64_t g = tile * OT + tid;
+      double w = 0.0;
+      int q = 0;
+      for (int a = 0; a < 6; ++a) { s_ra[a][tid] = -1; s_rb[a][tid] = -1; s_phi[a][tid] = 0.0; }
+      if (g < nq) {
+        const int e = (int)(g / 6);
+        q = (int)(g % 6);
+        const int v0 = B.edof[e], v1 = B.edof[B.ne + e], v2 = B.edof[2 * B.ne + e];
+        const double x0 = pbx[v0], y0 = pby[v0];
+        const double j00 = pbx[v1] - x0, j10 = pby[v1] - y0, j01 = pbx[v2] - x0, j11 = pby[v2] - y0;
+        // det J and the quadrature point exactly as k_element_matrices forms them (the same core test decisions)
+        double t1, t2;
+        asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t1) : "v"(j00), "v"(j11));
+        asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t2) : "v"(j01), "v"(j10));
+        const double det = t1 - t2;
+        const double xi = c_fqx[q], eta = c_fqy[q];
+        const double X = x0 + j00 * xi + j01 * eta, Y = y0 + j10 * xi + j11 * eta;
+        w = fabs(det) * c_fqw[q];
+        if (ncore >= 0) {
+          bool in_core = false;
+          for (int c = 0; c < ncore; ++c) {
+            const double dx = X - cores.c[3 * c], dy = Y - cores.c[3 * c + 1], r = cores.c[3 * c + 2];
+            in_core |= (dx * dx + dy * dy <= r * r);
+          }
+          w *= in_core ? inv_eps_core : inv_eps_clad;
+        }
+        double axi, aeta, inv[4];
+        const int ea = dev_locate(A, X, Y, axi, aeta, inv);
+        if (ea >= 0) {
+          double phi[6];
+          p2_phi(axi, aeta, phi);
+          for (int a = 0; a < 6; ++a) {
+            s_phi[a][tid] = phi[a];
+            s_ra[a][tid] = dev_row(A, ea, a);
+            s_rb[a][tid] = dev_row(B, e, a);
+          }
+        } else {
+          w = 0.0;
+        }
+      }
+      s_w[tid] = w;
+      s_q[tid] = q;
+    }
+    __syncthreads();
+    // ua[c][t][i] and w ub[c][t][j]: consecutive lanes read consecutive modes of one staged row
+    for (int idx = tid; idx < 2 * OT * OC; idx += 256) {
+      const int i = idx % OC, t = (idx / OC) % OT, c = idx / (OC * OT);
+      double ua = 0.0, ub = 0.0;
+      if (c < ncomp) {
+        const double* va = Va + c * nrows_a * ka;
+        const double* vb = Vb + c * nrows_b * kb;
+        const int q = s_q[t];
+        const double w = s_w[t];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          const int ra = s_ra[a][t], rb = s_rb[a][t];
+          if (ia0 + i < ka && ra >= 0) ua += s_phi[a][t] * va[(int64_t)ra * ka + ia0 + i];
+          if (jb0 + i < kb && rb >= 0) {
+            double ph;                        // B's basis at its own quadrature point q
+            const double x = c_fqx[q], y = c_fqy[q];
+            switch (a) {
+              case 0: ph = 1 - 3 * x - 3 * y + 2 * x * x + 4 * x * y + 2 * y * y; break;
+              case 1: ph = 2 * x * x - x; break;
+              case 2: ph = 2 * y * y - y; break;
+              case 3: ph = 4 * x - 4 * x * x - 4 * x * y; break;
+              case 4: ph = 4 * x * y; break;
+              default: ph = 4 * y - 4 * x * y - 4 * y * y; break;
+            }
+            ub += ph * vb[(int64_t)rb * kb + jb0 + i];
+          }
+        }
+        ub *= w;
+      }
+      s_ua[c][t][i] = ua;
+      s_ub[c][t][i] = ub;
+    }
+    __syncthreads();
+    for (int c = 0; c < ncomp; ++c) {
+      for (int t = 0; t < OT; ++t) {
+        const double2 a = *reinterpret_cast<const double2*>(&s_ua[c][t][2 * ti]);
+        const double2 b = *reinterpret_cast<const double2*>(&s_ub[c][t][2 * tj]);
+        acc[0][0] += a.x * b.x; acc[0][1] += a.x * b.y;
+        acc[1][0] += a.y * b.x; acc[1][1] += a.y * b.y;
+      }
+    }
+    __syncthreads();
+  }
+  double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (OC * OC);
+  for (int r = 0; r < 2; ++r)
+    for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[r][s];
+}
+
+// Second stage: O[i][j] = sum over the workgroups' partials in workgroup order (the k_axpy_first pattern: fixed order,
+// the same bits on every run).
+__global__ __launch_bounds__(256) void k_overlap_reduce(int ka, int kb, int nblk, int nchunk_b, const double* __restrict__ partial,
+                                                        double* __restrict__ O) {
+  const int ca = blockIdx.x / nchunk_b, cb = blockIdx.x % nchunk_b;
+  const double* pp = partial + (int64_t)blockIdx.x * nblk * (OC * OC);
+  for (int v = threadIdx.x; v < OC * OC; v += 256) {
+    const int i = ca * OC + v / OC, j = cb * OC + v % OC;
+    if (i >= ka || j >= kb) continue;
+    double s = 0.0;
+    for (int b = 0; b < nblk; ++b) s += pp[(int64_t)b * (OC * OC) + v];
+    O[(int64_t)i * kb + j] = s;
+  }
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int set_loc_err(plfem_locator* L, const std::string& m, int rc) {
+  L->err = m;
+  return rc;
+}
+
+int check_hip(plfem_locator* L, hipError_t e, const char* what) {
+  if (e != hipSuccess) return set_loc_err(L, std::string(what) + ": " + hipGetErrorString(e), PLFEM_EHIP);
+  return PLFEM_OK;
+}
+
+}  // namespace
+}  // namespace plfem
+
+using namespace plfem;
+
+namespace {
+struct LocLayout { size_t off_ptr, off_elems, off_edof, off_idx, off_pxy, total; };
+LocLayout loc_layout(const Symbolic& S) {
+  LocLayout l;
+  size_t o = 0;
+  l.off_ptr = o;   o += align256(S.loc_cell_ptr.size() * sizeof(int32_t));
+  l.off_elems = o; o += align256(std::max<size_t>(1, S.loc_cell_elems.size()) * sizeof(int32_t));
+  l.off_edof = o;  o += align256((size_t)6 * S.ne * sizeof(int32_t));
+  l.off_idx = o;   o += align256((size_t)S.N * sizeof(int32_t));
+  l.off_pxy = o;   o += align256((size_t)2 * S.nv * sizeof(double));
+  l.total = o;
+  return l;
+}
+}  // namespace
+
+extern "C" int plfem_locator_bytes(const plfem_symbolic* sym, int64_t* bytes) {
+  if (!sym || !bytes) return PLFEM_EINVAL;
+  ensure_locator(sym->S);
+  *bytes = (int64_t)loc_layout(sym->S).total;
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_locator_create(const plfem_symbolic* sym, int32_t device, void* hip_stream, void* mem_dev,
+                                    int64_t mem_bytes, plfem_locator** out, char* err, int32_t errlen) {
+  auto fail = [&](const std::string& m, int rc) {
+    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m.c_str());
+    return rc;
+  };
+  if (!out) return PLFEM_EINVAL;
+  *out = nullptr;
+  if (!sym || !mem_dev) return fail("plfem_locator_create: null analysis or device memory", PLFEM_EINVAL);
+  if ((uintptr_t)mem_dev & 255) return fail("plfem_locator_create: device memory must be 256-byte aligned", PLFEM_EINVAL);
+  const Symbolic& S = sym->S;
+  ensure_locator(S);
+  const LocLayout lay = loc_layout(S);
+  if (mem_bytes < (int64_t)lay.total) return fail("plfem_locator_create: device memory smaller than plfem_locator_bytes", PLFEM_EINVAL);
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(e), PLFEM_EHIP);
+  plfem_locator* L = new plfem_locator();
+  L->S = &S;
+  L->device = device;
+  L->stream = (hipStream_t)hip_stream;
+  L->nv = S.nv; L->ne = S.ne; L->N = S.N; L->nsolve = S.nsolve;
+  L->x0 = S.loc_grid[0]; L->y0 = S.loc_grid[1]; L->inv_hx = S.loc_grid[2]; L->inv_hy = S.loc_grid[3];
+  L->nx = (int)S.loc_grid[4]; L->ny = (int)S.loc_grid[5];
+  char* base = (char*)mem_dev;
+  L->d_cell_ptr = (int32_t*)(base + lay.off_ptr);
+  L->d_cell_elems = (int32_t*)(base + lay.off_elems);
+  L->d_edof = (int32_t*)(base + lay.off_edof);
+  L->d_int_index = (int32_t*)(base + lay.off_idx);
+  L->d_pxy = (double*)(base + lay.off_pxy);
+  // vertex coordinates = the first nv entries of both doflocs rows
+  std::vector<double> pxy((size_t)2 * S.nv);
+  std::memcpy(pxy.data(), S.doflocs.data(), sizeof(double) * S.nv);
+  std::memcpy(pxy.data() + S.nv, S.doflocs.data() + S.N, sizeof(double) * S.nv);
+  struct { void* d; const void* h; size_t b; } up[] = {
+      {L->d_cell_ptr, S.loc_cell_ptr.data(), S.loc_cell_ptr.size() * sizeof(int32_t)},
+      {L->d_cell_elems, S.loc_cell_elems.data(), S.loc_cell_elems.size() * sizeof(int32_t)},
+      {L->d_edof, S.edof.data(), S.edof.size() * sizeof(int32_t)},
+      {L->d_int_index, S.int_index.data(), S.int_index.size() * sizeof(int32_t)},
+      {L->d_pxy, pxy.data(), pxy.size() * sizeof(double)}};
+  for (auto& u : up) {
+    if (u.b == 0) continue;
+    e = hipMemcpyAsync(u.d, u.h, u.b, hipMemcpyHostToDevice, L->stream);
+    if (e != hipSuccess) { delete L; return fail(std::string("hipMemcpyAsync (locator upload): ") + hipGetErrorString(e), PLFEM_EHIP); }
+  }
+  e = hipStreamSynchronize(L->stream);         // (pxy is a local buffer)
+  if (e != hipSuccess) { delete L; return fail(std::string("hipStreamSynchronize: ") + hipGetErrorString(e), PLFEM_EHIP); }
+  *out = L;
+  return PLFEM_OK;
+}
+
+extern "C" void plfem_locator_destroy(plfem_locator* loc) {
+  if (!loc) return;
+  (void)hipSetDevice(loc->device);
+  (void)hipStreamSynchronize(loc->stream);     // nothing in flight may still read the caller's memory
+  delete loc;
+}
+
+extern "C" const char* plfem_locator_last_error(const plfem_locator* loc) { return loc ? loc->err.c_str() : "null locator"; }
+
+extern "C" int plfem_stage_modes(plfem_locator* L, int32_t ncomp, int32_t k, int32_t nrows, const double* src_dev, double* dst_dev) {
+  if (!L) return PLFEM_EINVAL;
+  if (ncomp < 1 || ncomp > 2 || k < 0 || nrows < 0 || ((!src_dev || !dst_dev) && k > 0 && nrows > 0))
+    return set_loc_err(L, "plfem_stage_modes: bad arguments", PLFEM_EINVAL);
+  if (k == 0 || nrows == 0) return PLFEM_OK;
+  int rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
+  if (rc) return rc;
+  dim3 grid((nrows + 31) / 32, (k + 31) / 32, ncomp);
+  hipLaunchKernelGGL(k_stage_modes, grid, dim3(256), 0, L->stream, (int)k, (int)nrows, src_dev, dst_dev);
+  return check_hip(L, hipGetLastError(), "k_stage_modes");
+}
+
+extern "C" int plfem_sample_fields(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                   const double* beta_dev, int32_t npts, const double* points_dev, double* out_dev,
+                                   int32_t* elem_dev) {
+  if (!L) return PLFEM_EINVAL;
+  if (ncomp < 1 || ncomp > 2 || k < 0 || npts < 0)
+    return set_loc_err(L, "plfem_sample_fields: ncomp must be 1 or 2, k and npts >= 0", PLFEM_EINVAL);
+  if (npts == 0) return PLFEM_OK;
+  if (!points_dev || !elem_dev || (k > 0 && (!modes_dev || !out_dev)))
+    return set_loc_err(L, "plfem_sample_fields: null device array", PLFEM_EINVAL);
+  if (indexed && L->S->nsolve == 0) return set_loc_err(L, "plfem_sample_fields: the analysis has no interior DOFs", PLFEM_EINVAL);
+  int rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
+  if (rc) return rc;
+  const int64_t nrows = indexed ? L->nsolve : L->N;
+  hipLaunchKernelGGL(k_sample_fields, dim3((npts + 255) / 256), dim3(256), 0, L->stream, loc_args(L, indexed != 0),
+                     (int)ncomp, (int)k, nrows, modes_dev, ncomp == 2 ? beta_dev : nullptr, (int)npts, points_dev, out_dev, elem_dev);
+  return check_hip(L, hipGetLastError(), "k_sample_fields");
+}
+
+namespace {
+int overlap_chunks(int k) { return (k + OC - 1) / OC; }
+}  // namespace
+
+extern "C" int plfem_overlap_work_bytes(int32_t ka, int32_t kb, int64_t* bytes) {
+  if (!bytes || ka < 0 || kb < 0) return PLFEM_EINVAL;
+  *bytes = (int64_t)(align256((size_t)ka * kb * sizeof(double)) +
+                     (size_t)overlap_chunks(ka) * overlap_chunks(kb) * OVL_BLOCKS * OC * OC * sizeof(double));
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev, int32_t ka, int32_t indexed_a,
+                                   plfem_locator* Lb, const double* modes_b_dev, int32_t kb, int32_t indexed_b, int32_t ncomp,
+                                   const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                                   void* work_dev, int64_t work_bytes, double* out_host) {
+  if (!La) return PLFEM_EINVAL;
+  if (!Lb || La->device != Lb->device) return set_loc_err(La, "plfem_field_overlap: the two locators must be on one device", PLFEM_EINVAL);
+  if (ncomp < 1 || ncomp > 2 || ka < 0 || kb < 0) return set_loc_err(La, "plfem_field_overlap: bad ncomp / ka / kb", PLFEM_EINVAL);
+  if (ka == 0 || kb == 0) return PLFEM_OK;
+  if (!modes_a_dev || !modes_b_dev || !work_dev || !out_host) return set_loc_err(La, "plfem_field_overlap: null array", PLFEM_EINVAL);
+  if (ncore > 64 || (ncore > 0 && !cores_host)) return set_loc_err(La, "plfem_field_overlap: at most 64 cores", PLFEM_EINVAL);
+  if ((indexed_a && La->nsolve == 0) || (indexed_b && Lb->nsolve == 0))
+    return set_loc_err(La, "plfem_field_overlap: the analysis has no interior DOFs", PLFEM_EINVAL);
+  int64_t need = 0;
+  plfem_overlap_work_bytes(ka, kb, &need);
+  if (work_bytes < need) return set_loc_err(La, "plfem_field_overlap: work buffer smaller than plfem_overlap_work_bytes", PLFEM_EINVAL);
+  if ((uintptr_t)work_dev & 255) return set_loc_err(La, "plfem_field_overlap: work buffer must be 256-byte aligned", PLFEM_EINVAL);
+  int rc = check_hip(La, hipSetDevice(La->device), "hipSetDevice");
+  if (rc) return rc;
+  CoreTable ct;
+  std::memset(&ct, 0, sizeof(ct));
+  if (ncore > 0) std::memcpy(ct.c, cores_host, sizeof(double) * 3 * ncore);
+  const int nca = overlap_chunks(ka), ncb = overlap_chunks(kb);
+  const int64_t ntiles = ((int64_t)6 * Lb->ne + OT - 1) / OT;
+  const int nblk = (int)std::min<int64_t>(OVL_BLOCKS, ntiles);
+  double* O = (double*)work_dev;
+  double* partial = (double*)((char*)work_dev + align256((size_t)ka * kb * sizeof(double)));
+  hipLaunchKernelGGL(k_field_overlap, dim3(nblk, nca * ncb), dim3(256), 0, La->stream, loc_args(La, indexed_a != 0),
+                     loc_args(Lb, indexed_b != 0), (int)ncomp, (int)ka, (int64_t)(indexed_a ? La->nsolve : La->N), modes_a_dev,
+                     (int)kb, (int64_t)(indexed_b ? Lb->nsolve : Lb->N), modes_b_dev, ct, ncore < 0 ? -1 : (int)ncore,
+                     1.0 / eps_core, 1.0 / eps_clad, ncb, partial);
+  rc = check_hip(La, hipGetLastError(), "k_field_overlap");
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_overlap_reduce, dim3(nca * ncb), dim3(256), 0, La->stream, (int)ka, (int)kb, nblk, ncb, partial, O);
+  rc = check_hip(La, hipGetLastError(), "k_overlap_reduce");
+  if (rc) return rc;
+  rc = check_hip(La, hipMemcpyAsync(out_host, O, sizeof(double) * ka * kb, hipMemcpyDeviceToHost, La->stream), "hipMemcpyAsync");
+  if (rc) return rc;
+  return check_hip(La, hipStreamSynchronize(La->stream), "hipStreamSynchronize");
+}

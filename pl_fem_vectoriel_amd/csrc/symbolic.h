@@ -77,6 +77,14 @@ struct Symbolic {
   double t_numbering = 0, t_pattern = 0, t_tree = 0, t_fronts = 0;  // seconds
   // ---- launch plan of the device kernels (plan.h): mesh-only, shared by every context on this analysis
   LaunchPlan plan;
+  // ---- point locator (locator.cpp): uniform cell grid over the vertex bounding box, built on first request only
+  // (ensure_locator: plfem_locator_bytes / plfem_locator_create / plfem_symbolic_get("loc_*")); the solve never builds it.
+  // Cell of a point: ix = clamp(floor((x - x0) inv_hx), 0, nx - 1), the same for y; an element is listed in every cell
+  // its vertex bounding box touches, element ids ascending within a cell.
+  mutable std::vector<double> loc_grid;        // [6] x0, y0, inv_hx, inv_hy, nx, ny
+  mutable std::vector<int32_t> loc_cell_ptr;   // [nx ny + 1], cell id = iy nx + ix
+  mutable std::vector<int32_t> loc_cell_elems; // [loc_cell_ptr[nx ny]]
+  mutable std::vector<double> loc_stats;       // [4] cells, mean candidates per cell, max candidates per cell, build seconds
 };
 
 // p: [2][nv] (x row then y row), t: [3][ne].  leaf_elems: target elements per leaf front.
@@ -87,6 +95,11 @@ std::string build_symbolic(int nv, int ne, const double* p, const int32_t* t, in
 // Host copy of the CSR column lists (sorted union of the DOFs of the elements adjacent to each node); no-op
 // if already built.  Not thread-safe against concurrent first calls on the same Symbolic.
 void ensure_pattern(const Symbolic& S);
+
+// The point locator of S (loc_* above); no-op if already built.  At most LOC_CELLS_PER_ELEM ne cells.  Not thread-safe
+// against concurrent first calls on the same Symbolic.
+constexpr int LOC_CELLS_PER_ELEM = 2;
+void ensure_locator(const Symbolic& S);
 
 // f(rank, nthreads) on nthreads threads (the caller is rank 0) of a worker pool from the process-wide cache of idle pools
 // the analysis uses -- for short host-side bursts outside the analysis (the staging copy of plfem_create), which would

@@ -1,0 +1,306 @@
+"""Mode fields at arbitrary points, and overlaps of modes across meshes, on the GPU.
+
+The solvers return their modes as P2 DOF vectors: ``TrueVectorialMaxwellSolver`` records hold ``Ex_dofs`` / ``Ey_dofs``
+(Hx / Hy on the interior DOFs), ``ScalarHelmholtzSolver`` records ``field_vector`` on all N DOFs.  In the reference the
+same vectors sit next to a scikit-fem ``Basis`` whose ``probes`` / ``interpolate`` turn them back into fields; here that
+is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary points"):
+
+* :class:`ModeFields` -- point location in the mesh (a uniform cell grid built lazily on the mesh's analysis) and P2
+  evaluation of many modes at many points in one kernel (``plfem_sample_fields``);
+* :func:`mode_overlap` -- ``O[i, j] = integral over mesh B of w(x) u_a,i . u_b,j`` with mesh B's six-point rule, A's
+  values located and evaluated inside the kernel (``plfem_field_overlap``).
+
+Containment (``PLFEM_LOC_TOL``): a point is inside an element when every barycentric coordinate is >= -1e-10 (minus
+that coordinate's floating-point rounding bound, which matters on sliver elements only); when
+several elements contain it the smallest element id wins; a point inside none gets element -1 and value 0.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+
+from . import _native
+from .solver_fem import _core_table, mesh_key
+
+LOC_TOL = 1e-10                    # PLFEM_LOC_TOL of include/plfem.h
+
+
+def _mesh_arrays(mesh):
+    p = np.asarray(getattr(mesh, "p", None) if mesh is not None else None)
+    t = np.asarray(getattr(mesh, "t", None) if mesh is not None else None)
+    if p.ndim != 2 or p.shape[0] != 2 or t.ndim != 2 or t.shape[0] != 3:
+        raise ValueError("mesh must have p (2, nv) and t (3, ne)")
+    return p, t
+
+
+def _records(modes) -> tuple:
+    """(kind, values (ncomp, k, n) float64, beta (k,)) of a list of mode records; kind is None for an empty list."""
+    if isinstance(modes, dict):
+        raise ValueError("modes must be a list of mode records, not one record")
+    modes = list(modes)
+    if not modes:
+        return None, None, None
+    kinds = set()
+    for m in modes:
+        if not hasattr(m, "keys"):
+            raise ValueError("every mode must be a record (dict) of a solver")
+        if "Ex_dofs" in m and "Ey_dofs" in m:
+            kinds.add("vectorial")
+        elif "field_vector" in m:
+            kinds.add("scalar")
+        else:
+            raise ValueError("a mode record needs 'Ex_dofs' / 'Ey_dofs' (vectorial) or 'field_vector' (scalar)")
+    if len(kinds) > 1:
+        raise ValueError("vectorial and scalar mode records cannot be mixed")
+    kind = kinds.pop()
+    cols = ("Ex_dofs", "Ey_dofs") if kind == "vectorial" else ("field_vector",)
+    comps = []
+    for c in cols:
+        vs = [np.asarray(m[c]) for m in modes]
+        if any(v.ndim != 1 for v in vs) or len({v.shape[0] for v in vs}) != 1:
+            raise ValueError(f"'{c}' vectors must be 1-D and of one length")
+        if any(np.iscomplexobj(v) for v in vs):
+            raise NotImplementedError("complex fields: the solvers of this package return real vectors")
+        comps.append(np.stack(vs).astype(np.float64, copy=False))
+    if comps[-1].shape != comps[0].shape:
+        raise ValueError("'Ex_dofs' and 'Ey_dofs' must have the same length")
+    vals = np.ascontiguousarray(np.stack(comps))
+    beta = np.array([float(m.get("beta", np.nan)) for m in modes], dtype=np.float64)
+    return kind, vals, beta
+
+
+class ModeFields:
+    """Point evaluation of the modes of one mesh.
+
+    ``ModeFields(mesh, device=None, solver=None)``: the mesh-only analysis is taken from ``solver``'s cache when it
+    holds this mesh (vectorial analysis), otherwise built here (host, a few ms); the locator grid is built on the host
+    on first use and uploaded with the mesh's index arrays to the device (``plfem_locator_create``).  Argument errors
+    raise ``ValueError`` before anything touches the device."""
+
+    CHUNK_BYTES = 256 << 20        # device memory of one chunk of sampled values
+
+    def __init__(self, mesh, device: Optional[int] = None, solver=None):
+        p, t = _mesh_arrays(mesh)
+        self.mesh = mesh
+        self.device = device
+        sym = None
+        if solver is not None:
+            ent = getattr(solver, "_cache", {}).get(mesh_key(mesh))
+            if ent is not None and ent["sym"].dofs_per_node == 2 and ent["sym"].info["nsolve"] < ent["sym"].N:
+                sym = ent["sym"]
+        self.sym = sym if sym is not None else _native.Symbolic(p, t)
+        self.N, self.nsolve, self.ne = self.sym.N, self.sym.nsolve, self.sym.ne
+        self.bbox = (float(p[0].min()), float(p[0].max()), float(p[1].min()), float(p[1].max()))
+        self._loc = None
+        self._mem = None
+        self._stats = None
+
+    # -- host-side -------------------------------------------------------------------------------------------
+    @property
+    def stats(self) -> Dict:
+        """Locator grid statistics (built on the host on first request): cells, mean / max candidates per cell."""
+        if self._stats is None:
+            g, s = self.sym.array("loc_grid"), self.sym.array("loc_stats")
+            self._stats = {"nx": int(g[4]), "ny": int(g[5]), "cells": int(s[0]), "mean_candidates": float(s[1]),
+                           "max_candidates": int(s[2]), "t_build": float(s[3])}
+        return self._stats
+
+    def _check_records(self, modes):
+        kind, vals, beta = _records(modes)
+        if kind == "vectorial" and vals.shape[2] != self.nsolve:
+            raise ValueError(f"'Ex_dofs' / 'Ey_dofs' must have one entry per interior P2 DOF of the mesh ({self.nsolve}), "
+                             f"got {vals.shape[2]}")
+        if kind == "scalar" and vals.shape[2] != self.N:
+            raise ValueError(f"'field_vector' must have one entry per P2 DOF of the mesh ({self.N}), got {vals.shape[2]}")
+        return kind, vals, beta
+
+    # -- device ----------------------------------------------------------------------------------------------
+    def _ensure_locator(self):
+        if self._loc is not None:
+            return
+        import torch
+        lib = _native.load_library()
+        if not torch.cuda.is_available():
+            raise RuntimeError("no HIP device visible: mode fields are evaluated on the GPU only")
+        dev = torch.cuda.current_device() if self.device is None else int(self.device)
+        self.tdev = torch.device("cuda", dev)
+        self.stream = torch.cuda.current_stream(self.tdev)
+        need = ctypes.c_int64(0)
+        rc = lib.plfem_locator_bytes(self.sym._h, ctypes.byref(need))
+        if rc != _native.PLFEM_OK:
+            raise RuntimeError(f"plfem_locator_bytes failed ({rc})")
+        self._mem = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=self.tdev)
+        aligned = (self._mem.data_ptr() + 255) & ~255
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(512)
+        rc = lib.plfem_locator_create(self.sym._h, dev, ctypes.c_void_p(self.stream.cuda_stream), ctypes.c_void_p(aligned),
+                                      ctypes.c_int64(int(need.value)), ctypes.byref(h), err, 512)
+        if rc != _native.PLFEM_OK:
+            raise RuntimeError(f"plfem_locator_create failed ({rc}): {err.value.decode()}")
+        self._lib = lib
+        self._loc = h
+        self.device = dev
+
+    def _check(self, rc, what):
+        if rc != _native.PLFEM_OK:
+            msg = self._lib.plfem_locator_last_error(self._loc).decode()
+            raise (ValueError if rc == _native.PLFEM_EINVAL else RuntimeError)(f"{what} failed ({rc}): {msg}")
+
+    def _stage(self, vals):
+        """Host (ncomp, k, n) -> device, DOF-major (ncomp, n, k) (``plfem_stage_modes``)."""
+        import torch
+        ncomp, k, n = vals.shape
+        with torch.cuda.stream(self.stream):
+            src = torch.from_numpy(vals).to(self.tdev)
+            dst = torch.empty((ncomp, n, k), dtype=torch.float64, device=self.tdev)
+            self._check(self._lib.plfem_stage_modes(self._loc, ncomp, k, n, ctypes.c_void_p(src.data_ptr()),
+                                                    ctypes.c_void_p(dst.data_ptr())), "plfem_stage_modes")
+        return dst, src
+
+    def sample(self, modes: Sequence[Dict], points, hz: bool = True) -> Dict[str, np.ndarray]:
+        """Values of the modes at ``points`` (2, npts): ``{"Hx", "Hy"[, "Hz_im"]}`` (vectorial records; ``Hz_im`` =
+        -(dHx/dx + dHy/dy) / beta when ``hz``) or ``{"u"}`` (scalar records), each (k, npts); ``"element"`` (npts,)
+        int32, the element each point was found in or -1 (value 0)."""
+        kind, vals, beta = self._check_records(modes)
+        pts = np.asarray(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[0] != 2:
+            raise ValueError("points must be an array of shape (2, npts)")
+        if kind == "vectorial" and hz and not np.all(np.isfinite(beta) & (beta != 0)):
+            raise ValueError("Hz_im needs a finite, non-zero 'beta' in every vectorial record (or hz=False)")
+        import torch
+        npts = pts.shape[1]
+        k = 0 if kind is None else vals.shape[1]
+        ncomp = 0 if kind is None else vals.shape[0]
+        names = {"vectorial": ["Hx", "Hy"] + (["Hz_im"] if hz else []), "scalar": ["u"], None: []}[kind]
+        nout = len(names)
+        res = {nm: np.empty((k, npts), dtype=np.float64) for nm in names}
+        res["element"] = np.empty(npts, dtype=np.int32)
+        if npts == 0:
+            return res
+        self._ensure_locator()
+        staged = beta_d = None
+        if k:
+            staged, _src = self._stage(vals)
+            del _src
+            if kind == "vectorial" and hz:
+                beta_d = torch.from_numpy(beta).to(self.tdev)
+        chunk = int(max(1024, min(npts, self.CHUNK_BYTES // (8 * max(1, nout * k) + 20), 1 << 30)))
+        with torch.cuda.stream(self.stream):
+            for s in range(0, npts, chunk):
+                e = min(npts, s + chunk)
+                n = e - s
+                pd = torch.from_numpy(np.ascontiguousarray(pts[:, s:e])).to(self.tdev)
+                od = torch.empty((max(nout, 1), k, n), dtype=torch.float64, device=self.tdev)
+                ed = torch.empty(n, dtype=torch.int32, device=self.tdev)
+                self._check(self._lib.plfem_sample_fields(
+                    self._loc, max(ncomp, 1), k, ctypes.c_void_p(staged.data_ptr() if staged is not None else 0),
+                    1 if kind == "vectorial" else 0, ctypes.c_void_p(beta_d.data_ptr() if beta_d is not None else 0), n,
+                    ctypes.c_void_p(pd.data_ptr()), ctypes.c_void_p(od.data_ptr()), ctypes.c_void_p(ed.data_ptr())),
+                    "plfem_sample_fields")
+                oh = od.cpu().numpy()
+                for c, nm in enumerate(names):
+                    res[nm][:, s:e] = oh[c]
+                res["element"][s:e] = ed.cpu().numpy()
+        return res
+
+    def sample_grid(self, modes: Sequence[Dict], nx: int, ny: int, extent=None, hz: bool = True) -> Dict[str, np.ndarray]:
+        """:meth:`sample` on the regular nx x ny grid over ``extent`` = (xmin, xmax, ymin, ymax) (default: the mesh's
+        bounding box): every component (k, ny, nx), ``"element"`` (ny, nx), and the axes ``"x"`` (nx,), ``"y"`` (ny,)."""
+        nx, ny = int(nx), int(ny)
+        if nx < 1 or ny < 1:
+            raise ValueError("nx and ny must be >= 1")
+        ext = self.bbox if extent is None else tuple(float(v) for v in extent)
+        if len(ext) != 4:
+            raise ValueError("extent must be (xmin, xmax, ymin, ymax)")
+        x = np.linspace(ext[0], ext[1], nx)
+        y = np.linspace(ext[2], ext[3], ny)
+        pts = np.empty((2, ny * nx), dtype=np.float64)
+        pts[0] = np.tile(x, ny)
+        pts[1] = np.repeat(y, nx)
+        res = self.sample(modes, pts, hz=hz)
+        out = {nm: (v.reshape(ny, nx) if nm == "element" else v.reshape(v.shape[0], ny, nx)) for nm, v in res.items()}
+        out["x"], out["y"] = x, y
+        return out
+
+    def close(self):
+        if getattr(self, "_loc", None):
+            self._lib.plfem_locator_destroy(self._loc)      # synchronises the stream before the memory goes back to torch
+            self._loc = None
+            self._mem = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _as_fields(m, device) -> ModeFields:
+    return m if isinstance(m, ModeFields) else ModeFields(m, device=device)
+
+
+def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_b, weight=None, normalize: bool = False,
+                 device: Optional[int] = None) -> np.ndarray:
+    """``O[i, j] = sum over the elements of mesh_b and its six-point rule |det J| w_q wt(x_q) u_a,i(x_q) . u_b,j(x_q)``
+    (transverse dot product for vectorial records), (ka, kb).  ``weight``: None (wt = 1) or a geometry (wt = 1/eps(x),
+    the closed-disc core test of the assembly: on one mesh O = V^T M_(1/eps) V, the B of the eigenproblem).
+    ``normalize=True``: the power coupling |O_ij|^2 / (O^aa_ii O^bb_jj), each self-overlap on its own mesh.  ``mesh_a`` /
+    ``mesh_b`` may be :class:`ModeFields` (their analyses and locators are reused)."""
+    ka_kind, va, _ = _records(modes_a)
+    kb_kind, vb, _ = _records(modes_b)
+    if ka_kind is not None and kb_kind is not None and ka_kind != kb_kind:
+        raise ValueError("vectorial and scalar mode records cannot be mixed")
+    if weight is not None and not all(hasattr(weight, a) for a in ("positions", "core_radii", "n_core", "n_clad")):
+        raise ValueError("weight must be None or a geometry (positions, core_radii, n_core, n_clad)")
+    fa = _as_fields(mesh_a, device)
+    fb = fa if (mesh_b is mesh_a or (not isinstance(mesh_b, ModeFields) and not isinstance(mesh_a, ModeFields)
+                                     and mesh_key(mesh_b) == mesh_key(mesh_a))) else _as_fields(mesh_b, device)
+    _, va, _ = fa._check_records(modes_a)
+    _, vb, _ = fb._check_records(modes_b)
+    ka = 0 if va is None else va.shape[1]
+    kb = 0 if vb is None else vb.shape[1]
+    if ka == 0 or kb == 0:
+        return np.zeros((ka, kb), dtype=np.float64)
+    indexed = 1 if ka_kind == "vectorial" else 0
+    if weight is None:
+        cores, ncore, ec, el = None, -1, 1.0, 1.0
+    else:
+        cores = _core_table(weight)
+        ncore, ec, el = cores.shape[0], float(weight.n_core) ** 2, float(weight.n_clad) ** 2
+        if ncore > 64:
+            raise ValueError("at most 64 cores")
+    fa._ensure_locator()
+    fb._ensure_locator()
+    if fa.device != fb.device:
+        raise ValueError("both meshes must be evaluated on one device")
+
+    def overlap(f1, v1, f2, v2):
+        import torch
+        lib = f1._lib
+        s1, _ = f1._stage(v1)
+        s2, _ = f2._stage(v2)
+        k1, k2 = v1.shape[1], v2.shape[1]
+        need = ctypes.c_int64(0)
+        lib.plfem_overlap_work_bytes(k1, k2, ctypes.byref(need))
+        work = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=f1.tdev)
+        aligned = (work.data_ptr() + 255) & ~255
+        out = np.empty((k1, k2), dtype=np.float64)
+        f2.stream.synchronize()                 # (B's staging ran on B's stream; the overlap runs on A's)
+        f1._check(lib.plfem_field_overlap(f1._loc, ctypes.c_void_p(s1.data_ptr()), k1, indexed,
+                                          f2._loc, ctypes.c_void_p(s2.data_ptr()), k2, indexed, v1.shape[0],
+                                          cores.ctypes.data_as(ctypes.c_void_p) if cores is not None else None, ncore,
+                                          ec, el, ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
+                                          out.ctypes.data_as(ctypes.c_void_p)), "plfem_field_overlap")
+        return out
+
+    O = overlap(fa, va, fb, vb)
+    if not normalize:
+        return O
+    daa = np.diag(overlap(fa, va, fa, va)).copy()
+    dbb = np.diag(overlap(fb, vb, fb, vb)).copy()
+    return O * O / (daa[:, None] * dbb[None, :])
+
+
+__all__ = ["ModeFields", "mode_overlap", "LOC_TOL"]

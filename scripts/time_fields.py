@@ -1,0 +1,106 @@
+"""Timing aid of the mode-field calls at C1 (vectorial, 22 modes): sampling on an nx x nx grid with Hx, Hy, Hz_im;
+mode_overlap C1 -> C1 refined (the C1 modes sampled at the DOF locations of mesh.refined(): ~1.1 M quadrature points of
+the finer mesh, 22 x 22); locator build times at C1 and L = 2; optionally the NumPy emulation of the same calls.
+
+    python scripts/time_fields.py [--grid 1024] [--reps 3] [--emulation] [--out FILE]
+
+Run it under ``rocprofv3 --kernel-trace --stats`` for the kernel times (k_sample_fields, k_field_overlap,
+k_overlap_reduce, k_stage_modes); the wall times printed here include the host-device copies."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--modes", type=int, default=22)
+    ap.add_argument("--emulation", action="store_true", help="also time the NumPy emulation (minutes)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from pl_fem_vectoriel_amd import MCFGeometry, ModeFields, generate_mesh, mode_overlap
+    from pl_fem_vectoriel_amd import _native
+    from pl_fem_vectoriel_amd.solver_fem import TrueVectorialMaxwellSolver
+
+    if not torch.cuda.is_available():
+        raise SystemExit("time_fields.py needs a GPU")
+    geom = MCFGeometry(7, 8.0, 1.5, 1.535, 1.0, wavelength_um=1.55)
+    mesh = generate_mesh(geom, 1.0, 1)
+    fine = mesh.refined()
+    solver = TrueVectorialMaxwellSolver(geom, device=0)
+    modes = solver.solve_vectorial_modes(mesh, args.modes)[:args.modes]
+    res = {"k": len(modes), "ne_c1": int(mesh.t.shape[1]), "ne_l2": int(fine.t.shape[1])}
+
+    # locator build (host) on fresh analyses
+    for name, m in (("c1", mesh), ("l2", fine)):
+        sym = _native.Symbolic(m.p, m.t)
+        t0 = time.perf_counter()
+        st = sym.array("loc_stats")
+        res[f"locator_{name}"] = {"build_ms": st[3] * 1e3, "wall_ms": (time.perf_counter() - t0) * 1e3, "cells": int(st[0]),
+                                  "mean_candidates": float(st[1]), "max_candidates": int(st[2])}
+
+    mf = ModeFields(mesh, device=0, solver=solver)
+    mf1 = ModeFields(fine, device=0)
+
+    def timed(f):
+        best = None
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = f()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            best = dt if best is None else min(best, dt)
+        return out, best
+
+    img, dt = timed(lambda: mf.sample_grid(modes, args.grid, args.grid))
+    out_bytes = 3 * len(modes) * args.grid * args.grid * 8
+    res["sample_grid"] = {"nx": args.grid, "wall_ms": dt * 1e3, "output_bytes": out_bytes,
+                          "inside": float((img["element"] >= 0).mean())}
+    dl1 = mf1.sym.array("doflocs").reshape(2, mf1.N)[:, mf1.sym.array("interior")]
+    s = mf.sample(modes, dl1, hz=False)
+    fine_modes = [{"Ex_dofs": s["Hx"][i], "Ey_dofs": s["Hy"][i]} for i in range(len(modes))]
+    O, dt = timed(lambda: mode_overlap(modes, mf, fine_modes, mf1))
+    nq = 6 * fine.t.shape[1]
+    res["overlap"] = {"nq": nq, "wall_ms": dt * 1e3, "flop": 2.0 * 2 * nq * len(modes) ** 2,
+                      "max_abs_offdiag": float(np.abs(O - np.diag(np.diag(O))).max()), "diag_min": float(np.diag(O).min())}
+    if args.emulation:
+        from fields_emulation import Emulation, overlap
+        em = Emulation(mesh.p, mesh.t)
+        em1 = Emulation(fine.p, fine.t)
+        vals = np.stack([np.array([m["Ex_dofs"] for m in modes]), np.array([m["Ey_dofs"] for m in modes])])
+        beta = np.array([m["beta"] for m in modes])
+        x = np.linspace(mf.bbox[0], mf.bbox[1], args.grid)
+        y = np.linspace(mf.bbox[2], mf.bbox[3], args.grid)
+        pts = np.vstack([np.tile(x, args.grid), np.repeat(y, args.grid)])
+        t0 = time.perf_counter()
+        ref, _ = em.sample(vals, pts, True, beta=beta)
+        res["emulation_sample_grid_s"] = time.perf_counter() - t0
+        for c, nm in enumerate(("Hx", "Hy")):
+            res[f"emulation_max_diff_{nm}"] = float(np.abs(ref[c] - img[nm].reshape(len(modes), -1)).max() / np.abs(ref[c]).max())
+        vf = np.stack([s["Hx"], s["Hy"]])
+        t0 = time.perf_counter()
+        Oe = overlap(em, vals, em1, vf, True)
+        res["emulation_overlap_s"] = time.perf_counter() - t0
+        res["emulation_overlap_rel_diff"] = float(np.abs(Oe - O).max() / np.abs(O).max())
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
