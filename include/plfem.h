@@ -336,6 +336,23 @@ int plfem_field_overlap(plfem_locator* loc_a, const double* modes_a_dev, int32_t
                         plfem_locator* loc_b, const double* modes_b_dev, int32_t kb, int32_t indexed_b, int32_t ncomp,
                         const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
                         void* work_dev, int64_t work_bytes, double* out_host);
+/* Same-mesh Grams of k staged modes (indexed as for plfem_sample_fields) under the element forms of the assembly, over
+ * the mesh's own six-point rule, split by the closed-disc core test of plfem_assemble_hfield (ncore in [0, 64]; r = core,
+ * clad; every sum is over the points of region r of |det J| w_q (...)):
+ *   ncomp = 2: out_host[0..4][k][k] = M_core, M_clad, K_core, K_clad, D with
+ *     M_r[m][n] = sum_r hx_m hx_n + hy_m hy_n,
+ *     K_r[m][n] = sum_r dy hx_m dy hx_n + dx hy_m dx hy_n - dx hx_m dy hy_n - dy hy_m dx hx_n  (the 1/eps-free part of
+ *                 [[Kxx, Kxy], [Kyx, Kyy]]),
+ *     D[m][n]   = sum dx hx_m dx hx_n + dy hy_m dy hy_n + dy hx_m dx hy_n + dx hy_m dy hx_n   ([[Dxx, Dxy], [Dxy^T, Dyy]]),
+ *     so that V^T A V = sum_r K_r / eps_r + alpha_p D - k0^2 (M_core + M_clad) and V^T B V = sum_r M_r / eps_r;
+ *   ncomp = 1: out_host[0..2][k][k] = M_core, M_clad, S (S[m][n] = sum grad u_m . grad u_n).
+ * Partial blocks per workgroup and the fixed-order second stage of plfem_field_overlap: the same bits on every run.
+ * work_dev: device scratch of plfem_gram_work_bytes(ncomp, k) bytes, 256-byte aligned; synchronises the locator's stream.
+ * Argument errors (k <= 0, ncore outside [0, 64], a null pointer, work_bytes too small) return PLFEM_EINVAL with the
+ * locator's last error set. */
+int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes);
+int plfem_mode_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                     const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host);
 
 #ifdef PLFEM_TEST_HOOKS
 /* ---------------------------------------------------------------------------------------------

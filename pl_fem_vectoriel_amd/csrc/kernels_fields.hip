@@ -1,6 +1,7 @@
 // gfx950 kernels and C-ABI of the mode-field calls (include/plfem.h, "Mode fields at arbitrary points"): the point
 // locator bound to a device, P2 evaluation of many modes at many points (k_sample_fields) and the overlap integral of
-// two mode sets living on two meshes (k_field_overlap + k_overlap_reduce).
+// two mode sets living on two meshes (k_field_overlap + k_overlap_reduce), and the same-mesh Grams of a mode set under
+// the assembly's element forms, split by material region (k_mode_grams + k_overlap_reduce).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field.
@@ -329,17 +330,168 @@ __global__ __launch_bounds__(256) void k_field_overlap(LocArgs A, LocArgs B, int
 }
 
 // Second stage: O[i][j] = sum over the workgroups' partials in workgroup order (the k_axpy_first pattern: fixed order,
-// the same bits on every run).
+// the same bits on every run).  blockIdx.y = output matrix: partials [gridDim.y][gridDim.x][nblk][OC * OC], O [gridDim.y][ka][kb]
+// (k_field_overlap: one matrix; k_mode_grams: five or three).  blockIdx.z = slice of the OC x OC entries (each entry is still
+// summed by one lane, in workgroup order).
 __global__ __launch_bounds__(256) void k_overlap_reduce(int ka, int kb, int nblk, int nchunk_b, const double* __restrict__ partial,
                                                         double* __restrict__ O) {
   const int ca = blockIdx.x / nchunk_b, cb = blockIdx.x % nchunk_b;
-  const double* pp = partial + (int64_t)blockIdx.x * nblk * (OC * OC);
-  for (int v = threadIdx.x; v < OC * OC; v += 256) {
+  const double* pp = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nblk * (OC * OC);
+  O += (int64_t)blockIdx.y * ka * kb;
+  for (int v = blockIdx.z * 256 + threadIdx.x; v < OC * OC; v += 256 * gridDim.z) {
     const int i = ca * OC + v / OC, j = cb * OC + v % OC;
     if (i >= ka || j >= kb) continue;
     double s = 0.0;
     for (int b = 0; b < nblk; ++b) s += pp[(int64_t)b * (OC * OC) + v];
     O[(int64_t)i * kb + j] = s;
+  }
+}
+
+// Same-mesh Grams of k modes under the element forms of the assembly, split by material region (plfem_mode_grams).  One
+// workgroup walks tiles of GT quadrature points of the mesh's own six-point rule (element-major) for one (32-mode chunk,
+// 32-mode chunk) pair.  Per tile: GT lanes form det J, J^-1, the quadrature point and its closed-disc core test exactly as
+// k_element_matrices does, and stage the physical basis gradients, the weight and the rows; all lanes then evaluate the
+// features of every (point, mode) -- ncomp = 2: hx, hy, dx hx, dy hx, dx hy, dy hy; ncomp = 1: u, dx u, dy u -- plain
+// for the row chunk, times |det J| w_q for the column chunk; every lane accumulates a 2 x 2 block of each output over the
+// tile.  The region of a point is the same for all lanes, so its branch costs no divergence and the region split costs
+// no extra products.  Outputs (ncomp = 2): M_core, M_clad, K_core, K_clad, D; (ncomp = 1): M_core, M_clad, S.
+constexpr int GT = 16;          // quadrature points per tile
+constexpr int GRAM_BLOCKS = 768;
+
+template <int NCOMP>
+__global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
+                                                    CoreTable cores, int ncore, int nchunk, double* __restrict__ partial) {
+  constexpr int NF = 3 * NCOMP;               // features per (point, mode)
+  constexpr int NOUT = NCOMP == 2 ? 5 : 3;
+  __shared__ double s_f[2][NF][GT][OC];       // [0]: row chunk, plain; [1]: column chunk, times the weight
+  __shared__ double s_gx[6][GT], s_gy[6][GT];
+  __shared__ int s_r[6][GT];
+  __shared__ double s_w[GT];
+  __shared__ int s_q[GT], s_core[GT];
+  const int tid = threadIdx.x;
+  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
+  const int i0 = ci * OC, j0 = cj * OC;
+  const int64_t nq = (int64_t)6 * L.ne;
+  const int64_t ntiles = (nq + GT - 1) / GT;
+  const int ti = tid >> 4, tj = tid & 15;
+  double acc[NOUT][2][2];
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
+  const double* px = L.pxy;
+  const double* py = L.pxy + L.nv;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < GT) {
+      const int64_t g = tile * GT + tid;
+      double w = 0.0;
+      int q = 0, core = 0;
+      for (int a = 0; a < 6; ++a) { s_r[a][tid] = -1; s_gx[a][tid] = 0.0; s_gy[a][tid] = 0.0; }
+      if (g < nq) {
+        const int e = (int)(g / 6);
+        q = (int)(g % 6);
+        const int v0 = L.edof[e], v1 = L.edof[L.ne + e], v2 = L.edof[2 * L.ne + e];
+        const double x0 = px[v0], y0 = py[v0];
+        const double j00 = px[v1] - x0, j10 = py[v1] - y0, j01 = px[v2] - x0, j11 = py[v2] - y0;
+        // det J, J^-1, the quadrature point and the core test exactly as k_element_matrices forms them
+        double t1, t2;
+        asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t1) : "v"(j00), "v"(j11));
+        asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t2) : "v"(j01), "v"(j10));
+        const double det = t1 - t2;
+        const double idet = 1.0 / det;
+        const double i00 = j11 * idet, i01 = -j01 * idet, i10 = -j10 * idet, i11 = j00 * idet;
+        const double xi = c_fqx[q], eta = c_fqy[q];
+        const double X = x0 + j00 * xi + j01 * eta, Y = y0 + j10 * xi + j11 * eta;
+        bool in_core = false;
+        for (int c = 0; c < ncore; ++c) {
+          const double dx = X - cores.c[3 * c], dy = Y - cores.c[3 * c + 1], r = cores.c[3 * c + 2];
+          in_core |= (dx * dx + dy * dy <= r * r);
+        }
+        core = in_core ? 1 : 0;
+        w = fabs(det) * c_fqw[q];
+        const double dxh[6] = {-3 + 4 * xi + 4 * eta, 4 * xi - 1, 0.0, 4 - 8 * xi - 4 * eta, 4 * eta, -4 * eta};
+        const double dyh[6] = {-3 + 4 * xi + 4 * eta, 0.0, 4 * eta - 1, -4 * xi, 4 * xi, 4 - 4 * xi - 8 * eta};
+        for (int a = 0; a < 6; ++a) {
+          s_gx[a][tid] = i00 * dxh[a] + i10 * dyh[a];
+          s_gy[a][tid] = i01 * dxh[a] + i11 * dyh[a];
+          s_r[a][tid] = dev_row(L, e, a);
+        }
+      }
+      s_w[tid] = w;
+      s_q[tid] = q;
+      s_core[tid] = core;
+    }
+    __syncthreads();
+    // features: consecutive lanes read consecutive modes of one staged row
+    for (int idx = tid; idx < 2 * GT * OC; idx += 256) {
+      const int i = idx % OC, t = (idx / OC) % GT, side = idx / (OC * GT);
+      const int m = (side ? j0 : i0) + i;
+      double f[NF];
+#pragma unroll
+      for (int c = 0; c < NF; ++c) f[c] = 0.0;
+      if (m < k) {
+        double phi[6];
+        p2_phi(c_fqx[s_q[t]], c_fqy[s_q[t]], phi);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          const int r = s_r[a][t];
+          if (r < 0) continue;
+          const double gx = s_gx[a][t], gy = s_gy[a][t];
+#pragma unroll
+          for (int c = 0; c < NCOMP; ++c) {
+            const double v = V[(int64_t)c * nrows * k + (int64_t)r * k + m];
+            f[c] += phi[a] * v;
+            f[NCOMP + 2 * c] += gx * v;
+            f[NCOMP + 2 * c + 1] += gy * v;
+          }
+        }
+        if (side) {
+          const double w = s_w[t];
+#pragma unroll
+          for (int c = 0; c < NF; ++c) f[c] *= w;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NF; ++c) s_f[side][c][t][i] = f[c];
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < GT; ++t) {
+      double2 a[NF], b[NF];
+#pragma unroll
+      for (int c = 0; c < NF; ++c) {
+        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
+        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
+      }
+      // acc[o] += s x a[p] (x) b[q]
+#define GRAM_ACC(o, p, q, s)                                          \
+      acc[o][0][0] += (s) * a[p].x * b[q].x; acc[o][0][1] += (s) * a[p].x * b[q].y; \
+      acc[o][1][0] += (s) * a[p].y * b[q].x; acc[o][1][1] += (s) * a[p].y * b[q].y;
+      const int r = s_core[t] ? 0 : 1;          // the same for every lane
+      if (NCOMP == 2) {
+        // M_r: hx hx + hy hy;  K_r: dy hx dy hx + dx hy dx hy - dx hx dy hy - dy hy dx hx;
+        // D: dx hx dx hx + dy hy dy hy + dy hx dx hy + dx hy dy hx  (features 0 hx, 1 hy, 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy)
+        if (r == 0) {
+          GRAM_ACC(0, 0, 0, 1.0) GRAM_ACC(0, 1, 1, 1.0)
+          GRAM_ACC(2, 3, 3, 1.0) GRAM_ACC(2, 4, 4, 1.0) GRAM_ACC(2, 2, 5, -1.0) GRAM_ACC(2, 5, 2, -1.0)
+        } else {
+          GRAM_ACC(1, 0, 0, 1.0) GRAM_ACC(1, 1, 1, 1.0)
+          GRAM_ACC(3, 3, 3, 1.0) GRAM_ACC(3, 4, 4, 1.0) GRAM_ACC(3, 2, 5, -1.0) GRAM_ACC(3, 5, 2, -1.0)
+        }
+        GRAM_ACC(NOUT - 1, 2, 2, 1.0) GRAM_ACC(NOUT - 1, 5, 5, 1.0) GRAM_ACC(NOUT - 1, 3, 4, 1.0) GRAM_ACC(NOUT - 1, 4, 3, 1.0)
+      } else {
+        // M_r: u u;  S: dx u dx u + dy u dy u  (features 0 u, 1 dx u, 2 dy u)
+        if (r == 0) { GRAM_ACC(0, 0, 0, 1.0) } else { GRAM_ACC(1, 0, 0, 1.0) }
+        GRAM_ACC(NOUT - 1, 1, 1, 1.0) GRAM_ACC(NOUT - 1, NF - 1, NF - 1, 1.0)
+      }
+#undef GRAM_ACC
+    }
+    __syncthreads();
+  }
+  const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) {
+    double* out = partial + (((int64_t)o * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+    for (int r = 0; r < 2; ++r)
+      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
   }
 }
 
@@ -520,4 +672,57 @@ extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev,
   rc = check_hip(La, hipMemcpyAsync(out_host, O, sizeof(double) * ka * kb, hipMemcpyDeviceToHost, La->stream), "hipMemcpyAsync");
   if (rc) return rc;
   return check_hip(La, hipStreamSynchronize(La->stream), "hipStreamSynchronize");
+}
+
+namespace {
+int gram_outputs(int ncomp) { return ncomp == 2 ? 5 : 3; }
+}  // namespace
+
+extern "C" int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
+  if (!bytes || ncomp < 1 || ncomp > 2 || k <= 0) return PLFEM_EINVAL;
+  const int nout = gram_outputs(ncomp), nc = overlap_chunks(k);
+  *bytes = (int64_t)(align256((size_t)nout * k * k * sizeof(double)) +
+                     (size_t)nout * nc * nc * GRAM_BLOCKS * OC * OC * sizeof(double));
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host) {
+  if (!L) return PLFEM_EINVAL;
+  if (ncomp < 1 || ncomp > 2 || k <= 0) return set_loc_err(L, "plfem_mode_grams: ncomp must be 1 or 2 and k > 0", PLFEM_EINVAL);
+  if (ncore < 0 || ncore > 64) return set_loc_err(L, "plfem_mode_grams: ncore must be in [0, 64]", PLFEM_EINVAL);
+  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host))
+    return set_loc_err(L, "plfem_mode_grams: null array", PLFEM_EINVAL);
+  if (indexed && L->nsolve == 0) return set_loc_err(L, "plfem_mode_grams: the analysis has no interior DOFs", PLFEM_EINVAL);
+  int64_t need = 0;
+  plfem_gram_work_bytes(ncomp, k, &need);
+  if (work_bytes < need) return set_loc_err(L, "plfem_mode_grams: work buffer smaller than plfem_gram_work_bytes", PLFEM_EINVAL);
+  if ((uintptr_t)work_dev & 255) return set_loc_err(L, "plfem_mode_grams: work buffer must be 256-byte aligned", PLFEM_EINVAL);
+  int rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
+  if (rc) return rc;
+  CoreTable ct;
+  std::memset(&ct, 0, sizeof(ct));
+  if (ncore > 0) std::memcpy(ct.c, cores_host, sizeof(double) * 3 * ncore);
+  const int nout = gram_outputs(ncomp), nc = overlap_chunks(k);
+  const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
+  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ntiles));
+  const int64_t nrows = indexed ? L->nsolve : L->N;
+  double* O = (double*)work_dev;
+  double* partial = (double*)((char*)work_dev + align256((size_t)nout * k * k * sizeof(double)));
+  const dim3 grid(nblk, nc * nc);
+  if (ncomp == 2)
+    hipLaunchKernelGGL(k_mode_grams<2>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
+                       ct, (int)ncore, nc, partial);
+  else
+    hipLaunchKernelGGL(k_mode_grams<1>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
+                       ct, (int)ncore, nc, partial);
+  rc = check_hip(L, hipGetLastError(), "k_mode_grams");
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_overlap_reduce, dim3(nc * nc, nout, OC * OC / 256), dim3(256), 0, L->stream, (int)k, (int)k, nblk, nc,
+                     partial, O);
+  rc = check_hip(L, hipGetLastError(), "k_overlap_reduce");
+  if (rc) return rc;
+  rc = check_hip(L, hipMemcpyAsync(out_host, O, sizeof(double) * nout * k * k, hipMemcpyDeviceToHost, L->stream), "hipMemcpyAsync");
+  if (rc) return rc;
+  return check_hip(L, hipStreamSynchronize(L->stream), "hipStreamSynchronize");
 }

@@ -8,7 +8,9 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
 * :class:`ModeFields` -- point location in the mesh (a uniform cell grid built lazily on the mesh's analysis) and P2
   evaluation of many modes at many points in one kernel (``plfem_sample_fields``);
 * :func:`mode_overlap` -- ``O[i, j] = integral over mesh B of w(x) u_a,i . u_b,j`` with mesh B's six-point rule, A's
-  values located and evaluated inside the kernel (``plfem_field_overlap``).
+  values located and evaluated inside the kernel (``plfem_field_overlap``);
+* :meth:`ModeFields.grams` -- the k x k Grams of one mesh's modes under the assembly's element forms, split by material
+  region (``plfem_mode_grams``): what :mod:`.dispersion` builds the group index and the k0-derivative coupling from.
 
 Containment (``PLFEM_LOC_TOL``): a point is inside an element when every barycentric coordinate is >= -1e-10 (minus
 that coordinate's floating-point rounding bound, which matters on sliver elements only); when
@@ -25,6 +27,7 @@ from . import _native
 from .solver_fem import _core_table, mesh_key
 
 LOC_TOL = 1e-10                    # PLFEM_LOC_TOL of include/plfem.h
+GRAM_NAMES = {"vectorial": ("M_core", "M_clad", "K_core", "K_clad", "D"), "scalar": ("M_core", "M_clad", "S")}
 
 
 def _mesh_arrays(mesh):
@@ -224,6 +227,38 @@ class ModeFields:
         out["x"], out["y"] = x, y
         return out
 
+    def grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
+        """Same-mesh Grams of the modes under the element forms of the assembly, split by material region
+        (``plfem_mode_grams``; the mesh's own six-point rule and the closed-disc core test of the assembly), each (k, k):
+        vectorial records ``M_core``, ``M_clad``, ``K_core``, ``K_clad``, ``D`` (so that ``V^T A V = sum_r K_r / eps_r +
+        alpha_p D - k0^2 (M_core + M_clad)`` and ``V^T B V = sum_r M_r / eps_r`` on the interior DOFs), scalar records
+        ``M_core``, ``M_clad``, ``S`` (``V^T A V = S - k0^2 sum_r eps_r M_r``, ``V^T B V = M_core + M_clad``)."""
+        kind, vals, _ = self._check_records(modes)
+        if not all(hasattr(geometry, a) for a in ("positions", "core_radii")):
+            raise ValueError("geometry must have positions and core_radii")
+        cores = _core_table(geometry)
+        if cores.shape[0] > 64:
+            raise ValueError("at most 64 cores")
+        names = GRAM_NAMES.get(kind, ())
+        k = 0 if kind is None else vals.shape[1]
+        if k == 0:
+            return {nm: np.zeros((0, 0)) for nm in names}
+        self._ensure_locator()
+        import torch
+        ncomp = vals.shape[0]
+        need = ctypes.c_int64(0)
+        if self._lib.plfem_gram_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
+            raise ValueError(f"plfem_gram_work_bytes rejected ncomp = {ncomp}, k = {k}")
+        staged, _src = self._stage(vals)
+        work = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=self.tdev)
+        aligned = (work.data_ptr() + 255) & ~255
+        out = np.empty((len(names), k, k), dtype=np.float64)
+        self._check(self._lib.plfem_mode_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
+                                               1 if kind == "vectorial" else 0, cores.ctypes.data_as(ctypes.c_void_p),
+                                               cores.shape[0], ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
+                                               out.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_grams")
+        return {nm: out[i] for i, nm in enumerate(names)}
+
     def close(self):
         if getattr(self, "_loc", None):
             self._lib.plfem_locator_destroy(self._loc)      # synchronises the stream before the memory goes back to torch
@@ -303,4 +338,4 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
     return O * O / (daa[:, None] * dbb[None, :])
 
 
-__all__ = ["ModeFields", "mode_overlap", "LOC_TOL"]
+__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES"]
