@@ -15,6 +15,7 @@
 
 #include "device.h"
 #include "host_eig.h"
+#include "p2_element.h"
 
 using plfem::LevelInfo;
 using plfem::Symbolic;
@@ -360,7 +361,7 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
   upload_span = c->slab_off;
   TRY(dalloc(c, &c->d_colind, (size_t)c->nnz));      // filled on the device by launch_pattern_fill below
   TRY(dalloc(c, &c->d_slot_row, (size_t)c->nnz));
-  TRY(dalloc(c, &c->d_cores, 64 * 3));
+  TRY(dalloc(c, &c->d_cores, plfem::MAX_CORES * 3));
   TRY(dalloc(c, &c->d_elem, (size_t)S.ne * plfem::ELEM_STRIDE));
   for (auto& p : c->d_vals) TRY(dalloc(c, &p, (size_t)c->nnz));
   const int64_t fnodes_total = S.fnode_ptr[S.nfronts];
@@ -468,7 +469,7 @@ int wait_for_upload(plfem_ctx* c) {
 }
 
 int upload_cores(plfem_ctx* c, const double* cores_host, int ncore) {
-  if (ncore < 0 || ncore > 64 || (ncore > 0 && !cores_host)) {
+  if (ncore < 0 || ncore > plfem::MAX_CORES || (ncore > 0 && !cores_host)) {
     c->err = "ncore must be in [0, 64]";
     return PLFEM_EINVAL;
   }

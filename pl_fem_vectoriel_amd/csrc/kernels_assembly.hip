@@ -4,18 +4,10 @@
 // (solver_fem.py:131-156), geometry.epsilon at the quadrature points (geometry_unified.py:325-336,
 // real part only) and the block build solver_fem.py:158-167.
 #include "device.h"
+#include "p2_element.h"
 
 namespace plfem {
 namespace {
-
-// 6-point degree-4 rule on the reference triangle (weights sum to 1/2) — scikit-fem's default
-// intorder = 2*maxdeg = 4 for ElementTriP2.
-__constant__ double c_qx[6] = {0.445948490915965, 0.10810301816807, 0.445948490915965,
-                               0.091576213509771, 0.816847572980458, 0.091576213509771};
-__constant__ double c_qy[6] = {0.445948490915965, 0.445948490915965, 0.10810301816807,
-                               0.091576213509771, 0.091576213509771, 0.816847572980458};
-__constant__ double c_qw[6] = {0.1116907948390055, 0.1116907948390055, 0.1116907948390055,
-                               0.054975871827661, 0.054975871827661, 0.054975871827661};
 
 constexpr int EPB = 7;   // elements per 256-thread block: 7*36 = 252 (i,j) pairs
 
@@ -36,52 +28,25 @@ __global__ __launch_bounds__(256) void k_element_matrices(
   const int e0 = blockIdx.x * EPB;
   if (tid < 36) {
     int i = tid / 6, q = tid % 6;
-    double x = c_qx[q], y = c_qy[q], v;
-    switch (i) {
-      case 0: v = 1 - 3 * x - 3 * y + 2 * x * x + 4 * x * y + 2 * y * y; break;
-      case 1: v = 2 * x * x - x; break;
-      case 2: v = 2 * y * y - y; break;
-      case 3: v = 4 * x - 4 * x * x - 4 * x * y; break;
-      case 4: v = 4 * x * y; break;
-      default: v = 4 * y - 4 * x * y - 4 * y * y; break;
-    }
-    s_phi[i][q] = v;
+    s_phi[i][q] = p2_phi(i, c_qx[q], c_qy[q]);
   }
   if (tid < EPB * 6) {
     int el = tid / 6, q = tid % 6;
     int e = e0 + el;
     if (e < ne) {
-      int v0 = tsorted[e], v1 = tsorted[ne + e], v2 = tsorted[2 * (size_t)ne + e];
-      double x0 = doflocs[v0], y0 = doflocs[N + v0];
-      double j00 = doflocs[v1] - x0, j10 = doflocs[N + v1] - y0;      // J = [p1-p0, p2-p0]
-      double j01 = doflocs[v2] - x0, j11 = doflocs[N + v2] - y0;
-      // det J of a sliver element cancels to ~1e-8 of its terms: keep the two products individually
-      // rounded (as the reference's NumPy arithmetic does); a fused multiply-add here changes 1e9-sized
-      // element entries at the 1e-8 relative level.  hipcc's default -ffp-contract=fast ignores the
-      // contract pragma, hence the opaque multiplies.
-      double t1, t2;
-      asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t1) : "v"(j00), "v"(j11));
-      asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t2) : "v"(j01), "v"(j10));
-      double det = t1 - t2;
-      double idet = 1.0 / det;
-      // J^-1 = 1/det [[j11, -j01], [-j10, j00]];  grad = J^-T grad_hat
-      double i00 = j11 * idet, i01 = -j01 * idet, i10 = -j10 * idet, i11 = j00 * idet;
-      double xi = c_qx[q], eta = c_qy[q];
-      double X = x0 + j00 * xi + j01 * eta, Y = y0 + j10 * xi + j11 * eta;
-      bool in_core = false;
-      for (int c = 0; c < ncore; ++c) {
-        double dx = X - cores[3 * c], dy = Y - cores[3 * c + 1], r = cores[3 * c + 2];
-        in_core |= (dx * dx + dy * dy <= r * r);
-      }
+      const P2Map M(tsorted, (size_t)ne, doflocs, doflocs + N, e);
+      const double xi = c_qx[q], eta = c_qy[q];
+      double det = M.det(), inv[4], X, Y, gx[6], gy[6];
+      M.inverse(det, inv);
+      M.point(xi, eta, X, Y);
       double w1 = fabs(det) * c_qw[q];
       s_w1[el][q] = w1;
-      s_we[el][q] = w1 * (in_core ? inv_eps_core : inv_eps_clad);
-      double dxh[6] = {-3 + 4 * xi + 4 * eta, 4 * xi - 1, 0.0, 4 - 8 * xi - 4 * eta, 4 * eta, -4 * eta};
-      double dyh[6] = {-3 + 4 * xi + 4 * eta, 0.0, 4 * eta - 1, -4 * xi, 4 * xi, 4 - 4 * xi - 8 * eta};
+      s_we[el][q] = w1 * (in_any_core(X, Y, cores, ncore) ? inv_eps_core : inv_eps_clad);
+      p2_grad(inv, xi, eta, gx, gy);
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        s_gx[el][i][q] = i00 * dxh[i] + i10 * dyh[i];
-        s_gy[el][i][q] = i01 * dxh[i] + i11 * dyh[i];
+        s_gx[el][i][q] = gx[i];
+        s_gy[el][i][q] = gy[i];
       }
     }
   }
@@ -133,9 +98,8 @@ __global__ __launch_bounds__(256) void k_element_matrices(
   }
 }
 
-// Number of quadrature points inside a core (same point and same closed-disc test as k_element_matrices): the
-// unweighted mean permittivity over all quadrature points that the reference's CMT form subtracts (config.py:297-300)
-// follows from it in closed form.  Integer atomics: order independent.
+// Number of quadrature points inside a core: the unweighted mean permittivity over all quadrature points that the
+// reference's CMT form subtracts (config.py:297-300) follows from it in closed form.  Integer atomics: order independent.
 __global__ __launch_bounds__(256) void k_count_core_qp(int ne, int N, const int32_t* __restrict__ tsorted,
                                                        const double* __restrict__ doflocs, const double* __restrict__ cores,
                                                        int ncore, unsigned long long* __restrict__ count) {
@@ -143,16 +107,9 @@ __global__ __launch_bounds__(256) void k_count_core_qp(int ne, int N, const int3
   bool in_core = false;
   if (t < (int64_t)ne * 6) {
     const int e = (int)(t / 6), q = (int)(t % 6);
-    int v0 = tsorted[e], v1 = tsorted[ne + e], v2 = tsorted[2 * (size_t)ne + e];
-    double x0 = doflocs[v0], y0 = doflocs[N + v0];
-    double j00 = doflocs[v1] - x0, j10 = doflocs[N + v1] - y0;
-    double j01 = doflocs[v2] - x0, j11 = doflocs[N + v2] - y0;
-    double xi = c_qx[q], eta = c_qy[q];
-    double X = x0 + j00 * xi + j01 * eta, Y = y0 + j10 * xi + j11 * eta;
-    for (int c = 0; c < ncore; ++c) {
-      double dx = X - cores[3 * c], dy = Y - cores[3 * c + 1], r = cores[3 * c + 2];
-      in_core |= (dx * dx + dy * dy <= r * r);
-    }
+    double X, Y;
+    P2Map(tsorted, (size_t)ne, doflocs, doflocs + N, e).point(c_qx[q], c_qy[q], X, Y);
+    in_core = in_any_core(X, Y, cores, ncore);
   }
   const unsigned long long b = __ballot(in_core);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));

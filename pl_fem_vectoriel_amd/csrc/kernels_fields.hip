@@ -12,6 +12,7 @@
 
 #include "../../include/plfem.h"
 #include "internal.h"
+#include "p2_element.h"
 #include <hip/hip_runtime.h>
 
 struct plfem_locator {
@@ -29,14 +30,6 @@ struct plfem_locator {
 namespace plfem {
 namespace {
 
-// 6-point degree-4 rule on the reference triangle: the values of kernels_assembly.hip (k_element_matrices)
-__constant__ double c_fqx[6] = {0.445948490915965, 0.10810301816807, 0.445948490915965,
-                                0.091576213509771, 0.816847572980458, 0.091576213509771};
-__constant__ double c_fqy[6] = {0.445948490915965, 0.445948490915965, 0.10810301816807,
-                                0.091576213509771, 0.091576213509771, 0.816847572980458};
-__constant__ double c_fqw[6] = {0.1116907948390055, 0.1116907948390055, 0.1116907948390055,
-                                0.054975871827661, 0.054975871827661, 0.054975871827661};
-
 struct LocArgs {
   double x0, y0, inv_hx, inv_hy;
   int nx, ny, nv, ne;
@@ -48,7 +41,7 @@ struct LocArgs {
 };
 
 struct CoreTable {
-  double c[64 * 3];
+  double c[MAX_CORES * 3];
 };
 
 LocArgs loc_args(const plfem_locator* L, bool indexed) {
@@ -61,15 +54,6 @@ __device__ __forceinline__ int dev_cell(double v, double v0, double inv_h, int n
   const double f = floor((v - v0) * inv_h);
   if (!(f >= 0.0)) return 0;
   return f >= (double)(n - 1) ? n - 1 : (int)f;
-}
-
-// IEEE product kept out of fused multiply-adds (hipcc's default -ffp-contract=fast ignores the contract pragma): the
-// barycentric numerators below must round exactly as the host's (NumPy's) arithmetic does, so that a point on a vertex
-// gets coordinates of exactly 0 / 1 and the emulation in tests/ reproduces every containment decision.
-__device__ __forceinline__ double mul_rn(double a, double b) {
-  double r;
-  asm volatile("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
 }
 
 // Smallest element id among the point's cell candidates that contain it (the lists are ascending, so that is the first
@@ -87,10 +71,9 @@ __device__ int dev_locate(const LocArgs& L, double x, double y, double& xi, doub
   const double* py = L.pxy + L.nv;
   for (int q = L.cell_ptr[cell]; q < q1; ++q) {
     const int e = L.cell_elems[q];
-    const int v0 = L.edof[e], v1 = L.edof[L.ne + e], v2 = L.edof[2 * L.ne + e];
-    const double ax = px[v0], ay = py[v0];
-    const double j00 = px[v1] - ax, j10 = py[v1] - ay, j01 = px[v2] - ax, j11 = py[v2] - ay;
-    const double det = mul_rn(j00, j11) - mul_rn(j01, j10);
+    const P2Map M(L.edof, L.ne, px, py, e);
+    const double ax = M.x0, ay = M.y0, j00 = M.j00, j10 = M.j10, j01 = M.j01, j11 = M.j11;
+    const double det = M.det();
     const double dx = x - ax, dy = y - ay;
     double a = (mul_rn(j11, dx) - mul_rn(j01, dy)) / det, b = (mul_rn(j00, dy) - mul_rn(j10, dx)) / det;
     const double mx = fabs(x) + fabs(ax), my = fabs(y) + fabs(ay);
@@ -109,21 +92,11 @@ __device__ int dev_locate(const LocArgs& L, double x, double y, double& xi, doub
       }
       xi = a;
       eta = b;
-      const double idet = 1.0 / det;
-      inv[0] = j11 * idet; inv[1] = -j01 * idet; inv[2] = -j10 * idet; inv[3] = j00 * idet;
+      M.inverse(det, inv);
       return e;
     }
   }
   return -1;
-}
-
-__device__ __forceinline__ void p2_phi(double x, double y, double phi[6]) {
-  phi[0] = 1 - 3 * x - 3 * y + 2 * x * x + 4 * x * y + 2 * y * y;
-  phi[1] = 2 * x * x - x;
-  phi[2] = 2 * y * y - y;
-  phi[3] = 4 * x - 4 * x * x - 4 * x * y;
-  phi[4] = 4 * x * y;
-  phi[5] = 4 * y - 4 * x * y - 4 * y * y;
 }
 
 // staged row of DOF d of element e, -1 = contributes nothing (boundary DOF of an interior-indexed record)
@@ -151,15 +124,7 @@ __global__ __launch_bounds__(256) void k_sample_fields(LocArgs L, int ncomp, int
   }
   double phi[6], gx[6], gy[6];
   p2_phi(xi, eta, phi);
-  {
-    const double dxh[6] = {-3 + 4 * xi + 4 * eta, 4 * xi - 1, 0.0, 4 - 8 * xi - 4 * eta, 4 * eta, -4 * eta};
-    const double dyh[6] = {-3 + 4 * xi + 4 * eta, 0.0, 4 * eta - 1, -4 * xi, 4 * xi, 4 - 4 * xi - 8 * eta};
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {            // grad = J^-T grad_hat
-      gx[a] = inv[0] * dxh[a] + inv[2] * dyh[a];
-      gy[a] = inv[1] * dxh[a] + inv[3] * dyh[a];
-    }
-  }
+  p2_grad(inv, xi, eta, gx, gy);
   int64_t row[6];
 #pragma unroll
   for (int a = 0; a < 6; ++a) {
@@ -244,25 +209,11 @@ __global__ __launch_bounds__(256) void k_field_overlap(LocArgs A, LocArgs B, int
       if (g < nq) {
         const int e = (int)(g / 6);
         q = (int)(g % 6);
-        const int v0 = B.edof[e], v1 = B.edof[B.ne + e], v2 = B.edof[2 * B.ne + e];
-        const double x0 = pbx[v0], y0 = pby[v0];
-        const double j00 = pbx[v1] - x0, j10 = pby[v1] - y0, j01 = pbx[v2] - x0, j11 = pby[v2] - y0;
-        // det J and the quadrature point exactly as k_element_matrices forms them (the same core test decisions)
-        double t1, t2;
-        asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t1) : "v"(j00), "v"(j11));
-        asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t2) : "v"(j01), "v"(j10));
-        const double det = t1 - t2;
-        const double xi = c_fqx[q], eta = c_fqy[q];
-        const double X = x0 + j00 * xi + j01 * eta, Y = y0 + j10 * xi + j11 * eta;
-        w = fabs(det) * c_fqw[q];
-        if (ncore >= 0) {
-          bool in_core = false;
-          for (int c = 0; c < ncore; ++c) {
-            const double dx = X - cores.c[3 * c], dy = Y - cores.c[3 * c + 1], r = cores.c[3 * c + 2];
-            in_core |= (dx * dx + dy * dy <= r * r);
-          }
-          w *= in_core ? inv_eps_core : inv_eps_clad;
-        }
+        const P2Map M(B.edof, B.ne, pbx, pby, e);
+        double X, Y;
+        M.point(c_qx[q], c_qy[q], X, Y);
+        w = fabs(M.det()) * c_qw[q];
+        if (ncore >= 0) w *= in_any_core(X, Y, cores.c, ncore) ? inv_eps_core : inv_eps_clad;
         double axi, aeta, inv[4];
         const int ea = dev_locate(A, X, Y, axi, aeta, inv);
         if (ea >= 0) {
@@ -295,16 +246,7 @@ __global__ __launch_bounds__(256) void k_field_overlap(LocArgs A, LocArgs B, int
           const int ra = s_ra[a][t], rb = s_rb[a][t];
           if (ia0 + i < ka && ra >= 0) ua += s_phi[a][t] * va[(int64_t)ra * ka + ia0 + i];
           if (jb0 + i < kb && rb >= 0) {
-            double ph;                        // B's basis at its own quadrature point q
-            const double x = c_fqx[q], y = c_fqy[q];
-            switch (a) {
-              case 0: ph = 1 - 3 * x - 3 * y + 2 * x * x + 4 * x * y + 2 * y * y; break;
-              case 1: ph = 2 * x * x - x; break;
-              case 2: ph = 2 * y * y - y; break;
-              case 3: ph = 4 * x - 4 * x * x - 4 * x * y; break;
-              case 4: ph = 4 * x * y; break;
-              default: ph = 4 * y - 4 * x * y - 4 * y * y; break;
-            }
+            const double ph = p2_phi(a, c_qx[q], c_qy[q]);   // B's basis at its own quadrature point q
             ub += ph * vb[(int64_t)rb * kb + jb0 + i];
           }
         }
@@ -349,8 +291,8 @@ __global__ __launch_bounds__(256) void k_overlap_reduce(int ka, int kb, int nblk
 
 // Same-mesh Grams of k modes under the element forms of the assembly, split by material region (plfem_mode_grams).  One
 // workgroup walks tiles of GT quadrature points of the mesh's own six-point rule (element-major) for one (32-mode chunk,
-// 32-mode chunk) pair.  Per tile: GT lanes form det J, J^-1, the quadrature point and its closed-disc core test exactly as
-// k_element_matrices does, and stage the physical basis gradients, the weight and the rows; all lanes then evaluate the
+// 32-mode chunk) pair.  Per tile: GT lanes form det J, J^-1, the quadrature point and its core test (p2_element.h, as the
+// assembly does), and stage the physical basis gradients, the weight and the rows; all lanes then evaluate the
 // features of every (point, mode) -- ncomp = 2: hx, hy, dx hx, dy hx, dx hy, dy hy; ncomp = 1: u, dx u, dy u -- plain
 // for the row chunk, times |det J| w_q for the column chunk; every lane accumulates a 2 x 2 block of each output over the
 // tile.  The region of a point is the same for all lanes, so its branch costs no divergence and the region split costs
@@ -388,30 +330,17 @@ __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nr
       if (g < nq) {
         const int e = (int)(g / 6);
         q = (int)(g % 6);
-        const int v0 = L.edof[e], v1 = L.edof[L.ne + e], v2 = L.edof[2 * L.ne + e];
-        const double x0 = px[v0], y0 = py[v0];
-        const double j00 = px[v1] - x0, j10 = py[v1] - y0, j01 = px[v2] - x0, j11 = py[v2] - y0;
-        // det J, J^-1, the quadrature point and the core test exactly as k_element_matrices forms them
-        double t1, t2;
-        asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t1) : "v"(j00), "v"(j11));
-        asm volatile("v_mul_f64 %0, %1, %2" : "=v"(t2) : "v"(j01), "v"(j10));
-        const double det = t1 - t2;
-        const double idet = 1.0 / det;
-        const double i00 = j11 * idet, i01 = -j01 * idet, i10 = -j10 * idet, i11 = j00 * idet;
-        const double xi = c_fqx[q], eta = c_fqy[q];
-        const double X = x0 + j00 * xi + j01 * eta, Y = y0 + j10 * xi + j11 * eta;
-        bool in_core = false;
-        for (int c = 0; c < ncore; ++c) {
-          const double dx = X - cores.c[3 * c], dy = Y - cores.c[3 * c + 1], r = cores.c[3 * c + 2];
-          in_core |= (dx * dx + dy * dy <= r * r);
-        }
-        core = in_core ? 1 : 0;
-        w = fabs(det) * c_fqw[q];
-        const double dxh[6] = {-3 + 4 * xi + 4 * eta, 4 * xi - 1, 0.0, 4 - 8 * xi - 4 * eta, 4 * eta, -4 * eta};
-        const double dyh[6] = {-3 + 4 * xi + 4 * eta, 0.0, 4 * eta - 1, -4 * xi, 4 * xi, 4 - 4 * xi - 8 * eta};
+        const P2Map M(L.edof, L.ne, px, py, e);
+        const double xi = c_qx[q], eta = c_qy[q];
+        double det = M.det(), inv[4], X, Y, gx[6], gy[6];
+        M.inverse(det, inv);
+        M.point(xi, eta, X, Y);
+        core = in_any_core(X, Y, cores.c, ncore) ? 1 : 0;
+        w = fabs(det) * c_qw[q];
+        p2_grad(inv, xi, eta, gx, gy);
         for (int a = 0; a < 6; ++a) {
-          s_gx[a][tid] = i00 * dxh[a] + i10 * dyh[a];
-          s_gy[a][tid] = i01 * dxh[a] + i11 * dyh[a];
+          s_gx[a][tid] = gx[a];
+          s_gy[a][tid] = gy[a];
           s_r[a][tid] = dev_row(L, e, a);
         }
       }
@@ -429,7 +358,7 @@ __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nr
       for (int c = 0; c < NF; ++c) f[c] = 0.0;
       if (m < k) {
         double phi[6];
-        p2_phi(c_fqx[s_q[t]], c_fqy[s_q[t]], phi);
+        p2_phi(c_qx[s_q[t]], c_qy[s_q[t]], phi);
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
           const int r = s_r[a][t];
@@ -625,6 +554,32 @@ extern "C" int plfem_sample_fields(plfem_locator* L, int32_t ncomp, int32_t k, c
 
 namespace {
 int overlap_chunks(int k) { return (k + OC - 1) / OC; }
+
+// the cores as the kernels' by-value table, zero past ncore
+CoreTable pack_cores(const double* cores_host, int ncore) {
+  CoreTable ct;
+  std::memset(&ct, 0, sizeof(ct));
+  if (ncore > 0) std::memcpy(ct.c, cores_host, sizeof(double) * 3 * ncore);
+  return ct;
+}
+
+// the caller's work buffer: at least `need` bytes (what `sizer` returns), 256-byte aligned
+int check_work(plfem_locator* L, const char* fn, const char* sizer, const void* work_dev, int64_t work_bytes, int64_t need) {
+  if (work_bytes < need) return set_loc_err(L, std::string(fn) + ": work buffer smaller than " + sizer, PLFEM_EINVAL);
+  if ((uintptr_t)work_dev & 255) return set_loc_err(L, std::string(fn) + ": work buffer must be 256-byte aligned", PLFEM_EINVAL);
+  return PLFEM_OK;
+}
+
+// k_overlap_reduce over `grid` (chunk pairs, output matrices, entry slices), then O [grid.y][ka][kb] to the host
+int reduce_to_host(plfem_locator* L, dim3 grid, int ka, int kb, int nblk, int nchunk_b, const double* partial, double* O,
+                   double* out_host) {
+  hipLaunchKernelGGL(k_overlap_reduce, grid, dim3(256), 0, L->stream, ka, kb, nblk, nchunk_b, partial, O);
+  int rc = check_hip(L, hipGetLastError(), "k_overlap_reduce");
+  if (rc) return rc;
+  rc = check_hip(L, hipMemcpyAsync(out_host, O, sizeof(double) * grid.y * ka * kb, hipMemcpyDeviceToHost, L->stream), "hipMemcpyAsync");
+  if (rc) return rc;
+  return check_hip(L, hipStreamSynchronize(L->stream), "hipStreamSynchronize");
+}
 }  // namespace
 
 extern "C" int plfem_overlap_work_bytes(int32_t ka, int32_t kb, int64_t* bytes) {
@@ -643,18 +598,15 @@ extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev,
   if (ncomp < 1 || ncomp > 2 || ka < 0 || kb < 0) return set_loc_err(La, "plfem_field_overlap: bad ncomp / ka / kb", PLFEM_EINVAL);
   if (ka == 0 || kb == 0) return PLFEM_OK;
   if (!modes_a_dev || !modes_b_dev || !work_dev || !out_host) return set_loc_err(La, "plfem_field_overlap: null array", PLFEM_EINVAL);
-  if (ncore > 64 || (ncore > 0 && !cores_host)) return set_loc_err(La, "plfem_field_overlap: at most 64 cores", PLFEM_EINVAL);
+  if (ncore > MAX_CORES || (ncore > 0 && !cores_host)) return set_loc_err(La, "plfem_field_overlap: at most 64 cores", PLFEM_EINVAL);
   if ((indexed_a && La->nsolve == 0) || (indexed_b && Lb->nsolve == 0))
     return set_loc_err(La, "plfem_field_overlap: the analysis has no interior DOFs", PLFEM_EINVAL);
   int64_t need = 0;
   plfem_overlap_work_bytes(ka, kb, &need);
-  if (work_bytes < need) return set_loc_err(La, "plfem_field_overlap: work buffer smaller than plfem_overlap_work_bytes", PLFEM_EINVAL);
-  if ((uintptr_t)work_dev & 255) return set_loc_err(La, "plfem_field_overlap: work buffer must be 256-byte aligned", PLFEM_EINVAL);
-  int rc = check_hip(La, hipSetDevice(La->device), "hipSetDevice");
+  int rc = check_work(La, "plfem_field_overlap", "plfem_overlap_work_bytes", work_dev, work_bytes, need);
   if (rc) return rc;
-  CoreTable ct;
-  std::memset(&ct, 0, sizeof(ct));
-  if (ncore > 0) std::memcpy(ct.c, cores_host, sizeof(double) * 3 * ncore);
+  rc = check_hip(La, hipSetDevice(La->device), "hipSetDevice");
+  if (rc) return rc;
   const int nca = overlap_chunks(ka), ncb = overlap_chunks(kb);
   const int64_t ntiles = ((int64_t)6 * Lb->ne + OT - 1) / OT;
   const int nblk = (int)std::min<int64_t>(OVL_BLOCKS, ntiles);
@@ -662,16 +614,11 @@ extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev,
   double* partial = (double*)((char*)work_dev + align256((size_t)ka * kb * sizeof(double)));
   hipLaunchKernelGGL(k_field_overlap, dim3(nblk, nca * ncb), dim3(256), 0, La->stream, loc_args(La, indexed_a != 0),
                      loc_args(Lb, indexed_b != 0), (int)ncomp, (int)ka, (int64_t)(indexed_a ? La->nsolve : La->N), modes_a_dev,
-                     (int)kb, (int64_t)(indexed_b ? Lb->nsolve : Lb->N), modes_b_dev, ct, ncore < 0 ? -1 : (int)ncore,
-                     1.0 / eps_core, 1.0 / eps_clad, ncb, partial);
+                     (int)kb, (int64_t)(indexed_b ? Lb->nsolve : Lb->N), modes_b_dev, pack_cores(cores_host, ncore),
+                     ncore < 0 ? -1 : (int)ncore, 1.0 / eps_core, 1.0 / eps_clad, ncb, partial);
   rc = check_hip(La, hipGetLastError(), "k_field_overlap");
   if (rc) return rc;
-  hipLaunchKernelGGL(k_overlap_reduce, dim3(nca * ncb), dim3(256), 0, La->stream, (int)ka, (int)kb, nblk, ncb, partial, O);
-  rc = check_hip(La, hipGetLastError(), "k_overlap_reduce");
-  if (rc) return rc;
-  rc = check_hip(La, hipMemcpyAsync(out_host, O, sizeof(double) * ka * kb, hipMemcpyDeviceToHost, La->stream), "hipMemcpyAsync");
-  if (rc) return rc;
-  return check_hip(La, hipStreamSynchronize(La->stream), "hipStreamSynchronize");
+  return reduce_to_host(La, dim3(nca * ncb), (int)ka, (int)kb, nblk, ncb, partial, O, out_host);
 }
 
 namespace {
@@ -690,19 +637,17 @@ extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
                                 const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host) {
   if (!L) return PLFEM_EINVAL;
   if (ncomp < 1 || ncomp > 2 || k <= 0) return set_loc_err(L, "plfem_mode_grams: ncomp must be 1 or 2 and k > 0", PLFEM_EINVAL);
-  if (ncore < 0 || ncore > 64) return set_loc_err(L, "plfem_mode_grams: ncore must be in [0, 64]", PLFEM_EINVAL);
+  if (ncore < 0 || ncore > MAX_CORES) return set_loc_err(L, "plfem_mode_grams: ncore must be in [0, 64]", PLFEM_EINVAL);
   if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host))
     return set_loc_err(L, "plfem_mode_grams: null array", PLFEM_EINVAL);
   if (indexed && L->nsolve == 0) return set_loc_err(L, "plfem_mode_grams: the analysis has no interior DOFs", PLFEM_EINVAL);
   int64_t need = 0;
   plfem_gram_work_bytes(ncomp, k, &need);
-  if (work_bytes < need) return set_loc_err(L, "plfem_mode_grams: work buffer smaller than plfem_gram_work_bytes", PLFEM_EINVAL);
-  if ((uintptr_t)work_dev & 255) return set_loc_err(L, "plfem_mode_grams: work buffer must be 256-byte aligned", PLFEM_EINVAL);
-  int rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
+  int rc = check_work(L, "plfem_mode_grams", "plfem_gram_work_bytes", work_dev, work_bytes, need);
   if (rc) return rc;
-  CoreTable ct;
-  std::memset(&ct, 0, sizeof(ct));
-  if (ncore > 0) std::memcpy(ct.c, cores_host, sizeof(double) * 3 * ncore);
+  rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
+  if (rc) return rc;
+  const CoreTable ct = pack_cores(cores_host, ncore);
   const int nout = gram_outputs(ncomp), nc = overlap_chunks(k);
   const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
   const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ntiles));
@@ -718,11 +663,5 @@ extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
                        ct, (int)ncore, nc, partial);
   rc = check_hip(L, hipGetLastError(), "k_mode_grams");
   if (rc) return rc;
-  hipLaunchKernelGGL(k_overlap_reduce, dim3(nc * nc, nout, OC * OC / 256), dim3(256), 0, L->stream, (int)k, (int)k, nblk, nc,
-                     partial, O);
-  rc = check_hip(L, hipGetLastError(), "k_overlap_reduce");
-  if (rc) return rc;
-  rc = check_hip(L, hipMemcpyAsync(out_host, O, sizeof(double) * nout * k * k, hipMemcpyDeviceToHost, L->stream), "hipMemcpyAsync");
-  if (rc) return rc;
-  return check_hip(L, hipStreamSynchronize(L->stream), "hipStreamSynchronize");
+  return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
 }

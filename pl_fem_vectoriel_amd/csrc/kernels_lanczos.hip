@@ -10,6 +10,7 @@
 #include <functional>
 
 #include "device.h"
+#include "p2_element.h"
 
 namespace plfem {
 namespace {
@@ -466,17 +467,14 @@ __global__ __launch_bounds__(256) void k_core_mask(int N, const double* __restri
                                                    const uint8_t* __restrict__ bmask, uint8_t* __restrict__ mask,
                                                    int32_t* __restrict__ counters) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  bool in = false;
+  bool counted = false;
   if (i < N) {
-    double X = doflocs[i], Y = doflocs[N + i];
-    for (int c = 0; c < ncore; ++c) {
-      double dx = X - cores[3 * c], dy = Y - cores[3 * c + 1], r = cores[3 * c + 2];
-      in |= (dx * dx + dy * dy <= r * r);
-    }
+    const bool in = in_any_core(doflocs[i], doflocs[N + i], cores, ncore);
     mask[i] = in ? 1 : 0;
+    counted = in && !bmask[i];
   }
   // integer count of interior DOF nodes inside a core (order independent => deterministic)
-  unsigned long long b = __ballot(i < N && in && !bmask[i]);
+  unsigned long long b = __ballot(counted);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(&counters[1], (int)__popcll(b));
 }
 

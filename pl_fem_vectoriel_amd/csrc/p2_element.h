@@ -1,0 +1,100 @@
+// The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
+// integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
+// k_field_overlap, k_mode_grams).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// the same way, in the assembly and in every kernel that must reproduce it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace plfem {
+
+constexpr int MAX_CORES = 64;   // capacity of the core tables (d_cores, CoreTable): 3 doubles (x, y, r) per core
+
+namespace {
+
+// 6-point degree-4 rule on the reference triangle (weights sum to 1/2) — scikit-fem's default
+// intorder = 2*maxdeg = 4 for ElementTriP2.
+__constant__ double c_qx[6] = {0.445948490915965, 0.10810301816807, 0.445948490915965,
+                               0.091576213509771, 0.816847572980458, 0.091576213509771};
+__constant__ double c_qy[6] = {0.445948490915965, 0.445948490915965, 0.10810301816807,
+                               0.091576213509771, 0.091576213509771, 0.816847572980458};
+__constant__ double c_qw[6] = {0.1116907948390055, 0.1116907948390055, 0.1116907948390055,
+                               0.054975871827661, 0.054975871827661, 0.054975871827661};
+
+// IEEE product kept out of fused multiply-adds: hipcc's default -ffp-contract=fast ignores the contract pragma.  det J
+// of a sliver element cancels to ~1e-8 of its terms, so its two products must round individually (as the reference's
+// NumPy arithmetic does; a fused multiply-add changes 1e9-sized element entries at the 1e-8 relative level), and the
+// locator's barycentric numerators must round as the host's do, so that a point on a vertex gets coordinates of exactly
+// 0 / 1 and the emulation in tests/ reproduces every containment decision.
+__device__ __forceinline__ double mul_rn(double a, double b) {
+  double r;
+  asm volatile("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// P2 basis function i at (x, y) of the reference triangle: vertices 0-2, then the midpoints of edges 01, 12, 20
+__device__ __forceinline__ double p2_phi(int i, double x, double y) {
+  switch (i) {
+    case 0: return 1 - 3 * x - 3 * y + 2 * x * x + 4 * x * y + 2 * y * y;
+    case 1: return 2 * x * x - x;
+    case 2: return 2 * y * y - y;
+    case 3: return 4 * x - 4 * x * x - 4 * x * y;
+    case 4: return 4 * x * y;
+    default: return 4 * y - 4 * x * y - 4 * y * y;
+  }
+}
+
+__device__ __forceinline__ void p2_phi(double x, double y, double phi[6]) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) phi[i] = p2_phi(i, x, y);
+}
+
+// physical gradients of the six basis functions at (xi, eta): J^-T grad_hat, inv = J^-1 row-major
+__device__ __forceinline__ void p2_grad(const double inv[4], double xi, double eta, double gx[6], double gy[6]) {
+  const double dxh[6] = {-3 + 4 * xi + 4 * eta, 4 * xi - 1, 0.0, 4 - 8 * xi - 4 * eta, 4 * eta, -4 * eta};
+  const double dyh[6] = {-3 + 4 * xi + 4 * eta, 0.0, 4 * eta - 1, -4 * xi, 4 * xi, 4 - 4 * xi - 8 * eta};
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    gx[i] = inv[0] * dxh[i] + inv[2] * dyh[i];
+    gy[i] = inv[1] * dxh[i] + inv[3] * dyh[i];
+  }
+}
+
+// Affine map of element e: vertices = rows 0-2 of vrow ([3+][ne], sorted), coordinates x[v], y[v].  The type of ne is
+// that of the row offsets (size_t or int).  det J is a call of its own: its opaque products are not dropped where unused.
+struct P2Map {
+  double x0, y0, j00, j01, j10, j11;   // J = [p1 - p0, p2 - p0]
+
+  template <typename Int>
+  __device__ __forceinline__ P2Map(const int32_t* vrow, Int ne, const double* x, const double* y, int e) {
+    const int v0 = vrow[e], v1 = vrow[ne + e], v2 = vrow[2 * ne + e];
+    x0 = x[v0];
+    y0 = y[v0];
+    j00 = x[v1] - x0;
+    j10 = y[v1] - y0;
+    j01 = x[v2] - x0;
+    j11 = y[v2] - y0;
+  }
+  __device__ __forceinline__ double det() const { return mul_rn(j00, j11) - mul_rn(j01, j10); }
+  // J^-1 = 1/det [[j11, -j01], [-j10, j00]]
+  __device__ __forceinline__ void inverse(double det, double inv[4]) const {
+    const double idet = 1.0 / det;
+    inv[0] = j11 * idet; inv[1] = -j01 * idet; inv[2] = -j10 * idet; inv[3] = j00 * idet;
+  }
+  __device__ __forceinline__ void point(double xi, double eta, double& X, double& Y) const {
+    X = x0 + j00 * xi + j01 * eta;
+    Y = y0 + j10 * xi + j11 * eta;
+  }
+};
+
+// the core test: union of closed discs, cores[3 c .. 3 c + 2] = (x, y, r)
+__device__ __forceinline__ bool in_any_core(double X, double Y, const double* cores, int ncore) {
+  bool in = false;
+  for (int c = 0; c < ncore; ++c) {
+    const double dx = X - cores[3 * c], dy = Y - cores[3 * c + 1], r = cores[3 * c + 2];
+    in |= (dx * dx + dy * dy <= r * r);
+  }
+  return in;
+}
+
+}  // namespace
+}  // namespace plfem
