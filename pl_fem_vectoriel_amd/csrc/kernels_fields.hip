@@ -390,10 +390,12 @@ __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nr
         a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
         b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
       }
-      // acc[o] += s x a[p] (x) b[q]
-#define GRAM_ACC(o, p, q, s)                                          \
-      acc[o][0][0] += (s) * a[p].x * b[q].x; acc[o][0][1] += (s) * a[p].x * b[q].y; \
-      acc[o][1][0] += (s) * a[p].y * b[q].x; acc[o][1][1] += (s) * a[p].y * b[q].y;
+      // acc[o] += s x a[p] (x) b[q], s = +-1.  Explicit fused multiply-adds: left to contraction, a product that both
+      // region branches share is hoisted above the branch, and the compiler then fuses it into some of the four
+      // accumulators of the 2 x 2 block and not others, so that an entry's rounding would depend on its place in the block
+#define GRAM_ACC(o, p, q, s)                                                                        \
+      acc[o][0][0] = fma((s) * a[p].x, b[q].x, acc[o][0][0]); acc[o][0][1] = fma((s) * a[p].x, b[q].y, acc[o][0][1]); \
+      acc[o][1][0] = fma((s) * a[p].y, b[q].x, acc[o][1][0]); acc[o][1][1] = fma((s) * a[p].y, b[q].y, acc[o][1][1]);
       const int r = s_core[t] ? 0 : 1;          // the same for every lane
       if (NCOMP == 2) {
         // M_r: hx hx + hy hy;  K_r: dy hx dy hx + dx hy dx hy - dx hx dy hy - dy hy dx hx;

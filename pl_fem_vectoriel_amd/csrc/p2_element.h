@@ -80,18 +80,22 @@ struct P2Map {
     const double idet = 1.0 / det;
     inv[0] = j11 * idet; inv[1] = -j01 * idet; inv[2] = -j10 * idet; inv[3] = j00 * idet;
   }
+  // the quadrature point in the reference's order, p0 + (J[r, 0] xi + J[r, 1] eta), every operation rounded on its own
+  // (oracle P2Basis.qx): a point within an ulp of a core circle must land where the reference puts it
   __device__ __forceinline__ void point(double xi, double eta, double& X, double& Y) const {
-    X = x0 + j00 * xi + j01 * eta;
-    Y = y0 + j10 * xi + j11 * eta;
+    X = x0 + (mul_rn(j00, xi) + mul_rn(j01, eta));
+    Y = y0 + (mul_rn(j10, xi) + mul_rn(j11, eta));
   }
 };
 
-// the core test: union of closed discs, cores[3 c .. 3 c + 2] = (x, y, r)
+// the core test: union of closed discs, cores[3 c .. 3 c + 2] = (x, y, r).  The reference's
+// (x - cx)**2 + (y - cy)**2 <= r**2 (MCFGeometry.epsilon) with each square rounded on its own: a fused multiply-add
+// would decide a point on the circle differently ("Core-boundary ties")
 __device__ __forceinline__ bool in_any_core(double X, double Y, const double* cores, int ncore) {
   bool in = false;
   for (int c = 0; c < ncore; ++c) {
     const double dx = X - cores[3 * c], dy = Y - cores[3 * c + 1], r = cores[3 * c + 2];
-    in |= (dx * dx + dy * dy <= r * r);
+    in |= (mul_rn(dx, dx) + mul_rn(dy, dy) <= mul_rn(r, r));
   }
   return in;
 }

@@ -136,9 +136,10 @@ class Emulation:
         return np.stack(out)
 
 
-def overlap(em_a, vals_a, em_b, vals_b, indexed, weight=None):
-    """O[i, j] over mesh B's quadrature, A located brute force (the emulation of k_field_overlap)."""
+def overlap(em_a, vals_a, em_b, vals_b, indexed, weight=None, located=None):
+    """O[i, j] over mesh B's quadrature, A located brute force (the emulation of k_field_overlap); ``located``: the
+    result of em_a.locate on B's quadrature points, when the caller reuses it."""
     qx, w = em_b.quadrature(weight)
-    ua, _ = em_a.sample(vals_a, qx, indexed)
+    ua, _ = em_a.sample(vals_a, qx, indexed, located=located)
     ub = em_b.own_values(vals_b, indexed)
     return sum(ua[c] @ (ub[c] * w[None]).T for c in range(vals_a.shape[0]))
