@@ -446,9 +446,9 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
   TRY(check_launch(c, "pattern fill"));
   {
     const size_t nc1p = (size_t)max_ncv + 2 + plfem::BLOCK_P;
-    // [0, 8192): scalars / counters / core table; then the projected matrix (nc1p^2); then two block-step slots
-    HIP_TRY(c, pinned_acquire(sizeof(double) * (8192 + nc1p * nc1p + 2 * nc1p * plfem::BLOCK_P), &c->h_pinned, &c->h_pinned_bytes));
-    c->h_slots = c->h_pinned + 8192 + nc1p * nc1p;
+    // the regions of device.h (plfem::PIN_*): the projected matrix (nc1p^2) last, then the two block-step slots
+    HIP_TRY(c, pinned_acquire(sizeof(double) * (plfem::PIN_PROJ + nc1p * nc1p + 2 * nc1p * plfem::BLOCK_P), &c->h_pinned, &c->h_pinned_bytes));
+    c->h_slots = c->h_pinned + plfem::PIN_PROJ + nc1p * nc1p;
   }
   HIP_TRY(c, hipEventRecord(c->ev[4][1], c->stream));
   const double tt4 = now_ms();
@@ -474,8 +474,8 @@ int upload_cores(plfem_ctx* c, const double* cores_host, int ncore) {
     return PLFEM_EINVAL;
   }
   if (ncore > 0) {
-    std::memcpy(c->h_pinned + 6144, cores_host, sizeof(double) * 3 * ncore);
-    HIP_TRY(c, hipMemcpyAsync(c->d_cores, c->h_pinned + 6144, sizeof(double) * 3 * ncore, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(c->h_pinned + plfem::PIN_CORES, cores_host, sizeof(double) * 3 * ncore);
+    HIP_TRY(c, hipMemcpyAsync(c->d_cores, c->h_pinned + plfem::PIN_CORES, sizeof(double) * 3 * ncore, hipMemcpyHostToDevice, c->stream));
   }
   return PLFEM_OK;
 }
@@ -600,7 +600,7 @@ extern "C" int plfem_cmt_coupling(plfem_ctx* c, int32_t n, const double* fields_
     plfem::launch_dot(c, fields_j_dev + (size_t)i * N, fields_j_dev + (size_t)i * N, Hd + (size_t)(n + 1) * ld + i);
   }
   TRY(check_launch(c, "cmt coupling"));
-  double* hs = c->h_pinned + 8192;
+  double* hs = c->h_pinned + plfem::PIN_PROJ;
   HIP_TRY(c, hipMemcpyAsync(hs, Hd, sizeof(double) * (size_t)(n + 2) * ld, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (int j = 0; j < n; ++j)
@@ -694,9 +694,128 @@ static void solve_block_refined(plfem_ctx* c, const double* b, double* y, bool b
 }
 
 // ------------------------------------------------------------------------------------------------
+// thick-restart Lanczos, shift-invert, B inner product, shared by the block driver (P = BLOCK_P) and the single-vector
+// one (P = 1).  A driver builds the basis (m columns, then the residual block) and fills the columns of T (upper triangle
+// authoritative, ld = m + P; R_m = T[mm:mm+P, mm-P:mm] upper triangular, beta_m for P = 1); this is the rest.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct ThickRestart {
+  plfem_ctx* c;
+  int P, k, ld;
+  double tol;
+  double* hH;                     // pinned staging of the rotation matrices (and the single-vector driver's d_Hcols mirror)
+  std::vector<double> T, Tm, theta, Svec;
+  std::vector<int> order;         // Ritz pairs by decreasing |theta|
+  int nconv = 0, restarts = 0;
+  double max_rel_res = 0.0;
+
+  ThickRestart(plfem_ctx* c_, int P_, int k_, int m, double tol_)
+      : c(c_), P(P_), k(k_), ld(m + P_), tol(tol_), hH(c_->h_pinned + plfem::PIN_PROJ), T((size_t)ld * ld, 0.0) {}
+
+  void fill_tm(int mm) {
+    Tm.assign((size_t)mm * mm, 0.0);     // symmetric mm x mm projected matrix from the upper triangle
+    for (int j = 0; j < mm; ++j)
+      for (int i = 0; i <= j; ++i) {
+        const double v = T[(size_t)j * ld + i];
+        Tm[(size_t)j * mm + i] = v;
+        Tm[(size_t)i * mm + j] = v;
+      }
+  }
+  // order the Ritz pairs (theta) and count the converged wanted ones.  Residual of pair `id`: || R_m s[mm-P:mm] ||;
+  // last(id, b) = component mm - P + b of its eigenvector
+  template <class Last>
+  void count_converged(int mm, Last last) {
+    order.resize(mm);
+    std::iota(order.begin(), order.end(), 0);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return std::fabs(theta[a]) > std::fabs(theta[b]); });
+    nconv = 0;
+    max_rel_res = 0.0;
+    for (int q = 0; q < std::min(k, mm); ++q) {
+      const int id = order[q];
+      double res;
+      if (P == 1) {
+        res = std::fabs(T[(size_t)(mm - 1) * ld + mm] * last(id, 0));
+      } else {
+        double r2 = 0.0;
+        for (int a = 0; a < P; ++a) {
+          double v = 0.0;
+          for (int b = a; b < P; ++b) v += T[(size_t)(mm - P + b) * ld + (mm + a)] * last(id, b);
+          r2 += v * v;
+        }
+        res = std::sqrt(r2);
+      }
+      const double rel = res / std::max(std::fabs(theta[id]), 3.7e-11);
+      max_rel_res = std::max(max_rel_res, rel);
+      if (rel <= tol) ++nconv;
+    }
+  }
+  void count_from_svec(int mm) { count_converged(mm, [&](int id, int b) { return Svec[(size_t)id * mm + (mm - P + b)]; }); }
+  // dense Ritz decomposition of the first mm columns
+  void ritz(int mm) {
+    fill_tm(mm);
+    plfem::sym_eig(mm, Tm, Svec, theta);
+    count_from_svec(mm);
+  }
+
+  // thick restart of mm columns: keep the k wanted pairs plus some of the next ones (ARPACK: kev + min(nconv, np/2)),
+  // followed by the residual block; pk = the columns kept
+  int restart(int mm, int& pk) {
+    const int64_t n = c->n2;
+    hipStream_t st = c->stream;
+    pk = k + std::min(nconv, (mm - k) / 2);
+    pk = std::max(pk, k + (mm - k) / 4);
+    pk = std::min(pk, mm - 2 * P);
+    for (int q = 0; q < pk; ++q) std::memcpy(hH + (size_t)q * mm, &Svec[(size_t)order[q] * mm], sizeof(double) * mm);
+    HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * mm * pk, hipMemcpyHostToDevice, st));
+    plfem::launch_rotate(c, c->d_V, mm, c->d_S, mm, pk, c->d_V2);
+    plfem::launch_rotate(c, c->d_BV, mm, c->d_S, mm, pk, c->d_BV2);
+    TRY(check_launch(c, "restart rotation"));
+    HIP_TRY(c, hipMemcpyAsync(c->d_V2 + (size_t)pk * n, c->d_V + (size_t)mm * n, sizeof(double) * n * P, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_BV2 + (size_t)pk * n, c->d_BV + (size_t)mm * n, sizeof(double) * n * P, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));   // (hH is reused by the next cycle)
+    std::swap(c->d_V, c->d_V2);
+    std::swap(c->d_BV, c->d_BV2);
+    std::fill(T.begin(), T.end(), 0.0);
+    for (int q = 0; q < pk; ++q) T[(size_t)q * ld + q] = theta[order[q]];
+    HIP_TRY(c, hipMemsetAsync(c->d_Hcols, 0, sizeof(double) * ld * ld, st));
+    ++restarts;
+    return PLFEM_OK;
+  }
+
+  // the wanted Ritz pairs of mm columns, ascending lambda = sigma + 1/theta: values to evals_host, vectors rotated into
+  // evecs_dev (nullptr: the context's own buffer, see lanczos_run); then the stats and the verdict
+  int finish(int mm, double sigma, double* evals_host, double* evecs_dev, double* stats_host, int nop, int nblock) {
+    hipStream_t st = c->stream;
+    std::vector<int> want(order.begin(), order.begin() + k);
+    std::vector<double> lam(mm);
+    for (int i = 0; i < mm; ++i) lam[i] = sigma + 1.0 / theta[i];
+    std::sort(want.begin(), want.end(), [&](int a, int b) { return lam[a] < lam[b]; });
+    for (int q = 0; q < k; ++q) {
+      evals_host[q] = lam[want[q]];
+      std::memcpy(hH + (size_t)q * mm, &Svec[(size_t)want[q] * mm], sizeof(double) * mm);
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * mm * k, hipMemcpyHostToDevice, st));
+    if (!evecs_dev) evecs_dev = c->d_V2;            // (idle since the last restart, if any)
+    c->modes_dev = evecs_dev;
+    c->modes_k = k;
+    plfem::launch_rotate(c, c->d_V, mm, c->d_S, mm, k, evecs_dev);
+    HIP_TRY(c, hipEventRecord(c->ev[2][1], st));
+    c->ev_used[2] = true;
+    TRY(check_launch(c, "ritz rotation"));
+    if (!c->defer_sync) HIP_TRY(c, hipStreamSynchronize(st));   // (plfem_solve_modes: its one synchronisation comes later)
+    if (stats_host) {
+      const double s[5] = {(double)nconv, (double)nop, (double)restarts, max_rel_res, (double)nblock};
+      std::copy(s, s + 5, stats_host);
+    }
+    if (nconv < k) { c->err = "Lanczos: no convergence within maxiter restarts"; return PLFEM_ENOCONV; }
+    return PLFEM_OK;
+  }
+};
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
 // block thick-restart Lanczos (BLOCK_P vectors per step): every pass over the factors of the
-// shift-invert operator serves BLOCK_P right-hand sides.  Same projected-matrix / restart logic as
-// the single-vector driver below; the block residual R_m (P x P) couples the last block.
+// shift-invert operator serves BLOCK_P right-hand sides.
 // ------------------------------------------------------------------------------------------------
 static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, double sigma, double* evals_host,
                          double* evecs_dev, double* stats_host) {
@@ -706,10 +825,9 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
   HIP_TRY(c, hipEventRecord(c->ev[2][0], st));
   int m = ((ncv + P - 1) / P) * P;                                 // basis columns before the residual block
   if (m > c->max_ncv) m = (c->max_ncv / P) * P;
-  const int ld = m + P;                                            // leading dimension of the projected matrix
-  std::vector<double> T((size_t)ld * ld, 0.0);
-  double* hH = c->h_pinned + 8192;
-  int nop = 0, nblock = 0, restarts = 0;
+  ThickRestart R(c, P, k, m, tol);
+  const int ld = R.ld;
+  int nop = 0, nblock = 0;
   {
     plfem::launch_start_field(c, P, c->d_V2);       // fixed pseudo-random interior block, generated on the device
     plfem::launch_spmv_b_block(c, c->d_V2, c->d_bw, n);
@@ -721,14 +839,10 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
     plfem::launch_block_scale(c, c->d_w, c->d_bw, n, c->d_Rinv, c->d_V, c->d_BV, n, nullptr, 0, nullptr, nullptr, c->d_fvec);
   }
   HIP_TRY(c, hipMemsetAsync(c->d_Hcols, 0, sizeof(double) * ld * ld, st));
-  int c0 = 0, mm = 0, nconv = 0;
-  double max_rel_res = 0.0;
-  bool done = false;
-  std::vector<double> theta, Svec, Tm;
-  std::vector<int> order;
+  int c0 = 0, mm = 0;
   // One block step = one pass over the factors for P vectors + CGS2 + CholQR, all asynchronous.  The
   // P new columns of the projected matrix and the rank flag follow it into a pinned slot, then an event.
-  int32_t* hcnt = reinterpret_cast<int32_t*>(c->h_pinned + 4096);
+  int32_t* hcnt = reinterpret_cast<int32_t*>(c->h_pinned + plfem::PIN_COUNTERS);
   double* slots_dev = nullptr;                   // device view of the pinned slots and counters
   int32_t* hcnt_dev = nullptr;
   HIP_TRY(c, hipHostGetDevicePointer((void**)&slots_dev, c->h_slots, 0));
@@ -780,66 +894,35 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
       for (int i = 0; i < ld; ++i) {
         const double v = src[(size_t)j * ld + i];
         if (!std::isfinite(v)) { c->err = "block Lanczos breakdown: non-finite projected matrix"; return PLFEM_ESINGULAR; }
-        T[(size_t)(c0_ + j) * ld + i] = v;
+        R.T[(size_t)(c0_ + j) * ld + i] = v;
       }
     return PLFEM_OK;
-  };
-  auto fill_tm = [&](int mm_) {
-    Tm.assign((size_t)mm_ * mm_, 0.0);     // symmetric mm x mm projected matrix from the upper triangle
-    for (int j = 0; j < mm_; ++j)
-      for (int i = 0; i <= j; ++i) {
-        const double v = T[(size_t)j * ld + i];
-        Tm[(size_t)j * mm_ + i] = v;
-        Tm[(size_t)i * mm_ + j] = v;
-      }
-  };
-  // residual of Ritz pair `id`: || R_m s[mm-P:mm] ||, R_m = T[mm:mm+P, mm-P:mm] (upper triangular);
-  // last(id, b) = component mm - P + b of its eigenvector
-  auto count_converged = [&](int mm_, auto last) {
-    order.resize(mm_);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return std::fabs(theta[a]) > std::fabs(theta[b]); });
-    nconv = 0;
-    max_rel_res = 0.0;
-    for (int q = 0; q < std::min(k, mm_); ++q) {
-      const int id = order[q];
-      double r2 = 0.0;
-      for (int a = 0; a < P; ++a) {
-        double v = 0.0;
-        for (int b = a; b < P; ++b) v += T[(size_t)(mm_ - P + b) * ld + (mm_ + a)] * last(id, b);
-        r2 += v * v;
-      }
-      const double rel = std::sqrt(r2) / std::max(std::fabs(theta[id]), 3.7e-11);
-      max_rel_res = std::max(max_rel_res, rel);
-      if (rel <= tol) ++nconv;
-    }
   };
   std::vector<double> Ylast;
   // convergence test only: Ritz values + last block of every Ritz vector (no eigenvector matrix)
   auto quick_check = [&](int mm_) {
-    fill_tm(mm_);
-    plfem::sym_eig_last_rows(mm_, P, Tm, Ylast, theta);
-    count_converged(mm_, [&](int id, int b) { return Ylast[(size_t)id * P + b]; });
+    R.fill_tm(mm_);
+    plfem::sym_eig_last_rows(mm_, P, R.Tm, Ylast, R.theta);
+    R.count_converged(mm_, [&](int id, int b) { return Ylast[(size_t)id * P + b]; });
   };
   // Ritz decomposition (theta, Svec, order) for the final rotation, or (need_all) for a restart.  Before the first
   // restart the projected matrix is block tridiagonal (half bandwidth P; what full reorthogonalisation leaves outside
   // the band is rounding) and the final rotation only needs the k wanted vectors: band path of host_eig.h, Svec
   // then holds the rows of order[0 .. k) only.
-  const bool band_path = !(getenv("PLFEM_RITZ_BAND") && atoi(getenv("PLFEM_RITZ_BAND")) == 0);
   auto full_check = [&](int mm_, bool need_all) {
-    fill_tm(mm_);
-    if (band_path && restarts == 0 && !need_all) {
-      plfem::sym_band_eigenvalues(mm_, P, Tm.data(), mm_, theta);
-      std::vector<int> ids(mm_);
-      std::iota(ids.begin(), ids.end(), 0);
-      std::sort(ids.begin(), ids.end(), [&](int a, int b) { return std::fabs(theta[a]) > std::fabs(theta[b]); });
-      ids.resize(std::min(k, mm_));
-      Svec.resize((size_t)mm_ * mm_);
-      plfem::sym_band_eigenvectors(mm_, P, Tm.data(), mm_, theta, ids, Svec.data(), mm_);
-    } else {
-      plfem::sym_eig(mm_, Tm, Svec, theta);
+    if (R.restarts > 0 || need_all) {
+      R.ritz(mm_);
+      return;
     }
-    count_converged(mm_, [&](int id, int b) { return Svec[(size_t)id * mm_ + (mm_ - P + b)]; });
+    R.fill_tm(mm_);
+    plfem::sym_band_eigenvalues(mm_, P, R.Tm.data(), mm_, R.theta);
+    std::vector<int> ids(mm_);
+    std::iota(ids.begin(), ids.end(), 0);
+    std::sort(ids.begin(), ids.end(), [&](int a, int b) { return std::fabs(R.theta[a]) > std::fabs(R.theta[b]); });
+    ids.resize(std::min(k, mm_));
+    R.Svec.resize((size_t)mm_ * mm_);
+    plfem::sym_band_eigenvectors(mm_, P, R.Tm.data(), mm_, R.theta, ids, R.Svec.data(), mm_);
+    R.count_from_svec(mm_);
   };
   // Pipeline: while the GPU runs block step j + 1, the host tests convergence on the projected matrix of
   // step j; the extra step in flight when the test succeeds is simply not used.  The largest residual of the
@@ -869,10 +952,10 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
           // a held step is expected to converge: go straight to the full decomposition the rotation needs
           if (predicted) { full_check(mm, false); have_full = true; } else { quick_check(mm); have_full = false; }
           res_prev = res_last;
-          res_last = max_rel_res;
+          res_last = R.max_rel_res;
           if (getenv("PLFEM_LANCZOS_TRACE"))
-            fprintf(stderr, "[lanczos] cols %d nconv %d max_rel_res %.3e%s\n", mm, nconv, max_rel_res, predicted ? " (held)" : "");
-          if (nconv >= k) { converged = true; inflight = new_c0 >= 0; break; }
+            fprintf(stderr, "[lanczos] cols %d nconv %d max_rel_res %.3e%s\n", mm, R.nconv, R.max_rel_res, predicted ? " (held)" : "");
+          if (R.nconv >= k) { converged = true; inflight = new_c0 >= 0; break; }
         }
         if (predicted) {                            // not converged after all: resume with the step that was held
           pend_c0 = -1;
@@ -886,7 +969,7 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
     }
     if (converged) {
       if (!have_full) full_check(mm, false);
-      if (nconv < k) {                              // the two eigensolvers disagree at the threshold: resume
+      if (R.nconv < k) {                            // the two eigensolvers disagree at the threshold: resume
         converged = false;
         if (inflight) { TRY(absorb_step(c0 - P, slot ^ 1)); }
         res_prev = res_last = 0.0;
@@ -899,75 +982,18 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
       full_check(mm, true);
     }
     res_prev = res_last = 0.0;                      // a restart changes the decay
-    if (nconv >= k || restarts >= maxiter) { done = nconv >= k; break; }
-    int pk = k + std::min(nconv, (mm - k) / 2);
-    pk = std::max(pk, k + (mm - k) / 4);
-    pk = std::min(pk, mm - 2 * P);
-    std::vector<double> Ssel((size_t)mm * pk);
-    for (int q = 0; q < pk; ++q) std::memcpy(&Ssel[(size_t)q * mm], &Svec[(size_t)order[q] * mm], sizeof(double) * mm);
-    std::memcpy(hH, Ssel.data(), sizeof(double) * mm * pk);
-    HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * mm * pk, hipMemcpyHostToDevice, st));
-    plfem::launch_rotate(c, c->d_V, mm, c->d_S, mm, pk, c->d_V2);
-    plfem::launch_rotate(c, c->d_BV, mm, c->d_S, mm, pk, c->d_BV2);
-    TRY(check_launch(c, "restart rotation"));
-    HIP_TRY(c, hipMemcpyAsync(c->d_V2 + (size_t)pk * n, c->d_V + (size_t)mm * n, sizeof(double) * n * P, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_BV2 + (size_t)pk * n, c->d_BV + (size_t)mm * n, sizeof(double) * n * P, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    std::swap(c->d_V, c->d_V2);
-    std::swap(c->d_BV, c->d_BV2);
-    std::fill(T.begin(), T.end(), 0.0);
-    for (int q = 0; q < pk; ++q) T[(size_t)q * ld + q] = theta[order[q]];
-    HIP_TRY(c, hipMemsetAsync(c->d_Hcols, 0, sizeof(double) * ld * ld, st));
+    if (R.nconv >= k || R.restarts >= maxiter) break;
+    int pk = 0;
+    TRY(R.restart(mm, pk));
     c0 = pk;
     cycle_start = pk;
     il_ready = -1;
-    ++restarts;
   }
-  std::vector<int> want(order.begin(), order.begin() + k);
-  std::vector<double> lam(mm);
-  for (int i = 0; i < mm; ++i) lam[i] = sigma + 1.0 / theta[i];
-  std::sort(want.begin(), want.end(), [&](int a, int b) { return lam[a] < lam[b]; });
-  for (int q = 0; q < k; ++q) {
-    evals_host[q] = lam[want[q]];
-    std::memcpy(hH + (size_t)q * mm, &Svec[(size_t)want[q] * mm], sizeof(double) * mm);
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * mm * k, hipMemcpyHostToDevice, st));
-  if (!evecs_dev) evecs_dev = c->d_V2;            // (idle since the last restart, if any)
-  c->modes_dev = evecs_dev;
-  c->modes_k = k;
-  plfem::launch_rotate(c, c->d_V, mm, c->d_S, mm, k, evecs_dev);
-  HIP_TRY(c, hipEventRecord(c->ev[2][1], st));
-  c->ev_used[2] = true;
-  TRY(check_launch(c, "ritz rotation"));
-  if (!c->defer_sync) HIP_TRY(c, hipStreamSynchronize(st));   // (plfem_solve_modes: its one synchronisation comes later)
-  if (stats_host) {
-    stats_host[0] = nconv;
-    stats_host[1] = nop;
-    stats_host[2] = restarts;
-    stats_host[3] = max_rel_res;
-    stats_host[4] = nblock;
-  }
-  if (!done) {
-    c->err = "Lanczos: no convergence within maxiter restarts";
-    return PLFEM_ENOCONV;
-  }
-  return PLFEM_OK;
+  return R.finish(mm, sigma, evals_host, evecs_dev, stats_host, nop, nblock);
 }
 
-// ------------------------------------------------------------------------------------------------
-// thick-restart Lanczos, shift-invert, B inner product
-// ------------------------------------------------------------------------------------------------
 // evecs_dev == nullptr: the vectors go into the context's own buffer (the idle restart double buffer d_V2; see
 // plfem_solve_modes / plfem_modes_dev)
-static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t maxiter,
-                       double sigma, double* evals_host, double* evecs_dev, double* stats_host);
-
-extern "C" int plfem_lanczos_shift_invert(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t maxiter,
-                                          double sigma, double* evals_host, double* evecs_dev, double* stats_host) {
-  if (!c || !evals_host || !evecs_dev) return PLFEM_EINVAL;
-  return lanczos_run(c, k, ncv, tol, maxiter, sigma, evals_host, evecs_dev, stats_host);
-}
-
 static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t maxiter,
                        double sigma, double* evals_host, double* evecs_dev, double* stats_host) {
   if (!c || !evals_host) return PLFEM_EINVAL;
@@ -991,10 +1017,10 @@ static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t
   hipStream_t st = c->stream;
   HIP_TRY(c, hipEventRecord(c->ev[2][0], st));
   const int m = ncv;
-  const int ld = m + 1;
-  std::vector<double> T((size_t)ld * ld, 0.0);   // projected matrix (upper triangle authoritative)
-  double* hH = c->h_pinned + 8192;                // pinned mirror of d_Hcols
-  int nop = 0, restarts = 0;
+  ThickRestart R(c, 1, k, m, tol);
+  const int ld = R.ld;
+  double* hH = R.hH;                              // pinned mirror of d_Hcols
+  int nop = 0;
 
   // start vector: fixed pseudo-random interior field pushed through OP once (as ARPACK does for mode 3)
   {
@@ -1009,11 +1035,6 @@ static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t
   HIP_TRY(c, hipMemsetAsync(c->d_Hcols, 0, sizeof(double) * ld * ld, st));
 
   int j0 = 0;        // first Lanczos column to compute in this cycle
-  std::vector<double> theta, Svec, Tm;
-  std::vector<int> order;
-  int nconv = 0;
-  double max_rel_res = 0.0;
-  bool done = false;
   while (true) {
     for (int j = j0; j < m; ++j) {
       double* Vj1 = c->d_V + (size_t)(j + 1) * n;
@@ -1034,84 +1055,20 @@ static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t
     HIP_TRY(c, hipMemcpyAsync(hH, c->d_Hcols, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     for (int j = j0; j < m; ++j)
-      for (int i = 0; i <= j + 1 && i < ld; ++i) T[(size_t)j * ld + i] = hH[(size_t)j * ld + i];
-    const double beta_m = T[(size_t)(m - 1) * ld + m];
+      for (int i = 0; i <= j + 1 && i < ld; ++i) R.T[(size_t)j * ld + i] = hH[(size_t)j * ld + i];
+    const double beta_m = R.T[(size_t)(m - 1) * ld + m];
     if (!std::isfinite(beta_m)) { c->err = "Lanczos breakdown: non-finite residual norm (is sigma an eigenvalue?)"; return PLFEM_ESINGULAR; }
-    // symmetric m x m projected matrix from the upper triangle
-    Tm.assign((size_t)m * m, 0.0);
-    for (int j = 0; j < m; ++j)
-      for (int i = 0; i <= j; ++i) {
-        double v = T[(size_t)j * ld + i];
-        Tm[(size_t)j * m + i] = v;
-        Tm[(size_t)i * m + j] = v;
-      }
-    plfem::sym_eig(m, Tm, Svec, theta);
-    order.resize(m);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return std::fabs(theta[a]) > std::fabs(theta[b]); });
-    nconv = 0;
-    max_rel_res = 0.0;
-    for (int q = 0; q < k; ++q) {
-      int id = order[q];
-      double res = std::fabs(beta_m * Svec[(size_t)id * m + (m - 1)]);
-      double rel = res / std::max(std::fabs(theta[id]), 3.7e-11);
-      max_rel_res = std::max(max_rel_res, rel);
-      if (rel <= tol) ++nconv;
-    }
-    if (nconv >= k || restarts >= maxiter) { done = nconv >= k; break; }
-    // thick restart: keep the k wanted pairs plus some of the next ones (ARPACK: kev + min(nconv, np/2))
-    int p = k + std::min(nconv, (m - k) / 2);
-    p = std::max(p, k + (m - k) / 4);
-    p = std::min(p, m - 2);
-    std::vector<double> Ssel((size_t)m * p);
-    for (int q = 0; q < p; ++q)
-      std::memcpy(&Ssel[(size_t)q * m], &Svec[(size_t)order[q] * m], sizeof(double) * m);
-    std::memcpy(hH, Ssel.data(), sizeof(double) * m * p);
-    HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * m * p, hipMemcpyHostToDevice, st));
-    plfem::launch_rotate(c, c->d_V, m, c->d_S, m, p, c->d_V2);
-    plfem::launch_rotate(c, c->d_BV, m, c->d_S, m, p, c->d_BV2);
-    TRY(check_launch(c, "restart rotation"));
-    HIP_TRY(c, hipMemcpyAsync(c->d_V2 + (size_t)p * n, c->d_V + (size_t)m * n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->d_BV2 + (size_t)p * n, c->d_BV + (size_t)m * n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipStreamSynchronize(st));   // hH is reused below
-    std::swap(c->d_V, c->d_V2);
-    std::swap(c->d_BV, c->d_BV2);
-    std::fill(T.begin(), T.end(), 0.0);
-    for (int q = 0; q < p; ++q) T[(size_t)q * ld + q] = theta[order[q]];
-    HIP_TRY(c, hipMemsetAsync(c->d_Hcols, 0, sizeof(double) * ld * ld, st));
-    j0 = p;
-    ++restarts;
+    R.ritz(m);
+    if (R.nconv >= k || R.restarts >= maxiter) break;
+    TRY(R.restart(m, j0));
   }
-  // wanted Ritz pairs, ascending lambda = sigma + 1/theta
-  std::vector<int> want(order.begin(), order.begin() + k);
-  std::vector<double> lam(m);
-  for (int i = 0; i < m; ++i) lam[i] = sigma + 1.0 / theta[i];
-  std::sort(want.begin(), want.end(), [&](int a, int b) { return lam[a] < lam[b]; });
-  for (int q = 0; q < k; ++q) {
-    evals_host[q] = lam[want[q]];
-    std::memcpy(hH + (size_t)q * m, &Svec[(size_t)want[q] * m], sizeof(double) * m);
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * m * k, hipMemcpyHostToDevice, st));
-  if (!evecs_dev) evecs_dev = c->d_V2;
-  c->modes_dev = evecs_dev;
-  c->modes_k = k;
-  plfem::launch_rotate(c, c->d_V, m, c->d_S, m, k, evecs_dev);
-  HIP_TRY(c, hipEventRecord(c->ev[2][1], st));
-  c->ev_used[2] = true;
-  TRY(check_launch(c, "ritz rotation"));
-  if (!c->defer_sync) HIP_TRY(c, hipStreamSynchronize(st));
-  if (stats_host) {
-    stats_host[0] = nconv;
-    stats_host[1] = nop;
-    stats_host[2] = restarts;
-    stats_host[3] = max_rel_res;
-    stats_host[4] = 0;
-  }
-  if (!done) {
-    c->err = "Lanczos: no convergence within maxiter restarts";
-    return PLFEM_ENOCONV;
-  }
-  return PLFEM_OK;
+  return R.finish(m, sigma, evals_host, evecs_dev, stats_host, nop, 0);
+}
+
+extern "C" int plfem_lanczos_shift_invert(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t maxiter,
+                                          double sigma, double* evals_host, double* evecs_dev, double* stats_host) {
+  if (!c || !evals_host || !evecs_dev) return PLFEM_EINVAL;
+  return lanczos_run(c, k, ncv, tol, maxiter, sigma, evals_host, evecs_dev, stats_host);
 }
 
 extern "C" int plfem_postprocess(plfem_ctx* c, int32_t k, double* evecs_dev, const double* cores_host, int32_t ncore,
@@ -1145,16 +1102,26 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
   HIP_TRY(c, hipSetDevice(c->device));
   if (!c->copy_stream) HIP_TRY(c, copy_stream_acquire(c->device, &c->copy_stream));
   if (!c->ev_copy) HIP_TRY(c, ctx_event_acquire(c->device, 1, &c->ev_copy));
-  struct Defer {                                   // the Lanczos drivers leave their final synchronisation to this call
+  // Whatever way the call is left: the Lanczos drivers leave their final synchronisation to this call, the mode copies
+  // queued on the copy stream land before the caller may release modes_int_host (the explicit synchronisations below
+  // clear copy_pending, so that the success path makes no extra call), and the trace events go back.
+  struct Defer {
     plfem_ctx* c;
     int saved_refine;
-    ~Defer() { c->defer_sync = false; c->refine_steps = saved_refine; }
+    bool copy_pending = false;
+    hipEvent_t tr_ev[3] = {nullptr, nullptr, nullptr};
+    ~Defer() {
+      if (copy_pending) (void)hipStreamSynchronize(c->copy_stream);
+      for (hipEvent_t e : tr_ev) if (e) (void)hipEventDestroy(e);
+      c->defer_sync = false;
+      c->refine_steps = saved_refine;
+    }
   } defer{c, c->refine_steps};
   c->defer_sync = true;
   // PLFEM_CALL_TRACE=1 (tuning aid): where the wall time of this call goes beyond its device phases -- host timestamps of the
   // enqueue points, the stream's backlog at entry (work of plfem_create still queued) and the tail of the mode copy
   static const bool call_trace = getenv("PLFEM_CALL_TRACE") != nullptr;
-  hipEvent_t tr_ev[3] = {nullptr, nullptr, nullptr};
+  auto& tr_ev = defer.tr_ev;
   double th_asm = 0, th_fac = 0, th_lan = 0, th_enq = 0, th_sync = 0;
   if (call_trace) {
     for (auto& e : tr_ev) (void)hipEventCreate(&e);
@@ -1169,7 +1136,19 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
   double first_res = 0.0, res = 0.0;
   int perturbed = 0, refined = 0;
   double n_opinv = 0, n_block = 0, restarts = 0;
-  const size_t modes_bytes = sizeof(double) * (size_t)k * c->dpn * c->nsolve;
+  // the one writer of stats_host: entries [lo, hi) (PLFEM_SOLVE_*) as they stand at the exit
+  auto put_stats = [&](int lo, int hi) {
+    if (!stats_host) return;
+    double v[PLFEM_SOLVE_STATS] = {st[0], n_opinv, restarts, st[3], n_block, first_res, res, (double)refined, (double)perturbed};
+    if (hi > PLFEM_SOLVE_T_ASSEMBLE_US) {
+      for (int q = 0; q < 6; ++q) {                 // assemble, factor, lanczos, post, upload, residual check
+        float ms = 0;
+        v[9 + q] = (c->ev_used[q] && hipEventElapsedTime(&ms, c->ev[q][0], c->ev[q][1]) == hipSuccess) ? ms * 1e3 : 0.0;
+      }
+      v[PLFEM_SOLVE_T_CALL_US] = (now_ms() - th0) * 1e3;
+    }
+    for (int q = lo; q < hi; ++q) stats_host[q] = v[q];
+  };
   for (int pass = 0; pass < 2; ++pass) {
     // second pass: refinement inside the operator (repairs an inaccurate factor) AND a tighter Ritz tolerance (repairs a
     // first pass that merely stopped too early: a residual above the bound with no perturbed pivot)
@@ -1179,7 +1158,7 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
     n_opinv += st[1]; n_block += st[4]; restarts += st[2];
     if (rc != PLFEM_OK) {
       (void)hipStreamSynchronize(c->stream);       // (PLFEM_ENOCONV: evals_host / plfem_modes_dev hold the current Ritz pairs)
-      if (stats_host) { stats_host[0] = st[0]; stats_host[1] = n_opinv; stats_host[2] = restarts; stats_host[3] = st[3]; stats_host[4] = n_block; }
+      put_stats(0, PLFEM_SOLVE_RESIDUAL_FIRST);
       return rc;
     }
     th_lan = now_ms();
@@ -1193,6 +1172,7 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
     const size_t row_bytes = sizeof(double) * (size_t)c->dpn * c->nsolve;
     const std::function<void(int, int)> send_group = [&](int g0, int kg) {
       if (copy_err != hipSuccess) return;
+      defer.copy_pending = true;
       copy_err = hipEventRecord(c->ev_copy, c->stream);
       if (copy_err == hipSuccess) copy_err = hipStreamWaitEvent(c->copy_stream, c->ev_copy, 0);
       if (copy_err == hipSuccess)
@@ -1203,7 +1183,6 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
     HIP_TRY(c, hipEventRecord(c->ev[3][1], c->stream));
     c->ev_used[3] = true;
     HIP_TRY(c, copy_err);
-    (void)modes_bytes;
     HIP_TRY(c, hipEventRecord(c->ev[5][0], c->stream));
     plfem::resid_enqueue(c, k, evals_host, modes);
     HIP_TRY(c, hipEventRecord(c->ev[5][1], c->stream));
@@ -1218,12 +1197,13 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
     th_sync = now_ms();
     plfem::post_finish(c, k, post_host, frac_core_host);
     plfem::resid_finish(c, k, resid_host);
-    perturbed = reinterpret_cast<const int32_t*>(c->h_pinned + 4096)[0];
+    perturbed = reinterpret_cast<const int32_t*>(c->h_pinned + plfem::PIN_COUNTERS)[0];
     res = 0.0;
     for (int i = 0; i < k; ++i) res = (resid_host[i] > res || !(resid_host[i] == resid_host[i])) ? resid_host[i] : res;
     if (pass == 0) first_res = res;
     if (res <= residual_tol && perturbed == 0) break;
     if (modes_int_host) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));   // (the vectors on their way: let them land, then redo)
+    defer.copy_pending = false;
     if (pass == 1) {
       if (res <= residual_tol) break;              // (perturbed pivots, repaired by the refinement)
       char msg[512];
@@ -1231,12 +1211,13 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
                     residual_tol, perturbed > 0 ? "vanishing pivots were perturbed: the shift-invert factorisation is inaccurate on this mesh"
                                                 : "no pivot was perturbed: the eigenpairs did not converge tightly enough");
       c->err = msg;
-      if (stats_host) { stats_host[5] = first_res; stats_host[6] = res; stats_host[7] = 1; stats_host[8] = perturbed; }
+      put_stats(PLFEM_SOLVE_RESIDUAL_FIRST, PLFEM_SOLVE_T_ASSEMBLE_US);
       return PLFEM_ERESIDUAL;
     }
     refined = 1;
   }
   if (modes_int_host) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+  defer.copy_pending = false;
   if (call_trace) {
     const double th_end = now_ms();
     float backlog = 0, total = 0, copy_tail = 0;
@@ -1247,18 +1228,8 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
                     "copy done +%.3f ms | device: entry -> assembly %.3f (backlog of plfem_create + launch), entry -> end of check %.3f, "
                     "check -> copy end %.3f ms\n",
             th_asm - th0, th_fac - th0, th_lan - th0, th_enq - th0, th_sync - th0, th_end - th0, backlog, total, copy_tail);
-    for (auto& e : tr_ev) (void)hipEventDestroy(e);
   }
-  if (stats_host) {
-    stats_host[0] = st[0]; stats_host[1] = n_opinv; stats_host[2] = restarts; stats_host[3] = st[3]; stats_host[4] = n_block;
-    stats_host[5] = first_res; stats_host[6] = res; stats_host[7] = refined; stats_host[8] = perturbed;
-    const int slot[6] = {0, 1, 2, 3, 4, 5};         // assemble, factor, lanczos, post, upload, residual check
-    for (int q = 0; q < 6; ++q) {
-      float ms = 0;
-      stats_host[9 + q] = (c->ev_used[slot[q]] && hipEventElapsedTime(&ms, c->ev[slot[q]][0], c->ev[slot[q]][1]) == hipSuccess) ? ms * 1e3 : 0.0;
-    }
-    stats_host[15] = (now_ms() - th0) * 1e3;
-  }
+  put_stats(0, PLFEM_SOLVE_STATS);
   return PLFEM_OK;
 }
 

@@ -11,6 +11,28 @@
 #include "internal.h"
 #include "plan.h"
 
+namespace plfem {
+
+// Layout of the context's pinned host block h_pinned, offsets in doubles.  The regions hold for any k <= PLFEM_MAX_NCV
+// and ncore <= MAX_CORES (the asserts below).
+constexpr size_t PIN_POST = 0;         // post-processing sums, 5 k (post_enqueue / post_finish)
+constexpr size_t PIN_RESID = 2048;     // residual check: lambda [0, k), sums [k, 3 k) (resid_enqueue / resid_finish)
+constexpr size_t PIN_CORE_QP = 4000;   // one u64: quadrature points inside a core (launch_delta_eps_mass)
+// int32 counters, shared in time: post_enqueue copies the 4 device counters here, and each of the two block-step
+// slots of the block Lanczos driver writes its 4 into [4 slot, 4 slot + 4); the two never run together
+constexpr size_t PIN_COUNTERS = 4096;
+constexpr int PIN_COUNTERS_N = 2 * 4;  // int32 entries
+constexpr size_t PIN_CORES = 6144;     // core table, 3 MAX_CORES (upload_cores)
+// projected matrix (max_ncv + 2 + BLOCK_P)^2: d_Hcols mirror, restart / Ritz rotation matrices; h_slots behind it
+constexpr size_t PIN_PROJ = 8192;
+static_assert(PIN_POST + 5 * PLFEM_MAX_NCV <= PIN_RESID, "pinned layout: post-processing sums");
+static_assert(PIN_RESID + 3 * PLFEM_MAX_NCV <= PIN_CORE_QP, "pinned layout: residual check");
+static_assert(PIN_CORE_QP + 1 <= PIN_COUNTERS, "pinned layout: core-point counter");
+static_assert(PIN_COUNTERS + PIN_COUNTERS_N * sizeof(int32_t) / sizeof(double) <= PIN_CORES, "pinned layout: counters");
+static_assert(PIN_CORES + 3 * MAX_CORES <= PIN_PROJ, "pinned layout: core table");
+
+}  // namespace plfem
+
 struct plfem_ctx {
   const plfem::Symbolic* S = nullptr;
   int device = 0;
@@ -75,7 +97,7 @@ struct plfem_ctx {
   double* d_post = nullptr;       // partial sums: post-processing in [0, post_doubles), residual check behind it
   size_t post_doubles = 0;
   int npartial = 0;
-  double* h_pinned = nullptr;     // pinned staging
+  double* h_pinned = nullptr;     // pinned staging, regions plfem::PIN_*
   size_t h_pinned_bytes = 0;      // size of that block (it returns to a process-wide cache)
   double* h_staging = nullptr;    // pinned staging block of the one upload of the host arrays (same cache)
   size_t h_staging_bytes = 0;

@@ -485,7 +485,7 @@ double launch_delta_eps_mass(plfem_ctx* c, int ncore, double eps_core, double ep
   const int64_t nq = (int64_t)c->ne * 6;
   hipLaunchKernelGGL(k_count_core_qp, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
                      c->d_doflocs, c->d_cores, ncore, cnt);
-  unsigned long long* h = reinterpret_cast<unsigned long long*>(c->h_pinned + 4000);
+  unsigned long long* h = reinterpret_cast<unsigned long long*>(c->h_pinned + PIN_CORE_QP);
   (void)hipMemcpyAsync(h, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
   (void)hipStreamSynchronize(c->stream);
   const double frac = (double)*h / (double)nq;

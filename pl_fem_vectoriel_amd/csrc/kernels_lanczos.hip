@@ -679,16 +679,15 @@ __global__ __launch_bounds__(64) void k_resid_finish(int nblocks, const double* 
 
 }  // namespace
 
-// pinned scratch of the two result read-backs (doubles from h_pinned): post-processing sums [0, 5 k), residual check
-// lambda up [2048, 2048 + k) and sums down [2048 + k, 2048 + 3 k) -- disjoint, so that both can be in flight together
-constexpr int RESID_HS = 2048;
+// the two result read-backs use disjoint pinned regions (PIN_POST, PIN_RESID: device.h), so that both can be in flight
+// together
 
 // enqueue only: the k residual sums end up in pinned memory once the stream has drained (resid_finish)
 void resid_enqueue(plfem_ctx* c, int k, const double* lam_host, const double* evecs) {
   hipStream_t st = c->stream;
   const int N = c->N;
   const int nblocks = (N + POST_ROWS - 1) / POST_ROWS;
-  double* hs = c->h_pinned + RESID_HS;
+  double* hs = c->h_pinned + PIN_RESID;
   for (int i = 0; i < k; ++i) hs[i] = lam_host[i];
   (void)hipMemcpyAsync(c->d_hacc, hs, sizeof(double) * k, hipMemcpyHostToDevice, st);
   double* partial = c->d_post + c->post_doubles;     // second half of d_post: [k][nblocks][2], then the sums
@@ -707,7 +706,7 @@ void resid_enqueue(plfem_ctx* c, int k, const double* lam_host, const double* ev
 
 // after the stream has been synchronised
 void resid_finish(plfem_ctx* c, int k, double* out_host) {
-  const double* hs = c->h_pinned + RESID_HS;
+  const double* hs = c->h_pinned + PIN_RESID;
   for (int i = 0; i < k; ++i) {
     const double r2 = hs[k + 2 * i], a2 = hs[k + 2 * i + 1];
     out_host[i] = a2 > 0.0 ? std::sqrt(r2 / a2) : (r2 > 0.0 ? INFINITY : 0.0);
@@ -882,16 +881,16 @@ void post_enqueue(plfem_ctx* c, int k, double* evecs, int ncore, double* modes_i
     if (group_done) (*group_done)(g0, kg);
   }
   // results to the host
-  double* hs = c->h_pinned;
+  double* hs = c->h_pinned + PIN_POST;
   (void)hipMemcpyAsync(hs, c->d_post + (int64_t)k * nblocks * 5, sizeof(double) * k * 5, hipMemcpyDeviceToHost, st);
-  int32_t* hc = reinterpret_cast<int32_t*>(c->h_pinned + 4096);
+  int32_t* hc = reinterpret_cast<int32_t*>(c->h_pinned + PIN_COUNTERS);
   (void)hipMemcpyAsync(hc, c->d_counters, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st);
 }
 
 // after the stream has been synchronised
 void post_finish(plfem_ctx* c, int k, double* out_host, double* frac_core) {
-  const double* hs = c->h_pinned;
-  const int32_t* hc = reinterpret_cast<const int32_t*>(c->h_pinned + 4096);
+  const double* hs = c->h_pinned + PIN_POST;
+  const int32_t* hc = reinterpret_cast<const int32_t*>(c->h_pinned + PIN_COUNTERS);
   for (int mode = 0; mode < k; ++mode) {
     const double* s = hs + mode * 5;
     double nrm2 = c->dpn == 2 ? s[0] + s[1] : s[4];      // scalar solver: M-norm (solver_fem.py:268)

@@ -5,9 +5,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace plfem {
+#include "plan.h"   // MAX_CORES
 
-constexpr int MAX_CORES = 64;   // capacity of the core tables (d_cores, CoreTable): 3 doubles (x, y, r) per core
+namespace plfem {
 
 namespace {
 

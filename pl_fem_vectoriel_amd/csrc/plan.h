@@ -56,6 +56,7 @@ inline int bwd_block_rows(int count, bool leaf) { return leaf ? 64 : count <= RO
 #endif
 constexpr int BLOCK_P = PLFEM_BLOCK_P;      // right-hand sides per block solve / block Lanczos step
 static_assert(BLOCK_P == 4 || BLOCK_P == 8, "a power of two: multi_reduce of the row-form sweeps");
+constexpr int MAX_CORES = 64;   // capacity of the core tables (d_cores, CoreTable): 3 doubles (x, y, r) per core
 constexpr int ELEM_FORMS = 8;   // Axx Axy Ayx Ayy Minv Dxx Dxy Dyy
 constexpr int ELEM_STRIDE = ELEM_FORMS * 36;
 
