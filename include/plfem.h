@@ -354,6 +354,23 @@ int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes);
 int plfem_mode_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
                      const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host);
 
+/* Quartic mode-overlap tensor of k staged modes over the locator's mesh (the input of multimode nonlinear propagation:
+ * f_ijkl, A_eff, gamma), on the 16-point degree-8 rule (products of four P2 fields are of degree 8).  Pairs i <= j are
+ * numbered p(i,j) = i k - i (i - 1) / 2 + (j - i), np = k (k + 1) / 2.
+ *   out_host[p(i,j)][p(l,m)] = sum over the elements and the 16 points of |det J| w_q wt(x_q) (u_i . u_j)(u_l . u_m),
+ * np x np, exactly symmetric (one triangle computed, mirrored); u . u' = hx hx' + hy hy' when ncomp = 2.  wt = 1 when
+ * ncore < 0, otherwise w_core / w_clad by the assembly's closed-disc core test (cores_host = (x, y, r) per core).
+ * modes_dev: staged by plfem_stage_modes ([ncomp][nrows][k]); indexed as in plfem_sample_fields.  Partial tiles per
+ * workgroup and a fixed-order second stage: the same bits on every run.  Synchronises the locator's stream.
+ * work_dev: device scratch of plfem_quartic_work_bytes(ncomp, k) bytes, 256-byte aligned.  The bound: np x np doubles
+ * for the result plus at most 2048 partial 64 x 64 tiles, so at most 34.6 MB + 67.1 MB (k = 64); 42 MB at k = 22.
+ * Argument errors (ncomp not 1 or 2, k outside [1, 64], ncore > 64, a null pointer, work_bytes too small) return
+ * PLFEM_EINVAL with the locator's last error set. */
+int plfem_quartic_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes);
+int plfem_mode_quartic(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                       const double* cores_host, int32_t ncore, double w_core, double w_clad,
+                       void* work_dev, int64_t work_bytes, double* out_host);
+
 #ifdef PLFEM_TEST_HOOKS
 /* ---------------------------------------------------------------------------------------------
  * TEST HOOKS -- NOT exported by libplfem_hip.so.  They live in the add-on libplfem_testhooks.so (csrc/api_debug.hip,

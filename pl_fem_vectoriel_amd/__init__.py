@@ -3,6 +3,7 @@ from .geometry import MCFGeometry, PhotonicLanternGeometry, mcf_positions  # noq
 from .mesh import TriMesh, generate_mesh  # noqa: F401
 from .fields import ModeFields, mode_overlap  # noqa: F401
 from .dispersion import mode_dispersion  # noqa: F401
+from .nonlinear import mode_nonlinearity  # noqa: F401
 
 __all__ = ["MCFGeometry", "PhotonicLanternGeometry", "mcf_positions", "TriMesh", "generate_mesh", "ModeFields", "mode_overlap",
-           "mode_dispersion"]
+           "mode_dispersion", "mode_nonlinearity"]

@@ -1,7 +1,8 @@
 // gfx950 kernels and C-ABI of the mode-field calls (include/plfem.h, "Mode fields at arbitrary points"): the point
 // locator bound to a device, P2 evaluation of many modes at many points (k_sample_fields) and the overlap integral of
 // two mode sets living on two meshes (k_field_overlap + k_overlap_reduce), and the same-mesh Grams of a mode set under
-// the assembly's element forms, split by material region (k_mode_grams + k_overlap_reduce).
+// the assembly's element forms, split by material region (k_mode_grams + k_overlap_reduce), and the quartic overlap of
+// products of four modes on a 16-point degree-8 rule (k_mode_quartic + k_quartic_reduce).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field.
@@ -426,6 +427,148 @@ __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nr
   }
 }
 
+// Quartic mode-overlap tensor (plfem_mode_quartic): Q[p(i,j)][p(l,m)] = sum over the points of the 16-point degree-8 rule
+// of |det J| w_q wt(x) (u_i . u_j)(u_l . u_m), i.e. Q = R^T diag(w) R with R[point][pair] = u_i . u_j.  R never reaches
+// HBM: one workgroup owns one 64 x 64 tile of Q on or above the diagonal (blockIdx.y, upper-triangle order) and walks
+// the elements blockIdx.x, blockIdx.x + gridDim.x, ...  Per element: the six staged DOF rows of all k modes go to LDS;
+// u[c][t][m] = sum_a phi_a(q_t) v[c][a][m] at the 16 points (the basis at the rule's points is one table, no J^-1);
+// the pair products of the tile's 64 row pairs (plain) and 64 column pairs (times the point's weight) go to LDS as the
+// A and B operands of v_mfma_f64_16x16x4_f64; each wave accumulates a 32 x 32 block (2 x 2 MFMA tiles) over the 16
+// points in four K-steps.  No region branch sits in the reduction: the weight is folded into B.  The workgroup's
+// partial tile goes to its own slot (no atomics); k_quartic_reduce sums the slots in a fixed order.
+constexpr int QP = 64;          // pairs per side of an output tile
+constexpr int QKMAX = 64;       // most modes per call (LDS rows of the element)
+constexpr int QB_MAX = 128;     // most element slices (partial tiles) per output tile
+constexpr int QWG = 2048;       // most partial tiles in all: slices = min(QB_MAX, QWG / tile pairs)
+constexpr int QLD = QP + 2;     // padded LDS row of the pair products
+
+typedef double dbl4 __attribute__((ext_vector_type(4)));
+
+// upper-triangle tile pair t -> (ti, tj), ti <= tj, over an nt x nt tiling
+__device__ __forceinline__ void quartic_tile(int t, int nt, int& ti, int& tj) {
+  ti = 0;
+  while (t >= nt - ti) { t -= nt - ti; ++ti; }
+  tj = ti + t;
+}
+
+template <int NCOMP>
+__global__ __launch_bounds__(256) void k_mode_quartic(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
+                                                      CoreTable cores, int ncore, double w_core, double w_clad, int npair,
+                                                      int ntile, double* __restrict__ partial) {
+  __shared__ double s_v[NCOMP][6][QKMAX];     // the element's DOF rows (0 for a boundary DOF of an indexed record)
+  __shared__ double s_u[NCOMP][16][QKMAX + 1];
+  __shared__ double s_r[2][16][QLD];          // [0]: row pairs' products, [1]: column pairs' products times the weight
+  __shared__ double s_phi[16][6];
+  __shared__ double s_w[16];
+  __shared__ int s_pi[2][QP], s_pj[2][QP];    // modes (i, j) of the tile's row / column pairs; -1 past np
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int ti, tj;
+  quartic_tile(blockIdx.y, ntile, ti, tj);
+  if (tid < 2 * QP) {
+    const int side = tid / QP, a = tid % QP;
+    const int P = (side ? tj : ti) * QP + a;
+    int i = -1, j = -1;
+    if (P < npair) {
+      int r = P;
+      i = 0;
+      while (r >= k - i) { r -= k - i; ++i; }
+      j = i + r;
+    }
+    s_pi[side][a] = i;
+    s_pj[side][a] = j;
+  }
+  if (tid < 96) s_phi[tid / 6][tid % 6] = p2_phi(tid % 6, c_q16x[tid / 6], c_q16y[tid / 6]);
+  const double* px = L.pxy;
+  const double* py = L.pxy + L.nv;
+  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;   // this wave's 32 x 32 block of the tile
+  const int l16 = lane & 15, l4 = lane >> 4;
+  dbl4 acc[2][2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) acc[r][s] = dbl4{0.0, 0.0, 0.0, 0.0};
+  for (int e = blockIdx.x; e < L.ne; e += gridDim.x) {
+    for (int idx = tid; idx < NCOMP * 6 * QKMAX; idx += 256) {
+      const int m = idx % QKMAX, a = (idx / QKMAX) % 6, c = idx / (6 * QKMAX);
+      double v = 0.0;
+      if (m < k) {
+        const int r = dev_row(L, e, a);
+        if (r >= 0) v = V[(int64_t)c * nrows * k + (int64_t)r * k + m];
+      }
+      s_v[c][a][m] = v;
+    }
+    if (tid < 16) {
+      const P2Map M(L.edof, L.ne, px, py, e);
+      double w = fabs(M.det()) * c_q16w[tid];
+      if (ncore >= 0) {
+        double X, Y;
+        M.point(c_q16x[tid], c_q16y[tid], X, Y);
+        w *= in_any_core(X, Y, cores.c, ncore) ? w_core : w_clad;
+      }
+      s_w[tid] = w;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < NCOMP * 16 * QKMAX; idx += 256) {
+      const int m = idx % QKMAX, t = (idx / QKMAX) % 16, c = idx / (16 * QKMAX);
+      double u = 0.0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) u += s_phi[t][a] * s_v[c][a][m];
+      s_u[c][t][m] = u;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < 2 * 16 * QP; idx += 256) {
+      const int a = idx % QP, t = (idx / QP) % 16, side = idx / (16 * QP);
+      const int i = s_pi[side][a], j = s_pj[side][a];
+      double r = 0.0;
+      if (i >= 0) {
+#pragma unroll
+        for (int c = 0; c < NCOMP; ++c) r += s_u[c][t][i] * s_u[c][t][j];
+        if (side) r *= s_w[t];
+      }
+      s_r[side][t][a] = r;
+    }
+    __syncthreads();
+    // A[row][kk] = R[t = 4 ks + kk][row pair], B[kk][col] = w R[t][col pair]; lane: row / col = lane & 15, kk = lane >> 4
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int t = 4 * ks + l4;
+      const double a0 = s_r[0][t][wr + l16], a1 = s_r[0][t][wr + 16 + l16];
+      const double b0 = s_r[1][t][wc + l16], b1 = s_r[1][t][wc + 16 + l16];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  // D of v_mfma_f64_16x16x4_f64: entry g of a lane is (row (lane >> 4) + 4 g, col lane & 15)
+  double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (QP * QP);
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) out[(wr + 16 * r + l4 + 4 * g) * QP + wc + 16 * s + l16] = acc[r][s][g];
+}
+
+// Second stage of k_mode_quartic: blockIdx.x = tile pair, its nblk partial tiles summed in slice order (one lane per
+// entry, the same bits on every run); entries with P <= P' < np are written to O[P][P'] and mirrored to O[P'][P], so the
+// np x np result is exactly symmetric.  blockIdx.z = slice of the tile's entries.
+__global__ __launch_bounds__(256) void k_quartic_reduce(int npair, int ntile, int nblk, const double* __restrict__ partial,
+                                                        double* __restrict__ O) {
+  int ti, tj;
+  quartic_tile(blockIdx.x, ntile, ti, tj);
+  const double* pp = partial + (int64_t)blockIdx.x * nblk * (QP * QP);
+  for (int v = blockIdx.z * 256 + threadIdx.x; v < QP * QP; v += 256 * gridDim.z) {
+    const int P = ti * QP + v / QP, P2 = tj * QP + v % QP;
+    if (P2 >= npair || P > P2) continue;
+    double s = 0.0;
+    for (int b = 0; b < nblk; ++b) s += pp[(int64_t)b * (QP * QP) + v];
+    O[(int64_t)P * npair + P2] = s;
+    O[(int64_t)P2 * npair + P] = s;
+  }
+}
+
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int set_loc_err(plfem_locator* L, const std::string& m, int rc) {
@@ -666,4 +809,61 @@ extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
   rc = check_hip(L, hipGetLastError(), "k_mode_grams");
   if (rc) return rc;
   return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
+}
+
+namespace {
+int quartic_pairs(int k) { return k * (k + 1) / 2; }
+int quartic_tiles(int k) { return (quartic_pairs(k) + QP - 1) / QP; }
+int quartic_tile_pairs(int k) { return quartic_tiles(k) * (quartic_tiles(k) + 1) / 2; }
+// element slices per output tile: at most QB_MAX, and at most QWG partial tiles in all (a tile pair count never exceeds
+// 561 = the k = 64 count, so that is always >= 1 slice)
+int quartic_slices(int k) { return std::max(1, std::min(QB_MAX, QWG / quartic_tile_pairs(k))); }
+}  // namespace
+
+extern "C" int plfem_quartic_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
+  if (!bytes || ncomp < 1 || ncomp > 2 || k < 1 || k > QKMAX) return PLFEM_EINVAL;
+  const size_t np = (size_t)quartic_pairs(k);
+  *bytes = (int64_t)(align256(np * np * sizeof(double)) +
+                     (size_t)quartic_slices(k) * quartic_tile_pairs(k) * QP * QP * sizeof(double));
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_mode_quartic(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                  const double* cores_host, int32_t ncore, double w_core, double w_clad, void* work_dev,
+                                  int64_t work_bytes, double* out_host) {
+  if (!L) return PLFEM_EINVAL;
+  if (ncomp < 1 || ncomp > 2 || k < 1 || k > QKMAX)
+    return set_loc_err(L, "plfem_mode_quartic: ncomp must be 1 or 2 and 1 <= k <= 64", PLFEM_EINVAL);
+  if (ncore > MAX_CORES) return set_loc_err(L, "plfem_mode_quartic: at most 64 cores", PLFEM_EINVAL);
+  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host))
+    return set_loc_err(L, "plfem_mode_quartic: null array", PLFEM_EINVAL);
+  if (indexed && L->nsolve == 0) return set_loc_err(L, "plfem_mode_quartic: the analysis has no interior DOFs", PLFEM_EINVAL);
+  int64_t need = 0;
+  plfem_quartic_work_bytes(ncomp, k, &need);
+  int rc = check_work(L, "plfem_mode_quartic", "plfem_quartic_work_bytes", work_dev, work_bytes, need);
+  if (rc) return rc;
+  rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
+  if (rc) return rc;
+  const CoreTable ct = pack_cores(cores_host, ncore);
+  const int np = quartic_pairs(k), nt = quartic_tiles(k), ntp = quartic_tile_pairs(k);
+  const int nblk = std::max(1, std::min(quartic_slices(k), L->ne));
+  const int64_t nrows = indexed ? L->nsolve : L->N;
+  double* O = (double*)work_dev;
+  double* partial = (double*)((char*)work_dev + align256((size_t)np * np * sizeof(double)));
+  const dim3 grid(nblk, ntp);
+  const int nc = ncore < 0 ? -1 : (int)ncore;
+  if (ncomp == 2)
+    hipLaunchKernelGGL(k_mode_quartic<2>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
+                       ct, nc, w_core, w_clad, np, nt, partial);
+  else
+    hipLaunchKernelGGL(k_mode_quartic<1>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
+                       ct, nc, w_core, w_clad, np, nt, partial);
+  rc = check_hip(L, hipGetLastError(), "k_mode_quartic");
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_quartic_reduce, dim3(ntp, 1, QP * QP / 256), dim3(256), 0, L->stream, np, nt, nblk, partial, O);
+  rc = check_hip(L, hipGetLastError(), "k_quartic_reduce");
+  if (rc) return rc;
+  rc = check_hip(L, hipMemcpyAsync(out_host, O, sizeof(double) * np * np, hipMemcpyDeviceToHost, L->stream), "hipMemcpyAsync");
+  if (rc) return rc;
+  return check_hip(L, hipStreamSynchronize(L->stream), "hipStreamSynchronize");
 }

@@ -1,6 +1,6 @@
 // The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
 // integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
-// k_field_overlap, k_mode_grams).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// k_field_overlap, k_mode_grams, k_mode_quartic).  One definition, so that a quadrature point lands in the same region, and det J rounds
 // the same way, in the assembly and in every kernel that must reproduce it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +19,26 @@ __constant__ double c_qy[6] = {0.445948490915965, 0.445948490915965, 0.108103018
                                0.091576213509771, 0.091576213509771, 0.816847572980458};
 __constant__ double c_qw[6] = {0.1116907948390055, 0.1116907948390055, 0.1116907948390055,
                                0.054975871827661, 0.054975871827661, 0.054975871827661};
+
+// 16-point degree-8 rule on the reference triangle (Dunavant 1985; positive interior weights summing to 1/2), the digits
+// polished to 20 places on the rule's moment equations: the products of four P2 fields of k_mode_quartic.  The centroid,
+// three 3-point orbits (a, a), then the 6-point orbit of (0.00839..., 0.26311...).  The Python copy is
+// pl_fem_vectoriel_amd/nonlinear.py (QUAD16_X / QUAD16_W).
+__constant__ double c_q16x[16] = {
+    0.33333333333333333333, 0.45929258829272315603, 0.45929258829272315603, 0.081414823414553687942,
+    0.17056930775176020662, 0.17056930775176020662, 0.65886138449647958676, 0.050547228317030975458,
+    0.050547228317030975458, 0.89890554336593804908, 0.0083947774099576053372, 0.0083947774099576053372,
+    0.26311282963463811342, 0.26311282963463811342, 0.72849239295540428124, 0.72849239295540428124};
+__constant__ double c_q16y[16] = {
+    0.33333333333333333333, 0.45929258829272315603, 0.081414823414553687942, 0.45929258829272315603,
+    0.17056930775176020662, 0.65886138449647958676, 0.17056930775176020662, 0.050547228317030975458,
+    0.89890554336593804908, 0.050547228317030975458, 0.26311282963463811342, 0.72849239295540428124,
+    0.0083947774099576053372, 0.72849239295540428124, 0.0083947774099576053372, 0.26311282963463811342};
+__constant__ double c_q16w[16] = {
+    0.072157803838893584126, 0.047545817133642312397, 0.047545817133642312397, 0.047545817133642312397,
+    0.051608685267359125141, 0.051608685267359125141, 0.051608685267359125141, 0.016229248811599040155,
+    0.016229248811599040155, 0.016229248811599040155, 0.013615157087217497132, 0.013615157087217497132,
+    0.013615157087217497132, 0.013615157087217497132, 0.013615157087217497132, 0.013615157087217497132};
 
 // IEEE product kept out of fused multiply-adds: hipcc's default -ffp-contract=fast ignores the contract pragma.  det J
 // of a sliver element cancels to ~1e-8 of its terms, so its two products must round individually (as the reference's

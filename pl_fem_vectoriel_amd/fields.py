@@ -10,7 +10,9 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
 * :func:`mode_overlap` -- ``O[i, j] = integral over mesh B of w(x) u_a,i . u_b,j`` with mesh B's six-point rule, A's
   values located and evaluated inside the kernel (``plfem_field_overlap``);
 * :meth:`ModeFields.grams` -- the k x k Grams of one mesh's modes under the assembly's element forms, split by material
-  region (``plfem_mode_grams``): what :mod:`.dispersion` builds the group index and the k0-derivative coupling from.
+  region (``plfem_mode_grams``): what :mod:`.dispersion` builds the group index and the k0-derivative coupling from;
+* :meth:`ModeFields.quartic` -- the packed overlap of products of four modes on a 16-point degree-8 rule
+  (``plfem_mode_quartic``): what :mod:`.nonlinear` builds the nonlinear coupling tensor, A_eff and gamma from.
 
 Containment (``PLFEM_LOC_TOL``): a point is inside an element when every barycentric coordinate is >= -1e-10 (minus
 that coordinate's floating-point rounding bound, which matters on sliver elements only); when
@@ -258,6 +260,50 @@ class ModeFields:
                                                cores.shape[0], ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
                                                out.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_grams")
         return {nm: out[i] for i, nm in enumerate(names)}
+
+    def quartic(self, modes: Sequence[Dict], geometry=None, weights=(1.0, 1.0)) -> np.ndarray:
+        """Packed quartic overlap of the modes over this mesh (``plfem_mode_quartic``), np x np with np = k (k + 1) / 2:
+        ``Q[p(i,j), p(l,m)] = sum over the elements and the 16-point degree-8 rule of |det J| w_q wt(x_q) (u_i . u_j)
+        (u_l . u_m)``, pairs i <= j numbered ``p(i,j) = i k - i (i - 1) / 2 + (j - i)`` (:func:`.nonlinear.pair_index`),
+        transverse dot product for vectorial records.  ``geometry=None``: wt = 1; otherwise wt = ``weights[0]`` in the
+        closed core discs of the assembly's core test and ``weights[1]`` outside.  At most 64 modes."""
+        kind, vals, _ = self._check_records(modes)
+        if kind is None:
+            return np.zeros((0, 0))
+        k = vals.shape[1]
+        if k > 64:
+            raise ValueError(f"at most 64 modes per quartic overlap, got {k}")
+        try:
+            wc, wl = (float(v) for v in weights)
+        except (TypeError, ValueError):
+            raise ValueError("weights must be two numbers (core, cladding)") from None
+        if geometry is None:
+            cores, ncore = np.zeros((0, 3)), -1
+        else:
+            if not all(hasattr(geometry, a) for a in ("positions", "core_radii")):
+                raise ValueError("geometry must have positions and core_radii")
+            if not (np.isfinite(wc) and np.isfinite(wl)):
+                raise ValueError("weights must be finite")
+            cores = _core_table(geometry)
+            ncore = cores.shape[0]
+            if ncore > 64:
+                raise ValueError("at most 64 cores")
+        self._ensure_locator()
+        import torch
+        ncomp = vals.shape[0]
+        need = ctypes.c_int64(0)
+        if self._lib.plfem_quartic_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
+            raise ValueError(f"plfem_quartic_work_bytes rejected ncomp = {ncomp}, k = {k}")
+        staged, _src = self._stage(vals)
+        work = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=self.tdev)
+        aligned = (work.data_ptr() + 255) & ~255
+        npair = k * (k + 1) // 2
+        out = np.empty((npair, npair), dtype=np.float64)
+        self._check(self._lib.plfem_mode_quartic(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
+                                                 1 if kind == "vectorial" else 0, cores.ctypes.data_as(ctypes.c_void_p),
+                                                 ncore, wc, wl, ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
+                                                 out.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_quartic")
+        return out
 
     def close(self):
         if getattr(self, "_loc", None):
