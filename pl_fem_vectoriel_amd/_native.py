@@ -43,8 +43,8 @@ EXPORTS = (
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
 # the test hooks (include/plfem.h under PLFEM_TEST_HOOKS): exported by the add-on libplfem_testhooks.so ONLY
-TEST_HOOK_EXPORTS = ("plfem_debug_factor_until", "plfem_debug_copy", "plfem_debug_solve_block", "plfem_debug_symeig",
-                     "plfem_debug_symeig_band", "plfem_debug_set_perturb")
+TEST_HOOK_EXPORTS = ("plfem_debug_factor_until", "plfem_debug_copy", "plfem_debug_symeig", "plfem_debug_symeig_band",
+                     "plfem_debug_set_perturb")
 MAX_NCV = 320                       # PLFEM_MAX_NCV of include/plfem.h
 PROF_SLOTS = ("k_fwd", "fwd_sweep", "bwd_sweep", "spmv_b")
 
@@ -225,7 +225,6 @@ def load_test_hooks() -> ctypes.CDLL:
     h = ctypes.CDLL(HOOKS_PATH)
     h.plfem_debug_factor_until.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     h.plfem_debug_copy.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
-    h.plfem_debug_solve_block.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
     h.plfem_debug_set_perturb.argtypes = [ctypes.c_void_p, ctypes.c_double]
     h.plfem_debug_symeig.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     h.plfem_debug_symeig_band.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
@@ -515,9 +514,6 @@ class Context:
         self._check(load_test_hooks().plfem_debug_copy(self._h, name.encode(), ctypes.c_int64(int(offset)),
                                                        ctypes.c_int64(int(count)), _ptr(out)), "plfem_debug_copy")
         return out
-
-    def debug_solve_block(self, reps: int = 1, front_filter: int = 0):
-        self._check(load_test_hooks().plfem_debug_solve_block(self._h, int(reps), int(front_filter)), "plfem_debug_solve_block")
 
     def debug_set_perturb(self, value: float):
         """Fault injection: D^-1 of the root front scaled by ``1 + value`` after every factorisation (0 = off)."""

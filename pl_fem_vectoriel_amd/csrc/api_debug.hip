@@ -60,21 +60,6 @@ extern "C" int plfem_debug_factor_until(plfem_ctx* c, double sigma, int32_t leve
   return check_launch(c, "debug factor");
 }
 
-// timing aid: reps block solves (BLOCK_P right-hand sides out of the Lanczos work buffers) with an optional front
-// filter (0 all fronts, 1 skip fronts with more than 128 owned DOFs, 2 only those: wrong results, kernel times only)
-extern "C" int plfem_debug_solve_block(plfem_ctx* c, int32_t reps, int32_t filter) {
-  if (!c || reps < 1) return PLFEM_EINVAL;
-  if (!c->factored) { c->err = "debug solve before factor"; return PLFEM_ESTATE; }
-  if (c->max_block_p < plfem::BLOCK_P) { c->err = "plfem_debug_solve_block: the LDS budget of this context allows one right-hand side per sweep only"; return PLFEM_EINVAL; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemsetAsync(c->d_bw, 0, sizeof(double) * c->n2 * plfem::BLOCK_P, c->stream));
-  c->debug_sweep_filter = filter;
-  for (int r = 0; r < reps; ++r) plfem::launch_solve_block(c, c->d_bw, c->d_w, c->n2, false);
-  c->debug_sweep_filter = 0;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return check_launch(c, "debug solve block");
-}
-
 extern "C" int plfem_debug_copy(plfem_ctx* c, const char* name, int64_t offset, int64_t count, double* out_host) {
   if (!c || !name || !out_host || offset < 0 || count < 0) return PLFEM_EINVAL;
   std::string n(name);

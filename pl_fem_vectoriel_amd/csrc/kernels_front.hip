@@ -1030,8 +1030,7 @@ void launch_factor(plfem_ctx* c, double sigma, int stop_level, int stop_step, in
       }
       // (measured on C1, level of 2048 / 1024 / 512 / 256 / 128 fronts: 678 / 257 / 399 / 539 / 441 us with one column
       // workgroup per front, 749 / 256 / 332 / 383 / 321 us with up to four)
-      static const int col_cap = getenv("PLFEM_COLUMN_WGS_CAP") ? std::max(1, atoi(getenv("PLFEM_COLUMN_WGS_CAP"))) : 0;
-      const int cap = col_cap > 0 ? col_cap : (li.count >= 1024 ? 1 : 4);
+      const int cap = li.count >= 1024 ? 1 : 4;
       const int n_pan = n_look > 0 ? panel_wgs(hpm[n_look - 1] - (k0 + NB) - 16, cap) : 1;
       const unsigned gridB = (unsigned)(n_look * n_pan + un + nact * (n_inv + 1));
       if ((kb & 1) == 0)

@@ -773,17 +773,15 @@ void launch_panel_axpy_block(plfem_ctx* c, const double* Pm, int ncols, const do
 }
 
 // first Gram-Schmidt pass over ncols <= 8 columns, fused with the permutation of the sweeps' result (d_xl, front order)
-// into W (global order): h -> Hout, W -= Vm h
+// into W (global order): h -> Hout, W -= Vm h.  (8 columns x P sums per thread: the two kernels are written for P = 4)
 void launch_first_pass_block(plfem_ctx* c, const double* BVm, const double* Vm, int ncols, double* W, int64_t ldw, double* Hout,
                              int ldh) {
   constexpr int P = BLOCK_P;
-  if constexpr (P == 4) {            // (8 columns x P sums per thread: the two kernels are written for P = 4; see lanczos_block)
-    const int nseg = (int)((c->n2 + FIRST_ROWS - 1) / FIRST_ROWS);      // (= npartial: PANEL_CHUNK rows per partial sum)
-    hipLaunchKernelGGL(k_permute_dot_first<P>, dim3(nseg), dim3(256), 0, c->stream, c->n2, c->N, nseg, ncols, c->d_npos, c->d_xl, W, ldw,
-                       BVm, c->d_partial);
-    hipLaunchKernelGGL(k_axpy_first<P>, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), 0, c->stream, c->n2, ncols, nseg, Vm,
-                       c->d_partial, Hout, ldh, W, ldw);
-  }
+  const int nseg = (int)((c->n2 + FIRST_ROWS - 1) / FIRST_ROWS);      // (= npartial: PANEL_CHUNK rows per partial sum)
+  hipLaunchKernelGGL(k_permute_dot_first<P>, dim3(nseg), dim3(256), 0, c->stream, c->n2, c->N, nseg, ncols, c->d_npos, c->d_xl, W, ldw,
+                     BVm, c->d_partial);
+  hipLaunchKernelGGL(k_axpy_first<P>, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), 0, c->stream, c->n2, ncols, nseg, Vm,
+                     c->d_partial, Hout, ldh, W, ldw);
 }
 
 void launch_chol_block(plfem_ctx* c, const double* G, int ldg, double* Tblk, int ldT, double* Rinv) {
@@ -858,8 +856,7 @@ void post_enqueue(plfem_ctx* c, int k, double* evecs, int ncore, double* modes_i
   hipLaunchKernelGGL(k_core_mask, dim3((N + 255) / 256), dim3(256), 0, st, N, c->d_doflocs, c->d_cores, ncore,
                      c->d_bmask, c->d_coremask, c->d_counters);
   const int nblocks = (N + POST_ROWS - 1) / POST_ROWS;
-  static const int post_group = getenv("PLFEM_POST_GROUP") ? std::max(1, atoi(getenv("PLFEM_POST_GROUP"))) : POST_GROUP;   // (tuning aid)
-  const int group = group_done ? post_group : k;
+  const int group = group_done ? POST_GROUP : k;
   for (int g0 = 0; g0 < k; g0 += group) {
     const int kg = std::min(group, k - g0);
     double* ev = evecs + (int64_t)g0 * c->n2;

@@ -26,35 +26,14 @@
 // their columns in the mirrored upper storage.  Backward: row form (contiguous columns of the lower storage)
 // except at the leaf level.  The cross-lane sums of the row forms use multi_reduce.  Deterministic throughout.
 #include <algorithm>
-#include <cstdlib>
 
 #include "device.h"
-
-#ifndef PLFEM_SWEEP_TB
-#define PLFEM_SWEEP_TB 8
-#endif
-#ifndef PLFEM_SWEEP_TB_FWD_TILE
-#define PLFEM_SWEEP_TB_FWD_TILE 8
-#endif
-#ifndef PLFEM_SWEEP_TB_BWD
-#define PLFEM_SWEEP_TB_BWD 8
-#endif
-#ifndef PLFEM_SWEEP_ROWLOADS
-#define PLFEM_SWEEP_ROWLOADS 8
-#endif
-#ifndef PLFEM_SWEEP_LD_TILE_DEFAULT
-#define PLFEM_SWEEP_LD_TILE_DEFAULT 4
-#endif
-#ifndef PLFEM_SWEEP_LD_ROWS_DEFAULT
-#define PLFEM_SWEEP_LD_ROWS_DEFAULT 4
-#endif
 
 namespace plfem {
 namespace {
 
 struct SweepArgs {
   int leaf_level;
-  int dbg;                         // timing experiments only (plfem_debug_solve_block): 1 skip fronts with s2 > 128, 2 only those
   int ldv;                         // row forms: leading dimension of the staged vector in LDS (component-major [u][i])
   int sh;                          // unknowns per node - 1: node of a local DOF = i >> sh, component = i & sh
   const int32_t *cinv0, *cinv1, *prow;
@@ -168,11 +147,10 @@ struct FwdOut {
 // forms now owns a row pair (2 rp, 2 rp + 1), rp = lane & 31, and the two halves of a wave take two different columns of
 // the same 64-row tile: one wave-level load = 2 columns x 64 rows = two 512-byte runs.  The halves' sums meet by one
 // v_permlane32-style shuffle (lane ^ 32) before the waves' sums meet in LDS as before.
-constexpr int TB = PLFEM_SWEEP_TB;      // matrix loads in flight per lane and trip (a long front is a chain of such trips)
-template <int P, int NW, int TBF = TB>
+// TBF: matrix loads in flight per lane and trip (a long front is a chain of such trips)
+template <int P, int NW, int TBF>
 __device__ __forceinline__ void fwd_tile_body(const SweepArgs& A, const SweepJob& J, double* __restrict__ sv, double* __restrict__ red) {
   const int f = J.f, m = J.m, s2 = J.s2;
-  if (A.dbg && ((A.dbg == 1) == (s2 > 128))) return;
   const int r0 = (J.rb & ~SWEEP_ROW_JOB_FLAG) * 64;
   const int64_t np = J.np;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -273,11 +251,10 @@ __device__ __forceinline__ void fwd_tile_body(const SweepArgs& A, const SweepJob
 // ---- forward, row form -------------------------------------------------------------------------------------------
 // (16-byte loads: the lane index runs along the row's contiguous run, two entries per lane; the staged vector is read as
 // double2 from its [u][i] planes, whose leading dimension ldv is even)
-template <int P, int NW, int R, int LOADS = PLFEM_SWEEP_ROWLOADS>
+template <int P, int NW, int R, int LOADS>
 __device__ __forceinline__ void fwd_rows_body(const SweepArgs& A, const SweepJob& J, double* __restrict__ sv) {
   constexpr int RB = NW * R, UNR = LOADS / R, V = R * P;
   const int f = J.f, m = J.m, s2 = J.s2;
-  if (A.dbg && ((A.dbg == 1) == (s2 > 128))) return;
   const int j0 = (J.rb & ~SWEEP_ROW_JOB_FLAG) * RB;
   const int64_t np = J.np;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -407,10 +384,9 @@ __device__ __forceinline__ void stage_bwd_rest(const SweepArgs& A, double* sv, i
   }
 }
 
-template <int P, int NW, int TBB = PLFEM_SWEEP_TB_BWD>
+template <int P, int NW, int TBB>
 __device__ __forceinline__ void bwd_tile_body(const SweepArgs& A, const SweepJob& J, double* __restrict__ sv, double* __restrict__ red) {
   const int rb = J.rb, m = J.m, s2 = J.s2;
-  if (A.dbg && ((A.dbg == 1) == (s2 > 128))) return;
   const int r0 = rb * 64;
   const int64_t np = J.np;
   const int64_t npp = J.npp;
@@ -495,12 +471,11 @@ __device__ __forceinline__ void bwd_tile_body(const SweepArgs& A, const SweepJob
 
 // Backward sweep, row form: x_j = sum_{i >= j} [L11^-1 ; Z](i, j) v_i with v = [ys ; -x_b] staged in LDS.
 // Column j of the lower storage is contiguous in i, so a wave reads 1-KB runs (two entries per lane, 16-byte loads); a wave
-// owns R rows (j0 + wave + NW q) and keeps R x 8/R loads in flight; a block (NW waves) shares one staged vector for NW R rows.
-template <int P, int NW, int R, int LOADS = PLFEM_SWEEP_ROWLOADS>
+// owns R rows (j0 + wave + NW q) and keeps R x LOADS/R loads in flight; a block (NW waves) shares one staged vector for NW R rows.
+template <int P, int NW, int R, int LOADS>
 __device__ __forceinline__ void bwd_rows_body(const SweepArgs& A, const SweepJob& J, double* __restrict__ sv) {
   constexpr int RB = NW * R, UNR = LOADS / R, V = R * P;
   const int rb = J.rb, m = J.m, s2 = J.s2;
-  if (A.dbg && ((A.dbg == 1) == (s2 > 128))) return;
   const int j0 = rb * RB;
   const int64_t np = J.np;
   const int64_t npp = J.npp;
@@ -575,20 +550,21 @@ __device__ __forceinline__ void bwd_rows_body(const SweepArgs& A, const SweepJob
 // The launch list comes as a kernel argument OF ITS OWN in front of the argument block: with kernel-argument preloading (Makefile:
 // -amdgpu-kernarg-preload-count) it sits in scalar registers when a wave starts, and the load of the workgroup's job record --
 // the head of every workgroup's chain of dependent memory round trips -- no longer waits for a load of the argument block.
-// LD = 16-byte matrix loads in flight per lane and trip (8: twice the bytes of round 3's eight 8-byte loads, at the price of
-// 16-28 more registers; 4: the same bytes in half the instructions); chosen per kernel form in sweeps() below
+// LD = 16-byte matrix loads in flight per lane and trip: 4, the bytes of round 3's eight 8-byte loads in half the instructions
+// (8 was measured and dropped: twice the bytes, at the price of 16-28 more registers).  Only LD = 4 is built; the parameter
+// stays in the kernel names because the committed counter files (profiles/r04_pmc_families_L*.json) key on them.
 template <int P, int R, int LD>
 __global__ __launch_bounds__(512) void k_fwd_rows(const SweepJob* __restrict__ blk, SweepArgs A) {
   extern __shared__ __attribute__((aligned(16))) double sv[];
   const SweepJob job = blk[blockIdx.x];
-  fwd_rows_body<P, 8, R, (LD < R ? R : LD)>(A, job, sv);
+  fwd_rows_body<P, 8, R, LD>(A, job, sv);
 }
 
 template <int P, int R, int LD>
 __global__ __launch_bounds__(512) void k_bwd_rows(const SweepJob* __restrict__ blk, SweepArgs A) {
   extern __shared__ __attribute__((aligned(16))) double sv[];
   const SweepJob job = blk[blockIdx.x];
-  bwd_rows_body<P, 8, R, (LD < R ? R : LD)>(A, job, sv);
+  bwd_rows_body<P, 8, R, LD>(A, job, sv);
 }
 
 // forward, tile form only (levels without a long front: the mixed kernel's register budget costs occupancy there)
@@ -605,7 +581,7 @@ __global__ __launch_bounds__(256) void k_fwd_mix(const SweepJob* __restrict__ bl
   extern __shared__ __attribute__((aligned(16))) double sv[];
   __shared__ __attribute__((aligned(16))) double red[4 * P * 64];
   const SweepJob job = blk[blockIdx.x];
-  if (job.rb & SWEEP_ROW_JOB_FLAG) fwd_rows_body<P, 4, 4, (LD < 4 ? 4 : LD)>(A, job, sv);
+  if (job.rb & SWEEP_ROW_JOB_FLAG) fwd_rows_body<P, 4, 4, LD>(A, job, sv);
   else fwd_tile_body<P, 4, LD>(A, job, sv, red);
 }
 
@@ -650,13 +626,9 @@ void sweeps(plfem_ctx* c) {
   hipStream_t st = c->stream;
   SweepArgs A;
   A.sh = c->sh;
-  A.dbg = c->debug_sweep_filter;
   A.cinv0 = c->d_cinv0; A.cinv1 = c->d_cinv1; A.prow = c->d_prow;
   A.front = c->d_front; A.dinv2 = reinterpret_cast<const double2*>(c->d_delta);
   A.fr = c->d_fvec; A.u0 = c->d_u0; A.u1 = c->d_u1; A.ys = c->d_fvec2; A.xl = c->d_xl;
-  // 16-byte loads in flight per lane: tile forms / row forms (PLFEM_SWEEP_LD_TILE, PLFEM_SWEEP_LD_ROWS = 4 | 8: tuning aid)
-  static const int ld_tile = getenv("PLFEM_SWEEP_LD_TILE") ? atoi(getenv("PLFEM_SWEEP_LD_TILE")) : PLFEM_SWEEP_LD_TILE_DEFAULT;
-  static const int ld_rows = getenv("PLFEM_SWEEP_LD_ROWS") ? atoi(getenv("PLFEM_SWEEP_LD_ROWS")) : PLFEM_SWEEP_LD_ROWS_DEFAULT;
   double sweep_total = 0.0;                     // algorithmic bytes of one whole sweep (either direction)
   for (const LevelInfo& li : c->levels) sweep_total += li.sweep_bytes + 8.0 * (P - 1) * li.sweep_vec_doubles;
   // Kernel form by level: fwd_block_rows / bwd_block_rows (device.h); workgroups come from the compact launch
@@ -673,21 +645,14 @@ void sweeps(plfem_ctx* c) {
     A.ldv = (li.max_s2 + 2) & ~1;                   // even: the row forms read the staged planes as double2
     const size_t lds = sizeof(double) * P * A.ldv;
     if (li.fwd_rows == 8) {
-      if (ld_rows == 8) hipLaunchKernelGGL((k_fwd_rows<P, 1, 8>), dim3(li.fwd_n), dim3(512), lds, st, blk, A);
-      else hipLaunchKernelGGL((k_fwd_rows<P, 1, 4>), dim3(li.fwd_n), dim3(512), lds, st, blk, A);
+      hipLaunchKernelGGL((k_fwd_rows<P, 1, 4>), dim3(li.fwd_n), dim3(512), lds, st, blk, A);
     } else if (li.fwd_rows == 16) {
-      if (ld_rows == 8) hipLaunchKernelGGL((k_fwd_rows<P, 2, 8>), dim3(li.fwd_n), dim3(512), lds, st, blk, A);
-      else hipLaunchKernelGGL((k_fwd_rows<P, 2, 4>), dim3(li.fwd_n), dim3(512), lds, st, blk, A);
+      hipLaunchKernelGGL((k_fwd_rows<P, 2, 4>), dim3(li.fwd_n), dim3(512), lds, st, blk, A);
     } else {
       // optional live timing of this kernel (bench.py roofline): HIP events on the launch stream
       const int pid = time_launches ? prof_open(c, PLFEM_PROF_KFWD, li.sweep_bytes + 8.0 * (P - 1) * li.sweep_vec_doubles) : -1;
-      if (li.fwd_mixed) {
-        if (ld_tile == 8) hipLaunchKernelGGL((k_fwd_mix<P, 8>), dim3(li.fwd_n), dim3(256), lds, st, blk, A);
-        else hipLaunchKernelGGL((k_fwd_mix<P, 4>), dim3(li.fwd_n), dim3(256), lds, st, blk, A);
-      } else {
-        if (ld_tile == 8) hipLaunchKernelGGL((k_fwd<P, 8>), dim3(li.fwd_n), dim3(256), lds, st, blk, A);
-        else hipLaunchKernelGGL((k_fwd<P, 4>), dim3(li.fwd_n), dim3(256), lds, st, blk, A);
-      }
+      if (li.fwd_mixed) hipLaunchKernelGGL((k_fwd_mix<P, 4>), dim3(li.fwd_n), dim3(256), lds, st, blk, A);
+      else hipLaunchKernelGGL((k_fwd<P, 4>), dim3(li.fwd_n), dim3(256), lds, st, blk, A);
       prof_close(c, pid);
     }
   }
@@ -700,16 +665,12 @@ void sweeps(plfem_ctx* c) {
     const SweepJob* blk = c->d_blk + li.bwd_off;
     A.ldv = (li.max_m + 2) & ~1;
     const size_t lds = sizeof(double) * P * A.ldv;
-    if (li.bwd_rows == 8) {        // few large fronts: one row per wave, most blocks
-      if (ld_rows == 8) hipLaunchKernelGGL((k_bwd_rows<P, 1, 8>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
-      else hipLaunchKernelGGL((k_bwd_rows<P, 1, 4>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
-    } else if (li.bwd_rows == 16) {
-      if (ld_rows == 8) hipLaunchKernelGGL((k_bwd_rows<P, 2, 8>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
-      else hipLaunchKernelGGL((k_bwd_rows<P, 2, 4>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
-    } else {                       // leaf level: tile form
-      if (ld_tile == 8) hipLaunchKernelGGL((k_bwd<P, 8>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
-      else hipLaunchKernelGGL((k_bwd<P, 4>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
-    }
+    if (li.bwd_rows == 8)          // few large fronts: one row per wave, most blocks
+      hipLaunchKernelGGL((k_bwd_rows<P, 1, 4>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
+    else if (li.bwd_rows == 16)
+      hipLaunchKernelGGL((k_bwd_rows<P, 2, 4>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
+    else                           // leaf level: tile form
+      hipLaunchKernelGGL((k_bwd<P, 4>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
   }
   prof_close(c, pid_bwd);
 }

@@ -2,7 +2,6 @@
 #include "plan.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <functional>
 
 #include "symbolic.h"
@@ -27,7 +26,6 @@ void build_launch_plan(const Symbolic& S, LaunchPlan& P, const PlanTasks& par) {
   std::vector<int32_t>& forder = P.forder;
   P.forder_s2.assign(nf, 0);
   P.forder_maxm.assign(nf, 0);
-  const int mix_big_s2 = getenv("PLFEM_MIX_BIG_S2") ? atoi(getenv("PLFEM_MIX_BIG_S2")) : MIX_BIG_S2;   // (tuning aid)
   auto cdiv = [](int a, int b) { return (a + b - 1) / b; };
   // ---- the generators of the workgroup lists: out == nullptr counts, else fills; both passes run the same code ----------
   // sweep workgroups of one level and direction (launch order: decreasing s2)
@@ -42,7 +40,7 @@ void build_launch_plan(const Symbolic& S, LaunchPlan& P, const PlanTasks& par) {
     for (int q = 0; q < li.count; ++q) {
       const int f = o[q];
       if (fwd) {
-        if (li.fwd_rows == 64 && fs2[f] > mix_big_s2)          // long front of a tile-form level: row-form workgroups
+        if (li.fwd_rows == 64 && fs2[f] > MIX_BIG_S2)          // long front of a tile-form level: row-form workgroups
           for (int t = 0; t * 16 < fm[f]; ++t) put(f, t | SWEEP_ROW_JOB_FLAG);
         else
           for (int t = 0; t * li.fwd_rows < fm[f]; ++t) put(f, t);
@@ -146,7 +144,7 @@ void build_launch_plan(const Symbolic& S, LaunchPlan& P, const PlanTasks& par) {
     li.fwd_rows = fwd_block_rows(li.count);
     li.bwd_rows = bwd_block_rows(li.count, lev == L);
     for (int q = 0; q < li.count; ++q)
-      if (li.fwd_rows == 64 && fs2[o[q]] > mix_big_s2) li.fwd_mixed = true;
+      if (li.fwd_rows == 64 && fs2[o[q]] > MIX_BIG_S2) li.fwd_mixed = true;
     Counts& c = cnt[lev];
     c.fwd = gen_jobs(lev, true, nullptr);
     c.bwd = gen_jobs(lev, false, nullptr);

@@ -64,7 +64,6 @@ struct Pool {
   std::mutex mu;
   std::condition_variable cv;
   std::atomic<bool> active{false}, stop{false}, failed{false};
-  const double linger_ms = getenv("PLFEM_POOL_LINGER_MS") ? atof(getenv("PLFEM_POOL_LINGER_MS")) : 0.0;
   std::exception_ptr error;              // first exception thrown inside a worker's job (rethrown by the leader's join)
   explicit Pool(int n);
   ~Pool() {
@@ -145,31 +144,22 @@ Pool::Pool(int n) : nt(n), slots(new Slot[n]) {
       uint32_t seen = 0;
       while (true) {
         // Wait for the next job.  Inside an analysis (active): spin.  Between analyses the workers park on the condition
-        // variable -- after lingering (still spinning, as OpenMP runtimes do after a parallel region) for PLFEM_POOL_LINGER_MS
-        // if that is set.  Workers woken from a condition variable come up on idle cores (deep C-state, cold caches): measured
-        // on the MI355X host, the analysis of C1 takes 3.7 ms that way against 2.85 ms back to back.  But lingering is OFF by
-        // default: the GPU boxes give a process a CPU QUOTA (16 cores per GPU), and 15 + 7 workers spinning through the 17 ms
-        // of GPU work between two cold solves exhaust it -- the kernel then throttles the whole process for the rest of the
-        // accounting period: every third step of the bench took 50 ms instead of 21 (measured with a linger of 30 ms).
-        clk::time_point idle_since{};
-        bool idle = false;
+        // variable at once.  (Lingering -- still spinning for a while, as OpenMP runtimes do after a parallel region -- was
+        // measured and dropped: workers woken from a condition variable come up on idle cores (deep C-state, cold caches), and
+        // on the MI355X host the analysis of C1 takes 3.7 ms that way against 2.85 ms back to back; but the GPU boxes give a
+        // process a CPU QUOTA (16 cores per GPU), and 15 + 7 workers spinning through the 17 ms of GPU work between two cold
+        // solves exhaust it -- the kernel then throttles the whole process for the rest of the accounting period: every third
+        // step of the bench took 50 ms instead of 21 with a linger of 30 ms.)
         for (int spins = 0; s.seq.load(std::memory_order_acquire) == seen; ++spins) {
           if (stop.load(std::memory_order_acquire)) return;
           if (active.load(std::memory_order_acquire)) {
-            if (idle) { idle = false; spins = 0; }
             cpu_relax(spins);
             continue;
           }
           if (spins <= 256) { __builtin_ia32_pause(); continue; }     // (the owner may be about to post the last jobs)
-          if (!idle) { idle = true; idle_since = clk::now(); }
-          if (linger_ms > 0 && ((spins & 1023) != 0 || secs(idle_since, clk::now()) * 1e3 < linger_ms)) {
-            __builtin_ia32_pause();
-            continue;
-          }
           std::unique_lock<std::mutex> lk(mu);
           cv.wait(lk, [&] { return active.load(std::memory_order_acquire) || stop.load(std::memory_order_acquire); });
           if (stop.load(std::memory_order_acquire)) return;
-          idle = false;
           spins = 0;
         }
         seen = s.seq.load(std::memory_order_acquire);
@@ -706,7 +696,7 @@ void nd_tree(Symbolic& S, const double* p, int leaf_elems, int nthreads) {
     if (n >= 192 && n >= 4 * min_side) {
       // both children must stay within a factor RHO of the ideal size ne / 2^(level+1): bounds the
       // leaf-size spread by RHO overall (no compounding), so batched front kernels stay balanced
-      static const double RHO = getenv("PLFEM_RHO") ? atof(getenv("PLFEM_RHO")) : 2.2;
+      constexpr double RHO = 2.2;
       const double ideal = (double)ne / (double)((int64_t)2 << level);
       const double clo = ideal / RHO, chi = ideal * RHO;
       const double a0s[2] = {x0, y0};
@@ -761,7 +751,7 @@ void nd_tree(Symbolic& S, const double* p, int leaf_elems, int nthreads) {
         const double cx = g.c[0] - O[0], cy = g.c[1] - O[1];
         return std::min(NBIN - 1, std::max(0, (int)(std::sqrt(cx * cx + cy * cy) * rscale)));
       };
-      static const int RADIAL_MIN = getenv("PLFEM_RADIAL_MIN") ? atoi(getenv("PLFEM_RADIAL_MIN")) : 2000;   // circular cuts pay in subdomains that still hold a whole core (measured: C1 flops 25.1 -> 24.7 G, level steps 125 -> 116)
+      constexpr int RADIAL_MIN = 2000;   // circular cuts pay in subdomains that still hold a whole core (measured: C1 flops 25.1 -> 24.7 G, level steps 125 -> 116)
       if (n < RADIAL_MIN) rscale = 0.0;
       if (rscale > 0.0) {
         auto rhist = [&](int64_t b, int64_t e_, int tid) {
@@ -871,7 +861,7 @@ void nd_tree(Symbolic& S, const double* p, int leaf_elems, int nthreads) {
   const int nteam = nthreads > 1 ? team_size() : 1;
   if (nteam > 1) {
     // ~2 subtrees per thread (uneven subtrees: dynamic hand-out evens them out)
-    const int want = getenv("PLFEM_TREE_SUBTREES") ? atoi(getenv("PLFEM_TREE_SUBTREES")) : 2 * nteam;
+    const int want = 2 * nteam;
     while ((1 << top) < want) ++top;
     top = std::min(top, L);
   }
@@ -1205,10 +1195,8 @@ std::string build_symbolic(int nv, int ne, const double* p, const int32_t* t, in
       err_side = std::string("exception in the numbering chain: ") + e.what();
     }
   };
-  static const bool chains_in_sequence = getenv("PLFEM_SYM_SEQUENTIAL") != nullptr;   // (A/B timing aid)
-  static const int side_share = getenv("PLFEM_SIDE_THREADS") ? atoi(getenv("PLFEM_SIDE_THREADS")) : 0;
-  if (nthreads > 1 && !chains_in_sequence) {
-    const int n_side = std::min(nthreads - 1, std::max(1, side_share > 0 ? side_share : (nthreads + 1) / 3));
+  if (nthreads > 1) {
+    const int n_side = (nthreads + 1) / 3;       // (in [1, nthreads - 1] for nthreads >= 2)
     team_fork2(nthreads - n_side, [&] { nd_tree(S, p, leaf_elems, nthreads); }, side);
   } else {
     side();
@@ -1221,7 +1209,7 @@ std::string build_symbolic(int nv, int ne, const double* p, const int32_t* t, in
   auto t4 = clk::now();
   S.t_numbering = secs(t0, t1) + t_num;        // (with a pool: t_num and t_pattern overlap the tree)
   S.t_pattern = t_side;
-  S.t_tree = secs(t1, t3) - (nthreads > 1 && !chains_in_sequence ? 0.0 : t_num + t_side);
+  S.t_tree = secs(t1, t3) - (nthreads > 1 ? 0.0 : t_num + t_side);
   S.t_fronts = secs(t3, t4);
   return err;
 }
