@@ -399,6 +399,20 @@ int plfem_debug_symeig_band(int32_t n, int32_t b, const double* a_host, int32_t 
 /* fault injection for the a-posteriori guard: from the next plfem_factor on, D^-1 of the root front is scaled by
  * 1 + value after every factorisation (0 = off) */
 int plfem_debug_set_perturb(plfem_ctx* ctx, double value);
+/* plfem_debug_solve_block: BLOCK_P (4) right-hand sides in global order, column u at rhs_dev + u ldx, through the block
+ * sweeps the block Lanczos driver runs (k_permute_in / k_permute_out and the P = 4 sweep kernels); the solutions go to
+ * the same columns of x_dev.  refine_steps passes of block iterative refinement against the assembled K = A - sigma B
+ * follow (block SpMVs; scratch: the Lanczos restart buffer, so 3 BLOCK_P ldx <= n2 (max_ncv + 1 + BLOCK_P)).  Nothing
+ * outside the n2 entries of each column is read or written.  PLFEM_ESTATE before plfem_factor; PLFEM_EINVAL when the
+ * LDS budget of the tree rules out P = 4 sweeps (largest front too large), when ldx < n2 or the scratch is too small.
+ * Synchronises.
+ * plfem_debug_level_plan: the context's launch plan, PLFEM_DEBUG_PLAN_FIELDS int64 per tree level (level 0 = root,
+ * cap >= that times L + 1): fronts, forward rows per workgroup (8 / 16: row form, 64: tile form), backward rows per
+ * workgroup (64: the leaf level's tile form), 1 if the forward launch is mixed (tiles + row jobs), largest s2, largest m,
+ * forward workgroups, backward workgroups, block steps of the factorisation, right-hand sides per sweep allowed. */
+#define PLFEM_DEBUG_PLAN_FIELDS 10
+int plfem_debug_solve_block(plfem_ctx* ctx, const double* rhs_dev, int64_t ldx, double* x_dev, int32_t refine_steps);
+int plfem_debug_level_plan(plfem_ctx* ctx, int64_t* out, int64_t cap);
 #endif /* PLFEM_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -44,7 +44,9 @@ SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", 
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
 # the test hooks (include/plfem.h under PLFEM_TEST_HOOKS): exported by the add-on libplfem_testhooks.so ONLY
 TEST_HOOK_EXPORTS = ("plfem_debug_factor_until", "plfem_debug_copy", "plfem_debug_symeig", "plfem_debug_symeig_band",
-                     "plfem_debug_set_perturb")
+                     "plfem_debug_set_perturb", "plfem_debug_solve_block", "plfem_debug_level_plan")
+# one record per tree level of plfem_debug_level_plan (PLFEM_DEBUG_PLAN_FIELDS of include/plfem.h)
+PLAN_FIELDS = ("count", "fwd_rows", "bwd_rows", "fwd_mixed", "max_s2", "max_m", "fwd_n", "bwd_n", "steps", "max_block_p")
 MAX_NCV = 320                       # PLFEM_MAX_NCV of include/plfem.h
 PROF_SLOTS = ("k_fwd", "fwd_sweep", "bwd_sweep", "spmv_b")
 
@@ -226,6 +228,8 @@ def load_test_hooks() -> ctypes.CDLL:
     h.plfem_debug_factor_until.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     h.plfem_debug_copy.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
     h.plfem_debug_set_perturb.argtypes = [ctypes.c_void_p, ctypes.c_double]
+    h.plfem_debug_solve_block.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32]
+    h.plfem_debug_level_plan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     h.plfem_debug_symeig.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     h.plfem_debug_symeig_band.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                           ctypes.c_void_p, ctypes.c_void_p]
@@ -518,6 +522,21 @@ class Context:
     def debug_set_perturb(self, value: float):
         """Fault injection: D^-1 of the root front scaled by ``1 + value`` after every factorisation (0 = off)."""
         self._check(load_test_hooks().plfem_debug_set_perturb(self._h, float(value)), "plfem_debug_set_perturb")
+
+    def debug_solve_block(self, rhs, x, ldx: int, refine_steps: int = 0):
+        """BLOCK_P right-hand sides (columns ``ldx`` apart in the flat device tensor ``rhs``) through the block sweeps into
+        the same columns of ``x`` (test hook ``plfem_debug_solve_block``)."""
+        self._check(load_test_hooks().plfem_debug_solve_block(self._h, ctypes.c_void_p(rhs.data_ptr()), ctypes.c_int64(int(ldx)),
+                                                              ctypes.c_void_p(x.data_ptr()), int(refine_steps)),
+                    "plfem_debug_solve_block")
+
+    def debug_level_plan(self):
+        """Per tree level (root first) a dict of ``PLAN_FIELDS``: the forms the sweeps and the factorisation launch."""
+        nl = self.sym.info["levels"] + 1
+        out = np.zeros(len(PLAN_FIELDS) * nl, dtype=np.int64)
+        self._check(load_test_hooks().plfem_debug_level_plan(self._h, _ptr(out), ctypes.c_int64(out.size)),
+                    "plfem_debug_level_plan")
+        return [dict(zip(PLAN_FIELDS, (int(v) for v in row))) for row in out.reshape(nl, len(PLAN_FIELDS))]
 
     def profile_begin(self, max_launches: int = 4096):
         self._check(self._lib.plfem_profile_begin(self._h, int(max_launches)), "plfem_profile_begin")

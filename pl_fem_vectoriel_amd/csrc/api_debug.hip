@@ -87,3 +87,54 @@ extern "C" int plfem_debug_copy(plfem_ctx* c, const char* name, int64_t offset, 
   HIP_TRY(c, hipMemcpy(out_host, src + offset, sizeof(double) * count, hipMemcpyDeviceToHost));
   return PLFEM_OK;
 }
+
+// BLOCK_P right-hand sides (global order, columns ldx apart) through the block sweeps, then refine_steps passes of block
+// iterative refinement against the assembled K = A - sigma B (the block SpMVs of the Lanczos driver's refined solve).
+// The refinement's scratch is the first 3 BLOCK_P columns (ldx apart) of d_V2, as in solve_block_refined.
+extern "C" int plfem_debug_solve_block(plfem_ctx* c, const double* rhs_dev, int64_t ldx, double* x_dev, int32_t refine_steps) {
+  constexpr int P = plfem::BLOCK_P;
+  if (!c || !rhs_dev || !x_dev || refine_steps < 0) return PLFEM_EINVAL;
+  if (!c->factored) { c->err = "debug block solve before plfem_factor"; return PLFEM_ESTATE; }
+  if (c->max_block_p < P) { c->err = "debug block solve: the LDS budget of this tree allows one right-hand side per sweep"; return PLFEM_EINVAL; }
+  if (ldx < c->n2) { c->err = "debug block solve: ldx < n2"; return PLFEM_EINVAL; }
+  const int64_t scratch = (int64_t)c->n2 * (c->max_ncv + 1 + P);
+  if (refine_steps > 0 && 3 * P * ldx > scratch) { c->err = "debug block solve: ldx too large for the refinement scratch"; return PLFEM_EINVAL; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  plfem::launch_solve_block(c, rhs_dev, x_dev, ldx);
+  double* ta = c->d_V2;
+  double* tb = c->d_V2 + (size_t)P * ldx;
+  double* dy = c->d_V2 + (size_t)2 * P * ldx;
+  for (int it = 0; it < refine_steps; ++it) {
+    plfem::launch_spmv_a_block(c, x_dev, ta, ldx);
+    plfem::launch_spmv_b_block(c, x_dev, tb, ldx);
+    for (int u = 0; u < P; ++u) {                 // column by column: the gaps between the columns stay untouched
+      const size_t o = (size_t)u * ldx;
+      plfem::launch_axpby_n(c, c->n2, -1.0, ta + o, c->sigma, tb + o, ta + o);     // ta = -A x + sigma B x
+      plfem::launch_axpby_n(c, c->n2, 1.0, rhs_dev + o, 1.0, ta + o, ta + o);      // ta = b - K x
+    }
+    plfem::launch_solve_block(c, ta, dy, ldx);
+    for (int u = 0; u < P; ++u) {
+      const size_t o = (size_t)u * ldx;
+      plfem::launch_axpby_n(c, c->n2, 1.0, x_dev + o, 1.0, dy + o, x_dev + o);
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return check_launch(c, "debug block solve");
+}
+
+// The launch plan the context's sweeps and factorisation run from, PLFEM_DEBUG_PLAN_FIELDS int64 per level (level 0 =
+// root): fronts, forward / backward rows per workgroup (64: tile form), mixed forward launch, largest s2, largest m,
+// forward / backward workgroups, block steps of the factorisation, right-hand sides per sweep the LDS budget allows.
+extern "C" int plfem_debug_level_plan(plfem_ctx* c, int64_t* out, int64_t cap) {
+  if (!c || !out) return PLFEM_EINVAL;
+  const int nl = (int)c->levels.size();
+  if (cap < (int64_t)PLFEM_DEBUG_PLAN_FIELDS * nl) { c->err = "debug level plan: cap too small"; return PLFEM_EINVAL; }
+  for (int l = 0; l < nl; ++l) {
+    const plfem::LevelInfo& li = c->levels[l];
+    const int next = l + 1 < nl ? c->levels[l + 1].step0 : (int)c->upd_n.size();
+    const int64_t rec[PLFEM_DEBUG_PLAN_FIELDS] = {li.count, li.fwd_rows, li.bwd_rows, li.fwd_mixed ? 1 : 0, li.max_s2, li.max_m,
+                                                  li.fwd_n, li.bwd_n, next - li.step0, c->max_block_p};
+    std::copy(rec, rec + PLFEM_DEBUG_PLAN_FIELDS, out + (int64_t)PLFEM_DEBUG_PLAN_FIELDS * l);
+  }
+  return PLFEM_OK;
+}
