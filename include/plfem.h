@@ -40,6 +40,7 @@ extern "C" {
 #define PLFEM_ESTATE (-5)   /* call order violated (e.g. solve before factor) -> RuntimeError */
 #define PLFEM_ESINGULAR (-6)/* factorisation broke down (sigma is an eigenvalue) -> RuntimeError */
 #define PLFEM_ERESIDUAL (-7)/* plfem_solve_modes: eigenpairs fail the a-posteriori check even after the refined pass -> RuntimeError */
+#define PLFEM_EHOST (-8)    /* host-side failure (out of memory, thread creation); the message has the cause -> RuntimeError */
 
 typedef struct plfem_symbolic plfem_symbolic; /* host-only, mesh-only analysis               */
 typedef struct plfem_ctx plfem_ctx;           /* device + stream + workspaces for one symbolic */

@@ -20,6 +20,7 @@ HOOKS_PATH = os.path.join(_HERE, "libplfem_testhooks.so")
 
 PLFEM_OK = 0
 PLFEM_EINVAL, PLFEM_EMESH, PLFEM_EHIP, PLFEM_ENOCONV, PLFEM_ESTATE, PLFEM_ESINGULAR, PLFEM_ERESIDUAL = -1, -2, -3, -4, -5, -6, -7
+PLFEM_EHOST = -8                    # host-side failure (out of memory, thread creation)
 BLOCKS = ("Axx", "Axy", "Ayx", "Ayy", "Minv", "Dxx", "Dxy", "Dyy")
 INFO_NAMES = ("nv", "ne", "nedges", "N", "nsolve", "nnz", "levels", "nfronts", "front_doubles", "max_front",
               "solve_entries", "factor_flops", "t_numbering_us", "t_pattern_us", "t_tree_us", "t_fronts_us", "dofs_per_node",

@@ -14,25 +14,7 @@
 #endif
 #include "device.h"
 
-#define HIP_TRY(ctx, call)                                                                   \
-  do {                                                                                       \
-    hipError_t e__ = (call);                                                                 \
-    if (e__ != hipSuccess) {                                                                 \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                       \
-      return PLFEM_EHIP;                                                                     \
-    }                                                                                        \
-  } while (0)
-
 namespace {
-int check_launch(plfem_ctx* c, const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    c->err = std::string(what) + ": " + hipGetErrorString(e);
-    return PLFEM_EHIP;
-  }
-  return PLFEM_OK;
-}
-
 // a slightly wrong factor: D^-1 of the root front scaled by 1 + test_perturb after every factorisation
 void perturb_root_pivots(plfem_ctx* c) {
   if (c->test_perturb != 0.0)
@@ -40,27 +22,24 @@ void perturb_root_pivots(plfem_ctx* c) {
 }
 }  // namespace
 
-extern "C" int plfem_debug_set_perturb(plfem_ctx* c, double value) {
+extern "C" int plfem_debug_set_perturb(plfem_ctx* c, double value) try {
   if (!c) return PLFEM_EINVAL;
   c->test_perturb = value;
   c->test_post_factor = value != 0.0 ? perturb_root_pivots : nullptr;
   c->factored = false;              // takes effect at the next plfem_factor
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_debug_factor_until(plfem_ctx* c, double sigma, int32_t level, int32_t step, int32_t stage) {
+extern "C" int plfem_debug_factor_until(plfem_ctx* c, double sigma, int32_t level, int32_t step, int32_t stage) try {
   if (!c) return PLFEM_EINVAL;
   if (!c->assembled) { c->err = "debug factor before assemble"; return PLFEM_ESTATE; }
-  if (c->upload_pending) {               // (as plfem_factor: the front-level index arrays travel on the copy stream)
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_upload, 0));
-    c->upload_pending = false;
-  }
+  TRY(wait_for_upload(c));              // (as plfem_factor)
   plfem::launch_factor(c, sigma, level, step, stage);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return check_launch(c, "debug factor");
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_debug_copy(plfem_ctx* c, const char* name, int64_t offset, int64_t count, double* out_host) {
+extern "C" int plfem_debug_copy(plfem_ctx* c, const char* name, int64_t offset, int64_t count, double* out_host) try {
   if (!c || !name || !out_host || offset < 0 || count < 0) return PLFEM_EINVAL;
   std::string n(name);
   const double* src = nullptr;
@@ -86,12 +65,12 @@ extern "C" int plfem_debug_copy(plfem_ctx* c, const char* name, int64_t offset, 
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(out_host, src + offset, sizeof(double) * count, hipMemcpyDeviceToHost));
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
 // BLOCK_P right-hand sides (global order, columns ldx apart) through the block sweeps, then refine_steps passes of block
 // iterative refinement against the assembled K = A - sigma B (the block SpMVs of the Lanczos driver's refined solve).
 // The refinement's scratch is the first 3 BLOCK_P columns (ldx apart) of d_V2, as in solve_block_refined.
-extern "C" int plfem_debug_solve_block(plfem_ctx* c, const double* rhs_dev, int64_t ldx, double* x_dev, int32_t refine_steps) {
+extern "C" int plfem_debug_solve_block(plfem_ctx* c, const double* rhs_dev, int64_t ldx, double* x_dev, int32_t refine_steps) try {
   constexpr int P = plfem::BLOCK_P;
   if (!c || !rhs_dev || !x_dev || refine_steps < 0) return PLFEM_EINVAL;
   if (!c->factored) { c->err = "debug block solve before plfem_factor"; return PLFEM_ESTATE; }
@@ -120,12 +99,12 @@ extern "C" int plfem_debug_solve_block(plfem_ctx* c, const double* rhs_dev, int6
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return check_launch(c, "debug block solve");
-}
+} catch (...) { return host_failure(c); }
 
 // The launch plan the context's sweeps and factorisation run from, PLFEM_DEBUG_PLAN_FIELDS int64 per level (level 0 =
 // root): fronts, forward / backward rows per workgroup (64: tile form), mixed forward launch, largest s2, largest m,
 // forward / backward workgroups, block steps of the factorisation, right-hand sides per sweep the LDS budget allows.
-extern "C" int plfem_debug_level_plan(plfem_ctx* c, int64_t* out, int64_t cap) {
+extern "C" int plfem_debug_level_plan(plfem_ctx* c, int64_t* out, int64_t cap) try {
   if (!c || !out) return PLFEM_EINVAL;
   const int nl = (int)c->levels.size();
   if (cap < (int64_t)PLFEM_DEBUG_PLAN_FIELDS * nl) { c->err = "debug level plan: cap too small"; return PLFEM_EINVAL; }
@@ -137,4 +116,4 @@ extern "C" int plfem_debug_level_plan(plfem_ctx* c, int64_t* out, int64_t cap) {
     std::copy(rec, rec + PLFEM_DEBUG_PLAN_FIELDS, out + (int64_t)PLFEM_DEBUG_PLAN_FIELDS * l);
   }
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }

@@ -20,26 +20,88 @@
 using plfem::LevelInfo;
 using plfem::Symbolic;
 
-#define HIP_TRY(ctx, call)                                                                   \
-  do {                                                                                       \
-    hipError_t e__ = (call);                                                                 \
-    if (e__ != hipSuccess) {                                                                 \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                       \
-      return PLFEM_EHIP;                                                                     \
-    }                                                                                        \
-  } while (0)
-
 namespace {
-// Pinned host blocks outlive their context in a small process-wide cache: hipHostMalloc / hipHostFree pin and unpin
-// pages through the driver (syscalls with unbounded latency on a busy host), and cold solves create a context each.
-struct PinnedBlock { double* p; size_t bytes; };
-std::mutex& pinned_mutex() { static std::mutex* m = new std::mutex(); return *m; }
-std::vector<PinnedBlock>& pinned_cache() { static std::vector<PinnedBlock>* v = new std::vector<PinnedBlock>(); return *v; }
+// Process-wide state: recycling pools of what is slow to create (hipHostMalloc / hipHostFree pin and unpin pages through
+// the driver, a HIP event costs ~10 us, a stream ~50 us) and would otherwise be created by every context of a cold-solve
+// loop.  Each pool is one object with its own mutex, created on first use and never destroyed (no exit-order hazard).
+template <class T>
+T& process_wide() {
+  static T* t = new T();
+  return *t;
+}
+
+// Idle HIP handles, one LIFO list per (device ordinal, kind): a handle belongs to the device that was current when it was
+// created.  give() keeps at most `cap` handles in the list and destroys the rest; it never throws (no memory: destroyed).
+template <class H, hipError_t (*Destroy)(H)>
+struct Recycler {
+  std::mutex m;
+  std::vector<std::vector<H>> lists;   // [device * 4 + kind]
+  std::vector<H>& list(int device, int kind) {
+    const size_t i = (size_t)device * 4 + kind;
+    if (lists.size() <= i) lists.resize(i + 1);
+    return lists[i];
+  }
+  bool take(int device, int kind, H* out) {
+    std::lock_guard<std::mutex> lk(m);
+    auto& l = list(device, kind);
+    if (l.empty()) return false;
+    *out = l.back();
+    l.pop_back();
+    return true;
+  }
+  void give(int device, int kind, H h, size_t cap) noexcept {
+    if (!h) return;
+    try {
+      std::lock_guard<std::mutex> lk(m);
+      auto& l = list(device, kind);
+      if (l.size() < cap) { l.push_back(h); return; }
+    } catch (const std::exception&) {
+    }
+    (void)Destroy(h);
+  }
+  // every idle handle of the list moves to `mine` / every handle of `mine` moves back (plfem_profile_begin / _end: two
+  // contexts profiling at once never share a vector -- the second one simply creates its own events)
+  void take_all(int device, int kind, std::vector<H>& mine) {
+    std::lock_guard<std::mutex> lk(m);
+    auto& l = list(device, kind);
+    mine.insert(mine.end(), l.begin(), l.end());
+    l.clear();
+  }
+  void give_all(int device, int kind, std::vector<H>& mine) noexcept {
+    for (H h : mine) give(device, kind, h, SIZE_MAX);
+    mine.clear();
+  }
+};
+// Events by kind: the dozen a context owns (phase timing pairs; block-step completion and copy hand-over, without
+// timing), at most 256 idle per kind, and the timing events of plfem_profile_* (taken and given back whole).  Streams:
+// the side streams of the mode-vector copy (plfem_solve_modes).
+enum EventKind { EV_TIMING, EV_NO_TIMING, EV_PROFILE };
+using EventPool = Recycler<hipEvent_t, hipEventDestroy>;
+using StreamPool = Recycler<hipStream_t, hipStreamDestroy>;
+
+hipError_t ctx_event_acquire(int device, EventKind kind, hipEvent_t* out) {
+  if (process_wide<EventPool>().take(device, kind, out)) return hipSuccess;
+  return kind == EV_TIMING ? hipEventCreate(out) : hipEventCreateWithFlags(out, hipEventDisableTiming);
+}
+void ctx_event_release(int device, EventKind kind, hipEvent_t e) { process_wide<EventPool>().give(device, kind, e, 256); }
+
+hipError_t copy_stream_acquire(int device, hipStream_t* out) {
+  if (process_wide<StreamPool>().take(device, 0, out)) return hipSuccess;
+  return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
+}
+
+// Pinned host blocks outlive their context in a small cache (at most 8 blocks), reused best-fit.
+struct PinnedCache {
+  struct Block { double* p; size_t bytes; };
+  std::mutex m;
+  std::vector<Block> blocks;
+};
 
 hipError_t pinned_acquire(size_t bytes, double** out, size_t* got) {
   {
-    std::lock_guard<std::mutex> lk(pinned_mutex());
-    auto& cache = pinned_cache();
+    auto& pc = process_wide<PinnedCache>();
+    std::lock_guard<std::mutex> lk(pc.m);
+    auto& cache = pc.blocks;
     int best = -1;
     for (int i = 0; i < (int)cache.size(); ++i)
       if (cache[i].bytes >= bytes && (best < 0 || cache[i].bytes < cache[best].bytes)) best = i;
@@ -54,93 +116,14 @@ hipError_t pinned_acquire(size_t bytes, double** out, size_t* got) {
   return hipHostMalloc((void**)out, bytes, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable);
 }
 
-void pinned_release(double* p, size_t bytes) {
-  {
-    std::lock_guard<std::mutex> lk(pinned_mutex());
-    auto& cache = pinned_cache();
-    if (cache.size() < 8) { cache.push_back({p, bytes}); return; }
+void pinned_release(double* p, size_t bytes) noexcept {
+  try {
+    auto& pc = process_wide<PinnedCache>();
+    std::lock_guard<std::mutex> lk(pc.m);
+    if (pc.blocks.size() < 8) { pc.blocks.push_back({p, bytes}); return; }
+  } catch (const std::exception&) {
   }
   (void)hipHostFree(p);
-}
-}  // namespace
-
-namespace {
-// Process-wide pools of timing events for plfem_profile_*, one per device ordinal (an event belongs to the device that was
-// current when it was created): contexts come and go in a cold-solve loop, the events (a few hundred, ~10 us each to
-// create) stay.  A profiling context TAKES its device's pool at profile_begin and hands the events back at profile_end
-// (on every path), both under the mutex: two contexts profiling at once (sweep lanes) never share a vector -- the second
-// one simply creates its own events.
-std::mutex& event_mutex() { static std::mutex* m = new std::mutex(); return *m; }
-std::vector<std::vector<hipEvent_t>>& event_pools() { static auto* v = new std::vector<std::vector<hipEvent_t>>(); return *v; }
-void events_take(int device, std::vector<hipEvent_t>& mine) {
-  std::lock_guard<std::mutex> lk(event_mutex());
-  auto& pools = event_pools();
-  if ((int)pools.size() <= device) pools.resize(device + 1);
-  mine.insert(mine.end(), pools[device].begin(), pools[device].end());
-  pools[device].clear();
-}
-void events_give(int device, std::vector<hipEvent_t>& mine) {
-  std::lock_guard<std::mutex> lk(event_mutex());
-  auto& pools = event_pools();
-  if ((int)pools.size() <= device) pools.resize(device + 1);
-  pools[device].insert(pools[device].end(), mine.begin(), mine.end());
-  mine.clear();
-}
-}  // namespace
-
-namespace {
-// The dozen events a context owns (phase timing pairs, block-step completion, copy hand-over) come from process-wide
-// pools too, by kind (0 = timing, 1 = hipEventDisableTiming): creating and destroying them cost ~0.15 ms per cold solve.
-std::vector<hipEvent_t>& ctx_event_pool(int device, int kind) {
-  static auto* v = new std::vector<std::vector<hipEvent_t>>();
-  const size_t idx = (size_t)device * 2 + kind;
-  if (v->size() <= idx) v->resize(idx + 1);
-  return (*v)[idx];
-}
-hipError_t ctx_event_acquire(int device, int kind, hipEvent_t* out) {
-  {
-    std::lock_guard<std::mutex> lk(event_mutex());
-    auto& pool = ctx_event_pool(device, kind);
-    if (!pool.empty()) {
-      *out = pool.back();
-      pool.pop_back();
-      return hipSuccess;
-    }
-  }
-  return kind == 0 ? hipEventCreate(out) : hipEventCreateWithFlags(out, hipEventDisableTiming);
-}
-void ctx_event_release(int device, int kind, hipEvent_t e) {
-  if (!e) return;
-  std::lock_guard<std::mutex> lk(event_mutex());
-  auto& pool = ctx_event_pool(device, kind);
-  if (pool.size() < 256) pool.push_back(e);
-  else (void)hipEventDestroy(e);
-}
-}  // namespace
-
-namespace {
-// Side streams for the device-to-host copy of the mode vectors (plfem_solve_modes), one pool per device ordinal: a
-// stream costs ~50 us to create and cold solves create a context each.
-std::mutex& stream_mutex() { static std::mutex* m = new std::mutex(); return *m; }
-std::vector<std::vector<hipStream_t>>& stream_pools() { static auto* v = new std::vector<std::vector<hipStream_t>>(); return *v; }
-hipError_t copy_stream_acquire(int device, hipStream_t* out) {
-  {
-    std::lock_guard<std::mutex> lk(stream_mutex());
-    auto& pools = stream_pools();
-    if ((int)pools.size() <= device) pools.resize(device + 1);
-    if (!pools[device].empty()) {
-      *out = pools[device].back();
-      pools[device].pop_back();
-      return hipSuccess;
-    }
-  }
-  return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
-}
-void copy_stream_release(int device, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(stream_mutex());
-  auto& pools = stream_pools();
-  if ((int)pools.size() <= device) pools.resize(device + 1);
-  pools[device].push_back(s);
 }
 }  // namespace
 
@@ -219,7 +202,7 @@ int flush_uploads(plfem_ctx* c, const std::vector<UploadItem>& items, size_t spa
       }
       done[pc].fetch_add(1, std::memory_order_release);
       if (t != 0) continue;
-      while (done[pc].load(std::memory_order_acquire) < nt) __builtin_ia32_pause();
+      for (int spins = 0; done[pc].load(std::memory_order_acquire) < nt; ++spins) plfem::cpu_relax(spins);
       const size_t q0 = first[pc], q1 = first[pc + 1];
       if (q0 == q1 || herr != hipSuccess) continue;
       const size_t plo = items[q0].off, phi = q1 < items.size() ? items[q1].off : span;
@@ -237,21 +220,6 @@ int flush_uploads(plfem_ctx* c, const std::vector<UploadItem>& items, size_t spa
   return PLFEM_OK;
 }
 
-#define TRY(x)                      \
-  do {                              \
-    int rc__ = (x);                 \
-    if (rc__ != PLFEM_OK) return rc__; \
-  } while (0)
-
-int check_launch(plfem_ctx* c, const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    c->err = std::string(what) + ": " + hipGetErrorString(e);
-    return PLFEM_EHIP;
-  }
-  return PLFEM_OK;
-}
-
 void free_all(plfem_ctx* c) {
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);   // (the tail of the index upload reads the staging block)
   if (c->own_slab && c->slab) (void)hipFree(c->slab);
@@ -262,16 +230,16 @@ void free_all(plfem_ctx* c) {
   }
   // (the stream has been synchronised by plfem_destroy: none of these events is pending)
   for (auto& pr : c->ev)
-    for (auto& e : pr) ctx_event_release(c->device, 0, e);
-  for (auto& e : c->ev_step) ctx_event_release(c->device, 1, e);
-  if (!c->prof_ev.empty()) events_give(c->device, c->prof_ev);
+    for (auto& e : pr) ctx_event_release(c->device, EV_TIMING, e);
+  for (auto& e : c->ev_step) ctx_event_release(c->device, EV_NO_TIMING, e);
+  process_wide<EventPool>().give_all(c->device, EV_PROFILE, c->prof_ev);
   if (c->copy_stream) {
     (void)hipStreamSynchronize(c->copy_stream);
-    copy_stream_release(c->device, c->copy_stream);
+    process_wide<StreamPool>().give(c->device, 0, c->copy_stream, SIZE_MAX);
     c->copy_stream = nullptr;
   }
-  ctx_event_release(c->device, 1, c->ev_copy);
-  ctx_event_release(c->device, 1, c->ev_upload);
+  ctx_event_release(c->device, EV_NO_TIMING, c->ev_copy);
+  ctx_event_release(c->device, EV_NO_TIMING, c->ev_upload);
 }
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -284,12 +252,12 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
   c->stream = (hipStream_t)stream;   // NULL = the device's default (null) stream
   if (!size_only) {
     HIP_TRY(c, hipSetDevice(device));
-    for (int q = 0; q < 6; ++q)
-      for (int r = 0; r < 2; ++r) HIP_TRY(c, ctx_event_acquire(device, 0, &c->ev[q][r]));
-    for (int r = 0; r < 2; ++r) HIP_TRY(c, ctx_event_acquire(device, 1, &c->ev_step[r]));
-    HIP_TRY(c, ctx_event_acquire(device, 1, &c->ev_upload));
+    for (auto& pr : c->ev)
+      for (auto& e : pr) HIP_TRY(c, ctx_event_acquire(device, EV_TIMING, &e));
+    for (auto& e : c->ev_step) HIP_TRY(c, ctx_event_acquire(device, EV_NO_TIMING, &e));
+    HIP_TRY(c, ctx_event_acquire(device, EV_NO_TIMING, &c->ev_upload));
     HIP_TRY(c, copy_stream_acquire(device, &c->copy_stream));
-    HIP_TRY(c, hipEventRecord(c->ev[4][0], c->stream));
+    HIP_TRY(c, phase_begin(c, plfem::PH_UPLOAD));
   }
   c->nv = S.nv; c->ne = S.ne; c->N = S.N; c->nnz = S.rowptr.empty() ? 0 : (int)S.rowptr[S.N]; c->nsolve = S.nsolve;
   c->L = S.L; c->nfronts = S.nfronts; c->dpn = S.dpn; c->sh = S.dpn - 1; c->n2 = S.dpn * (int64_t)S.N; c->max_ncv = max_ncv;
@@ -310,7 +278,6 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
   if (!size_only) {
     int lim = 0;
     HIP_TRY(c, hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
-    c->lds_limit = lim;
     const int worst = P.worst_m;
     auto need = [&](int Pn) { return (int64_t)sizeof(double) * Pn * (worst + 2) + (int64_t)sizeof(double) * 8 * Pn * 64; };
     if (need(plfem::BLOCK_P) <= lim) c->max_block_p = plfem::BLOCK_P;
@@ -450,21 +417,11 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
     HIP_TRY(c, pinned_acquire(sizeof(double) * (plfem::PIN_PROJ + nc1p * nc1p + 2 * nc1p * plfem::BLOCK_P), &c->h_pinned, &c->h_pinned_bytes));
     c->h_slots = c->h_pinned + plfem::PIN_PROJ + nc1p * nc1p;
   }
-  HIP_TRY(c, hipEventRecord(c->ev[4][1], c->stream));
+  HIP_TRY(c, phase_end(c, plfem::PH_UPLOAD));
   const double tt4 = now_ms();
   // no synchronisation: the upload and the pattern kernel run on while the caller prepares the assembly (every
   // later use of the context is ordered behind them on the stream)
   if (ctx_trace) fprintf(stderr, "[ctx] lists %.3f  size pass %.3f  upload pass %.3f  pinned+launch %.3f  sync %.3f ms\n", tt1 - tt0, tt2 - tt1, tt3 - tt2, tt4 - tt3, now_ms() - tt4);
-  c->ev_used[4] = true;
-  return PLFEM_OK;
-}
-
-// the front-level index arrays travel on the copy stream (flush_uploads): their first reader orders the context's stream
-// behind them
-int wait_for_upload(plfem_ctx* c) {
-  if (!c->upload_pending) return PLFEM_OK;
-  HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_upload, 0));
-  c->upload_pending = false;
   return PLFEM_OK;
 }
 
@@ -484,38 +441,33 @@ int upload_cores(plfem_ctx* c, const double* cores_host, int ncore) {
 
 extern "C" int plfem_create(const plfem_symbolic* sym, int32_t device, void* hip_stream, int32_t max_ncv,
                             void* workspace_dev, int64_t workspace_bytes, plfem_ctx** out, char* err,
-                            int32_t errlen) {
+                            int32_t errlen) try {
   if (!out) return PLFEM_EINVAL;
   *out = nullptr;
-  auto fail = [&](const std::string& m, int code) {
-    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m.c_str());
-    return code;
-  };
-  if (!sym) return fail("plfem_create: null symbolic handle", PLFEM_EINVAL);
-  if (max_ncv < 3 || max_ncv > PLFEM_MAX_NCV) return fail("plfem_create: max_ncv must be in [3, " + std::to_string(PLFEM_MAX_NCV) + "]", PLFEM_EINVAL);
+  if (!sym) return write_err(err, errlen, "plfem_create: null symbolic handle", PLFEM_EINVAL);
+  if (max_ncv < 3 || max_ncv > PLFEM_MAX_NCV)
+    return write_err(err, errlen, "plfem_create: max_ncv must be in [3, " + std::to_string(PLFEM_MAX_NCV) + "]", PLFEM_EINVAL);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return fail("plfem_create: no HIP device available (this library has no CPU fallback)", PLFEM_EHIP);
-  if (device < 0 || device >= ndev) return fail("plfem_create: device index out of range", PLFEM_EINVAL);
-  plfem_ctx* c = new plfem_ctx();
-  int rc = create_impl(c, sym, device, hip_stream, max_ncv, workspace_dev, workspace_bytes, false);
-  if (rc != PLFEM_OK) {
-    std::string m = c->err;
-    free_all(c);
-    delete c;
-    return fail(m, rc);
-  }
-  *out = c;
+    return write_err(err, errlen, "plfem_create: no HIP device available (this library has no CPU fallback)", PLFEM_EHIP);
+  if (device < 0 || device >= ndev) return write_err(err, errlen, "plfem_create: device index out of range", PLFEM_EINVAL);
+  struct FreeCtx {
+    void operator()(plfem_ctx* c) const { free_all(c); delete c; }
+  };
+  std::unique_ptr<plfem_ctx, FreeCtx> c(new plfem_ctx());
+  const int rc = create_impl(c.get(), sym, device, hip_stream, max_ncv, workspace_dev, workspace_bytes, false);
+  if (rc != PLFEM_OK) return write_err(err, errlen, c->err, rc);
+  *out = c.release();
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(err, errlen); }
 
-extern "C" int plfem_workspace_bytes(const plfem_symbolic* sym, int32_t max_ncv, int64_t* bytes) {
+extern "C" int plfem_workspace_bytes(const plfem_symbolic* sym, int32_t max_ncv, int64_t* bytes) try {
   if (!sym || !bytes || max_ncv < 3 || max_ncv > PLFEM_MAX_NCV) return PLFEM_EINVAL;
   plfem_ctx tmp;
   int rc = create_impl(&tmp, sym, 0, nullptr, max_ncv, nullptr, 0, true);
   *bytes = tmp.workspace_need;
   return rc;
-}
+} catch (...) { return host_failure(nullptr, 0); }
 
 extern "C" void plfem_destroy(plfem_ctx* ctx) {
   if (!ctx) return;
@@ -527,54 +479,50 @@ extern "C" void plfem_destroy(plfem_ctx* ctx) {
 
 extern "C" const char* plfem_last_error(const plfem_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
-extern "C" int plfem_synchronize(plfem_ctx* ctx) {
+extern "C" int plfem_synchronize(plfem_ctx* ctx) try {
   if (!ctx) return PLFEM_EINVAL;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(ctx); }
 
 extern "C" int plfem_assemble_hfield(plfem_ctx* c, const double* cores_host, int32_t ncore, double eps_core,
-                                     double eps_clad, double k0, double alpha_p) {
+                                     double eps_clad, double k0, double alpha_p) try {
   if (!c) return PLFEM_EINVAL;
   if (!(eps_core > 0) || !(eps_clad > 0)) { c->err = "permittivities must be positive"; return PLFEM_EINVAL; }
   if (c->dpn != 2) { c->err = "plfem_assemble_hfield: the analysis of this context has one unknown per node (use plfem_assemble_scalar)"; return PLFEM_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(upload_cores(c, cores_host, ncore));
-  HIP_TRY(c, hipEventRecord(c->ev[0][0], c->stream));
+  HIP_TRY(c, phase_begin(c, plfem::PH_ASSEMBLE));
   plfem::launch_element_matrices(c, ncore, eps_core, eps_clad, k0, alpha_p);
   plfem::launch_csr_gather(c);
-  HIP_TRY(c, hipEventRecord(c->ev[0][1], c->stream));
-  c->ev_used[0] = true;
+  HIP_TRY(c, phase_end(c, plfem::PH_ASSEMBLE));
   TRY(check_launch(c, "assemble"));
   c->assembled = true;
   c->factored = false;
-  c->k0 = k0;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
 extern "C" int plfem_assemble_scalar(plfem_ctx* c, const double* cores_host, int32_t ncore, double eps_core,
-                                     double eps_clad, double k0) {
+                                     double eps_clad, double k0) try {
   if (!c) return PLFEM_EINVAL;
   if (!(eps_core > 0) || !(eps_clad > 0)) { c->err = "permittivities must be positive"; return PLFEM_EINVAL; }
   if (c->dpn != 1) { c->err = "plfem_assemble_scalar: the analysis of this context has two unknowns per node (plfem_symbolic_create_ex(..., 1, 0, ...))"; return PLFEM_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(upload_cores(c, cores_host, ncore));
-  HIP_TRY(c, hipEventRecord(c->ev[0][0], c->stream));
+  HIP_TRY(c, phase_begin(c, plfem::PH_ASSEMBLE));
   plfem::launch_element_matrices_scalar(c, ncore, eps_core, eps_clad, k0);
   plfem::launch_csr_gather(c);
-  HIP_TRY(c, hipEventRecord(c->ev[0][1], c->stream));
-  c->ev_used[0] = true;
+  HIP_TRY(c, phase_end(c, plfem::PH_ASSEMBLE));
   TRY(check_launch(c, "assemble scalar"));
   c->assembled = true;
   c->factored = false;
-  c->k0 = k0;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
 // CMT coupling integrals: raw[i + j n] = E_i^T M_deps F_j, norms
 extern "C" int plfem_cmt_coupling(plfem_ctx* c, int32_t n, const double* fields_i_dev, const double* fields_j_dev,
                                   const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
-                                  double* raw_host, double* pi_host, double* pj_host, double* eps_mean_host) {
+                                  double* raw_host, double* pi_host, double* pj_host, double* eps_mean_host) try {
   if (!c || !fields_i_dev || !fields_j_dev || !raw_host || !pi_host || !pj_host || n < 1) return PLFEM_EINVAL;
   if (c->dpn != 1) { c->err = "plfem_cmt_coupling: needs a context with one unknown per node (scalar fields)"; return PLFEM_EINVAL; }
   if (n > c->max_ncv) { c->err = "plfem_cmt_coupling: more fields than the context's max_ncv"; return PLFEM_EINVAL; }
@@ -608,56 +556,55 @@ extern "C" int plfem_cmt_coupling(plfem_ctx* c, int32_t n, const double* fields_
   for (int i = 0; i < n; ++i) { pi_host[i] = hs[(size_t)n * ld + i]; pj_host[i] = hs[(size_t)(n + 1) * ld + i]; }
   if (eps_mean_host) *eps_mean_host = mean;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_block_values_dev(plfem_ctx* c, int32_t block, const double** values_dev) {
+extern "C" int plfem_block_values_dev(plfem_ctx* c, int32_t block, const double** values_dev) try {
   if (!c || !values_dev || block < 0 || block >= PLFEM_BLK_COUNT) return PLFEM_EINVAL;
   *values_dev = c->d_vals[block];
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_block_values_host(plfem_ctx* c, int32_t block, double* values_host) {
+extern "C" int plfem_block_values_host(plfem_ctx* c, int32_t block, double* values_host) try {
   if (!c || !values_host || block < 0 || block >= PLFEM_BLK_COUNT) return PLFEM_EINVAL;
   if (!c->assembled) { c->err = "plfem_block_values_host before plfem_assemble_hfield"; return PLFEM_ESTATE; }
   HIP_TRY(c, hipMemcpyAsync(values_host, c->d_vals[block], sizeof(double) * c->nnz, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_spmv(plfem_ctx* c, int32_t which, const double* x_dev, double* y_dev) {
+extern "C" int plfem_spmv(plfem_ctx* c, int32_t which, const double* x_dev, double* y_dev) try {
   if (!c || !x_dev || !y_dev || (which != 0 && which != 1)) return PLFEM_EINVAL;
   if (!c->assembled) { c->err = "plfem_spmv before plfem_assemble_hfield"; return PLFEM_ESTATE; }
   HIP_TRY(c, hipSetDevice(c->device));
   plfem::launch_spmv(c, which, x_dev, y_dev);
   return check_launch(c, "spmv");
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_factor(plfem_ctx* c, double sigma) {
+extern "C" int plfem_factor(plfem_ctx* c, double sigma) try {
   if (!c) return PLFEM_EINVAL;
   if (!c->assembled) { c->err = "plfem_factor before plfem_assemble_hfield"; return PLFEM_ESTATE; }
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(wait_for_upload(c));
-  HIP_TRY(c, hipEventRecord(c->ev[1][0], c->stream));
+  HIP_TRY(c, phase_begin(c, plfem::PH_FACTOR));
   HIP_TRY(c, hipMemsetAsync(c->d_fvec, 0, sizeof(double) * 2 * c->fnodes_total * plfem::BLOCK_P, c->stream));   // (see plfem_create)
   plfem::launch_factor(c, sigma);
   if (c->test_post_factor) c->test_post_factor(c);   // null unless the test-hook add-on library installed one (api_debug.hip)
-  HIP_TRY(c, hipEventRecord(c->ev[1][1], c->stream));
-  c->ev_used[1] = true;
+  HIP_TRY(c, phase_end(c, plfem::PH_FACTOR));
   TRY(check_launch(c, "factor"));
   c->sigma = sigma;
   c->factored = true;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
 static void solve_refined(plfem_ctx* c, const double* b, double* y, int steps);
 
-extern "C" int plfem_solve(plfem_ctx* c, const double* rhs_dev, double* x_dev, int32_t refine_steps) {
+extern "C" int plfem_solve(plfem_ctx* c, const double* rhs_dev, double* x_dev, int32_t refine_steps) try {
   if (!c || !rhs_dev || !x_dev || refine_steps < 0) return PLFEM_EINVAL;
   if (!c->factored) { c->err = "plfem_solve before plfem_factor"; return PLFEM_ESTATE; }
   HIP_TRY(c, hipSetDevice(c->device));
   solve_refined(c, rhs_dev, x_dev, refine_steps);
   return check_launch(c, "solve");
-}
+} catch (...) { return host_failure(c); }
 
 // y = K^-1 b followed by `steps` passes of iterative refinement against the ASSEMBLED K = A - sigma B:
 //   r = b - (A y - sigma B y),  y += K^-1 r.
@@ -799,8 +746,7 @@ struct ThickRestart {
     c->modes_dev = evecs_dev;
     c->modes_k = k;
     plfem::launch_rotate(c, c->d_V, mm, c->d_S, mm, k, evecs_dev);
-    HIP_TRY(c, hipEventRecord(c->ev[2][1], st));
-    c->ev_used[2] = true;
+    HIP_TRY(c, phase_end(c, plfem::PH_LANCZOS));
     TRY(check_launch(c, "ritz rotation"));
     if (!c->defer_sync) HIP_TRY(c, hipStreamSynchronize(st));   // (plfem_solve_modes: its one synchronisation comes later)
     if (stats_host) {
@@ -822,7 +768,7 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
   constexpr int P = plfem::BLOCK_P;
   const int64_t n = c->n2;
   hipStream_t st = c->stream;
-  HIP_TRY(c, hipEventRecord(c->ev[2][0], st));
+  HIP_TRY(c, phase_begin(c, plfem::PH_LANCZOS));
   int m = ((ncv + P - 1) / P) * P;                                 // basis columns before the residual block
   if (m > c->max_ncv) m = (c->max_ncv / P) * P;
   ThickRestart R(c, P, k, m, tol);
@@ -1015,7 +961,7 @@ static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t
       return lanczos_block(c, k, ncv, tol, maxiter, sigma, evals_host, evecs_dev, stats_host);
   }
   hipStream_t st = c->stream;
-  HIP_TRY(c, hipEventRecord(c->ev[2][0], st));
+  HIP_TRY(c, phase_begin(c, plfem::PH_LANCZOS));
   const int m = ncv;
   ThickRestart R(c, 1, k, m, tol);
   const int ld = R.ld;
@@ -1066,25 +1012,24 @@ static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t
 }
 
 extern "C" int plfem_lanczos_shift_invert(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t maxiter,
-                                          double sigma, double* evals_host, double* evecs_dev, double* stats_host) {
+                                          double sigma, double* evals_host, double* evecs_dev, double* stats_host) try {
   if (!c || !evals_host || !evecs_dev) return PLFEM_EINVAL;
   return lanczos_run(c, k, ncv, tol, maxiter, sigma, evals_host, evecs_dev, stats_host);
-}
+} catch (...) { return host_failure(c); }
 
 extern "C" int plfem_postprocess(plfem_ctx* c, int32_t k, double* evecs_dev, const double* cores_host, int32_t ncore,
-                                 double* out_host, double* frac_core_host, double* modes_int_dev) {
+                                 double* out_host, double* frac_core_host, double* modes_int_dev) try {
   if (!c || !evecs_dev || !out_host || k < 1 || k > c->max_ncv) return PLFEM_EINVAL;
   if (!c->assembled) { c->err = "plfem_postprocess before plfem_assemble_hfield"; return PLFEM_ESTATE; }
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(upload_cores(c, cores_host, ncore));
-  HIP_TRY(c, hipEventRecord(c->ev[3][0], c->stream));
+  HIP_TRY(c, phase_begin(c, plfem::PH_POST));
   plfem::launch_post(c, k, evecs_dev, ncore, out_host, frac_core_host, modes_int_dev);
-  HIP_TRY(c, hipEventRecord(c->ev[3][1], c->stream));
-  c->ev_used[3] = true;
+  HIP_TRY(c, phase_end(c, plfem::PH_POST));
   TRY(check_launch(c, "postprocess"));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
 // ------------------------------------------------------------------------------------------------
 // One call for the whole numeric solve (include/plfem.h): assembly, factorisation, eigen-solve, post-processing, the
@@ -1095,13 +1040,13 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
                                  double k0, double alpha_p, double sigma, int32_t k, int32_t ncv, double tol,
                                  int32_t maxiter, double residual_tol, double tol_refined, double* evals_host,
                                  double* post_host, double* frac_core_host, double* resid_host, double* modes_int_host,
-                                 double* stats_host) {
+                                 double* stats_host) try {
   if (!c || !evals_host || !post_host || !resid_host) return PLFEM_EINVAL;
   if (k < 1 || k > c->max_ncv) { c->err = "plfem_solve_modes: need 1 <= k <= max_ncv"; return PLFEM_EINVAL; }
   const double th0 = now_ms();
   HIP_TRY(c, hipSetDevice(c->device));
   if (!c->copy_stream) HIP_TRY(c, copy_stream_acquire(c->device, &c->copy_stream));
-  if (!c->ev_copy) HIP_TRY(c, ctx_event_acquire(c->device, 1, &c->ev_copy));
+  if (!c->ev_copy) HIP_TRY(c, ctx_event_acquire(c->device, EV_NO_TIMING, &c->ev_copy));
   // Whatever way the call is left: the Lanczos drivers leave their final synchronisation to this call, the mode copies
   // queued on the copy stream land before the caller may release modes_int_host (the explicit synchronisations below
   // clear copy_pending, so that the success path makes no extra call), and the trace events go back.
@@ -1141,10 +1086,7 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
     if (!stats_host) return;
     double v[PLFEM_SOLVE_STATS] = {st[0], n_opinv, restarts, st[3], n_block, first_res, res, (double)refined, (double)perturbed};
     if (hi > PLFEM_SOLVE_T_ASSEMBLE_US) {
-      for (int q = 0; q < 6; ++q) {                 // assemble, factor, lanczos, post, upload, residual check
-        float ms = 0;
-        v[9 + q] = (c->ev_used[q] && hipEventElapsedTime(&ms, c->ev[q][0], c->ev[q][1]) == hipSuccess) ? ms * 1e3 : 0.0;
-      }
+      for (int ph = 0; ph < plfem::PH_COUNT; ++ph) v[PLFEM_SOLVE_T_ASSEMBLE_US + ph] = phase_us(c, (plfem::Phase)ph);
       v[PLFEM_SOLVE_T_CALL_US] = (now_ms() - th0) * 1e3;
     }
     for (int q = lo; q < hi; ++q) stats_host[q] = v[q];
@@ -1164,7 +1106,7 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
     th_lan = now_ms();
     double* modes = c->modes_dev;
     double* modes_int = c->d_BV2 != modes ? c->d_BV2 : c->d_BV;   // (a restart swaps the double buffers: take the idle one)
-    HIP_TRY(c, hipEventRecord(c->ev[3][0], c->stream));
+    HIP_TRY(c, phase_begin(c, plfem::PH_POST));
     // The copy of the mode vectors (~30 MB at C1: 0.58 ms on the host link, the longest item behind the Lanczos run) leaves
     // on its own stream, group of modes by group of modes as their post-processing completes, while the later groups and
     // the check below occupy this stream.
@@ -1180,13 +1122,11 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
                                   kg * row_bytes, hipMemcpyDeviceToHost, c->copy_stream);
     };
     plfem::post_enqueue(c, k, modes, ncore, modes_int_host ? modes_int : nullptr, modes_int_host ? &send_group : nullptr);
-    HIP_TRY(c, hipEventRecord(c->ev[3][1], c->stream));
-    c->ev_used[3] = true;
+    HIP_TRY(c, phase_end(c, plfem::PH_POST));
     HIP_TRY(c, copy_err);
-    HIP_TRY(c, hipEventRecord(c->ev[5][0], c->stream));
+    HIP_TRY(c, phase_begin(c, plfem::PH_RESIDUAL));
     plfem::resid_enqueue(c, k, evals_host, modes);
-    HIP_TRY(c, hipEventRecord(c->ev[5][1], c->stream));
-    c->ev_used[5] = true;
+    HIP_TRY(c, phase_end(c, plfem::PH_RESIDUAL));
     TRY(check_launch(c, "post-processing + residual check"));
     if (call_trace) {
       (void)hipEventRecord(tr_ev[1], c->stream);
@@ -1221,7 +1161,7 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
   if (call_trace) {
     const double th_end = now_ms();
     float backlog = 0, total = 0, copy_tail = 0;
-    (void)hipEventElapsedTime(&backlog, tr_ev[0], c->ev[0][0]);      // entry -> first assembly kernel may start
+    (void)hipEventElapsedTime(&backlog, tr_ev[0], c->ev[plfem::PH_ASSEMBLE][0]);      // entry -> first assembly kernel may start
     (void)hipEventElapsedTime(&total, tr_ev[0], tr_ev[1]);
     (void)hipEventElapsedTime(&copy_tail, tr_ev[1], tr_ev[2]);        // end of the residual check -> end of the mode copy
     fprintf(stderr, "[call] host: assemble enqueued +%.3f, factor +%.3f, lanczos returned +%.3f, post + check enqueued +%.3f, stream done +%.3f, "
@@ -1231,49 +1171,44 @@ extern "C" int plfem_solve_modes(plfem_ctx* c, const double* cores_host, int32_t
   }
   put_stats(0, PLFEM_SOLVE_STATS);
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_modes_dev(plfem_ctx* c, const double** evecs_dev, int32_t* k) {
+extern "C" int plfem_modes_dev(plfem_ctx* c, const double** evecs_dev, int32_t* k) try {
   if (!c || !evecs_dev) return PLFEM_EINVAL;
   if (!c->modes_dev) { c->err = "plfem_modes_dev: no eigen-solve has run on this context"; return PLFEM_ESTATE; }
   *evecs_dev = c->modes_dev;
   if (k) *k = c->modes_k;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_timings(plfem_ctx* c, double* out_host) {
+extern "C" int plfem_timings(plfem_ctx* c, double* out_host) try {
   if (!c || !out_host) return PLFEM_EINVAL;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   int32_t cnt[4] = {0, 0, 0, 0};
   HIP_TRY(c, hipMemcpy(cnt, c->d_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-  for (int q = 0; q < 5; ++q) {
-    float ms = 0;
-    if (c->ev_used[q] && hipEventElapsedTime(&ms, c->ev[q][0], c->ev[q][1]) == hipSuccess) c->timings[q] = ms * 1e3;
-  }
-  for (int i = 0; i < 8; ++i) out_host[i] = c->timings[i];
+  // slots 0-4: assemble, factor, lanczos, post, upload (us); 5: pivot perturbations; 6: residual check (us); 7: 0
+  for (int ph = plfem::PH_ASSEMBLE; ph <= plfem::PH_UPLOAD; ++ph) out_host[ph] = phase_us(c, (plfem::Phase)ph);
   out_host[5] = cnt[0];
-  {
-    float ms = 0;
-    if (c->ev_used[5] && hipEventElapsedTime(&ms, c->ev[5][0], c->ev[5][1]) == hipSuccess) out_host[6] = ms * 1e3;
-  }
+  out_host[6] = phase_us(c, plfem::PH_RESIDUAL);
+  out_host[7] = 0.0;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
 // ---- live kernel timing for bench.py's roofline object -------------------------------------------
-extern "C" int plfem_profile_begin(plfem_ctx* c, int32_t max_ranges) {
+extern "C" int plfem_profile_begin(plfem_ctx* c, int32_t max_ranges) try {
   if (!c || max_ranges < 1) return PLFEM_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   c->prof_max = max_ranges;                          // event pairs are created on demand at the launch site
-  if (c->prof_ev.empty()) events_take(c->device, c->prof_ev);
+  if (c->prof_ev.empty()) process_wide<EventPool>().take_all(c->device, EV_PROFILE, c->prof_ev);
   c->prof_n = 0;
   c->prof_toggle = 0;
   c->prof_slot.clear();
   c->prof_rbytes.clear();
   c->prof_on = true;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_profile_end(plfem_ctx* c, double* out_host) {
+extern "C" int plfem_profile_end(plfem_ctx* c, double* out_host) try {
   if (!c || !out_host) return PLFEM_EINVAL;
   c->prof_on = false;
   for (int q = 0; q < 3 * PLFEM_PROF_COUNT; ++q) out_host[q] = 0.0;
@@ -1287,24 +1222,24 @@ extern "C" int plfem_profile_end(plfem_ctx* c, double* out_host) {
     o[1] += ms * 1e3;
     o[2] += c->prof_rbytes[q];
   }
-  events_give(c->device, c->prof_ev);                 // (on the error path too)
+  process_wide<EventPool>().give_all(c->device, EV_PROFILE, c->prof_ev);   // (on the error path too)
   if (e != hipSuccess) {
     c->err = std::string("plfem_profile_end: ") + hipGetErrorString(e);
     return PLFEM_EHIP;
   }
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }
 
 // ---- a-posteriori residuals, options ---------------------------------------------------------------
-extern "C" int plfem_residuals(plfem_ctx* c, int32_t k, const double* evals_host, const double* evecs_dev, double* out_host) {
+extern "C" int plfem_residuals(plfem_ctx* c, int32_t k, const double* evals_host, const double* evecs_dev, double* out_host) try {
   if (!c || !evals_host || !evecs_dev || !out_host || k < 1 || k > c->max_ncv) return PLFEM_EINVAL;
   if (!c->assembled) { c->err = "plfem_residuals before plfem_assemble_hfield"; return PLFEM_ESTATE; }
   HIP_TRY(c, hipSetDevice(c->device));
   plfem::launch_residuals(c, k, evals_host, evecs_dev, out_host);
   return check_launch(c, "residuals");
-}
+} catch (...) { return host_failure(c); }
 
-extern "C" int plfem_set_option(plfem_ctx* c, const char* name, double value) {
+extern "C" int plfem_set_option(plfem_ctx* c, const char* name, double value) try {
   if (!c || !name) return PLFEM_EINVAL;
   const std::string n(name);
   if (n == "refine_steps") {
@@ -1315,4 +1250,4 @@ extern "C" int plfem_set_option(plfem_ctx* c, const char* name, double value) {
     return PLFEM_EINVAL;
   }
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(c); }

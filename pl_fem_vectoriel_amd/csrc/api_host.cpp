@@ -4,7 +4,6 @@
 #include <cstdio>
 #include <cstring>
 #include <numeric>
-#include <new>
 #include <string>
 #include <utility>
 
@@ -14,12 +13,6 @@
 
 using plfem::Symbolic;
 
-static void set_err(char* err, int32_t errlen, const std::string& msg) {
-  if (err && errlen > 0) {
-    std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
-  }
-}
-
 extern "C" int plfem_symbolic_create(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
                                      int32_t leaf_elems, int32_t nthreads, plfem_symbolic** out,
                                      char* err, int32_t errlen) {
@@ -28,19 +21,14 @@ extern "C" int plfem_symbolic_create(int32_t nv, int32_t ne, const double* p_hos
 
 extern "C" int plfem_symbolic_create_ex(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
                                         int32_t leaf_elems, int32_t nthreads, int32_t dofs_per_node, int32_t dirichlet,
-                                        plfem_symbolic** out, char* err, int32_t errlen) {
+                                        plfem_symbolic** out, char* err, int32_t errlen) try {
   if (!out) return PLFEM_EINVAL;
   *out = nullptr;
-  if (!p_host || !t_host || nv < 3 || ne < 1) {
-    set_err(err, errlen, "plfem_symbolic_create: empty mesh or null pointer");
-    return PLFEM_EINVAL;
-  }
-  if (dofs_per_node != 1 && dofs_per_node != 2) {
-    set_err(err, errlen, "plfem_symbolic_create_ex: dofs_per_node must be 1 (scalar) or 2 (vectorial)");
-    return PLFEM_EINVAL;
-  }
-  plfem_symbolic* h = new (std::nothrow) plfem_symbolic();
-  if (!h) { set_err(err, errlen, "out of memory"); return PLFEM_EINVAL; }
+  if (!p_host || !t_host || nv < 3 || ne < 1)
+    return write_err(err, errlen, "plfem_symbolic_create: empty mesh or null pointer", PLFEM_EINVAL);
+  if (dofs_per_node != 1 && dofs_per_node != 2)
+    return write_err(err, errlen, "plfem_symbolic_create_ex: dofs_per_node must be 1 (scalar) or 2 (vectorial)", PLFEM_EINVAL);
+  Owned<plfem_symbolic> h(new plfem_symbolic());
   std::string msg;
   try {
     msg = plfem::build_symbolic(nv, ne, p_host, t_host, leaf_elems <= 0 ? 24 : leaf_elems,
@@ -48,14 +36,10 @@ extern "C" int plfem_symbolic_create_ex(int32_t nv, int32_t ne, const double* p_
   } catch (const std::exception& e) {
     msg = std::string("exception in symbolic analysis: ") + e.what();
   }
-  if (!msg.empty()) {
-    set_err(err, errlen, msg);
-    delete h;
-    return PLFEM_EMESH;
-  }
-  *out = h;
+  if (!msg.empty()) return write_err(err, errlen, msg, PLFEM_EMESH);
+  *out = h.release();
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(err, errlen); }
 
 extern "C" void plfem_symbolic_destroy(plfem_symbolic* sym) { delete sym; }
 
@@ -138,41 +122,41 @@ bool lookup(const Symbolic& S, const char* name, ArrayRef& r) {
 }
 }  // namespace
 
-extern "C" int64_t plfem_symbolic_array_bytes(const plfem_symbolic* sym, const char* name) {
+extern "C" int64_t plfem_symbolic_array_bytes(const plfem_symbolic* sym, const char* name) try {
   if (!sym) return PLFEM_EINVAL;
   ArrayRef r;
   if (!lookup(sym->S, name, r)) return PLFEM_EINVAL;
   return r.bytes;
-}
+} catch (...) { return host_failure(nullptr, 0); }
 
-extern "C" int plfem_symbolic_get(const plfem_symbolic* sym, const char* name, void* out_host, int64_t nbytes) {
+extern "C" int plfem_symbolic_get(const plfem_symbolic* sym, const char* name, void* out_host, int64_t nbytes) try {
   if (!sym || !out_host) return PLFEM_EINVAL;
   ArrayRef r;
   if (!lookup(sym->S, name, r)) return PLFEM_EINVAL;
   if (r.bytes != nbytes) return PLFEM_EINVAL;
   std::memcpy(out_host, r.ptr, (size_t)nbytes);
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(nullptr, 0); }
 
 // ---------------------------------------------------------------------------------------------
 // Uniform red refinement (mesh producer).
 // ---------------------------------------------------------------------------------------------
 extern "C" int plfem_mesh_edge_count(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
-                                     int32_t* nedges, char* err, int32_t errlen) {
+                                     int32_t* nedges, char* err, int32_t errlen) try {
   if (!p_host || !t_host || !nedges) return PLFEM_EINVAL;
   plfem::Symbolic S;
   std::string msg = plfem::numbering_only(nv, ne, p_host, t_host, S);
-  if (!msg.empty()) { set_err(err, errlen, msg); return PLFEM_EMESH; }
+  if (!msg.empty()) return write_err(err, errlen, msg, PLFEM_EMESH);
   *nedges = S.nedges;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(err, errlen); }
 
 extern "C" int plfem_mesh_refine(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
-                                 double* p_out, int32_t* t_out, char* err, int32_t errlen) {
+                                 double* p_out, int32_t* t_out, char* err, int32_t errlen) try {
   if (!p_host || !t_host || !p_out || !t_out) return PLFEM_EINVAL;
   plfem::Symbolic S;
   std::string msg = plfem::numbering_only(nv, ne, p_host, t_host, S);
-  if (!msg.empty()) { set_err(err, errlen, msg); return PLFEM_EMESH; }
+  if (!msg.empty()) return write_err(err, errlen, msg, PLFEM_EMESH);
   const int N = S.N;
   std::memcpy(p_out, S.doflocs.data(), sizeof(double) * 2 * (size_t)N);   // vertices, then edge midpoints
   const int32_t* d = S.edof.data();
@@ -194,4 +178,4 @@ extern "C" int plfem_mesh_refine(int32_t nv, int32_t ne, const double* p_host, c
     }
   }
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(err, errlen); }

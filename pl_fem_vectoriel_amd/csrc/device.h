@@ -31,13 +31,33 @@ static_assert(PIN_CORE_QP + 1 <= PIN_COUNTERS, "pinned layout: core-point counte
 static_assert(PIN_COUNTERS + PIN_COUNTERS_N * sizeof(int32_t) / sizeof(double) <= PIN_CORES, "pinned layout: counters");
 static_assert(PIN_CORES + 3 * MAX_CORES <= PIN_PROJ, "pinned layout: core table");
 
+// Phases of a context timed on the device by an event pair each (plfem_timings, the *_us entries of plfem_solve_modes)
+enum Phase { PH_ASSEMBLE, PH_FACTOR, PH_LANCZOS, PH_POST, PH_UPLOAD, PH_RESIDUAL, PH_COUNT };
+static_assert(PLFEM_SOLVE_T_ASSEMBLE_US + PH_RESIDUAL == PLFEM_SOLVE_T_RESIDUAL_US, "phases in PLFEM_SOLVE_T_* order");
+
 }  // namespace plfem
+
+// Error vocabulary of the C ABI for a handle with a `std::string err` (plfem_ctx, plfem_locator): a failed HIP call or
+// launch sets the handle's error text and returns PLFEM_EHIP; TRY passes a non-zero status on.
+#define HIP_TRY(owner, call)                                                                 \
+  do {                                                                                       \
+    hipError_t e__ = (call);                                                                 \
+    if (e__ != hipSuccess) {                                                                 \
+      (owner)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
+      return PLFEM_EHIP;                                                                     \
+    }                                                                                        \
+  } while (0)
+
+#define TRY(x)                         \
+  do {                                 \
+    int rc__ = (x);                    \
+    if (rc__ != PLFEM_OK) return rc__; \
+  } while (0)
 
 struct plfem_ctx {
   const plfem::Symbolic* S = nullptr;
   int device = 0;
   hipStream_t stream = nullptr;
-  bool own_stream = false;
   std::string err;
   // sizes
   int nv = 0, ne = 0, N = 0, nnz = 0, nsolve = 0, L = 0, nfronts = 0, max_ncv = 0;
@@ -118,7 +138,6 @@ struct plfem_ctx {
   bool prof_on = false;
   unsigned prof_toggle = 0;       // block solves alternate between timing whole sweeps and timing single launches
   int prof_n = 0, prof_max = 0;
-  double prof_bytes = 0;
   std::vector<hipEvent_t> prof_ev;   // taken from the process-wide pool at profile_begin, handed back at profile_end
   std::vector<int> prof_slot;        // PLFEM_PROF_* of every timed range
   std::vector<double> prof_rbytes;   // algorithmic bytes of every timed range
@@ -129,14 +148,44 @@ struct plfem_ctx {
   void (*test_post_factor)(plfem_ctx*) = nullptr;   // called at the end of every plfem_factor
   double test_perturb = 0.0;      // plfem_debug_set_perturb: relative perturbation of the root front's D^-1
   int max_block_p = plfem::BLOCK_P;   // right-hand sides per sweep the LDS budget allows (BLOCK_P or 1)
-  int lds_limit = 0;              // bytes of LDS one workgroup may use on this device
-  double sigma = 0.0, k0 = 0.0;
-  hipEvent_t ev[6][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-  bool ev_used[6] = {false, false, false, false, false, false};   // assemble, factor, lanczos, post, upload, residual check
+  double sigma = 0.0;
+  hipEvent_t ev[plfem::PH_COUNT][2] = {};   // device timing of the phases (phase_begin / phase_end)
+  bool ev_used[plfem::PH_COUNT] = {};
   double* modes_dev = nullptr;    // where the last eigen-solve left its vectors (caller's buffer or the context's own)
   int modes_k = 0;
-  double timings[8] = {0};
 };
+
+namespace {
+// HIP_TRY for the kernel launches just made (hipGetLastError): the message names `what`
+template <class Owner>
+int check_launch(Owner* owner, const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return PLFEM_OK;
+  owner->err = std::string(what) + ": " + hipGetErrorString(e);
+  return PLFEM_EHIP;
+}
+
+// the front-level index arrays travel on the copy stream (flush_uploads): their first reader orders the context's stream
+// behind them
+int wait_for_upload(plfem_ctx* c) {
+  if (!c->upload_pending) return PLFEM_OK;
+  HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_upload, 0));
+  c->upload_pending = false;
+  return PLFEM_OK;
+}
+
+hipError_t phase_begin(plfem_ctx* c, plfem::Phase ph) { return hipEventRecord(c->ev[ph][0], c->stream); }
+hipError_t phase_end(plfem_ctx* c, plfem::Phase ph) {
+  const hipError_t e = hipEventRecord(c->ev[ph][1], c->stream);
+  if (e == hipSuccess) c->ev_used[ph] = true;
+  return e;
+}
+// device time of the phase's last run in microseconds (0 if it has not run); its events must have completed
+double phase_us(const plfem_ctx* c, plfem::Phase ph) {
+  float ms = 0;
+  return (c->ev_used[ph] && hipEventElapsedTime(&ms, c->ev[ph][0], c->ev[ph][1]) == hipSuccess) ? ms * 1e3 : 0.0;
+}
+}  // namespace
 
 namespace plfem {
 

@@ -11,10 +11,8 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/plfem.h"
-#include "internal.h"
+#include "device.h"
 #include "p2_element.h"
-#include <hip/hip_runtime.h>
 
 struct plfem_locator {
   const plfem::Symbolic* S = nullptr;
@@ -571,16 +569,6 @@ __global__ __launch_bounds__(256) void k_quartic_reduce(int npair, int ntile, in
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-int set_loc_err(plfem_locator* L, const std::string& m, int rc) {
-  L->err = m;
-  return rc;
-}
-
-int check_hip(plfem_locator* L, hipError_t e, const char* what) {
-  if (e != hipSuccess) return set_loc_err(L, std::string(what) + ": " + hipGetErrorString(e), PLFEM_EHIP);
-  return PLFEM_OK;
-}
-
 }  // namespace
 }  // namespace plfem
 
@@ -601,30 +589,25 @@ LocLayout loc_layout(const Symbolic& S) {
 }
 }  // namespace
 
-extern "C" int plfem_locator_bytes(const plfem_symbolic* sym, int64_t* bytes) {
+extern "C" int plfem_locator_bytes(const plfem_symbolic* sym, int64_t* bytes) try {
   if (!sym || !bytes) return PLFEM_EINVAL;
   ensure_locator(sym->S);
   *bytes = (int64_t)loc_layout(sym->S).total;
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(nullptr, 0); }
 
 extern "C" int plfem_locator_create(const plfem_symbolic* sym, int32_t device, void* hip_stream, void* mem_dev,
-                                    int64_t mem_bytes, plfem_locator** out, char* err, int32_t errlen) {
-  auto fail = [&](const std::string& m, int rc) {
-    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m.c_str());
-    return rc;
-  };
+                                    int64_t mem_bytes, plfem_locator** out, char* err, int32_t errlen) try {
   if (!out) return PLFEM_EINVAL;
   *out = nullptr;
-  if (!sym || !mem_dev) return fail("plfem_locator_create: null analysis or device memory", PLFEM_EINVAL);
-  if ((uintptr_t)mem_dev & 255) return fail("plfem_locator_create: device memory must be 256-byte aligned", PLFEM_EINVAL);
+  if (!sym || !mem_dev) return write_err(err, errlen, "plfem_locator_create: null analysis or device memory", PLFEM_EINVAL);
+  if ((uintptr_t)mem_dev & 255) return write_err(err, errlen, "plfem_locator_create: device memory must be 256-byte aligned", PLFEM_EINVAL);
   const Symbolic& S = sym->S;
   ensure_locator(S);
   const LocLayout lay = loc_layout(S);
-  if (mem_bytes < (int64_t)lay.total) return fail("plfem_locator_create: device memory smaller than plfem_locator_bytes", PLFEM_EINVAL);
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(std::string("hipSetDevice: ") + hipGetErrorString(e), PLFEM_EHIP);
-  plfem_locator* L = new plfem_locator();
+  if (mem_bytes < (int64_t)lay.total)
+    return write_err(err, errlen, "plfem_locator_create: device memory smaller than plfem_locator_bytes", PLFEM_EINVAL);
+  Owned<plfem_locator> L(new plfem_locator());
   L->S = &S;
   L->device = device;
   L->stream = (hipStream_t)hip_stream;
@@ -647,16 +630,18 @@ extern "C" int plfem_locator_create(const plfem_symbolic* sym, int32_t device, v
       {L->d_edof, S.edof.data(), S.edof.size() * sizeof(int32_t)},
       {L->d_int_index, S.int_index.data(), S.int_index.size() * sizeof(int32_t)},
       {L->d_pxy, pxy.data(), pxy.size() * sizeof(double)}};
-  for (auto& u : up) {
-    if (u.b == 0) continue;
-    e = hipMemcpyAsync(u.d, u.h, u.b, hipMemcpyHostToDevice, L->stream);
-    if (e != hipSuccess) { delete L; return fail(std::string("hipMemcpyAsync (locator upload): ") + hipGetErrorString(e), PLFEM_EHIP); }
-  }
-  e = hipStreamSynchronize(L->stream);         // (pxy is a local buffer)
-  if (e != hipSuccess) { delete L; return fail(std::string("hipStreamSynchronize: ") + hipGetErrorString(e), PLFEM_EHIP); }
-  *out = L;
+  auto upload = [&] {
+    HIP_TRY(L, hipSetDevice(device));
+    for (auto& u : up)
+      if (u.b > 0) HIP_TRY(L, hipMemcpyAsync(u.d, u.h, u.b, hipMemcpyHostToDevice, L->stream));
+    HIP_TRY(L, hipStreamSynchronize(L->stream));       // (pxy is a local buffer)
+    return PLFEM_OK;
+  };
+  const int rc = upload();
+  if (rc != PLFEM_OK) return write_err(err, errlen, L->err, rc);
+  *out = L.release();
   return PLFEM_OK;
-}
+} catch (...) { return host_failure(err, errlen); }
 
 extern "C" void plfem_locator_destroy(plfem_locator* loc) {
   if (!loc) return;
@@ -667,35 +652,39 @@ extern "C" void plfem_locator_destroy(plfem_locator* loc) {
 
 extern "C" const char* plfem_locator_last_error(const plfem_locator* loc) { return loc ? loc->err.c_str() : "null locator"; }
 
-extern "C" int plfem_stage_modes(plfem_locator* L, int32_t ncomp, int32_t k, int32_t nrows, const double* src_dev, double* dst_dev) {
+extern "C" int plfem_stage_modes(plfem_locator* L, int32_t ncomp, int32_t k, int32_t nrows, const double* src_dev, double* dst_dev) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k < 0 || nrows < 0 || ((!src_dev || !dst_dev) && k > 0 && nrows > 0))
-    return set_loc_err(L, "plfem_stage_modes: bad arguments", PLFEM_EINVAL);
+  if (ncomp < 1 || ncomp > 2 || k < 0 || nrows < 0 || ((!src_dev || !dst_dev) && k > 0 && nrows > 0)) {
+    L->err = "plfem_stage_modes: bad arguments";
+    return PLFEM_EINVAL;
+  }
   if (k == 0 || nrows == 0) return PLFEM_OK;
-  int rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
-  if (rc) return rc;
+  HIP_TRY(L, hipSetDevice(L->device));
   dim3 grid((nrows + 31) / 32, (k + 31) / 32, ncomp);
   hipLaunchKernelGGL(k_stage_modes, grid, dim3(256), 0, L->stream, (int)k, (int)nrows, src_dev, dst_dev);
-  return check_hip(L, hipGetLastError(), "k_stage_modes");
-}
+  return check_launch(L, "k_stage_modes");
+} catch (...) { return host_failure(L); }
 
 extern "C" int plfem_sample_fields(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
                                    const double* beta_dev, int32_t npts, const double* points_dev, double* out_dev,
-                                   int32_t* elem_dev) {
+                                   int32_t* elem_dev) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k < 0 || npts < 0)
-    return set_loc_err(L, "plfem_sample_fields: ncomp must be 1 or 2, k and npts >= 0", PLFEM_EINVAL);
+  if (ncomp < 1 || ncomp > 2 || k < 0 || npts < 0) {
+    L->err = "plfem_sample_fields: ncomp must be 1 or 2, k and npts >= 0";
+    return PLFEM_EINVAL;
+  }
   if (npts == 0) return PLFEM_OK;
-  if (!points_dev || !elem_dev || (k > 0 && (!modes_dev || !out_dev)))
-    return set_loc_err(L, "plfem_sample_fields: null device array", PLFEM_EINVAL);
-  if (indexed && L->S->nsolve == 0) return set_loc_err(L, "plfem_sample_fields: the analysis has no interior DOFs", PLFEM_EINVAL);
-  int rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
-  if (rc) return rc;
+  if (!points_dev || !elem_dev || (k > 0 && (!modes_dev || !out_dev))) {
+    L->err = "plfem_sample_fields: null device array";
+    return PLFEM_EINVAL;
+  }
+  if (indexed && L->S->nsolve == 0) { L->err = "plfem_sample_fields: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  HIP_TRY(L, hipSetDevice(L->device));
   const int64_t nrows = indexed ? L->nsolve : L->N;
   hipLaunchKernelGGL(k_sample_fields, dim3((npts + 255) / 256), dim3(256), 0, L->stream, loc_args(L, indexed != 0),
                      (int)ncomp, (int)k, nrows, modes_dev, ncomp == 2 ? beta_dev : nullptr, (int)npts, points_dev, out_dev, elem_dev);
-  return check_hip(L, hipGetLastError(), "k_sample_fields");
-}
+  return check_launch(L, "k_sample_fields");
+} catch (...) { return host_failure(L); }
 
 namespace {
 int overlap_chunks(int k) { return (k + OC - 1) / OC; }
@@ -710,8 +699,8 @@ CoreTable pack_cores(const double* cores_host, int ncore) {
 
 // the caller's work buffer: at least `need` bytes (what `sizer` returns), 256-byte aligned
 int check_work(plfem_locator* L, const char* fn, const char* sizer, const void* work_dev, int64_t work_bytes, int64_t need) {
-  if (work_bytes < need) return set_loc_err(L, std::string(fn) + ": work buffer smaller than " + sizer, PLFEM_EINVAL);
-  if ((uintptr_t)work_dev & 255) return set_loc_err(L, std::string(fn) + ": work buffer must be 256-byte aligned", PLFEM_EINVAL);
+  if (work_bytes < need) { L->err = std::string(fn) + ": work buffer smaller than " + sizer; return PLFEM_EINVAL; }
+  if ((uintptr_t)work_dev & 255) { L->err = std::string(fn) + ": work buffer must be 256-byte aligned"; return PLFEM_EINVAL; }
   return PLFEM_OK;
 }
 
@@ -719,11 +708,10 @@ int check_work(plfem_locator* L, const char* fn, const char* sizer, const void* 
 int reduce_to_host(plfem_locator* L, dim3 grid, int ka, int kb, int nblk, int nchunk_b, const double* partial, double* O,
                    double* out_host) {
   hipLaunchKernelGGL(k_overlap_reduce, grid, dim3(256), 0, L->stream, ka, kb, nblk, nchunk_b, partial, O);
-  int rc = check_hip(L, hipGetLastError(), "k_overlap_reduce");
-  if (rc) return rc;
-  rc = check_hip(L, hipMemcpyAsync(out_host, O, sizeof(double) * grid.y * ka * kb, hipMemcpyDeviceToHost, L->stream), "hipMemcpyAsync");
-  if (rc) return rc;
-  return check_hip(L, hipStreamSynchronize(L->stream), "hipStreamSynchronize");
+  TRY(check_launch(L, "k_overlap_reduce"));
+  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * grid.y * ka * kb, hipMemcpyDeviceToHost, L->stream));
+  HIP_TRY(L, hipStreamSynchronize(L->stream));
+  return PLFEM_OK;
 }
 }  // namespace
 
@@ -737,21 +725,21 @@ extern "C" int plfem_overlap_work_bytes(int32_t ka, int32_t kb, int64_t* bytes) 
 extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev, int32_t ka, int32_t indexed_a,
                                    plfem_locator* Lb, const double* modes_b_dev, int32_t kb, int32_t indexed_b, int32_t ncomp,
                                    const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
-                                   void* work_dev, int64_t work_bytes, double* out_host) {
+                                   void* work_dev, int64_t work_bytes, double* out_host) try {
   if (!La) return PLFEM_EINVAL;
-  if (!Lb || La->device != Lb->device) return set_loc_err(La, "plfem_field_overlap: the two locators must be on one device", PLFEM_EINVAL);
-  if (ncomp < 1 || ncomp > 2 || ka < 0 || kb < 0) return set_loc_err(La, "plfem_field_overlap: bad ncomp / ka / kb", PLFEM_EINVAL);
+  if (!Lb || La->device != Lb->device) { La->err = "plfem_field_overlap: the two locators must be on one device"; return PLFEM_EINVAL; }
+  if (ncomp < 1 || ncomp > 2 || ka < 0 || kb < 0) { La->err = "plfem_field_overlap: bad ncomp / ka / kb"; return PLFEM_EINVAL; }
   if (ka == 0 || kb == 0) return PLFEM_OK;
-  if (!modes_a_dev || !modes_b_dev || !work_dev || !out_host) return set_loc_err(La, "plfem_field_overlap: null array", PLFEM_EINVAL);
-  if (ncore > MAX_CORES || (ncore > 0 && !cores_host)) return set_loc_err(La, "plfem_field_overlap: at most 64 cores", PLFEM_EINVAL);
-  if ((indexed_a && La->nsolve == 0) || (indexed_b && Lb->nsolve == 0))
-    return set_loc_err(La, "plfem_field_overlap: the analysis has no interior DOFs", PLFEM_EINVAL);
+  if (!modes_a_dev || !modes_b_dev || !work_dev || !out_host) { La->err = "plfem_field_overlap: null array"; return PLFEM_EINVAL; }
+  if (ncore > MAX_CORES || (ncore > 0 && !cores_host)) { La->err = "plfem_field_overlap: at most 64 cores"; return PLFEM_EINVAL; }
+  if ((indexed_a && La->nsolve == 0) || (indexed_b && Lb->nsolve == 0)) {
+    La->err = "plfem_field_overlap: the analysis has no interior DOFs";
+    return PLFEM_EINVAL;
+  }
   int64_t need = 0;
   plfem_overlap_work_bytes(ka, kb, &need);
-  int rc = check_work(La, "plfem_field_overlap", "plfem_overlap_work_bytes", work_dev, work_bytes, need);
-  if (rc) return rc;
-  rc = check_hip(La, hipSetDevice(La->device), "hipSetDevice");
-  if (rc) return rc;
+  TRY(check_work(La, "plfem_field_overlap", "plfem_overlap_work_bytes", work_dev, work_bytes, need));
+  HIP_TRY(La, hipSetDevice(La->device));
   const int nca = overlap_chunks(ka), ncb = overlap_chunks(kb);
   const int64_t ntiles = ((int64_t)6 * Lb->ne + OT - 1) / OT;
   const int nblk = (int)std::min<int64_t>(OVL_BLOCKS, ntiles);
@@ -761,10 +749,9 @@ extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev,
                      loc_args(Lb, indexed_b != 0), (int)ncomp, (int)ka, (int64_t)(indexed_a ? La->nsolve : La->N), modes_a_dev,
                      (int)kb, (int64_t)(indexed_b ? Lb->nsolve : Lb->N), modes_b_dev, pack_cores(cores_host, ncore),
                      ncore < 0 ? -1 : (int)ncore, 1.0 / eps_core, 1.0 / eps_clad, ncb, partial);
-  rc = check_hip(La, hipGetLastError(), "k_field_overlap");
-  if (rc) return rc;
+  TRY(check_launch(La, "k_field_overlap"));
   return reduce_to_host(La, dim3(nca * ncb), (int)ka, (int)kb, nblk, ncb, partial, O, out_host);
-}
+} catch (...) { return host_failure(La); }
 
 namespace {
 int gram_outputs(int ncomp) { return ncomp == 2 ? 5 : 3; }
@@ -779,19 +766,19 @@ extern "C" int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
 }
 
 extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
-                                const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host) {
+                                const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k <= 0) return set_loc_err(L, "plfem_mode_grams: ncomp must be 1 or 2 and k > 0", PLFEM_EINVAL);
-  if (ncore < 0 || ncore > MAX_CORES) return set_loc_err(L, "plfem_mode_grams: ncore must be in [0, 64]", PLFEM_EINVAL);
-  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host))
-    return set_loc_err(L, "plfem_mode_grams: null array", PLFEM_EINVAL);
-  if (indexed && L->nsolve == 0) return set_loc_err(L, "plfem_mode_grams: the analysis has no interior DOFs", PLFEM_EINVAL);
+  if (ncomp < 1 || ncomp > 2 || k <= 0) { L->err = "plfem_mode_grams: ncomp must be 1 or 2 and k > 0"; return PLFEM_EINVAL; }
+  if (ncore < 0 || ncore > MAX_CORES) { L->err = "plfem_mode_grams: ncore must be in [0, 64]"; return PLFEM_EINVAL; }
+  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host)) {
+    L->err = "plfem_mode_grams: null array";
+    return PLFEM_EINVAL;
+  }
+  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
   int64_t need = 0;
   plfem_gram_work_bytes(ncomp, k, &need);
-  int rc = check_work(L, "plfem_mode_grams", "plfem_gram_work_bytes", work_dev, work_bytes, need);
-  if (rc) return rc;
-  rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
-  if (rc) return rc;
+  TRY(check_work(L, "plfem_mode_grams", "plfem_gram_work_bytes", work_dev, work_bytes, need));
+  HIP_TRY(L, hipSetDevice(L->device));
   const CoreTable ct = pack_cores(cores_host, ncore);
   const int nout = gram_outputs(ncomp), nc = overlap_chunks(k);
   const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
@@ -806,10 +793,9 @@ extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
   else
     hipLaunchKernelGGL(k_mode_grams<1>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
                        ct, (int)ncore, nc, partial);
-  rc = check_hip(L, hipGetLastError(), "k_mode_grams");
-  if (rc) return rc;
+  TRY(check_launch(L, "k_mode_grams"));
   return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
-}
+} catch (...) { return host_failure(L); }
 
 namespace {
 int quartic_pairs(int k) { return k * (k + 1) / 2; }
@@ -830,20 +816,22 @@ extern "C" int plfem_quartic_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes
 
 extern "C" int plfem_mode_quartic(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
                                   const double* cores_host, int32_t ncore, double w_core, double w_clad, void* work_dev,
-                                  int64_t work_bytes, double* out_host) {
+                                  int64_t work_bytes, double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k < 1 || k > QKMAX)
-    return set_loc_err(L, "plfem_mode_quartic: ncomp must be 1 or 2 and 1 <= k <= 64", PLFEM_EINVAL);
-  if (ncore > MAX_CORES) return set_loc_err(L, "plfem_mode_quartic: at most 64 cores", PLFEM_EINVAL);
-  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host))
-    return set_loc_err(L, "plfem_mode_quartic: null array", PLFEM_EINVAL);
-  if (indexed && L->nsolve == 0) return set_loc_err(L, "plfem_mode_quartic: the analysis has no interior DOFs", PLFEM_EINVAL);
+  if (ncomp < 1 || ncomp > 2 || k < 1 || k > QKMAX) {
+    L->err = "plfem_mode_quartic: ncomp must be 1 or 2 and 1 <= k <= 64";
+    return PLFEM_EINVAL;
+  }
+  if (ncore > MAX_CORES) { L->err = "plfem_mode_quartic: at most 64 cores"; return PLFEM_EINVAL; }
+  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host)) {
+    L->err = "plfem_mode_quartic: null array";
+    return PLFEM_EINVAL;
+  }
+  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_quartic: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
   int64_t need = 0;
   plfem_quartic_work_bytes(ncomp, k, &need);
-  int rc = check_work(L, "plfem_mode_quartic", "plfem_quartic_work_bytes", work_dev, work_bytes, need);
-  if (rc) return rc;
-  rc = check_hip(L, hipSetDevice(L->device), "hipSetDevice");
-  if (rc) return rc;
+  TRY(check_work(L, "plfem_mode_quartic", "plfem_quartic_work_bytes", work_dev, work_bytes, need));
+  HIP_TRY(L, hipSetDevice(L->device));
   const CoreTable ct = pack_cores(cores_host, ncore);
   const int np = quartic_pairs(k), nt = quartic_tiles(k), ntp = quartic_tile_pairs(k);
   const int nblk = std::max(1, std::min(quartic_slices(k), L->ne));
@@ -858,12 +846,10 @@ extern "C" int plfem_mode_quartic(plfem_locator* L, int32_t ncomp, int32_t k, co
   else
     hipLaunchKernelGGL(k_mode_quartic<1>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
                        ct, nc, w_core, w_clad, np, nt, partial);
-  rc = check_hip(L, hipGetLastError(), "k_mode_quartic");
-  if (rc) return rc;
+  TRY(check_launch(L, "k_mode_quartic"));
   hipLaunchKernelGGL(k_quartic_reduce, dim3(ntp, 1, QP * QP / 256), dim3(256), 0, L->stream, np, nt, nblk, partial, O);
-  rc = check_hip(L, hipGetLastError(), "k_quartic_reduce");
-  if (rc) return rc;
-  rc = check_hip(L, hipMemcpyAsync(out_host, O, sizeof(double) * np * np, hipMemcpyDeviceToHost, L->stream), "hipMemcpyAsync");
-  if (rc) return rc;
-  return check_hip(L, hipStreamSynchronize(L->stream), "hipStreamSynchronize");
-}
+  TRY(check_launch(L, "k_quartic_reduce"));
+  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * np * np, hipMemcpyDeviceToHost, L->stream));
+  HIP_TRY(L, hipStreamSynchronize(L->stream));
+  return PLFEM_OK;
+} catch (...) { return host_failure(L); }

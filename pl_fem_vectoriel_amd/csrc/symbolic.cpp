@@ -22,14 +22,6 @@ inline double secs(clk::time_point a, clk::time_point b) {
   return std::chrono::duration<double>(b - a).count();
 }
 
-// The pool's waits are short (the regions are 10-500 us apart): spin on the cache line with a pause instruction
-// first -- a yield costs a system call and several microseconds of wake-up latency per region, ~100 regions per
-// analysis -- and only fall back to yielding when the wait drags on (oversubscribed host).
-inline void cpu_relax(int spins) {
-  if (spins < 4096) __builtin_ia32_pause();
-  else std::this_thread::yield();
-}
-
 // Type-erased reference to a callable void(int rank) that outlives the call (fork-join: the caller waits).
 struct FnRef {
   void (*call)(void*, int) = nullptr;

@@ -13,6 +13,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "plan.h"
@@ -100,6 +101,15 @@ void ensure_pattern(const Symbolic& S);
 // against concurrent first calls on the same Symbolic.
 constexpr int LOC_CELLS_PER_ELEM = 2;
 void ensure_locator(const Symbolic& S);
+
+// One step of a spin wait on another host thread.  The waits of the analysis pool are short (its regions are 10-500 us
+// apart): spin on the cache line with a pause instruction first -- a yield costs a system call and several microseconds
+// of wake-up latency per region, ~100 regions per analysis -- and only fall back to yielding when the wait drags on
+// (oversubscribed host, CPU quota).
+inline void cpu_relax(int spins) {
+  if (spins < 4096) __builtin_ia32_pause();
+  else std::this_thread::yield();
+}
 
 // f(rank, nthreads) on nthreads threads (the caller is rank 0) of a worker pool from the process-wide cache of idle pools
 // the analysis uses -- for short host-side bursts outside the analysis (the staging copy of plfem_create), which would
