@@ -414,6 +414,56 @@ int plfem_debug_set_perturb(plfem_ctx* ctx, double value);
 #define PLFEM_DEBUG_PLAN_FIELDS 10
 int plfem_debug_solve_block(plfem_ctx* ctx, const double* rhs_dev, int64_t ldx, double* x_dev, int32_t refine_steps);
 int plfem_debug_level_plan(plfem_ctx* ctx, int64_t* out, int64_t cap);
+/* The device kernels of the two Lanczos drivers on caller device buffers, for the kernel-level tests (each hook runs the
+ * product's own launch function on the context's stream and synchronises).  Vectors have n2 = dofs_per_node N entries
+ * (component-major); column c of a panel Pm starts at Pm + c n2, column q of a block at W + q ldw (ldw >= n2).
+ * plfem_debug_panel, 1 <= ncols <= max_ncv + BLOCK_P:
+ *   PLFEM_DEBUG_PANEL_DOT        H[c] = Pm[:, c] . W                  (single-vector driver; W one vector)
+ *   PLFEM_DEBUG_PANEL_AXPY       W -= Pm H[0:ncols]
+ *   PLFEM_DEBUG_PANEL_DOT_BLOCK  H[c + q ldh] = Pm[:, c] . W[:, q], q < BLOCK_P; hacc (may be NULL): hacc[c + q ldacc] += the same
+ *   PLFEM_DEBUG_PANEL_AXPY_BLOCK W[:, q] -= sum_c Pm[:, c] H[c + q ldh]; wil (may be NULL, n2 BLOCK_P): the updated block
+ *                                interleaved, wil[(node dofs_per_node + component) BLOCK_P + q]
+ *   PLFEM_DEBUG_VEC_ADD          hacc[0:ncols] += H[0:ncols]
+ * plfem_debug_scale_store: v = w / beta, bv = bw / beta, beta = sqrt(max(*beta2, 0)) (zero vectors when beta = 0), beta ->
+ *   *beta_out (device, may be NULL); beta2 is a device pointer.
+ * plfem_debug_first_pass: xl_front (2 fnode_ptr[nfronts] BLOCK_P doubles, the sweeps' front-order result) is copied into the
+ *   context's backward-sweep buffer, then the fused first Gram-Schmidt pass of a block step: W = the block in global order
+ *   (Dirichlet rows 0), h = BVm^T W -> Hout[c + q ldh], W -= Vm h; 1 <= ncols <= 8.
+ * plfem_debug_spmv_block (after assembly): y[:, q] = B x[:, q] (PLFEM_DEBUG_SPMV_B_BLOCK), the same with x interleaved as wil
+ *   above (..._IL), and with the Gram partials of x^T (B x) (..._IL_GRAM: *nparts partials per entry, gram_out[(p BLOCK_P + q)
+ *   nparts + b] when gram_out is not NULL; they also stay where plfem_debug_chol with use_partials and G = NULL reads them),
+ *   y[:, q] = A x[:, q] (PLFEM_DEBUG_SPMV_A_BLOCK); columns ld apart.
+ * plfem_debug_chol: G = R^T R of a BLOCK_P x BLOCK_P matrix, ready-made (G[i + j ldg], use_partials = 0) or as nchunks partials
+ *   per entry (use_partials = 1; G = NULL: the partials the last ..._IL_GRAM product left).  R -> Tblk[i + j ldT], R^-1 ->
+ *   Rinv[i + j BLOCK_P] (device); *rank_flag = non-positive pivots met (each replaced by 1).
+ * plfem_debug_block_scale: Vn = W R^-1, BVn = BW R^-1 (Rinv as above; columns ldv apart); exp_dst (may be NULL): exp_dst[0:exp_n]
+ *   = exp_src[0:exp_n] and cnt_dst[0:4] = the device counters (plfem_debug_copy "counters"); want_front: BVn also to the
+ *   front-order buffer "fvec" (BLOCK_P values per DOF together).
+ * plfem_debug_rotate: out[:, 0:p] = V[:, 0:m] S[0:m, 0:p] (S[r + c ldS]; columns n2 apart), 1 <= m <= PLFEM_MAX_NCV + BLOCK_P.
+ * plfem_debug_start_field: the start block of the drivers, nvec <= BLOCK_P vectors (n2 apart) of the 64-bit LCG stream over
+ *   (vector, component, interior DOF), Dirichlet entries 0.
+ * plfem_debug_copy also knows "V", "BV" (the Lanczos basis and B times it, n2 per column) and "Hcols" (the device projected
+ * matrix, column major with leading dimension ld = m + P for a basis of m columns and blocks of P vectors: P = BLOCK_P for
+ * the block driver, 1 for the single-vector one), valid after a run without restart (a restart swaps the bases), and
+ * "counters" (the 4 int32 device counters, [2] the rank flag of the block driver). */
+enum { PLFEM_DEBUG_PANEL_DOT = 0, PLFEM_DEBUG_PANEL_AXPY, PLFEM_DEBUG_PANEL_DOT_BLOCK, PLFEM_DEBUG_PANEL_AXPY_BLOCK,
+       PLFEM_DEBUG_VEC_ADD };
+enum { PLFEM_DEBUG_SPMV_B_BLOCK = 0, PLFEM_DEBUG_SPMV_B_BLOCK_IL, PLFEM_DEBUG_SPMV_B_BLOCK_IL_GRAM, PLFEM_DEBUG_SPMV_A_BLOCK };
+int plfem_debug_panel(plfem_ctx* ctx, int32_t form, int32_t ncols, const double* Pm, double* W, int64_t ldw, double* H,
+                      int32_t ldh, double* hacc, int32_t ldacc, double* wil);
+int plfem_debug_scale_store(plfem_ctx* ctx, const double* w, const double* bw, const double* beta2, double* v, double* bv,
+                            double* beta_out);
+int plfem_debug_first_pass(plfem_ctx* ctx, const double* xl_front, const double* BVm, const double* Vm, int32_t ncols,
+                           double* W, int64_t ldw, double* Hout, int32_t ldh);
+int plfem_debug_spmv_block(plfem_ctx* ctx, int32_t form, const double* x, double* y, int64_t ld, double* gram_out,
+                           int32_t* nparts);
+int plfem_debug_chol(plfem_ctx* ctx, const double* G, int32_t ldg, int32_t use_partials, int32_t nchunks, double* Tblk,
+                     int32_t ldT, double* Rinv, int32_t* rank_flag);
+int plfem_debug_block_scale(plfem_ctx* ctx, const double* W, const double* BW, int64_t ldw, const double* Rinv, double* Vn,
+                            double* BVn, int64_t ldv, const double* exp_src, int32_t exp_n, double* exp_dst, int32_t* cnt_dst,
+                            int32_t want_front);
+int plfem_debug_rotate(plfem_ctx* ctx, const double* V, int32_t m, const double* S, int32_t ldS, int32_t p, double* out);
+int plfem_debug_start_field(plfem_ctx* ctx, int32_t nvec, double* out);
 #endif /* PLFEM_TEST_HOOKS */
 
 #ifdef __cplusplus

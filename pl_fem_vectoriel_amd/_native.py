@@ -45,7 +45,13 @@ SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", 
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
 # the test hooks (include/plfem.h under PLFEM_TEST_HOOKS): exported by the add-on libplfem_testhooks.so ONLY
 TEST_HOOK_EXPORTS = ("plfem_debug_factor_until", "plfem_debug_copy", "plfem_debug_symeig", "plfem_debug_symeig_band",
-                     "plfem_debug_set_perturb", "plfem_debug_solve_block", "plfem_debug_level_plan")
+                     "plfem_debug_set_perturb", "plfem_debug_solve_block", "plfem_debug_level_plan", "plfem_debug_panel",
+                     "plfem_debug_scale_store", "plfem_debug_first_pass", "plfem_debug_spmv_block", "plfem_debug_chol",
+                     "plfem_debug_block_scale", "plfem_debug_rotate", "plfem_debug_start_field")
+# forms of plfem_debug_panel and plfem_debug_spmv_block (PLFEM_DEBUG_PANEL_* / PLFEM_DEBUG_SPMV_* of include/plfem.h)
+PANEL_FORMS = ("dot", "axpy", "dot_block", "axpy_block", "vec_add")
+SPMV_BLOCK_FORMS = ("b_block", "b_block_il", "b_block_il_gram", "a_block")
+BLOCK_P = 4                         # plfem::BLOCK_P (csrc/plan.h): vectors per block of the block Lanczos driver
 # one record per tree level of plfem_debug_level_plan (PLFEM_DEBUG_PLAN_FIELDS of include/plfem.h)
 PLAN_FIELDS = ("count", "fwd_rows", "bwd_rows", "fwd_mixed", "max_s2", "max_m", "fwd_n", "bwd_n", "steps", "max_block_p")
 MAX_NCV = 320                       # PLFEM_MAX_NCV of include/plfem.h
@@ -234,6 +240,15 @@ def load_test_hooks() -> ctypes.CDLL:
     h.plfem_debug_symeig.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     h.plfem_debug_symeig_band.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                           ctypes.c_void_p, ctypes.c_void_p]
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    h.plfem_debug_panel.argtypes = [vp, i32, i32, vp, vp, i64, vp, i32, vp, i32, vp]
+    h.plfem_debug_scale_store.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    h.plfem_debug_first_pass.argtypes = [vp, vp, vp, vp, i32, vp, i64, vp, i32]
+    h.plfem_debug_spmv_block.argtypes = [vp, i32, vp, vp, i64, vp, vp]
+    h.plfem_debug_chol.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
+    h.plfem_debug_block_scale.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, vp, i32, vp, vp, i32]
+    h.plfem_debug_rotate.argtypes = [vp, vp, i32, vp, i32, i32, vp]
+    h.plfem_debug_start_field.argtypes = [vp, i32, vp]
     _hooks = h
     return h
 
@@ -530,6 +545,65 @@ class Context:
         self._check(load_test_hooks().plfem_debug_solve_block(self._h, ctypes.c_void_p(rhs.data_ptr()), ctypes.c_int64(int(ldx)),
                                                               ctypes.c_void_p(x.data_ptr()), int(refine_steps)),
                     "plfem_debug_solve_block")
+
+    # The device kernels of the Lanczos drivers on caller buffers (flat float64 device tensors; see include/plfem.h).
+    # Offsets are in doubles from the start of each tensor; None = a null pointer.
+    @staticmethod
+    def _dev(t, offset: int = 0):
+        return None if t is None else ctypes.c_void_p(t.data_ptr() + 8 * int(offset))
+
+    def debug_panel(self, form: str, ncols: int, Pm, W, ldw: int, H, ldh: int, hacc=None, ldacc: int = 0, wil=None):
+        """``plfem_debug_panel``: one of ``PANEL_FORMS`` (the panel products of both Lanczos drivers)."""
+        d = self._dev
+        self._check(load_test_hooks().plfem_debug_panel(self._h, PANEL_FORMS.index(form), int(ncols), d(Pm), d(W), int(ldw), d(H),
+                                                        int(ldh), d(hacc), int(ldacc), d(wil)), "plfem_debug_panel")
+
+    def debug_scale_store(self, w, bw, beta2, v, bv, beta_out=None):
+        """``plfem_debug_scale_store``: v = w / beta, bv = bw / beta with beta = sqrt(max(beta2[0], 0)) (device scalar)."""
+        d = self._dev
+        self._check(load_test_hooks().plfem_debug_scale_store(self._h, d(w), d(bw), d(beta2), d(v), d(bv), d(beta_out)),
+                    "plfem_debug_scale_store")
+
+    def debug_first_pass(self, xl_front, BVm, Vm, ncols: int, W, ldw: int, Hout, ldh: int):
+        """``plfem_debug_first_pass``: the fused first Gram-Schmidt pass of a block step from a front-order block."""
+        d = self._dev
+        self._check(load_test_hooks().plfem_debug_first_pass(self._h, d(xl_front), d(BVm), d(Vm), int(ncols), d(W), int(ldw),
+                                                             d(Hout), int(ldh)), "plfem_debug_first_pass")
+
+    def debug_spmv_block(self, form: str, x, y, ld: int, gram_out=None) -> int:
+        """``plfem_debug_spmv_block``: one of ``SPMV_BLOCK_FORMS``; returns the Gram partials per entry (0 without)."""
+        nparts = ctypes.c_int32(0)
+        d = self._dev
+        self._check(load_test_hooks().plfem_debug_spmv_block(self._h, SPMV_BLOCK_FORMS.index(form), d(x), d(y), int(ld),
+                                                             d(gram_out), ctypes.byref(nparts)), "plfem_debug_spmv_block")
+        return int(nparts.value)
+
+    def debug_chol(self, G, ldg: int, use_partials: bool, nchunks: int, Tblk, ldT: int, Rinv, Tblk_offset: int = 0) -> int:
+        """``plfem_debug_chol``: R -> Tblk (from ``Tblk_offset``), R^-1 -> Rinv; returns the rank flag."""
+        flag = ctypes.c_int32(0)
+        d = self._dev
+        self._check(load_test_hooks().plfem_debug_chol(self._h, d(G), int(ldg), 1 if use_partials else 0, int(nchunks),
+                                                       d(Tblk, Tblk_offset), int(ldT), d(Rinv), ctypes.byref(flag)),
+                    "plfem_debug_chol")
+        return int(flag.value)
+
+    def debug_block_scale(self, W, BW, ldw: int, Rinv, Vn, BVn, ldv: int, exp_src=None, exp_n: int = 0, exp_dst=None,
+                          cnt_dst=None, want_front: bool = False):
+        """``plfem_debug_block_scale``: Vn = W R^-1, BVn = BW R^-1, the optional export and the front-order copy."""
+        d = self._dev
+        self._check(load_test_hooks().plfem_debug_block_scale(self._h, d(W), d(BW), int(ldw), d(Rinv), d(Vn), d(BVn), int(ldv),
+                                                              d(exp_src), int(exp_n), d(exp_dst), d(cnt_dst),
+                                                              1 if want_front else 0), "plfem_debug_block_scale")
+
+    def debug_rotate(self, V, m: int, S, ldS: int, p: int, out):
+        """``plfem_debug_rotate``: out[:, :p] = V[:, :m] S[:m, :p] (the MFMA Ritz rotation)."""
+        d = self._dev
+        self._check(load_test_hooks().plfem_debug_rotate(self._h, d(V), int(m), d(S), int(ldS), int(p), d(out)),
+                    "plfem_debug_rotate")
+
+    def debug_start_field(self, nvec: int, out):
+        """``plfem_debug_start_field``: the drivers' pseudo-random start block, nvec vectors n2 apart."""
+        self._check(load_test_hooks().plfem_debug_start_field(self._h, int(nvec), self._dev(out)), "plfem_debug_start_field")
 
     def debug_level_plan(self):
         """Per tree level (root first) a dict of ``PLAN_FIELDS``: the forms the sweeps and the factorisation launch."""

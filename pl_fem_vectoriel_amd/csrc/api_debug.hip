@@ -53,6 +53,17 @@ extern "C" int plfem_debug_copy(plfem_ctx* c, const char* name, int64_t offset, 
   else if (n == "fvec2") src = c->d_fvec2;
   else if (n == "xl") src = c->d_xl;
   else if (n == "elem") src = c->d_elem;
+  else if (n == "V") src = c->d_V;                      // the Lanczos basis, B times it, the projected matrix (plfem.h)
+  else if (n == "BV") src = c->d_BV;
+  else if (n == "Hcols") src = c->d_Hcols;
+  else if (n == "counters") {                             // the 4 int32 device counters, delivered as doubles
+    if (offset + count > 4) return PLFEM_EINVAL;
+    int32_t tmp[4];
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(tmp, c->d_counters, sizeof(tmp), hipMemcpyDeviceToHost));
+    for (int64_t q = 0; q < count; ++q) out_host[q] = (double)tmp[offset + q];
+    return PLFEM_OK;
+  }
   else if (n == "colind" || n == "slot_row") {            // int32 index arrays, delivered as doubles
     if (offset + count > c->nnz) return PLFEM_EINVAL;
     std::vector<int32_t> tmp((size_t)count);
@@ -116,4 +127,122 @@ extern "C" int plfem_debug_level_plan(plfem_ctx* c, int64_t* out, int64_t cap) t
     std::copy(rec, rec + PLFEM_DEBUG_PLAN_FIELDS, out + (int64_t)PLFEM_DEBUG_PLAN_FIELDS * l);
   }
   return PLFEM_OK;
+} catch (...) { return host_failure(c); }
+
+// ---- the device kernels of the Lanczos drivers on caller device buffers (kernels_lanczos.hip, block SpMVs of
+// kernels_assembly.hip); every hook runs the product's launch_* function on the context's stream and synchronises
+namespace {
+int lanczos_hook_done(plfem_ctx* c, const char* what) {
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return check_launch(c, what);
+}
+}  // namespace
+
+extern "C" int plfem_debug_panel(plfem_ctx* c, int32_t form, int32_t ncols, const double* Pm, double* W, int64_t ldw, double* H,
+                                 int32_t ldh, double* hacc, int32_t ldacc, double* wil) try {
+  constexpr int P = plfem::BLOCK_P;
+  if (!c || !H || form < PLFEM_DEBUG_PANEL_DOT || form > PLFEM_DEBUG_VEC_ADD) return PLFEM_EINVAL;
+  if (form != PLFEM_DEBUG_VEC_ADD && (!Pm || !W)) return PLFEM_EINVAL;
+  if (ncols < 1 || ncols > c->max_ncv + P) { c->err = "debug panel: need 1 <= ncols <= max_ncv + BLOCK_P"; return PLFEM_EINVAL; }
+  const bool block = form == PLFEM_DEBUG_PANEL_DOT_BLOCK || form == PLFEM_DEBUG_PANEL_AXPY_BLOCK;
+  if (block && (ldw < c->n2 || ldh < ncols || (hacc && ldacc < ncols))) { c->err = "debug panel: leading dimension too small"; return PLFEM_EINVAL; }
+  if (form == PLFEM_DEBUG_VEC_ADD && !hacc) return PLFEM_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  switch (form) {
+    case PLFEM_DEBUG_PANEL_DOT: plfem::launch_panel_dot(c, Pm, ncols, W, H); break;
+    case PLFEM_DEBUG_PANEL_AXPY: plfem::launch_panel_axpy(c, Pm, ncols, H, W); break;
+    case PLFEM_DEBUG_PANEL_DOT_BLOCK: plfem::launch_panel_dot_block(c, Pm, ncols, W, ldw, H, ldh, hacc, ldacc); break;
+    case PLFEM_DEBUG_PANEL_AXPY_BLOCK: plfem::launch_panel_axpy_block(c, Pm, ncols, H, ldh, W, ldw, wil); break;
+    default: plfem::launch_vec_add(c, hacc, H, ncols); break;
+  }
+  return lanczos_hook_done(c, "debug panel");
+} catch (...) { return host_failure(c); }
+
+extern "C" int plfem_debug_scale_store(plfem_ctx* c, const double* w, const double* bw, const double* beta2, double* v, double* bv,
+                                       double* beta_out) try {
+  if (!c || !w || !bw || !beta2 || !v || !bv) return PLFEM_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  plfem::launch_scale_store(c, w, bw, beta2, v, bv, beta_out);
+  return lanczos_hook_done(c, "debug scale store");
+} catch (...) { return host_failure(c); }
+
+extern "C" int plfem_debug_first_pass(plfem_ctx* c, const double* xl_front, const double* BVm, const double* Vm, int32_t ncols,
+                                      double* W, int64_t ldw, double* Hout, int32_t ldh) try {
+  if (!c || !xl_front || !BVm || !Vm || !W || !Hout) return PLFEM_EINVAL;
+  if (ncols < 1 || ncols > 8 || ldw < c->n2 || ldh < ncols) { c->err = "debug first pass: need 1 <= ncols <= 8, ldw >= n2, ldh >= ncols"; return PLFEM_EINVAL; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(c->d_xl, xl_front, sizeof(double) * 2 * c->fnodes_total * plfem::BLOCK_P, hipMemcpyDeviceToDevice, c->stream));
+  plfem::launch_first_pass_block(c, BVm, Vm, ncols, W, ldw, Hout, ldh);
+  return lanczos_hook_done(c, "debug first pass");
+} catch (...) { return host_failure(c); }
+
+extern "C" int plfem_debug_spmv_block(plfem_ctx* c, int32_t form, const double* x, double* y, int64_t ld, double* gram_out,
+                                      int32_t* nparts) try {
+  constexpr int P = plfem::BLOCK_P;
+  if (!c || !x || !y || form < PLFEM_DEBUG_SPMV_B_BLOCK || form > PLFEM_DEBUG_SPMV_A_BLOCK) return PLFEM_EINVAL;
+  if (!c->assembled) { c->err = "debug block spmv before assemble"; return PLFEM_ESTATE; }
+  if (ld < c->n2) { c->err = "debug block spmv: ld < n2"; return PLFEM_EINVAL; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int np = 0;
+  switch (form) {
+    case PLFEM_DEBUG_SPMV_B_BLOCK: plfem::launch_spmv_b_block(c, x, y, ld); break;
+    case PLFEM_DEBUG_SPMV_B_BLOCK_IL: plfem::launch_spmv_b_block_il(c, x, y, ld); break;
+    case PLFEM_DEBUG_SPMV_B_BLOCK_IL_GRAM:
+      np = plfem::launch_spmv_b_block_il(c, x, y, ld, c->d_partial);      // (where the Lanczos step leaves them for the CholQR)
+      if (gram_out) HIP_TRY(c, hipMemcpyAsync(gram_out, c->d_partial, sizeof(double) * P * P * np, hipMemcpyDeviceToDevice, c->stream));
+      break;
+    default: plfem::launch_spmv_a_block(c, x, y, ld); break;
+  }
+  if (nparts) *nparts = np;
+  return lanczos_hook_done(c, "debug block spmv");
+} catch (...) { return host_failure(c); }
+
+extern "C" int plfem_debug_chol(plfem_ctx* c, const double* G, int32_t ldg, int32_t use_partials, int32_t nchunks, double* Tblk,
+                                int32_t ldT, double* Rinv, int32_t* rank_flag) try {
+  constexpr int P = plfem::BLOCK_P;
+  if (!c || !Tblk || !Rinv || ldT < P) return PLFEM_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (use_partials) {
+    const int64_t cap = std::max((int64_t)c->npartial * (c->max_ncv + 1 + P + 8) * P, (int64_t)P * P * ((c->N * (int64_t)8 + 255) / 256));
+    if (nchunks < 1 || (int64_t)P * P * nchunks > cap) { c->err = "debug chol: nchunks out of range"; return PLFEM_EINVAL; }
+    if (G) HIP_TRY(c, hipMemcpyAsync(c->d_partial, G, sizeof(double) * P * P * nchunks, hipMemcpyDeviceToDevice, c->stream));
+  } else if (!G || ldg < P) {
+    return PLFEM_EINVAL;
+  }
+  HIP_TRY(c, hipMemsetAsync(c->d_counters + 2, 0, sizeof(int32_t), c->stream));
+  if (use_partials) plfem::launch_chol_from_partials(c, nchunks, Tblk, ldT, Rinv);
+  else plfem::launch_chol_block(c, G, ldg, Tblk, ldT, Rinv);
+  int32_t flag = 0;
+  HIP_TRY(c, hipMemcpyAsync(&flag, c->d_counters + 2, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_counters + 2, 0, sizeof(int32_t), c->stream));
+  TRY(lanczos_hook_done(c, "debug chol"));
+  if (rank_flag) *rank_flag = flag;
+  return PLFEM_OK;
+} catch (...) { return host_failure(c); }
+
+extern "C" int plfem_debug_block_scale(plfem_ctx* c, const double* W, const double* BW, int64_t ldw, const double* Rinv, double* Vn,
+                                       double* BVn, int64_t ldv, const double* exp_src, int32_t exp_n, double* exp_dst,
+                                       int32_t* cnt_dst, int32_t want_front) try {
+  if (!c || !W || !BW || !Rinv || !Vn || !BVn || exp_n < 0) return PLFEM_EINVAL;
+  if (ldw < c->n2 || ldv < c->n2) { c->err = "debug block scale: leading dimension < n2"; return PLFEM_EINVAL; }
+  if (exp_dst && (!exp_src || !cnt_dst)) { c->err = "debug block scale: an export needs exp_src and cnt_dst"; return PLFEM_EINVAL; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  plfem::launch_block_scale(c, W, BW, ldw, Rinv, Vn, BVn, ldv, exp_src, exp_dst ? exp_n : 0, exp_dst, cnt_dst,
+                            want_front ? c->d_fvec : nullptr);
+  return lanczos_hook_done(c, "debug block scale");
+} catch (...) { return host_failure(c); }
+
+extern "C" int plfem_debug_rotate(plfem_ctx* c, const double* V, int32_t m, const double* S, int32_t ldS, int32_t p, double* out) try {
+  if (!c || !V || !S || !out) return PLFEM_EINVAL;
+  if (m < 1 || m > PLFEM_MAX_NCV + plfem::BLOCK_P || p < 1 || ldS < m) { c->err = "debug rotate: need 1 <= m <= PLFEM_MAX_NCV + BLOCK_P, p >= 1, ldS >= m"; return PLFEM_EINVAL; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  plfem::launch_rotate(c, V, m, S, ldS, p, out);
+  return lanczos_hook_done(c, "debug rotate");
+} catch (...) { return host_failure(c); }
+
+extern "C" int plfem_debug_start_field(plfem_ctx* c, int32_t nvec, double* out) try {
+  if (!c || !out || nvec < 1 || nvec > plfem::BLOCK_P) return PLFEM_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  plfem::launch_start_field(c, nvec, out);
+  return lanczos_hook_done(c, "debug start field");
 } catch (...) { return host_failure(c); }
