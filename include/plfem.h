@@ -418,12 +418,12 @@ int plfem_debug_level_plan(plfem_ctx* ctx, int64_t* out, int64_t cap);
  * product's own launch function on the context's stream and synchronises).  Vectors have n2 = dofs_per_node N entries
  * (component-major); column c of a panel Pm starts at Pm + c n2, column q of a block at W + q ldw (ldw >= n2).
  * plfem_debug_panel, 1 <= ncols <= max_ncv + BLOCK_P:
- *   PLFEM_DEBUG_PANEL_DOT        H[c] = Pm[:, c] . W                  (single-vector driver; W one vector)
+ *   PLFEM_DEBUG_PANEL_DOT        H[c] = Pm[:, c] . W (single-vector driver, the P = 1 instance of the block form; W one
+ *                                vector); hacc (may be NULL): hacc[c] += the same
  *   PLFEM_DEBUG_PANEL_AXPY       W -= Pm H[0:ncols]
  *   PLFEM_DEBUG_PANEL_DOT_BLOCK  H[c + q ldh] = Pm[:, c] . W[:, q], q < BLOCK_P; hacc (may be NULL): hacc[c + q ldacc] += the same
  *   PLFEM_DEBUG_PANEL_AXPY_BLOCK W[:, q] -= sum_c Pm[:, c] H[c + q ldh]; wil (may be NULL, n2 BLOCK_P): the updated block
  *                                interleaved, wil[(node dofs_per_node + component) BLOCK_P + q]
- *   PLFEM_DEBUG_VEC_ADD          hacc[0:ncols] += H[0:ncols]
  * plfem_debug_scale_store: v = w / beta, bv = bw / beta, beta = sqrt(max(*beta2, 0)) (zero vectors when beta = 0), beta ->
  *   *beta_out (device, may be NULL); beta2 is a device pointer.
  * plfem_debug_first_pass: xl_front (2 fnode_ptr[nfronts] BLOCK_P doubles, the sweeps' front-order result) is copied into the
@@ -446,8 +446,7 @@ int plfem_debug_level_plan(plfem_ctx* ctx, int64_t* out, int64_t cap);
  * matrix, column major with leading dimension ld = m + P for a basis of m columns and blocks of P vectors: P = BLOCK_P for
  * the block driver, 1 for the single-vector one), valid after a run without restart (a restart swaps the bases), and
  * "counters" (the 4 int32 device counters, [2] the rank flag of the block driver). */
-enum { PLFEM_DEBUG_PANEL_DOT = 0, PLFEM_DEBUG_PANEL_AXPY, PLFEM_DEBUG_PANEL_DOT_BLOCK, PLFEM_DEBUG_PANEL_AXPY_BLOCK,
-       PLFEM_DEBUG_VEC_ADD };
+enum { PLFEM_DEBUG_PANEL_DOT = 0, PLFEM_DEBUG_PANEL_AXPY, PLFEM_DEBUG_PANEL_DOT_BLOCK, PLFEM_DEBUG_PANEL_AXPY_BLOCK };
 enum { PLFEM_DEBUG_SPMV_B_BLOCK = 0, PLFEM_DEBUG_SPMV_B_BLOCK_IL, PLFEM_DEBUG_SPMV_B_BLOCK_IL_GRAM, PLFEM_DEBUG_SPMV_A_BLOCK };
 int plfem_debug_panel(plfem_ctx* ctx, int32_t form, int32_t ncols, const double* Pm, double* W, int64_t ldw, double* H,
                       int32_t ldh, double* hacc, int32_t ldacc, double* wil);

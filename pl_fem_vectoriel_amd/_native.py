@@ -49,7 +49,7 @@ TEST_HOOK_EXPORTS = ("plfem_debug_factor_until", "plfem_debug_copy", "plfem_debu
                      "plfem_debug_scale_store", "plfem_debug_first_pass", "plfem_debug_spmv_block", "plfem_debug_chol",
                      "plfem_debug_block_scale", "plfem_debug_rotate", "plfem_debug_start_field")
 # forms of plfem_debug_panel and plfem_debug_spmv_block (PLFEM_DEBUG_PANEL_* / PLFEM_DEBUG_SPMV_* of include/plfem.h)
-PANEL_FORMS = ("dot", "axpy", "dot_block", "axpy_block", "vec_add")
+PANEL_FORMS = ("dot", "axpy", "dot_block", "axpy_block")
 SPMV_BLOCK_FORMS = ("b_block", "b_block_il", "b_block_il_gram", "a_block")
 BLOCK_P = 4                         # plfem::BLOCK_P (csrc/plan.h): vectors per block of the block Lanczos driver
 # one record per tree level of plfem_debug_level_plan (PLFEM_DEBUG_PLAN_FIELDS of include/plfem.h)

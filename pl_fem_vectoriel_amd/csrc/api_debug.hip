@@ -18,7 +18,8 @@ namespace {
 // a slightly wrong factor: D^-1 of the root front scaled by 1 + test_perturb after every factorisation
 void perturb_root_pivots(plfem_ctx* c) {
   if (c->test_perturb != 0.0)
-    plfem::launch_scale(c, (int64_t)2 * c->dpn * c->S->fs[0], 1.0 + c->test_perturb, c->d_delta);
+    plfem::launch_axpby(c, (int64_t)2 * c->dpn * c->S->fs[0], 1.0 + c->test_perturb, c->d_delta, 0.0, c->d_delta,
+                        c->d_delta);              // x = (1 + p) x + 0 x: D^-1 is finite
 }
 }  // namespace
 
@@ -80,7 +81,7 @@ extern "C" int plfem_debug_copy(plfem_ctx* c, const char* name, int64_t offset, 
 
 // BLOCK_P right-hand sides (global order, columns ldx apart) through the block sweeps, then refine_steps passes of block
 // iterative refinement against the assembled K = A - sigma B (the block SpMVs of the Lanczos driver's refined solve).
-// The refinement's scratch is the first 3 BLOCK_P columns (ldx apart) of d_V2, as in solve_block_refined.
+// The refinement's scratch is the first 3 BLOCK_P columns (ldx apart) of d_V2, as in the block Lanczos driver.
 extern "C" int plfem_debug_solve_block(plfem_ctx* c, const double* rhs_dev, int64_t ldx, double* x_dev, int32_t refine_steps) try {
   constexpr int P = plfem::BLOCK_P;
   if (!c || !rhs_dev || !x_dev || refine_steps < 0) return PLFEM_EINVAL;
@@ -90,24 +91,8 @@ extern "C" int plfem_debug_solve_block(plfem_ctx* c, const double* rhs_dev, int6
   const int64_t scratch = (int64_t)c->n2 * (c->max_ncv + 1 + P);
   if (refine_steps > 0 && 3 * P * ldx > scratch) { c->err = "debug block solve: ldx too large for the refinement scratch"; return PLFEM_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
-  plfem::launch_solve_block(c, rhs_dev, x_dev, ldx);
-  double* ta = c->d_V2;
-  double* tb = c->d_V2 + (size_t)P * ldx;
-  double* dy = c->d_V2 + (size_t)2 * P * ldx;
-  for (int it = 0; it < refine_steps; ++it) {
-    plfem::launch_spmv_a_block(c, x_dev, ta, ldx);
-    plfem::launch_spmv_b_block(c, x_dev, tb, ldx);
-    for (int u = 0; u < P; ++u) {                 // column by column: the gaps between the columns stay untouched
-      const size_t o = (size_t)u * ldx;
-      plfem::launch_axpby_n(c, c->n2, -1.0, ta + o, c->sigma, tb + o, ta + o);     // ta = -A x + sigma B x
-      plfem::launch_axpby_n(c, c->n2, 1.0, rhs_dev + o, 1.0, ta + o, ta + o);      // ta = b - K x
-    }
-    plfem::launch_solve_block(c, ta, dy, ldx);
-    for (int u = 0; u < P; ++u) {
-      const size_t o = (size_t)u * ldx;
-      plfem::launch_axpby_n(c, c->n2, 1.0, x_dev + o, 1.0, dy + o, x_dev + o);
-    }
-  }
+  plfem::solve_refined(c, P, rhs_dev, x_dev, ldx, false, refine_steps, c->d_V2, c->d_V2 + (size_t)P * ldx,
+                       c->d_V2 + (size_t)2 * P * ldx);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return check_launch(c, "debug block solve");
 } catch (...) { return host_failure(c); }
@@ -141,19 +126,16 @@ int lanczos_hook_done(plfem_ctx* c, const char* what) {
 extern "C" int plfem_debug_panel(plfem_ctx* c, int32_t form, int32_t ncols, const double* Pm, double* W, int64_t ldw, double* H,
                                  int32_t ldh, double* hacc, int32_t ldacc, double* wil) try {
   constexpr int P = plfem::BLOCK_P;
-  if (!c || !H || form < PLFEM_DEBUG_PANEL_DOT || form > PLFEM_DEBUG_VEC_ADD) return PLFEM_EINVAL;
-  if (form != PLFEM_DEBUG_VEC_ADD && (!Pm || !W)) return PLFEM_EINVAL;
+  if (!c || !H || !Pm || !W || form < PLFEM_DEBUG_PANEL_DOT || form > PLFEM_DEBUG_PANEL_AXPY_BLOCK) return PLFEM_EINVAL;
   if (ncols < 1 || ncols > c->max_ncv + P) { c->err = "debug panel: need 1 <= ncols <= max_ncv + BLOCK_P"; return PLFEM_EINVAL; }
   const bool block = form == PLFEM_DEBUG_PANEL_DOT_BLOCK || form == PLFEM_DEBUG_PANEL_AXPY_BLOCK;
   if (block && (ldw < c->n2 || ldh < ncols || (hacc && ldacc < ncols))) { c->err = "debug panel: leading dimension too small"; return PLFEM_EINVAL; }
-  if (form == PLFEM_DEBUG_VEC_ADD && !hacc) return PLFEM_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   switch (form) {
-    case PLFEM_DEBUG_PANEL_DOT: plfem::launch_panel_dot(c, Pm, ncols, W, H); break;
-    case PLFEM_DEBUG_PANEL_AXPY: plfem::launch_panel_axpy(c, Pm, ncols, H, W); break;
-    case PLFEM_DEBUG_PANEL_DOT_BLOCK: plfem::launch_panel_dot_block(c, Pm, ncols, W, ldw, H, ldh, hacc, ldacc); break;
-    case PLFEM_DEBUG_PANEL_AXPY_BLOCK: plfem::launch_panel_axpy_block(c, Pm, ncols, H, ldh, W, ldw, wil); break;
-    default: plfem::launch_vec_add(c, hacc, H, ncols); break;
+    case PLFEM_DEBUG_PANEL_DOT: plfem::launch_panel_dot(c, 1, Pm, ncols, W, ldw, H, ldh, hacc, ldacc); break;
+    case PLFEM_DEBUG_PANEL_AXPY: plfem::launch_panel_axpy(c, 1, Pm, ncols, H, ldh, W, ldw); break;
+    case PLFEM_DEBUG_PANEL_DOT_BLOCK: plfem::launch_panel_dot(c, P, Pm, ncols, W, ldw, H, ldh, hacc, ldacc); break;
+    default: plfem::launch_panel_axpy(c, P, Pm, ncols, H, ldh, W, ldw, wil); break;
   }
   return lanczos_hook_done(c, "debug panel");
 } catch (...) { return host_failure(c); }
@@ -185,13 +167,13 @@ extern "C" int plfem_debug_spmv_block(plfem_ctx* c, int32_t form, const double* 
   HIP_TRY(c, hipSetDevice(c->device));
   int np = 0;
   switch (form) {
-    case PLFEM_DEBUG_SPMV_B_BLOCK: plfem::launch_spmv_b_block(c, x, y, ld); break;
+    case PLFEM_DEBUG_SPMV_B_BLOCK: plfem::launch_spmv(c, 1, P, x, y, ld); break;
     case PLFEM_DEBUG_SPMV_B_BLOCK_IL: plfem::launch_spmv_b_block_il(c, x, y, ld); break;
     case PLFEM_DEBUG_SPMV_B_BLOCK_IL_GRAM:
       np = plfem::launch_spmv_b_block_il(c, x, y, ld, c->d_partial);      // (where the Lanczos step leaves them for the CholQR)
       if (gram_out) HIP_TRY(c, hipMemcpyAsync(gram_out, c->d_partial, sizeof(double) * P * P * np, hipMemcpyDeviceToDevice, c->stream));
       break;
-    default: plfem::launch_spmv_a_block(c, x, y, ld); break;
+    default: plfem::launch_spmv(c, 0, P, x, y, ld); break;
   }
   if (nparts) *nparts = np;
   return lanczos_hook_done(c, "debug block spmv");

@@ -540,8 +540,8 @@ extern "C" int plfem_cmt_coupling(plfem_ctx* c, int32_t n, const double* fields_
   const int ld = n;
   double* Hd = c->d_Hcols;                    // [n + 2][n]: columns of the raw matrix, then the two norm vectors
   for (int j = 0; j < n; ++j) {
-    plfem::launch_spmv(c, 1, fields_j_dev + (size_t)j * N, c->d_w);                       // y = M_deps F_j
-    plfem::launch_panel_dot(c, fields_i_dev, n, c->d_w, Hd + (size_t)j * ld);            // column j: E_i^T y
+    plfem::launch_spmv(c, 1, 1, fields_j_dev + (size_t)j * N, c->d_w, N);                     // y = M_deps F_j
+    plfem::launch_panel_dot(c, 1, fields_i_dev, n, c->d_w, N, Hd + (size_t)j * ld, ld);           // column j: E_i^T y
   }
   for (int i = 0; i < n; ++i) {
     plfem::launch_dot(c, fields_i_dev + (size_t)i * N, fields_i_dev + (size_t)i * N, Hd + (size_t)n * ld + i);
@@ -576,7 +576,7 @@ extern "C" int plfem_spmv(plfem_ctx* c, int32_t which, const double* x_dev, doub
   if (!c || !x_dev || !y_dev || (which != 0 && which != 1)) return PLFEM_EINVAL;
   if (!c->assembled) { c->err = "plfem_spmv before plfem_assemble_hfield"; return PLFEM_ESTATE; }
   HIP_TRY(c, hipSetDevice(c->device));
-  plfem::launch_spmv(c, which, x_dev, y_dev);
+  plfem::launch_spmv(c, which, 1, x_dev, y_dev, c->n2);
   return check_launch(c, "spmv");
 } catch (...) { return host_failure(c); }
 
@@ -596,49 +596,14 @@ extern "C" int plfem_factor(plfem_ctx* c, double sigma) try {
   return PLFEM_OK;
 } catch (...) { return host_failure(c); }
 
-static void solve_refined(plfem_ctx* c, const double* b, double* y, int steps);
-
 extern "C" int plfem_solve(plfem_ctx* c, const double* rhs_dev, double* x_dev, int32_t refine_steps) try {
   if (!c || !rhs_dev || !x_dev || refine_steps < 0) return PLFEM_EINVAL;
   if (!c->factored) { c->err = "plfem_solve before plfem_factor"; return PLFEM_ESTATE; }
   HIP_TRY(c, hipSetDevice(c->device));
-  solve_refined(c, rhs_dev, x_dev, refine_steps);
+  // scratch: d_t1 / d_t2, not d_V2 -- after plfem_solve_modes that holds the vectors plfem_modes_dev hands out
+  plfem::solve_refined(c, 1, rhs_dev, x_dev, c->n2, false, refine_steps, c->d_t1, c->d_t2, c->d_t2);
   return check_launch(c, "solve");
 } catch (...) { return host_failure(c); }
-
-// y = K^-1 b followed by `steps` passes of iterative refinement against the ASSEMBLED K = A - sigma B:
-//   r = b - (A y - sigma B y),  y += K^-1 r.
-// Scratch: d_t1 / d_t2 (the sweeps of the single-vector solve do not use them).
-static void solve_refined(plfem_ctx* c, const double* b, double* y, int steps) {
-  plfem::launch_solve(c, b, y);
-  for (int it = 0; it < steps; ++it) {
-    plfem::launch_spmv(c, 0, y, c->d_t1);
-    plfem::launch_spmv(c, 1, y, c->d_t2);
-    plfem::launch_axpby(c, -1.0, c->d_t1, c->sigma, c->d_t2, c->d_t1);   // t1 = -A y + sigma B y
-    plfem::launch_axpby(c, 1.0, b, 1.0, c->d_t1, c->d_t1);               // t1 = b - K y
-    plfem::launch_solve(c, c->d_t1, c->d_t2);
-    plfem::launch_axpby(c, 1.0, y, 1.0, c->d_t2, y);
-  }
-}
-
-// the same for BLOCK_P columns (leading dimension n2, contiguous); scratch: the first 3 BLOCK_P columns of d_V2
-// (the restart double buffer, idle between restarts)
-static void solve_block_refined(plfem_ctx* c, const double* b, double* y, bool b_in_front_order, int steps) {
-  constexpr int P = plfem::BLOCK_P;
-  const int64_t n = c->n2;
-  plfem::launch_solve_block(c, b, y, n, b_in_front_order);
-  double* ta = c->d_V2;
-  double* tb = c->d_V2 + (size_t)P * n;
-  double* dy = c->d_V2 + (size_t)2 * P * n;
-  for (int it = 0; it < steps; ++it) {
-    plfem::launch_spmv_a_block(c, y, ta, n);
-    plfem::launch_spmv_b_block(c, y, tb, n);
-    plfem::launch_axpby_n(c, n * P, -1.0, ta, c->sigma, tb, ta);          // ta = -A y + sigma B y
-    plfem::launch_axpby_n(c, n * P, 1.0, b, 1.0, ta, ta);                 // ta = b - K y
-    plfem::launch_solve_block(c, ta, dy, n, false);
-    plfem::launch_axpby_n(c, n * P, 1.0, y, 1.0, dy, y);
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // thick-restart Lanczos, shift-invert, B inner product, shared by the block driver (P = BLOCK_P) and the single-vector
@@ -776,11 +741,11 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
   int nop = 0, nblock = 0;
   {
     plfem::launch_start_field(c, P, c->d_V2);       // fixed pseudo-random interior block, generated on the device
-    plfem::launch_spmv_b_block(c, c->d_V2, c->d_bw, n);
-    plfem::launch_solve_block(c, c->d_bw, c->d_w, n);      // (start block: any vector will do, no refinement)
+    plfem::launch_spmv(c, 1, P, c->d_V2, c->d_bw, n);
+    plfem::launch_solve(c, P, c->d_bw, c->d_w, n);    // (start block: any vector will do, no refinement)
     nop += P; ++nblock;
-    plfem::launch_spmv_b_block(c, c->d_w, c->d_bw, n);
-    plfem::launch_panel_dot_block(c, c->d_w, P, c->d_bw, n, c->d_G, P);
+    plfem::launch_spmv(c, 1, P, c->d_w, c->d_bw, n);
+    plfem::launch_panel_dot(c, P, c->d_w, P, c->d_bw, n, c->d_G, P);
     plfem::launch_chol_block(c, c->d_G, P, c->d_hblk, P, c->d_Rinv);      // R itself is not needed for the start block
     plfem::launch_block_scale(c, c->d_w, c->d_bw, n, c->d_Rinv, c->d_V, c->d_BV, n, nullptr, 0, nullptr, nullptr, c->d_fvec);
   }
@@ -805,16 +770,18 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
     double* Hblk = c->d_Hcols + (size_t)c0_ * ld;                             // T[0:nc, c0:c0+P] (zero before the step)
     if (c->refine_steps == 0 && nc - lo <= 8) {
       // W = OP V_j left in front order by the sweeps; the first pass permutes it on the way (two launches instead of four)
-      plfem::launch_solve_block(c, c->d_BV + (size_t)c0_ * n, nullptr, n, il_ready == c0_);
+      plfem::launch_solve(c, P, c->d_BV + (size_t)c0_ * n, nullptr, n, il_ready == c0_);
       plfem::launch_first_pass_block(c, c->d_BV + (size_t)lo * n, c->d_V + (size_t)lo * n, nc - lo, c->d_w, n, Hblk + lo, ld);
     } else {
-      solve_block_refined(c, c->d_BV + (size_t)c0_ * n, c->d_w, il_ready == c0_, c->refine_steps);   // W = OP V_j
-      plfem::launch_panel_dot_block(c, c->d_BV + (size_t)lo * n, nc - lo, c->d_w, n, Hblk + lo, ld);
-      plfem::launch_panel_axpy_block(c, c->d_V + (size_t)lo * n, nc - lo, Hblk + lo, ld, c->d_w, n);
+      // W = OP V_j; scratch: the first 3 P columns of d_V2 (the restart double buffer, idle between restarts)
+      plfem::solve_refined(c, P, c->d_BV + (size_t)c0_ * n, c->d_w, n, il_ready == c0_, c->refine_steps, c->d_V2,
+                           c->d_V2 + (size_t)P * n, c->d_V2 + (size_t)2 * P * n);
+      plfem::launch_panel_dot(c, P, c->d_BV + (size_t)lo * n, nc - lo, c->d_w, n, Hblk + lo, ld);
+      plfem::launch_panel_axpy(c, P, c->d_V + (size_t)lo * n, nc - lo, Hblk + lo, ld, c->d_w, n);
     }
-    plfem::launch_panel_dot_block(c, c->d_BV, nc, c->d_w, n, c->d_hblk, ld, Hblk, ld);  // second pass, T += h2
+    plfem::launch_panel_dot(c, P, c->d_BV, nc, c->d_w, n, c->d_hblk, ld, Hblk, ld);  // second pass, T += h2
     // (the second pass also leaves the block interleaved in d_t1 -- idle in this driver -- for the SpMV's gathers)
-    plfem::launch_panel_axpy_block(c, c->d_V, nc, c->d_hblk, ld, c->d_w, n, c->d_t1);
+    plfem::launch_panel_axpy(c, P, c->d_V, nc, c->d_hblk, ld, c->d_w, n, c->d_t1);
     {
       const int pid = plfem::prof_open(c, PLFEM_PROF_SPMV_B, 12.0 * c->nnz + 4.0 * (c->N + 1) + 2.0 * 8.0 * P * (double)n);
       // (the B product also leaves the chunk partials of the Gram matrix W^T B W: no panel-dot launch for the CholQR)
@@ -971,10 +938,10 @@ static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t
   // start vector: fixed pseudo-random interior field pushed through OP once (as ARPACK does for mode 3)
   {
     plfem::launch_start_field(c, 1, c->d_t1);
-    plfem::launch_spmv(c, 1, c->d_t1, c->d_bw);
-    plfem::launch_solve(c, c->d_bw, c->d_w);
+    plfem::launch_spmv(c, 1, 1, c->d_t1, c->d_bw, n);
+    plfem::launch_solve(c, 1, c->d_bw, c->d_w, n);
     ++nop;
-    plfem::launch_spmv(c, 1, c->d_w, c->d_bw);
+    plfem::launch_spmv(c, 1, 1, c->d_w, c->d_bw, n);
     plfem::launch_dot(c, c->d_w, c->d_bw, c->d_scal);
     plfem::launch_scale_store(c, c->d_w, c->d_bw, c->d_scal, c->d_V, c->d_BV, nullptr);
   }
@@ -985,15 +952,15 @@ static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t
     for (int j = j0; j < m; ++j) {
       double* Vj1 = c->d_V + (size_t)(j + 1) * n;
       double* BVj1 = c->d_BV + (size_t)(j + 1) * n;
-      solve_refined(c, c->d_BV + (size_t)j * n, c->d_w, c->refine_steps);   // w = OP v_j = K^-1 B v_j
+      plfem::solve_refined(c, 1, c->d_BV + (size_t)j * n, c->d_w, n, false, c->refine_steps, c->d_t1, c->d_t2,
+                           c->d_t2);                                      // w = OP v_j = K^-1 B v_j
       ++nop;
       double* hcol = c->d_Hcols + (size_t)j * ld;
-      plfem::launch_panel_dot(c, c->d_BV, j + 1, c->d_w, hcol);          // h = V^T B w
-      plfem::launch_panel_axpy(c, c->d_V, j + 1, hcol, c->d_w);
-      plfem::launch_panel_dot(c, c->d_BV, j + 1, c->d_w, c->d_h);        // CGS2 second pass
-      plfem::launch_panel_axpy(c, c->d_V, j + 1, c->d_h, c->d_w);
-      plfem::launch_vec_add(c, hcol, c->d_h, j + 1);
-      plfem::launch_spmv(c, 1, c->d_w, c->d_bw);
+      plfem::launch_panel_dot(c, 1, c->d_BV, j + 1, c->d_w, n, hcol, ld);                 // h = V^T B w
+      plfem::launch_panel_axpy(c, 1, c->d_V, j + 1, hcol, ld, c->d_w, n);
+      plfem::launch_panel_dot(c, 1, c->d_BV, j + 1, c->d_w, n, c->d_h, ld, hcol, ld);     // CGS2 second pass, T += h2
+      plfem::launch_panel_axpy(c, 1, c->d_V, j + 1, c->d_h, ld, c->d_w, n);
+      plfem::launch_spmv(c, 1, 1, c->d_w, c->d_bw, n);
       plfem::launch_dot(c, c->d_w, c->d_bw, c->d_scal);
       plfem::launch_scale_store(c, c->d_w, c->d_bw, c->d_scal, Vj1, BVj1, hcol + (j + 1));
     }

@@ -213,36 +213,33 @@ void launch_element_matrices_scalar(plfem_ctx* c, int ncore, double eps_core, do
 double launch_delta_eps_mass(plfem_ctx* c, int ncore, double eps_core, double eps_clad);   // MINV slot <- asm((eps - mean eps) u v)
 void launch_csr_gather(plfem_ctx* c);
 void launch_pattern_fill(plfem_ctx* c);   // colind / slot_row from the node -> element adjacency (once per context)
-void launch_spmv(plfem_ctx* c, int which, const double* x, double* y);
-void launch_spmv_b_block(plfem_ctx* c, const double* x, double* y, int64_t ld);   // y_q = B x_q, BLOCK_P vectors
-// same, x as [node][component][q]; gram != nullptr: also the chunk partials of the Gram matrix x^T (B x), gram[(p P + q) nb + b]
-// for workgroup b of nb (returned)
+// y_q = A x_q (which = 0) or B x_q (which = 1) for P vectors ld apart.  Here and below P is 1 or BLOCK_P.
+void launch_spmv(plfem_ctx* c, int which, int P, const double* x, double* y, int64_t ld);
+// y_q = B x_q for BLOCK_P vectors, x as [node][component][q]; gram != nullptr: also the chunk partials of the Gram matrix
+// x^T (B x), gram[(p P + q) nb + b] for workgroup b of nb (returned)
 int launch_spmv_b_block_il(plfem_ctx* c, const double* x_interleaved, double* y, int64_t ld, double* gram = nullptr);
-void launch_spmv_a_block(plfem_ctx* c, const double* x, double* y, int64_t ld);   // y_q = A x_q, BLOCK_P vectors
 // out_host[i] = ||A v_i - lambda_i B v_i|| / ||A v_i||  (k vectors, row i of evecs; synchronises)
 void launch_residuals(plfem_ctx* c, int k, const double* lam_host, const double* evecs, double* out_host);
 // kernels_front.hip (factorisation), kernels_sweep.hip (solve sweeps)
 void launch_factor(plfem_ctx* c, double sigma, int stop_level = -1, int stop_step = 0, int stop_stage = 0);
-void launch_solve(plfem_ctx* c, const double* rhs, double* x);
-// BLOCK_P right-hand sides; x == nullptr: the result stays in front order in d_xl (the caller permutes it itself)
-void launch_solve_block(plfem_ctx* c, const double* rhs, double* x, int64_t ldx, bool rhs_in_front_order = false);
+// P right-hand sides, columns ldx apart; x == nullptr: the result stays in front order in d_xl (the caller permutes it itself)
+void launch_solve(plfem_ctx* c, int P, const double* rhs, double* x, int64_t ldx, bool rhs_in_front_order = false);
+// y = K^-1 b, then `steps` passes y += K^-1 (b - K y) against the assembled K; scratch ta, tb, dy: P columns ld apart each
+void solve_refined(plfem_ctx* c, int P, const double* b, double* y, int64_t ld, bool b_in_front_order, int steps, double* ta,
+                   double* tb, double* dy);
 // kernels_lanczos.hip
-void launch_panel_dot(plfem_ctx* c, const double* P, int ncols, const double* w, double* h);   // h = P^T w
-void launch_panel_axpy(plfem_ctx* c, const double* P, int ncols, const double* h, double* w);  // w -= P h
+// panel products on P vectors (columns ldw apart); H matrices are column major with leading dimension ldh
+// h = Pm^T W (ncols x P); hacc (optional) += the same coefficients
+void launch_panel_dot(plfem_ctx* c, int P, const double* Pm, int ncols, const double* W, int64_t ldw, double* h, int ldh,
+                      double* hacc = nullptr, int ldacc = 0);
+// W -= Pm H; w_interleaved (block only): see k_spmv_b_block_il
+void launch_panel_axpy(plfem_ctx* c, int P, const double* Pm, int ncols, const double* H, int ldh, double* W, int64_t ldw,
+                       double* w_interleaved = nullptr);
 void launch_dot(plfem_ctx* c, const double* a, const double* b, double* out);                  // *out = a.b
-void launch_vec_add(plfem_ctx* c, double* acc, const double* h, int n);                        // acc += h
 void launch_scale_store(plfem_ctx* c, const double* w, const double* bw, const double* beta2, double* v, double* bv,
                         double* beta_out);  // v = w/sqrt(beta2), bv = bw/sqrt(beta2)
-void launch_axpby(plfem_ctx* c, double a, const double* x, double b, const double* y, double* z);  // z = a x + b y
-void launch_axpby_n(plfem_ctx* c, int64_t n, double a, const double* x, double b, const double* y, double* z);
-void launch_scale(plfem_ctx* c, int64_t n, double a, double* x);   // x *= a
+void launch_axpby(plfem_ctx* c, int64_t n, double a, const double* x, double b, const double* y, double* z);  // z = a x + b y
 void launch_rotate(plfem_ctx* c, const double* V, int m, const double* Smat, int ldS, int p, double* out);  // out = V[:, :m] S
-// block (BLOCK_P vectors) variants; H matrices are column major with leading dimension ldh
-// h = Pm^T W (ncols x BLOCK_P); hacc (optional) += the same coefficients
-void launch_panel_dot_block(plfem_ctx* c, const double* Pm, int ncols, const double* W, int64_t ldw, double* h, int ldh,
-                            double* hacc = nullptr, int ldacc = 0);
-void launch_panel_axpy_block(plfem_ctx* c, const double* Pm, int ncols, const double* H, int ldh, double* W, int64_t ldw,
-                             double* w_interleaved = nullptr);   // w_interleaved: see k_spmv_b_block_il
 // first Gram-Schmidt pass of a block step over ncols <= 8 columns in two launches: reads the sweeps' result d_xl (front
 // order), writes W in global order (what k_permute_out would have done), h = BVm^T W -> Hout, W -= Vm h
 void launch_first_pass_block(plfem_ctx* c, const double* BVm, const double* Vm, int ncols, double* W, int64_t ldw, double* Hout, int ldh);

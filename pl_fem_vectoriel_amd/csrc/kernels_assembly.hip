@@ -246,50 +246,12 @@ __global__ __launch_bounds__(256) void k_csr_gather(int nnz, int ne, const int32
   v4[k] = acc[4]; v5[k] = acc[5]; v6[k] = acc[6]; v7[k] = acc[7];
 }
 
-// y = A_int x (which = 0) or y = B_int x (which = 1) on 2N-vectors; Dirichlet rows forced to zero,
-// Dirichlet columns are zero in x by construction.  8 lanes per scalar row (avg 11.5 nnz / row),
-// both field components of the row computed in the same pass over the shared pattern.
-template <int WHICH, int DPN>
-__global__ __launch_bounds__(256) void k_spmv(int N, const int32_t* __restrict__ rowptr,
-                                              const int32_t* __restrict__ colind, const uint8_t* __restrict__ bmask,
-                                              const double* __restrict__ vxx, const double* __restrict__ vxy,
-                                              const double* __restrict__ vyx, const double* __restrict__ vyy,
-                                              const double* __restrict__ x, double* __restrict__ y) {
-  int gt = blockIdx.x * blockDim.x + threadIdx.x;
-  int row = gt >> 3, sub = gt & 7;
-  double sx = 0, sy = 0;
-  if (row < N && !bmask[row]) {
-    int q0 = rowptr[row], q1 = rowptr[row + 1];
-    for (int q = q0 + sub; q < q1; q += 8) {
-      int c = colind[q];
-      if (DPN == 1) {                       // scalar pencil: one block (A: the AXX slot, B: the MINV slot)
-        sx += vxx[q] * x[c];
-        continue;
-      }
-      double xx = x[c], xy = x[N + c];
-      if (WHICH == 0) {
-        sx += vxx[q] * xx + vxy[q] * xy;
-        sy += vyx[q] * xx + vyy[q] * xy;
-      } else {
-        double mv = vxx[q];
-        sx += mv * xx;
-        sy += mv * xy;
-      }
-    }
-  }
-#pragma unroll
-  for (int off = 4; off >= 1; off >>= 1) {
-    sx += __shfl_xor(sx, off, 8);
-    sy += __shfl_xor(sy, off, 8);
-  }
-  if (row < N && sub == 0) {
-    y[row] = sx;
-    if (DPN == 2) y[N + row] = sy;
-  }
-}
+// Restricted SpMVs on dpn N-vectors: Dirichlet rows forced to zero, Dirichlet columns are zero in x by construction.
+// 8 lanes per scalar row (avg 11.5 nnz / row), both field components of the row computed in the same pass over the
+// shared pattern.  Every kernel is a template on the number of vectors P it serves per pass (1 or BLOCK_P).
 
 // y_q = B_int x_q for the P vectors of a block (column q at offset q*ld): the pattern and the Minv
-// values are read once for all P vectors.
+// values are read once for all P vectors.  (DPN = 1, the scalar pencil: A is one block as well and goes through here.)
 template <int P, int DPN>
 __global__ __launch_bounds__(256) void k_spmv_b_block(int N, int64_t ld, const int32_t* __restrict__ rowptr,
                                                       const int32_t* __restrict__ colind,
@@ -453,19 +415,6 @@ __global__ __launch_bounds__(256) void k_spmv_a_block(int N, int64_t ld, const i
 
 }  // namespace
 
-void launch_spmv_a_block(plfem_ctx* c, const double* x, double* y, int64_t ld) {
-  int64_t threads = (int64_t)c->N * 8;
-  int grid = (int)((threads + 255) / 256);
-  if (c->dpn == 1) {       // scalar pencil: A is one block (the AXX slot)
-    hipLaunchKernelGGL((k_spmv_b_block<BLOCK_P, 1>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                       c->d_bmask, c->d_vals[PLFEM_BLK_AXX], x, y);
-    return;
-  }
-  hipLaunchKernelGGL(k_spmv_a_block<BLOCK_P>, dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                     c->d_bmask, c->d_vals[PLFEM_BLK_AXX], c->d_vals[PLFEM_BLK_AXY], c->d_vals[PLFEM_BLK_AYX],
-                     c->d_vals[PLFEM_BLK_AYY], x, y);
-}
-
 void launch_element_matrices(plfem_ctx* c, int ncore, double eps_core, double eps_clad, double k0, double alpha_p) {
   int grid = (c->ne + EPB - 1) / EPB;
   hipLaunchKernelGGL(k_element_matrices, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
@@ -511,15 +460,28 @@ void launch_csr_gather(plfem_ctx* c) {
                      c->d_vals[6], c->d_vals[7]);
 }
 
-void launch_spmv_b_block(plfem_ctx* c, const double* x, double* y, int64_t ld) {
+namespace {
+template <int P>
+void spmv(plfem_ctx* c, int which, const double* x, double* y, int64_t ld) {
   int64_t threads = (int64_t)c->N * 8;
   int grid = (int)((threads + 255) / 256);
-  if (c->dpn == 1)
-    hipLaunchKernelGGL((k_spmv_b_block<BLOCK_P, 1>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                       c->d_bmask, c->d_vals[PLFEM_BLK_MINV], x, y);
+  const double* v = c->d_vals[which == 0 ? PLFEM_BLK_AXX : PLFEM_BLK_MINV];
+  if (c->dpn == 1)         // scalar pencil: A is one block too (the AXX slot)
+    hipLaunchKernelGGL((k_spmv_b_block<P, 1>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
+                       c->d_bmask, v, x, y);
+  else if (which == 0)
+    hipLaunchKernelGGL(k_spmv_a_block<P>, dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
+                       c->d_bmask, c->d_vals[PLFEM_BLK_AXX], c->d_vals[PLFEM_BLK_AXY], c->d_vals[PLFEM_BLK_AYX],
+                       c->d_vals[PLFEM_BLK_AYY], x, y);
   else
-    hipLaunchKernelGGL((k_spmv_b_block<BLOCK_P, 2>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                       c->d_bmask, c->d_vals[PLFEM_BLK_MINV], x, y);
+    hipLaunchKernelGGL((k_spmv_b_block<P, 2>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
+                       c->d_bmask, v, x, y);
+}
+}  // namespace
+
+void launch_spmv(plfem_ctx* c, int which, int P, const double* x, double* y, int64_t ld) {
+  if (P == 1) spmv<1>(c, which, x, y, ld);
+  else spmv<BLOCK_P>(c, which, x, y, ld);
 }
 
 // gram != nullptr: also the Gram partials of the block, gram[(p P + q) nblocks + block]; returns the number of workgroups
@@ -543,23 +505,6 @@ int launch_spmv_b_block_il(plfem_ctx* c, const double* xi, double* y, int64_t ld
                          c->d_bmask, c->d_vals[PLFEM_BLK_MINV], xi, y, gram);
   }
   return grid;
-}
-
-void launch_spmv(plfem_ctx* c, int which, const double* x, double* y) {
-  int64_t threads = (int64_t)c->N * 8;
-  int grid = (int)((threads + 255) / 256);
-  if (c->dpn == 1) {
-    hipLaunchKernelGGL((k_spmv<1, 1>), dim3(grid), dim3(256), 0, c->stream, c->N, c->d_rowptr, c->d_colind, c->d_bmask,
-                       c->d_vals[which == 0 ? PLFEM_BLK_AXX : PLFEM_BLK_MINV], nullptr, nullptr, nullptr, x, y);
-    return;
-  }
-  if (which == 0)
-    hipLaunchKernelGGL((k_spmv<0, 2>), dim3(grid), dim3(256), 0, c->stream, c->N, c->d_rowptr, c->d_colind, c->d_bmask,
-                       c->d_vals[PLFEM_BLK_AXX], c->d_vals[PLFEM_BLK_AXY], c->d_vals[PLFEM_BLK_AYX],
-                       c->d_vals[PLFEM_BLK_AYY], x, y);
-  else
-    hipLaunchKernelGGL((k_spmv<1, 2>), dim3(grid), dim3(256), 0, c->stream, c->N, c->d_rowptr, c->d_colind, c->d_bmask,
-                       c->d_vals[PLFEM_BLK_MINV], nullptr, nullptr, nullptr, x, y);
 }
 
 }  // namespace plfem

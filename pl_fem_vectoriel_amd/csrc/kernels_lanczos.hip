@@ -18,50 +18,6 @@ namespace {
 typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr int CHUNK = PANEL_CHUNK;   // rows per partial sum
 
-// partial[c * nchunks + chunk] = sum_{i in chunk} P[i, c] * w[i];  one wave per (chunk, column)
-__global__ __launch_bounds__(256) void k_panel_dot(int64_t n, int ncols, int nchunks, const double* __restrict__ P,
-                                                   const double* __restrict__ w, double* __restrict__ partial) {
-  const int c = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (c >= ncols) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t i0 = (int64_t)blockIdx.x * CHUNK;
-  const int64_t i1 = min(n, i0 + CHUNK);
-  const double* col = P + (int64_t)c * n;
-  double acc = 0.0;
-  for (int64_t i = i0 + lane; i < i1; i += 64) acc += col[i] * w[i];
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-  if (lane == 0) partial[(int64_t)c * nchunks + blockIdx.x] = acc;
-}
-
-// h[c] = sum over chunks of partial[c][*]: one wave per column, fixed (lane-strided, then butterfly) order
-__global__ __launch_bounds__(64) void k_panel_dot_finish(int ncols, int nchunks, const double* __restrict__ partial,
-                                                         double* __restrict__ h) {
-  const int c = blockIdx.x;
-  if (c >= ncols) return;
-  double acc = 0.0;
-  for (int q = threadIdx.x; q < nchunks; q += 64) acc += partial[(int64_t)c * nchunks + q];
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-  if (threadIdx.x == 0) h[c] = acc;
-}
-
-// w[i] -= sum_c P[i, c] h[c]
-__global__ __launch_bounds__(256) void k_panel_axpy(int64_t n, int ncols, const double* __restrict__ P,
-                                                    const double* __restrict__ h, double* __restrict__ w) {
-  __shared__ double sh[PLFEM_MAX_NCV + 8];
-  for (int c = threadIdx.x; c < ncols; c += 256) sh[c] = h[c];
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  double acc = 0.0;
-  for (int c = 0; c < ncols; ++c) acc += P[(int64_t)c * n + i] * sh[c];
-  w[i] -= acc;
-}
-
-__global__ void k_vec_add(int n, double* __restrict__ acc, const double* __restrict__ h) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) acc[i] += h[i];
-}
-
 // v = w / sqrt(beta2), bv = bw / sqrt(beta2); beta written to *beta_out
 __global__ __launch_bounds__(256) void k_scale_store(int64_t n, const double* __restrict__ w,
                                                      const double* __restrict__ bw, const double* __restrict__ beta2,
@@ -83,20 +39,15 @@ __global__ __launch_bounds__(256) void k_axpby(int64_t n, double a, const double
   if (i < n) z[i] = a * x[i] + b * y[i];
 }
 
-__global__ __launch_bounds__(256) void k_scale(int64_t n, double a, double* __restrict__ x) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) x[i] *= a;
-}
-
-// ---- block (P-vector) variants for block Lanczos --------------------------------------------------
+// ---- panel products of the two Lanczos drivers: P vectors per pass, P = BLOCK_P (block driver) or 1 ----------------
 // partial[(c*P + q) * nchunks + chunk] = sum_{i in chunk} Pm[i, c] * W[i, q].  One wave per (chunk, 4 columns):
 // the P values of W are loaded once for four columns of the panel (a wave per column re-read W from L2 ncols
 // times, which cost more than streaming the panel itself), two row groups per iteration = 16 loads in flight.
-template <int P>
+// P = 1 runs with CW = 1: one wave per (chunk, column), nothing to share between columns.
+template <int P, int CW>
 __global__ __launch_bounds__(256) void k_panel_dot_p(int64_t n, int ncols, int nchunks, const double* __restrict__ Pm,
                                                      const double* __restrict__ W, int64_t ldw,
                                                      double* __restrict__ partial) {
-  constexpr int CW = 4;                                  // columns per wave
   const int c0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * CW;
   if (c0 >= ncols) return;
   const int lane = threadIdx.x & 63;
@@ -719,30 +670,8 @@ void launch_residuals(plfem_ctx* c, int k, const double* lam_host, const double*
   resid_finish(c, k, out_host);
 }
 
-void launch_axpby_n(plfem_ctx* c, int64_t n, double a, const double* x, double b, const double* y, double* z) {
+void launch_axpby(plfem_ctx* c, int64_t n, double a, const double* x, double b, const double* y, double* z) {
   hipLaunchKernelGGL(k_axpby, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, a, x, b, y, z);
-}
-
-void launch_scale(plfem_ctx* c, int64_t n, double a, double* x) {
-  hipLaunchKernelGGL(k_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, a, x);
-}
-
-void launch_panel_dot(plfem_ctx* c, const double* P, int ncols, const double* w, double* h) {
-  const int nchunks = c->npartial;
-  hipLaunchKernelGGL(k_panel_dot, dim3(nchunks, (ncols + 3) / 4), dim3(256), 0, c->stream, c->n2, ncols, nchunks, P,
-                     w, c->d_partial);
-  hipLaunchKernelGGL(k_panel_dot_finish, dim3(ncols), dim3(64), 0, c->stream, ncols, nchunks, c->d_partial, h);
-}
-
-void launch_panel_axpy(plfem_ctx* c, const double* P, int ncols, const double* h, double* w) {
-  hipLaunchKernelGGL(k_panel_axpy, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), 0, c->stream, c->n2, ncols, P, h,
-                     w);
-}
-
-void launch_dot(plfem_ctx* c, const double* a, const double* b, double* out) { launch_panel_dot(c, a, 1, b, out); }
-
-void launch_vec_add(plfem_ctx* c, double* acc, const double* h, int n) {
-  hipLaunchKernelGGL(k_vec_add, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, acc, h);
 }
 
 void launch_scale_store(plfem_ctx* c, const double* w, const double* bw, const double* beta2, double* v, double* bv,
@@ -751,26 +680,37 @@ void launch_scale_store(plfem_ctx* c, const double* w, const double* bw, const d
                      beta2, v, bv, beta_out);
 }
 
-void launch_axpby(plfem_ctx* c, double a, const double* x, double b, const double* y, double* z) {
-  hipLaunchKernelGGL(k_axpby, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), 0, c->stream, c->n2, a, x, b, y, z);
-}
-
-void launch_panel_dot_block(plfem_ctx* c, const double* Pm, int ncols, const double* W, int64_t ldw, double* h, int ldh,
-                            double* hacc, int ldacc) {
-  constexpr int P = BLOCK_P;
+namespace {
+template <int P, int CW>
+void panel_dot(plfem_ctx* c, const double* Pm, int ncols, const double* W, int64_t ldw, double* h, int ldh, double* hacc,
+               int ldacc) {
   const int nchunks = c->npartial;
-  hipLaunchKernelGGL(k_panel_dot_p<P>, dim3(nchunks, (ncols + 15) / 16), dim3(256), 0, c->stream, c->n2, ncols, nchunks,
-                     Pm, W, ldw, c->d_partial);
+  hipLaunchKernelGGL((k_panel_dot_p<P, CW>), dim3(nchunks, (ncols + 4 * CW - 1) / (4 * CW)), dim3(256), 0, c->stream, c->n2,
+                     ncols, nchunks, Pm, W, ldw, c->d_partial);
   hipLaunchKernelGGL(k_panel_dot_finish_p, dim3(ncols * P), dim3(64), 0, c->stream, P, nchunks, c->d_partial, h, ldh,
                      hacc, ldacc);
 }
 
-void launch_panel_axpy_block(plfem_ctx* c, const double* Pm, int ncols, const double* H, int ldh, double* W, int64_t ldw,
-                             double* w_interleaved) {
-  constexpr int P = BLOCK_P;
+template <int P>
+void panel_axpy(plfem_ctx* c, const double* Pm, int ncols, const double* H, int ldh, double* W, int64_t ldw, double* wil) {
   hipLaunchKernelGGL(k_panel_axpy_p<P>, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), sizeof(double) * ncols * P,
-                     c->stream, c->n2, ncols, Pm, H, ldh, W, ldw, w_interleaved, c->N, c->dpn);
+                     c->stream, c->n2, ncols, Pm, H, ldh, W, ldw, wil, c->N, c->dpn);
 }
+}  // namespace
+
+void launch_panel_dot(plfem_ctx* c, int P, const double* Pm, int ncols, const double* W, int64_t ldw, double* h, int ldh,
+                      double* hacc, int ldacc) {
+  if (P == 1) panel_dot<1, 1>(c, Pm, ncols, W, ldw, h, ldh, hacc, ldacc);
+  else panel_dot<BLOCK_P, 4>(c, Pm, ncols, W, ldw, h, ldh, hacc, ldacc);
+}
+
+void launch_panel_axpy(plfem_ctx* c, int P, const double* Pm, int ncols, const double* H, int ldh, double* W, int64_t ldw,
+                       double* w_interleaved) {
+  if (P == 1) panel_axpy<1>(c, Pm, ncols, H, ldh, W, ldw, w_interleaved);
+  else panel_axpy<BLOCK_P>(c, Pm, ncols, H, ldh, W, ldw, w_interleaved);
+}
+
+void launch_dot(plfem_ctx* c, const double* a, const double* b, double* out) { launch_panel_dot(c, 1, a, 1, b, c->n2, out, 1); }
 
 // first Gram-Schmidt pass over ncols <= 8 columns, fused with the permutation of the sweeps' result (d_xl, front order)
 // into W (global order): h -> Hout, W -= Vm h.  (8 columns x P sums per thread: the two kernels are written for P = 4)

@@ -677,22 +677,46 @@ void sweeps(plfem_ctx* c) {
 
 }  // namespace
 
-void launch_solve(plfem_ctx* c, const double* rhs, double* x) {
-  const unsigned grid = (unsigned)((c->n2 + 255) / 256);
-  hipLaunchKernelGGL(k_permute_in<1>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, rhs, c->n2, c->d_fvec);
-  sweeps<1>(c);
-  hipLaunchKernelGGL(k_permute_out<1>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, c->d_xl, x, c->n2);
-}
-
-// BLOCK_P right-hand sides given as columns (ldx apart); inside the sweeps the P values of a DOF are one 32-byte
-// access.  rhs_in_front_order: the caller's previous kernel (k_block_scale) already left the right-hand side in the
-// sweeps' layout (context buffer d_fvec)
-void launch_solve_block(plfem_ctx* c, const double* rhs, double* x, int64_t ldx, bool rhs_in_front_order) {
+namespace {
+template <int P>
+void solve(plfem_ctx* c, const double* rhs, double* x, int64_t ldx, bool rhs_in_front_order) {
   const unsigned grid = (unsigned)((c->n2 + 255) / 256);
   if (!rhs_in_front_order)
-    hipLaunchKernelGGL(k_permute_in<BLOCK_P>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, rhs, ldx, c->d_fvec);
-  sweeps<BLOCK_P>(c);
-  if (x) hipLaunchKernelGGL(k_permute_out<BLOCK_P>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, c->d_xl, x, ldx);
+    hipLaunchKernelGGL(k_permute_in<P>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, rhs, ldx, c->d_fvec);
+  sweeps<P>(c);
+  if (x) hipLaunchKernelGGL(k_permute_out<P>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, c->d_xl, x, ldx);
+}
+}  // namespace
+
+// P (1 or BLOCK_P) right-hand sides given as columns (ldx apart); inside the sweeps the P values of a DOF are one 8 P-byte
+// access.  rhs_in_front_order: the caller's previous kernel (k_block_scale) already left the right-hand side in the
+// sweeps' layout (context buffer d_fvec)
+void launch_solve(plfem_ctx* c, int P, const double* rhs, double* x, int64_t ldx, bool rhs_in_front_order) {
+  if (P == 1) solve<1>(c, rhs, x, ldx, rhs_in_front_order);
+  else solve<BLOCK_P>(c, rhs, x, ldx, rhs_in_front_order);
+}
+
+// y = K^-1 b followed by `steps` passes of iterative refinement against the ASSEMBLED K = A - sigma B:
+//   r = b - (A y - sigma B y),  y += K^-1 r.
+// Scratch ta, tb, dy: P columns ld apart each.  ld == n2: the columns of a block are contiguous and every update is one
+// launch; otherwise column by column, so that the gaps between the columns stay untouched.
+void solve_refined(plfem_ctx* c, int P, const double* b, double* y, int64_t ld, bool b_in_front_order, int steps, double* ta,
+                   double* tb, double* dy) {
+  launch_solve(c, P, b, y, ld, b_in_front_order);
+  const bool contiguous = ld == c->n2;
+  const int nrun = contiguous ? 1 : P;
+  const int64_t len = contiguous ? c->n2 * P : c->n2;
+  auto axpby = [&](double a, const double* x, double bb, const double* yy, double* z) {
+    for (int u = 0; u < nrun; ++u) launch_axpby(c, len, a, x + u * ld, bb, yy + u * ld, z + u * ld);
+  };
+  for (int it = 0; it < steps; ++it) {
+    launch_spmv(c, 0, P, y, ta, ld);
+    launch_spmv(c, 1, P, y, tb, ld);
+    axpby(-1.0, ta, c->sigma, tb, ta);          // ta = -A y + sigma B y
+    axpby(1.0, b, 1.0, ta, ta);                 // ta = b - K y
+    launch_solve(c, P, ta, dy, ld);
+    axpby(1.0, y, 1.0, dy, y);
+  }
 }
 
 }  // namespace plfem

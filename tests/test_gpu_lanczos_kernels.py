@@ -120,8 +120,8 @@ def ok(gpu, ref, bound, what):
 @pytest.mark.parametrize("name", CASES)
 def test_panel_products_block_and_single(cases, name):
     """k_panel_dot_p + k_panel_dot_finish_p (with and without the CGS2 hacc accumulation), k_panel_axpy_p (with and without
-    the interleaved wil copy), and the single-vector k_panel_dot / k_panel_dot_finish / k_panel_axpy / k_vec_add, at column
-    counts off the 16-column workgroups up to max_ncv + P."""
+    the interleaved wil copy) at P = BLOCK_P, and their P = 1 instances of the single-vector driver (one column per wave, the
+    hacc accumulation included), at column counts off the 16-column workgroups up to max_ncv + P."""
     c = cases(name)
     n2, ldw = c.n2, c.n2 + GAP
     nmax = max(c.ncols)
@@ -175,12 +175,13 @@ def test_panel_products_block_and_single(cases, name):
         r1, b1 = le.panel_axpy(w1, Pm_h[:, :ncols], h1[:ncols, None])
         ok(c.host(wd)[:, None], r1, b1, f"axpy ncols={ncols}")
         le.assert_margins(r1, b1, le.panel_axpy_mutants(w1, Pm_h[:, :ncols], h1[:ncols, None]))
-        # k_vec_add: acc[0:ncols] += h
+        # CGS2 at P = 1: acc[0:ncols] += h (same h bits into the second output)
         a0 = c.random(ncols + 1)
         ad = c.dev(a0)
-        c.ctx.debug_panel("vec_add", ncols, None, None, 0, hs, 0, hacc=ad)
+        c.ctx.debug_panel("dot", ncols, Pm, c.dev(w1), n2, hs, ncols, hacc=ad, ldacc=ncols)
         ah = c.host(ad)
         assert np.array_equal(ah[:ncols], a0[:ncols] + h1[:ncols]) and ah[ncols] == a0[ncols]
+        assert np.array_equal(c.host(hs), h1, equal_nan=True)
 
 
 @pytest.mark.parametrize("name", CASES)
