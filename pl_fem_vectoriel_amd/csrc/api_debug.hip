@@ -88,7 +88,7 @@ extern "C" int plfem_debug_solve_block(plfem_ctx* c, const double* rhs_dev, int6
   if (!c->factored) { c->err = "debug block solve before plfem_factor"; return PLFEM_ESTATE; }
   if (c->max_block_p < P) { c->err = "debug block solve: the LDS budget of this tree allows one right-hand side per sweep"; return PLFEM_EINVAL; }
   if (ldx < c->n2) { c->err = "debug block solve: ldx < n2"; return PLFEM_EINVAL; }
-  const int64_t scratch = (int64_t)c->n2 * (c->max_ncv + 1 + P);
+  const int64_t scratch = (int64_t)c->n2 * plfem::basis_cols(c->max_ncv);
   if (refine_steps > 0 && 3 * P * ldx > scratch) { c->err = "debug block solve: ldx too large for the refinement scratch"; return PLFEM_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
   plfem::solve_refined(c, P, rhs_dev, x_dev, ldx, false, refine_steps, c->d_V2, c->d_V2 + (size_t)P * ldx,
@@ -102,11 +102,12 @@ extern "C" int plfem_debug_solve_block(plfem_ctx* c, const double* rhs_dev, int6
 // forward / backward workgroups, block steps of the factorisation, right-hand sides per sweep the LDS budget allows.
 extern "C" int plfem_debug_level_plan(plfem_ctx* c, int64_t* out, int64_t cap) try {
   if (!c || !out) return PLFEM_EINVAL;
-  const int nl = (int)c->levels.size();
+  const plfem::LaunchPlan& plan = *c->plan;
+  const int nl = (int)plan.levels.size();
   if (cap < (int64_t)PLFEM_DEBUG_PLAN_FIELDS * nl) { c->err = "debug level plan: cap too small"; return PLFEM_EINVAL; }
   for (int l = 0; l < nl; ++l) {
-    const plfem::LevelInfo& li = c->levels[l];
-    const int next = l + 1 < nl ? c->levels[l + 1].step0 : (int)c->upd_n.size();
+    const plfem::LevelInfo& li = plan.levels[l];
+    const int next = l + 1 < nl ? plan.levels[l + 1].step0 : (int)plan.upd_n.size();
     const int64_t rec[PLFEM_DEBUG_PLAN_FIELDS] = {li.count, li.fwd_rows, li.bwd_rows, li.fwd_mixed ? 1 : 0, li.max_s2, li.max_m,
                                                   li.fwd_n, li.bwd_n, next - li.step0, c->max_block_p};
     std::copy(rec, rec + PLFEM_DEBUG_PLAN_FIELDS, out + (int64_t)PLFEM_DEBUG_PLAN_FIELDS * l);
@@ -151,7 +152,7 @@ extern "C" int plfem_debug_scale_store(plfem_ctx* c, const double* w, const doub
 extern "C" int plfem_debug_first_pass(plfem_ctx* c, const double* xl_front, const double* BVm, const double* Vm, int32_t ncols,
                                       double* W, int64_t ldw, double* Hout, int32_t ldh) try {
   if (!c || !xl_front || !BVm || !Vm || !W || !Hout) return PLFEM_EINVAL;
-  if (ncols < 1 || ncols > 8 || ldw < c->n2 || ldh < ncols) { c->err = "debug first pass: need 1 <= ncols <= 8, ldw >= n2, ldh >= ncols"; return PLFEM_EINVAL; }
+  if (ncols < 1 || ncols > plfem::FIRST_COLS || ldw < c->n2 || ldh < ncols) { c->err = "debug first pass: need 1 <= ncols <= FIRST_COLS, ldw >= n2, ldh >= ncols"; return PLFEM_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemcpyAsync(c->d_xl, xl_front, sizeof(double) * 2 * c->fnodes_total * plfem::BLOCK_P, hipMemcpyDeviceToDevice, c->stream));
   plfem::launch_first_pass_block(c, BVm, Vm, ncols, W, ldw, Hout, ldh);
@@ -185,8 +186,7 @@ extern "C" int plfem_debug_chol(plfem_ctx* c, const double* G, int32_t ldg, int3
   if (!c || !Tblk || !Rinv || ldT < P) return PLFEM_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   if (use_partials) {
-    const int64_t cap = std::max((int64_t)c->npartial * (c->max_ncv + 1 + P + 8) * P, (int64_t)P * P * ((c->N * (int64_t)8 + 255) / 256));
-    if (nchunks < 1 || (int64_t)P * P * nchunks > cap) { c->err = "debug chol: nchunks out of range"; return PLFEM_EINVAL; }
+    if (nchunks < 1 || (size_t)P * P * nchunks > c->partial_doubles) { c->err = "debug chol: nchunks out of range"; return PLFEM_EINVAL; }
     if (G) HIP_TRY(c, hipMemcpyAsync(c->d_partial, G, sizeof(double) * P * P * nchunks, hipMemcpyDeviceToDevice, c->stream));
   } else if (!G || ldg < P) {
     return PLFEM_EINVAL;

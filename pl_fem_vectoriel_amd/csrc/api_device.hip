@@ -17,7 +17,6 @@
 #include "host_eig.h"
 #include "p2_element.h"
 
-using plfem::LevelInfo;
 using plfem::Symbolic;
 
 namespace {
@@ -244,6 +243,106 @@ void free_all(plfem_ctx* c) {
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// What place_buffers leaves for flush_uploads: the recorded host arrays, the slab bytes they span, how many of them are
+// mesh-level
+struct Placement {
+  std::vector<UploadItem> items;
+  size_t upload_span = 0, mesh_items = 0;
+};
+
+// One pass over every device buffer of the context, in slab order (see dalloc: measuring or placing)
+int place_buffers(plfem_ctx* c, int max_ncv, Placement& pl) {
+  const Symbolic& S = *c->S;
+  const plfem::LaunchPlan& P = *c->plan;
+  auto& items = pl.items;
+  c->slab_off = 0;
+  items.clear();
+  // mesh-level arrays first: all that the CSR pattern kernel and the assembly read.  They go up on the context's stream,
+  // the front-level arrays behind them on the copy stream, so that pattern and assembly run beside the rest of the upload
+  TRY(upload(c, items, &c->d_edof, S.edof));
+  c->d_tsorted = c->d_edof;          // rows 0-2 of the element DOF table ARE the column-sorted vertex table
+  TRY(upload(c, items, &c->d_rowptr, S.rowptr));
+  TRY(upload(c, items, &c->d_nptr, S.nptr));
+  TRY(upload(c, items, &c->d_nadj, S.nadj));
+  TRY(upload(c, items, &c->d_nloc, S.nloc));
+  TRY(upload(c, items, &c->d_interior, S.interior));
+  TRY(upload(c, items, &c->d_bmask, S.bmask));
+  TRY(upload(c, items, &c->d_doflocs, S.doflocs));
+  pl.mesh_items = items.size();
+  TRY(upload(c, items, &c->d_blk, P.jobs));
+  TRY(upload(c, items, reinterpret_cast<plfem::Tile**>(&c->d_tiles), P.tiles));   // (Tile has int2's layout)
+  TRY(upload(c, items, &c->d_forder, P.forder));
+  TRY(upload(c, items, &c->d_frec, P.frec));
+  TRY(upload(c, items, &c->d_fs2, P.fs2));
+  TRY(upload(c, items, &c->d_fm, P.fm));
+  TRY(upload(c, items, &c->d_fnode_ptr, S.fnode_ptr));
+  TRY(upload(c, items, &c->d_foff, S.foff));
+  TRY(upload(c, items, &c->d_soff, S.soff));
+  TRY(upload(c, items, &c->d_fnodes, S.fnodes));
+  TRY(upload(c, items, &c->d_cinv0, S.cinv0));
+  TRY(upload(c, items, &c->d_cinv1, S.cinv1));
+  TRY(upload(c, items, &c->d_epos, S.epos));
+  TRY(upload(c, items, &c->d_leaf_elem_ptr, S.leaf_elem_ptr));
+  TRY(upload(c, items, &c->d_leaf_elems, S.leaf_elems));
+  TRY(upload(c, items, &c->d_npos, S.npos));
+  TRY(upload(c, items, &c->d_prow, S.prow));
+  pl.upload_span = c->slab_off;
+  TRY(dalloc(c, &c->d_colind, (size_t)c->nnz));      // filled on the device by launch_pattern_fill below
+  TRY(dalloc(c, &c->d_slot_row, (size_t)c->nnz));
+  TRY(dalloc(c, &c->d_cores, plfem::MAX_CORES * 3));
+  TRY(dalloc(c, &c->d_elem, (size_t)S.ne * plfem::ELEM_STRIDE));
+  for (auto& p : c->d_vals) TRY(dalloc(c, &p, (size_t)c->nnz));
+  TRY(dalloc(c, &c->d_front, (size_t)S.foff[S.nfronts]));
+  c->arena_doubles = (S.arena_doubles + 31) & ~(int64_t)31;
+  const int64_t fnodes_total = c->fnodes_total = S.fnode_ptr[S.nfronts];
+  TRY(dalloc(c, &c->d_fvec, (size_t)2 * fnodes_total * plfem::BLOCK_P));
+  // What only the factorisation needs (Schur arenas, panels) and what only the Lanczos drivers need (the bases V, B V and
+  // their restart copies) are never alive at the same time -- a context factorises, then iterates, on one stream -- and
+  // share one region of the workspace.
+  const size_t union_start = c->slab_off;
+  TRY(dalloc(c, &c->d_schur, (size_t)2 * c->arena_doubles));
+  // (panels of the largest tree level, one level at a time; three thirds: block steps kb mod 3)
+  TRY(dalloc(c, &c->d_wbuf, (size_t)6 * P.level_nodes_max * plfem::NB));
+  TRY(dalloc(c, &c->d_rbuf, (size_t)6 * P.level_nodes_max * plfem::NB));
+  const size_t factor_end = c->slab_off;
+  const size_t n2 = (size_t)c->n2, nc1 = (size_t)plfem::basis_cols(max_ncv), ncp = (size_t)plfem::proj_cols(max_ncv);
+  c->slab_off = union_start;
+  TRY(dalloc(c, &c->d_V, n2 * nc1));
+  TRY(dalloc(c, &c->d_BV, n2 * nc1));
+  TRY(dalloc(c, &c->d_V2, n2 * nc1));
+  TRY(dalloc(c, &c->d_BV2, n2 * nc1));
+  c->slab_off = std::max(c->slab_off, factor_end);
+  TRY(dalloc(c, &c->d_dinv, (size_t)2 * S.nfronts * plfem::NB * plfem::NB));   // X of the pivot blocks, by block-step parity
+  TRY(dalloc(c, &c->d_delta, (size_t)4 * fnodes_total));   // D^-1: (diagonal, off-diagonal) per front row
+  TRY(dalloc(c, &c->d_fvec2, (size_t)2 * fnodes_total * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_u0, (size_t)2 * fnodes_total * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_u1, (size_t)2 * fnodes_total * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_xl, (size_t)2 * fnodes_total * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_counters, 4));
+  TRY(dalloc(c, &c->d_w, n2 * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_bw, n2 * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_hblk, ncp * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_G, 64));
+  TRY(dalloc(c, &c->d_Rinv, 64));
+  TRY(dalloc(c, &c->d_t1, n2 * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_t2, n2 * plfem::BLOCK_P));
+  TRY(dalloc(c, &c->d_h, ncp));
+  TRY(dalloc(c, &c->d_hacc, ncp));
+  // three users, one after the other on the context's stream: a panel dot, the Gram partials of the fused block B product,
+  // the fused first pass
+  c->partial_doubles = std::max({plfem::panel_dot_partial_doubles(c->n2, (int)ncp), plfem::gram_partial_doubles(S.N),
+                                 plfem::first_pass_partial_doubles(c->n2)});
+  TRY(dalloc(c, &c->d_partial, c->partial_doubles));
+  TRY(dalloc(c, &c->d_scal, 16));
+  TRY(dalloc(c, &c->d_S, nc1 * nc1));
+  TRY(dalloc(c, &c->d_Hcols, (nc1 + 1) * (nc1 + 1)));
+  TRY(dalloc(c, &c->d_coremask, (size_t)S.N));
+  // two halves of post_doubles each: the post-processing, and the residual check in flight beside it
+  c->post_doubles = std::max(plfem::post_sum_doubles(S.N, (int)nc1), plfem::resid_sum_doubles(S.N, (int)nc1)) + 16;
+  TRY(dalloc(c, &c->d_post, 2 * c->post_doubles));
+  return PLFEM_OK;
+}
+
 int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* stream, int max_ncv, void* workspace,
                 int64_t workspace_bytes, bool size_only) {
   const Symbolic& S = sym->S;
@@ -262,26 +361,17 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
   c->nv = S.nv; c->ne = S.ne; c->N = S.N; c->nnz = S.rowptr.empty() ? 0 : (int)S.rowptr[S.N]; c->nsolve = S.nsolve;
   c->L = S.L; c->nfronts = S.nfronts; c->dpn = S.dpn; c->sh = S.dpn - 1; c->n2 = S.dpn * (int64_t)S.N; c->max_ncv = max_ncv;
   // The launch plan (kernel forms by level, launch order, workgroup lists) depends on the mesh only: it is part of the
-  // analysis (plan.cpp, built at the end of build_symbolic) and every context on that analysis uploads the same one.
-  const plfem::LaunchPlan& P = S.plan;
-  if (!P.built) { c->err = "plfem_create: the analysis carries no launch plan"; return PLFEM_ESTATE; }
-  c->levels = P.levels;
-  c->forder_s2 = P.forder_s2;
-  c->forder_maxm = P.forder_maxm;
-  c->upd_off = P.upd_off;
-  c->upd_n.assign(P.upd_n.begin(), P.upd_n.end());
-  c->formz_all_off = P.formz_all_off; c->formz_all_n = P.formz_all_n;
-  c->mirrorx_all_off = P.mirrorx_all_off; c->mirrorx_all_n = P.mirrorx_all_n;
-  // The solve sweeps stage one front's right-hand sides in LDS: 8 P (max_m + 1) bytes dynamic + the static
-  // partial-sum buffer of the tile kernels (P x 4 KB backward, 8 waves).  Beyond the device limit the launch would
-  // fail as an opaque "invalid argument" much later, so decide here: P = BLOCK_P, else P = 1, else a clear error.
+  // analysis (plan.cpp, built at the end of build_symbolic); every context on that analysis reads and uploads the same one.
+  if (!S.plan.built) { c->err = "plfem_create: the analysis carries no launch plan"; return PLFEM_ESTATE; }
+  c->plan = &S.plan;
+  // The solve sweeps stage one front's right-hand sides in LDS (sweep_lds, device.h).  Beyond the device limit the launch
+  // would fail as an opaque "invalid argument" much later, so decide here: P = BLOCK_P, else P = 1, else a clear error.
   if (!size_only) {
     int lim = 0;
     HIP_TRY(c, hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
-    const int worst = P.worst_m;
-    auto need = [&](int Pn) { return (int64_t)sizeof(double) * Pn * (worst + 2) + (int64_t)sizeof(double) * 8 * Pn * 64; };
-    if (need(plfem::BLOCK_P) <= lim) c->max_block_p = plfem::BLOCK_P;
-    else if (need(1) <= lim) c->max_block_p = 1;
+    const int worst = c->plan->worst_m;
+    if (plfem::sweep_lds(plfem::BLOCK_P, worst) <= (size_t)lim) c->max_block_p = plfem::BLOCK_P;
+    else if (plfem::sweep_lds(1, worst) <= (size_t)lim) c->max_block_p = 1;
     else {
       c->err = "plfem_create: largest front has " + std::to_string(worst) + " DOFs; the solve sweeps stage 8 (m + 1) bytes of it in LDS, "
                "which exceeds this device's " + std::to_string(lim) + " bytes per workgroup (use a smaller leaf size / a coarser mesh)";
@@ -289,101 +379,9 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
     }
   }
   const bool ctx_trace = getenv("PLFEM_CTX_TRACE") != nullptr;
-  const double tt0 = now_ms();
   const double tt1 = now_ms();
-  std::vector<UploadItem> items;
-  size_t upload_span = 0, mesh_items = 0;
-  auto place = [&]() -> int {
-  c->slab_off = 0;
-  items.clear();
-  // mesh-level arrays first: all that the CSR pattern kernel and the assembly read.  They go up on the context's stream,
-  // the front-level arrays behind them on the copy stream, so that pattern and assembly run beside the rest of the upload
-  TRY(upload(c, items, &c->d_edof, S.edof));
-  c->d_tsorted = c->d_edof;          // rows 0-2 of the element DOF table ARE the column-sorted vertex table
-  TRY(upload(c, items, &c->d_rowptr, S.rowptr));
-  TRY(upload(c, items, &c->d_nptr, S.nptr));
-  TRY(upload(c, items, &c->d_nadj, S.nadj));
-  TRY(upload(c, items, &c->d_nloc, S.nloc));
-  TRY(upload(c, items, &c->d_interior, S.interior));
-  TRY(upload(c, items, &c->d_bmask, S.bmask));
-  TRY(upload(c, items, &c->d_doflocs, S.doflocs));
-  mesh_items = items.size();
-  TRY(upload(c, items, &c->d_blk, P.jobs));
-  TRY(upload(c, items, reinterpret_cast<plfem::Tile**>(&c->d_tiles), P.tiles));   // (Tile has int2's layout)
-  TRY(upload(c, items, &c->d_forder, P.forder));
-  TRY(upload(c, items, &c->d_frec, P.frec));
-  TRY(upload(c, items, &c->d_fs2, P.fs2));
-  TRY(upload(c, items, &c->d_fm, P.fm));
-  TRY(upload(c, items, &c->d_fnode_ptr, S.fnode_ptr));
-  TRY(upload(c, items, &c->d_foff, S.foff));
-  TRY(upload(c, items, &c->d_soff, S.soff));
-  TRY(upload(c, items, &c->d_fnodes, S.fnodes));
-  TRY(upload(c, items, &c->d_cinv0, S.cinv0));
-  TRY(upload(c, items, &c->d_cinv1, S.cinv1));
-  TRY(upload(c, items, &c->d_epos, S.epos));
-  TRY(upload(c, items, &c->d_leaf_elem_ptr, S.leaf_elem_ptr));
-  TRY(upload(c, items, &c->d_leaf_elems, S.leaf_elems));
-  TRY(upload(c, items, &c->d_npos, S.npos));
-  TRY(upload(c, items, &c->d_prow, S.prow));
-  upload_span = c->slab_off;
-  TRY(dalloc(c, &c->d_colind, (size_t)c->nnz));      // filled on the device by launch_pattern_fill below
-  TRY(dalloc(c, &c->d_slot_row, (size_t)c->nnz));
-  TRY(dalloc(c, &c->d_cores, plfem::MAX_CORES * 3));
-  TRY(dalloc(c, &c->d_elem, (size_t)S.ne * plfem::ELEM_STRIDE));
-  for (auto& p : c->d_vals) TRY(dalloc(c, &p, (size_t)c->nnz));
-  const int64_t fnodes_total = S.fnode_ptr[S.nfronts];
-  TRY(dalloc(c, &c->d_front, (size_t)S.foff[S.nfronts]));
-  c->arena_doubles = (S.arena_doubles + 31) & ~(int64_t)31;
-  TRY(dalloc(c, &c->d_fvec, (size_t)2 * fnodes_total * plfem::BLOCK_P));
-  c->fnodes_total = fnodes_total;
-  const int64_t level_nodes = P.level_nodes_max;   // (largest tree level: the panel scratch holds one level at a time)
-  c->level_nodes_max = level_nodes;
-  // What only the factorisation needs (Schur arenas, panels) and what only the Lanczos drivers need (the bases V, B V and
-  // their restart copies) are never alive at the same time -- a context factorises, then iterates, on one stream -- and
-  // share one region of the workspace.
-  const size_t union_start = c->slab_off;
-  TRY(dalloc(c, &c->d_schur, (size_t)2 * c->arena_doubles));
-  TRY(dalloc(c, &c->d_wbuf, (size_t)6 * level_nodes * plfem::NB));   // three thirds: panels of block steps kb mod 3
-  TRY(dalloc(c, &c->d_rbuf, (size_t)6 * level_nodes * plfem::NB));
-  const size_t factor_end = c->slab_off;
-  const size_t n2 = (size_t)c->n2, nc1 = (size_t)max_ncv + 1 + plfem::BLOCK_P;
-  c->slab_off = union_start;
-  TRY(dalloc(c, &c->d_V, n2 * nc1));
-  TRY(dalloc(c, &c->d_BV, n2 * nc1));
-  TRY(dalloc(c, &c->d_V2, n2 * nc1));
-  TRY(dalloc(c, &c->d_BV2, n2 * nc1));
-  c->slab_off = std::max(c->slab_off, factor_end);
-  TRY(dalloc(c, &c->d_dinv, (size_t)2 * S.nfronts * plfem::NB * plfem::NB));   // X of the pivot blocks, by block-step parity
-  TRY(dalloc(c, &c->d_delta, (size_t)4 * fnodes_total));   // D^-1: (diagonal, off-diagonal) per front row
-  TRY(dalloc(c, &c->d_fvec2, (size_t)2 * fnodes_total * plfem::BLOCK_P));
-  TRY(dalloc(c, &c->d_u0, (size_t)2 * fnodes_total * plfem::BLOCK_P));
-  TRY(dalloc(c, &c->d_u1, (size_t)2 * fnodes_total * plfem::BLOCK_P));
-  TRY(dalloc(c, &c->d_xl, (size_t)2 * fnodes_total * plfem::BLOCK_P));
-  TRY(dalloc(c, &c->d_counters, 4));
-  TRY(dalloc(c, &c->d_w, n2 * plfem::BLOCK_P));
-  TRY(dalloc(c, &c->d_bw, n2 * plfem::BLOCK_P));
-  TRY(dalloc(c, &c->d_hblk, (nc1 + 8) * plfem::BLOCK_P));
-  TRY(dalloc(c, &c->d_G, 64));
-  TRY(dalloc(c, &c->d_Rinv, 64));
-  TRY(dalloc(c, &c->d_t1, n2 * plfem::BLOCK_P));
-  TRY(dalloc(c, &c->d_t2, n2 * plfem::BLOCK_P));
-  c->npartial = (int)((c->n2 + plfem::PANEL_CHUNK - 1) / plfem::PANEL_CHUNK);
-  TRY(dalloc(c, &c->d_h, nc1 + 8));
-  TRY(dalloc(c, &c->d_hacc, nc1 + 8));
-  // (also the Gram partials of the fused block B product: P x P entries x one partial per workgroup of 32 rows)
-  TRY(dalloc(c, &c->d_partial, std::max((size_t)c->npartial * (nc1 + 8) * plfem::BLOCK_P,
-                                        (size_t)plfem::BLOCK_P * plfem::BLOCK_P * (((size_t)S.N * 8 + 255) / 256) + 64 +
-                                            (size_t)8 * plfem::BLOCK_P * (n2 / 256 + 2))));   // (and the fused first pass: 8 columns x P per 512 rows or fewer)
-  TRY(dalloc(c, &c->d_scal, 16));
-  TRY(dalloc(c, &c->d_S, nc1 * nc1));
-  TRY(dalloc(c, &c->d_Hcols, (nc1 + 1) * (nc1 + 1)));
-  TRY(dalloc(c, &c->d_coremask, (size_t)S.N));
-  const size_t post_blocks = (size_t)(S.N + 255) / 256;
-  c->post_doubles = nc1 * post_blocks * 5 + nc1 * 5 + 16;
-  TRY(dalloc(c, &c->d_post, 2 * c->post_doubles));   // (second half: the residual check, in flight beside the post-processing)
-  return PLFEM_OK;
-  };
-  TRY(place());                      // pass 0: measure
+  Placement pl;
+  TRY(place_buffers(c, max_ncv, pl));   // pass 0: measure
   const size_t need = c->slab_off;
   c->workspace_need = (int64_t)need;
   if (size_only) return PLFEM_OK;
@@ -397,13 +395,13 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
   }
   c->slab_bytes = need;
   const double tt2 = now_ms();
-  TRY(place());                      // pass 1: place, then one staged upload
+  TRY(place_buffers(c, max_ncv, pl));   // pass 1: place, then one staged upload
   double* staging = nullptr;
   size_t staging_bytes = 0;
-  HIP_TRY(c, pinned_acquire(upload_span, &staging, &staging_bytes));
+  HIP_TRY(c, pinned_acquire(pl.upload_span, &staging, &staging_bytes));
   c->h_staging = staging;               // owned by the context from here on: released with it (free_all), so that
   c->h_staging_bytes = staging_bytes;   // creation does not have to wait for the copy
-  TRY(flush_uploads(c, items, upload_span, reinterpret_cast<char*>(staging), mesh_items));
+  TRY(flush_uploads(c, pl.items, pl.upload_span, reinterpret_cast<char*>(staging), pl.mesh_items));
   const double tt3 = now_ms();
   HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, 4 * sizeof(int32_t), c->stream));
   // the padding rows of the front-ordered right-hand side are never written and are multiplied by exact zeros of the
@@ -421,7 +419,7 @@ int create_impl(plfem_ctx* c, const plfem_symbolic* sym, int device, void* strea
   const double tt4 = now_ms();
   // no synchronisation: the upload and the pattern kernel run on while the caller prepares the assembly (every
   // later use of the context is ordered behind them on the stream)
-  if (ctx_trace) fprintf(stderr, "[ctx] lists %.3f  size pass %.3f  upload pass %.3f  pinned+launch %.3f  sync %.3f ms\n", tt1 - tt0, tt2 - tt1, tt3 - tt2, tt4 - tt3, now_ms() - tt4);
+  if (ctx_trace) fprintf(stderr, "[ctx] size pass %.3f  upload pass %.3f  pinned+launch %.3f  sync %.3f ms\n", tt2 - tt1, tt3 - tt2, tt4 - tt3, now_ms() - tt4);
   return PLFEM_OK;
 }
 
@@ -485,38 +483,39 @@ extern "C" int plfem_synchronize(plfem_ctx* ctx) try {
   return PLFEM_OK;
 } catch (...) { return host_failure(ctx); }
 
-extern "C" int plfem_assemble_hfield(plfem_ctx* c, const double* cores_host, int32_t ncore, double eps_core,
-                                     double eps_clad, double k0, double alpha_p) try {
-  if (!c) return PLFEM_EINVAL;
+namespace {
+// the two assembly calls: cores up, the element matrices (`element_matrices`, the one launch that differs), CSR gather
+template <class ElementMatrices>
+int assemble(plfem_ctx* c, const double* cores_host, int ncore, double eps_core, double eps_clad, const char* what,
+             ElementMatrices element_matrices) {
   if (!(eps_core > 0) || !(eps_clad > 0)) { c->err = "permittivities must be positive"; return PLFEM_EINVAL; }
-  if (c->dpn != 2) { c->err = "plfem_assemble_hfield: the analysis of this context has one unknown per node (use plfem_assemble_scalar)"; return PLFEM_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(upload_cores(c, cores_host, ncore));
   HIP_TRY(c, phase_begin(c, plfem::PH_ASSEMBLE));
-  plfem::launch_element_matrices(c, ncore, eps_core, eps_clad, k0, alpha_p);
+  element_matrices();
   plfem::launch_csr_gather(c);
   HIP_TRY(c, phase_end(c, plfem::PH_ASSEMBLE));
-  TRY(check_launch(c, "assemble"));
+  TRY(check_launch(c, what));
   c->assembled = true;
   c->factored = false;
   return PLFEM_OK;
+}
+}  // namespace
+
+extern "C" int plfem_assemble_hfield(plfem_ctx* c, const double* cores_host, int32_t ncore, double eps_core,
+                                     double eps_clad, double k0, double alpha_p) try {
+  if (!c) return PLFEM_EINVAL;
+  if (c->dpn != 2) { c->err = "plfem_assemble_hfield: the analysis of this context has one unknown per node (use plfem_assemble_scalar)"; return PLFEM_EINVAL; }
+  return assemble(c, cores_host, ncore, eps_core, eps_clad, "assemble",
+                  [&] { plfem::launch_element_matrices(c, ncore, eps_core, eps_clad, k0, alpha_p); });
 } catch (...) { return host_failure(c); }
 
 extern "C" int plfem_assemble_scalar(plfem_ctx* c, const double* cores_host, int32_t ncore, double eps_core,
                                      double eps_clad, double k0) try {
   if (!c) return PLFEM_EINVAL;
-  if (!(eps_core > 0) || !(eps_clad > 0)) { c->err = "permittivities must be positive"; return PLFEM_EINVAL; }
   if (c->dpn != 1) { c->err = "plfem_assemble_scalar: the analysis of this context has two unknowns per node (plfem_symbolic_create_ex(..., 1, 0, ...))"; return PLFEM_EINVAL; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  TRY(upload_cores(c, cores_host, ncore));
-  HIP_TRY(c, phase_begin(c, plfem::PH_ASSEMBLE));
-  plfem::launch_element_matrices_scalar(c, ncore, eps_core, eps_clad, k0);
-  plfem::launch_csr_gather(c);
-  HIP_TRY(c, phase_end(c, plfem::PH_ASSEMBLE));
-  TRY(check_launch(c, "assemble scalar"));
-  c->assembled = true;
-  c->factored = false;
-  return PLFEM_OK;
+  return assemble(c, cores_host, ncore, eps_core, eps_clad, "assemble scalar",
+                  [&] { plfem::launch_element_matrices_scalar(c, ncore, eps_core, eps_clad, k0); });
 } catch (...) { return host_failure(c); }
 
 // CMT coupling integrals: raw[i + j n] = E_i^T M_deps F_j, norms
@@ -768,7 +767,7 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
     const int nc = c0_ + P;
     const int lo = (c0_ == cycle_start) ? 0 : std::max(0, nc - 2 * P);
     double* Hblk = c->d_Hcols + (size_t)c0_ * ld;                             // T[0:nc, c0:c0+P] (zero before the step)
-    if (c->refine_steps == 0 && nc - lo <= 8) {
+    if (c->refine_steps == 0 && nc - lo <= plfem::FIRST_COLS) {
       // W = OP V_j left in front order by the sweeps; the first pass permutes it on the way (two launches instead of four)
       plfem::launch_solve(c, P, c->d_BV + (size_t)c0_ * n, nullptr, n, il_ready == c0_);
       plfem::launch_first_pass_block(c, c->d_BV + (size_t)lo * n, c->d_V + (size_t)lo * n, nc - lo, c->d_w, n, Hblk + lo, ld);

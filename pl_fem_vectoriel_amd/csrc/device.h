@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/plfem.h"
@@ -56,6 +57,7 @@ static_assert(PLFEM_SOLVE_T_ASSEMBLE_US + PH_RESIDUAL == PLFEM_SOLVE_T_RESIDUAL_
 
 struct plfem_ctx {
   const plfem::Symbolic* S = nullptr;
+  const plfem::LaunchPlan* plan = nullptr;   // S->plan: kernel forms by level, launch order, workgroup lists (plan.h)
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
@@ -63,20 +65,11 @@ struct plfem_ctx {
   int nv = 0, ne = 0, N = 0, nnz = 0, nsolve = 0, L = 0, nfronts = 0, max_ncv = 0;
   int dpn = 2, sh = 1;            // unknowns per node (2: Hx, Hy; 1: scalar Helmholtz) and sh = dpn - 1: node = dof >> sh, component = dof & sh
   int64_t fnodes_total = 0;       // sum over fronts of (padded) nodes = fnode_ptr[nfronts]
-  int64_t level_nodes_max = 0;    // the same sum over the fronts of one tree level, largest level
   int64_t n2 = 0;   // dpn N: length of every global vector (component-major blocks of N)
-  std::vector<plfem::LevelInfo> levels;
   // ---- index structures on the device
   int32_t* d_forder = nullptr;    // [nfronts] per level: front ids in order of decreasing s2 (factorisation launches)
   plfem::FrontRec* d_frec = nullptr;   // the same order, with the front's parameters
-  std::vector<int> forder_s2, forder_maxm;   // host: s2 in that order, running max of m in that order
   int2* d_tiles = nullptr;        // (front, tx | ty << 16) of every useful 64 x 64 workgroup of the factorisation
-  std::vector<int64_t> upd_off;   // per (level, block step): first entry / entries of the trailing-update list
-  std::vector<int> upd_n;
-  int64_t formz_all_off = 0;      // d_tiles: the Z blocks of every front in one list (root first)
-  int formz_all_n = 0;
-  int64_t mirrorx_all_off = 0;    // d_tiles: (front, block row >= 1) of every front, for k_mirror_x
-  int mirrorx_all_n = 0;
   plfem::SweepJob* d_blk = nullptr;   // one entry per sweep workgroup, level by level
   int32_t *d_tsorted = nullptr, *d_edof = nullptr, *d_rowptr = nullptr, *d_colind = nullptr;
   int32_t *d_slot_row = nullptr, *d_nptr = nullptr, *d_nadj = nullptr, *d_interior = nullptr;
@@ -116,7 +109,7 @@ struct plfem_ctx {
   uint8_t* d_coremask = nullptr;  // [N]
   double* d_post = nullptr;       // partial sums: post-processing in [0, post_doubles), residual check behind it
   size_t post_doubles = 0;
-  int npartial = 0;
+  size_t partial_doubles = 0;     // capacity of d_partial: the largest of its three users' needs (create_impl)
   double* h_pinned = nullptr;     // pinned staging, regions plfem::PIN_*
   size_t h_pinned_bytes = 0;      // size of that block (it returns to a process-wide cache)
   double* h_staging = nullptr;    // pinned staging block of the one upload of the host arrays (same cache)
@@ -207,6 +200,23 @@ inline void prof_close(plfem_ctx* c, int id) {
   if (id >= 0) (void)hipEventRecord(c->prof_ev[2 * id + 1], c->stream);
 }
 
+// A run-time value as a template argument: f(std::integral_constant<int, V>()) for the V of the list that equals v (the
+// last one if none does).  A launch with a template-valued kernel is then written once, inside a generic lambda.
+template <int V, int... Rest, class F>
+inline void with_constant(int v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>());
+  else if (v == V) f(std::integral_constant<int, V>());
+  else with_constant<Rest...>(v, f);
+}
+
+// Below, beside every launch function: the grid and scratch numbers it is shaped by (constants: plan.h).  Whoever else
+// needs one -- create_impl for the buffer sizes, the test hooks for their bounds -- calls these.
+inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// columns of the basis buffers d_V, d_BV (and restart copies): max_ncv, then the residual column or block
+inline int basis_cols(int max_ncv) { return max_ncv + 1 + BLOCK_P; }
+// column capacity of the projected-matrix blocks d_h, d_hacc, d_hblk and of one panel dot (its partials in d_partial)
+inline int proj_cols(int max_ncv) { return basis_cols(max_ncv) + 8; }
+
 // kernels_assembly.hip
 void launch_element_matrices(plfem_ctx* c, int ncore, double eps_core, double eps_clad, double k0, double alpha_p);
 void launch_element_matrices_scalar(plfem_ctx* c, int ncore, double eps_core, double eps_clad, double k0);
@@ -218,12 +228,20 @@ void launch_spmv(plfem_ctx* c, int which, int P, const double* x, double* y, int
 // y_q = B x_q for BLOCK_P vectors, x as [node][component][q]; gram != nullptr: also the chunk partials of the Gram matrix
 // x^T (B x), gram[(p P + q) nb + b] for workgroup b of nb (returned)
 int launch_spmv_b_block_il(plfem_ctx* c, const double* x_interleaved, double* y, int64_t ld, double* gram = nullptr);
+inline int spmv_workgroups(int N) { return ceil_div(N, SPMV_WG_ROWS); }
+inline size_t gram_partial_doubles(int N) { return (size_t)BLOCK_P * BLOCK_P * spmv_workgroups(N); }
 // out_host[i] = ||A v_i - lambda_i B v_i|| / ||A v_i||  (k vectors, row i of evecs; synchronises)
 void launch_residuals(plfem_ctx* c, int k, const double* lam_host, const double* evecs, double* out_host);
 // kernels_front.hip (factorisation), kernels_sweep.hip (solve sweeps)
 void launch_factor(plfem_ctx* c, double sigma, int stop_level = -1, int stop_step = 0, int stop_stage = 0);
 // P right-hand sides, columns ldx apart; x == nullptr: the result stays in front order in d_xl (the caller permutes it itself)
 void launch_solve(plfem_ctx* c, int P, const double* rhs, double* x, int64_t ldx, bool rhs_in_front_order = false);
+// LDS of a sweep workgroup for a front of order m: its P right-hand sides staged in planes of sweep_ldv(m) doubles
+// (dynamic; even: the row forms read the planes as double2) and the static partial-sum tile of the backward tile form
+// (8 waves x P x 64).  plfem_create decides P from it: past the device limit a launch fails as "invalid argument".
+inline int sweep_ldv(int m) { return (m + 2) & ~1; }
+inline size_t sweep_dynamic_lds(int P, int m) { return sizeof(double) * P * sweep_ldv(m); }
+inline size_t sweep_lds(int P, int m) { return sweep_dynamic_lds(P, m) + sizeof(double) * 8 * P * 64; }
 // y = K^-1 b, then `steps` passes y += K^-1 (b - K y) against the assembled K; scratch ta, tb, dy: P columns ld apart each
 void solve_refined(plfem_ctx* c, int P, const double* b, double* y, int64_t ld, bool b_in_front_order, int steps, double* ta,
                    double* tb, double* dy);
@@ -232,6 +250,8 @@ void solve_refined(plfem_ctx* c, int P, const double* b, double* y, int64_t ld, 
 // h = Pm^T W (ncols x P); hacc (optional) += the same coefficients
 void launch_panel_dot(plfem_ctx* c, int P, const double* Pm, int ncols, const double* W, int64_t ldw, double* h, int ldh,
                       double* hacc = nullptr, int ldacc = 0);
+inline int panel_chunks(int64_t n2) { return ceil_div(n2, PANEL_CHUNK); }
+inline size_t panel_dot_partial_doubles(int64_t n2, int ncols) { return (size_t)panel_chunks(n2) * ncols * BLOCK_P; }
 // W -= Pm H; w_interleaved (block only): see k_spmv_b_block_il
 void launch_panel_axpy(plfem_ctx* c, int P, const double* Pm, int ncols, const double* H, int ldh, double* W, int64_t ldw,
                        double* w_interleaved = nullptr);
@@ -240,9 +260,11 @@ void launch_scale_store(plfem_ctx* c, const double* w, const double* bw, const d
                         double* beta_out);  // v = w/sqrt(beta2), bv = bw/sqrt(beta2)
 void launch_axpby(plfem_ctx* c, int64_t n, double a, const double* x, double b, const double* y, double* z);  // z = a x + b y
 void launch_rotate(plfem_ctx* c, const double* V, int m, const double* Smat, int ldS, int p, double* out);  // out = V[:, :m] S
-// first Gram-Schmidt pass of a block step over ncols <= 8 columns in two launches: reads the sweeps' result d_xl (front
+// first Gram-Schmidt pass of a block step over ncols <= FIRST_COLS columns in two launches: reads the sweeps' result d_xl (front
 // order), writes W in global order (what k_permute_out would have done), h = BVm^T W -> Hout, W -= Vm h
 void launch_first_pass_block(plfem_ctx* c, const double* BVm, const double* Vm, int ncols, double* W, int64_t ldw, double* Hout, int ldh);
+inline int first_pass_segments(int64_t n2) { return ceil_div(n2, FIRST_ROWS); }
+inline size_t first_pass_partial_doubles(int64_t n2) { return (size_t)FIRST_COLS * BLOCK_P * first_pass_segments(n2); }
 // the Cholesky half alone, from nchunks Gram partials per entry already in d_partial (launch_spmv_b_block_il with gram)
 void launch_chol_from_partials(plfem_ctx* c, int nchunks, double* Tblk, int ldT, double* Rinv);
 void launch_chol_block(plfem_ctx* c, const double* G, int ldg, double* Tblk, int ldT, double* Rinv);
@@ -256,5 +278,9 @@ void post_enqueue(plfem_ctx* c, int k, double* evecs, int ncore, double* modes_i
 void post_finish(plfem_ctx* c, int k, double* out_host, double* frac_core);
 void resid_enqueue(plfem_ctx* c, int k, const double* lam_host, const double* evecs);
 void resid_finish(plfem_ctx* c, int k, double* out_host);
+// the sums of both: per mode one partial per workgroup of POST_ROWS rows, then the totals
+inline int post_blocks(int N) { return ceil_div(N, POST_ROWS); }
+inline size_t post_sum_doubles(int N, int modes) { return (size_t)POST_SUMS * modes * (post_blocks(N) + 1); }
+inline size_t resid_sum_doubles(int N, int modes) { return (size_t)RESID_SUMS * modes * (post_blocks(N) + 1); }
 
 }  // namespace plfem

@@ -460,50 +460,36 @@ void launch_csr_gather(plfem_ctx* c) {
                      c->d_vals[6], c->d_vals[7]);
 }
 
-namespace {
-template <int P>
-void spmv(plfem_ctx* c, int which, const double* x, double* y, int64_t ld) {
-  int64_t threads = (int64_t)c->N * 8;
-  int grid = (int)((threads + 255) / 256);
-  const double* v = c->d_vals[which == 0 ? PLFEM_BLK_AXX : PLFEM_BLK_MINV];
-  if (c->dpn == 1)         // scalar pencil: A is one block too (the AXX slot)
-    hipLaunchKernelGGL((k_spmv_b_block<P, 1>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                       c->d_bmask, v, x, y);
-  else if (which == 0)
-    hipLaunchKernelGGL(k_spmv_a_block<P>, dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                       c->d_bmask, c->d_vals[PLFEM_BLK_AXX], c->d_vals[PLFEM_BLK_AXY], c->d_vals[PLFEM_BLK_AYX],
-                       c->d_vals[PLFEM_BLK_AYY], x, y);
-  else
-    hipLaunchKernelGGL((k_spmv_b_block<P, 2>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                       c->d_bmask, v, x, y);
-}
-}  // namespace
-
 void launch_spmv(plfem_ctx* c, int which, int P, const double* x, double* y, int64_t ld) {
-  if (P == 1) spmv<1>(c, which, x, y, ld);
-  else spmv<BLOCK_P>(c, which, x, y, ld);
+  const int grid = spmv_workgroups(c->N);
+  if (c->dpn == 2 && which == 0) {
+    with_constant<1, BLOCK_P>(P, [&](auto p) {
+      hipLaunchKernelGGL(k_spmv_a_block<decltype(p)::value>, dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr,
+                         c->d_colind, c->d_bmask, c->d_vals[PLFEM_BLK_AXX], c->d_vals[PLFEM_BLK_AXY], c->d_vals[PLFEM_BLK_AYX],
+                         c->d_vals[PLFEM_BLK_AYY], x, y);
+    });
+    return;
+  }
+  // one block: B, or A of the scalar pencil (the AXX slot)
+  const double* v = c->d_vals[which == 0 ? PLFEM_BLK_AXX : PLFEM_BLK_MINV];
+  with_constant<1, BLOCK_P>(P, [&](auto p) {
+    with_constant<1, 2>(c->dpn, [&](auto dpn) {
+      hipLaunchKernelGGL((k_spmv_b_block<decltype(p)::value, decltype(dpn)::value>), dim3(grid), dim3(256), 0, c->stream, c->N, ld,
+                         c->d_rowptr, c->d_colind, c->d_bmask, v, x, y);
+    });
+  });
 }
 
 // gram != nullptr: also the Gram partials of the block, gram[(p P + q) nblocks + block]; returns the number of workgroups
 // (= partials per entry)
 int launch_spmv_b_block_il(plfem_ctx* c, const double* xi, double* y, int64_t ld, double* gram) {
-  int64_t threads = (int64_t)c->N * 8;
-  int grid = (int)((threads + 255) / 256);
-  if (c->dpn == 1) {
-    if (gram)
-      hipLaunchKernelGGL((k_spmv_b_block_il<BLOCK_P, 1, true>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                         c->d_bmask, c->d_vals[PLFEM_BLK_MINV], xi, y, gram);
-    else
-      hipLaunchKernelGGL((k_spmv_b_block_il<BLOCK_P, 1, false>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                         c->d_bmask, c->d_vals[PLFEM_BLK_MINV], xi, y, gram);
-  } else {
-    if (gram)
-      hipLaunchKernelGGL((k_spmv_b_block_il<BLOCK_P, 2, true>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                         c->d_bmask, c->d_vals[PLFEM_BLK_MINV], xi, y, gram);
-    else
-      hipLaunchKernelGGL((k_spmv_b_block_il<BLOCK_P, 2, false>), dim3(grid), dim3(256), 0, c->stream, c->N, ld, c->d_rowptr, c->d_colind,
-                         c->d_bmask, c->d_vals[PLFEM_BLK_MINV], xi, y, gram);
-  }
+  const int grid = spmv_workgroups(c->N);
+  with_constant<1, 2>(c->dpn, [&](auto dpn) {
+    with_constant<1, 0>(gram != nullptr, [&](auto with_gram) {
+      hipLaunchKernelGGL((k_spmv_b_block_il<BLOCK_P, decltype(dpn)::value, decltype(with_gram)::value != 0>), dim3(grid), dim3(256), 0,
+                         c->stream, c->N, ld, c->d_rowptr, c->d_colind, c->d_bmask, c->d_vals[PLFEM_BLK_MINV], xi, y, gram);
+    });
+  });
   return grid;
 }
 

@@ -715,10 +715,21 @@ int reduce_to_host(plfem_locator* L, dim3 grid, int ka, int kb, int nblk, int nc
 }
 }  // namespace
 
+namespace {
+// A field call's work buffer: the result (`result` doubles), then, 256-byte aligned, `partial` doubles of partial sums
+struct WorkLayout { size_t off_partial, total; };   // bytes
+WorkLayout work_layout(size_t result, size_t partial) {
+  const size_t off = align256(result * sizeof(double));
+  return {off, off + partial * sizeof(double)};
+}
+WorkLayout overlap_layout(int ka, int kb) {
+  return work_layout((size_t)ka * kb, (size_t)overlap_chunks(ka) * overlap_chunks(kb) * OVL_BLOCKS * OC * OC);
+}
+}  // namespace
+
 extern "C" int plfem_overlap_work_bytes(int32_t ka, int32_t kb, int64_t* bytes) {
   if (!bytes || ka < 0 || kb < 0) return PLFEM_EINVAL;
-  *bytes = (int64_t)(align256((size_t)ka * kb * sizeof(double)) +
-                     (size_t)overlap_chunks(ka) * overlap_chunks(kb) * OVL_BLOCKS * OC * OC * sizeof(double));
+  *bytes = (int64_t)overlap_layout(ka, kb).total;
   return PLFEM_OK;
 }
 
@@ -736,15 +747,13 @@ extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev,
     La->err = "plfem_field_overlap: the analysis has no interior DOFs";
     return PLFEM_EINVAL;
   }
-  int64_t need = 0;
-  plfem_overlap_work_bytes(ka, kb, &need);
-  TRY(check_work(La, "plfem_field_overlap", "plfem_overlap_work_bytes", work_dev, work_bytes, need));
+  const WorkLayout lay = overlap_layout(ka, kb);
+  TRY(check_work(La, "plfem_field_overlap", "plfem_overlap_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
   HIP_TRY(La, hipSetDevice(La->device));
   const int nca = overlap_chunks(ka), ncb = overlap_chunks(kb);
   const int64_t ntiles = ((int64_t)6 * Lb->ne + OT - 1) / OT;
   const int nblk = (int)std::min<int64_t>(OVL_BLOCKS, ntiles);
-  double* O = (double*)work_dev;
-  double* partial = (double*)((char*)work_dev + align256((size_t)ka * kb * sizeof(double)));
+  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
   hipLaunchKernelGGL(k_field_overlap, dim3(nblk, nca * ncb), dim3(256), 0, La->stream, loc_args(La, indexed_a != 0),
                      loc_args(Lb, indexed_b != 0), (int)ncomp, (int)ka, (int64_t)(indexed_a ? La->nsolve : La->N), modes_a_dev,
                      (int)kb, (int64_t)(indexed_b ? Lb->nsolve : Lb->N), modes_b_dev, pack_cores(cores_host, ncore),
@@ -755,13 +764,15 @@ extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev,
 
 namespace {
 int gram_outputs(int ncomp) { return ncomp == 2 ? 5 : 3; }
+WorkLayout gram_layout(int ncomp, int k) {
+  const size_t nout = gram_outputs(ncomp), nc = overlap_chunks(k);
+  return work_layout(nout * k * k, nout * nc * nc * GRAM_BLOCKS * OC * OC);
+}
 }  // namespace
 
 extern "C" int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
   if (!bytes || ncomp < 1 || ncomp > 2 || k <= 0) return PLFEM_EINVAL;
-  const int nout = gram_outputs(ncomp), nc = overlap_chunks(k);
-  *bytes = (int64_t)(align256((size_t)nout * k * k * sizeof(double)) +
-                     (size_t)nout * nc * nc * GRAM_BLOCKS * OC * OC * sizeof(double));
+  *bytes = (int64_t)gram_layout(ncomp, k).total;
   return PLFEM_OK;
 }
 
@@ -775,24 +786,20 @@ extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
     return PLFEM_EINVAL;
   }
   if (indexed && L->nsolve == 0) { L->err = "plfem_mode_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
-  int64_t need = 0;
-  plfem_gram_work_bytes(ncomp, k, &need);
-  TRY(check_work(L, "plfem_mode_grams", "plfem_gram_work_bytes", work_dev, work_bytes, need));
+  const WorkLayout lay = gram_layout(ncomp, k);
+  TRY(check_work(L, "plfem_mode_grams", "plfem_gram_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
   HIP_TRY(L, hipSetDevice(L->device));
   const CoreTable ct = pack_cores(cores_host, ncore);
   const int nout = gram_outputs(ncomp), nc = overlap_chunks(k);
   const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
   const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ntiles));
   const int64_t nrows = indexed ? L->nsolve : L->N;
-  double* O = (double*)work_dev;
-  double* partial = (double*)((char*)work_dev + align256((size_t)nout * k * k * sizeof(double)));
+  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
   const dim3 grid(nblk, nc * nc);
-  if (ncomp == 2)
-    hipLaunchKernelGGL(k_mode_grams<2>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
-                       ct, (int)ncore, nc, partial);
-  else
-    hipLaunchKernelGGL(k_mode_grams<1>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
-                       ct, (int)ncore, nc, partial);
+  with_constant<2, 1>(ncomp, [&](auto nco) {
+    hipLaunchKernelGGL(k_mode_grams<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows,
+                       modes_dev, ct, (int)ncore, nc, partial);
+  });
   TRY(check_launch(L, "k_mode_grams"));
   return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
 } catch (...) { return host_failure(L); }
@@ -804,13 +811,15 @@ int quartic_tile_pairs(int k) { return quartic_tiles(k) * (quartic_tiles(k) + 1)
 // element slices per output tile: at most QB_MAX, and at most QWG partial tiles in all (a tile pair count never exceeds
 // 561 = the k = 64 count, so that is always >= 1 slice)
 int quartic_slices(int k) { return std::max(1, std::min(QB_MAX, QWG / quartic_tile_pairs(k))); }
+WorkLayout quartic_layout(int k) {
+  const size_t np = quartic_pairs(k);
+  return work_layout(np * np, (size_t)quartic_slices(k) * quartic_tile_pairs(k) * QP * QP);
+}
 }  // namespace
 
 extern "C" int plfem_quartic_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
   if (!bytes || ncomp < 1 || ncomp > 2 || k < 1 || k > QKMAX) return PLFEM_EINVAL;
-  const size_t np = (size_t)quartic_pairs(k);
-  *bytes = (int64_t)(align256(np * np * sizeof(double)) +
-                     (size_t)quartic_slices(k) * quartic_tile_pairs(k) * QP * QP * sizeof(double));
+  *bytes = (int64_t)quartic_layout(k).total;
   return PLFEM_OK;
 }
 
@@ -828,24 +837,20 @@ extern "C" int plfem_mode_quartic(plfem_locator* L, int32_t ncomp, int32_t k, co
     return PLFEM_EINVAL;
   }
   if (indexed && L->nsolve == 0) { L->err = "plfem_mode_quartic: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
-  int64_t need = 0;
-  plfem_quartic_work_bytes(ncomp, k, &need);
-  TRY(check_work(L, "plfem_mode_quartic", "plfem_quartic_work_bytes", work_dev, work_bytes, need));
+  const WorkLayout lay = quartic_layout(k);
+  TRY(check_work(L, "plfem_mode_quartic", "plfem_quartic_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
   HIP_TRY(L, hipSetDevice(L->device));
   const CoreTable ct = pack_cores(cores_host, ncore);
   const int np = quartic_pairs(k), nt = quartic_tiles(k), ntp = quartic_tile_pairs(k);
   const int nblk = std::max(1, std::min(quartic_slices(k), L->ne));
   const int64_t nrows = indexed ? L->nsolve : L->N;
-  double* O = (double*)work_dev;
-  double* partial = (double*)((char*)work_dev + align256((size_t)np * np * sizeof(double)));
+  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
   const dim3 grid(nblk, ntp);
   const int nc = ncore < 0 ? -1 : (int)ncore;
-  if (ncomp == 2)
-    hipLaunchKernelGGL(k_mode_quartic<2>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
-                       ct, nc, w_core, w_clad, np, nt, partial);
-  else
-    hipLaunchKernelGGL(k_mode_quartic<1>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows, modes_dev,
-                       ct, nc, w_core, w_clad, np, nt, partial);
+  with_constant<2, 1>(ncomp, [&](auto nco) {
+    hipLaunchKernelGGL(k_mode_quartic<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows,
+                       modes_dev, ct, nc, w_core, w_clad, np, nt, partial);
+  });
   TRY(check_launch(L, "k_mode_quartic"));
   hipLaunchKernelGGL(k_quartic_reduce, dim3(ntp, 1, QP * QP / 256), dim3(256), 0, L->stream, np, nt, nblk, partial, O);
   TRY(check_launch(L, "k_quartic_reduce"));

@@ -940,9 +940,10 @@ void launch_factor(plfem_ctx* c, double sigma, int stop_level, int stop_step, in
   // stages: 0 assembled, 1 or 2 pivot block + panel of the step done (its own launch for step 0, the launch of the step before
   // otherwise), 3 or 4 the step's launch done (update + inverse row + pivot write-back; next pivot block + panel), 5 level done
   hipStream_t st = c->stream;
+  const LaunchPlan& plan = *c->plan;
   (void)hipMemsetAsync(c->d_counters, 0, 4 * sizeof(int32_t), st);
   for (int lev = c->L; lev >= 0; --lev) {
-    const LevelInfo& li = c->levels[lev];
+    const LevelInfo& li = plan.levels[lev];
     if (lev == c->L) {
       const int64_t lo = c->S->foff[li.first], hi = c->S->foff[li.first + li.count];
       (void)hipMemsetAsync(c->d_front + lo, 0, sizeof(double) * (size_t)(hi - lo), st);
@@ -952,32 +953,26 @@ void launch_factor(plfem_ctx* c, double sigma, int stop_level, int stop_step, in
         sch = std::max(sch, c->S->soff[f] + b2 * b2);
       }
       (void)hipMemsetAsync(c->d_schur + (size_t)(lev & 1) * c->arena_doubles, 0, sizeof(double) * (size_t)sch, st);
-      if (c->sh)
-        hipLaunchKernelGGL(k_leaf_assemble<1>, dim3(li.count), dim3(256), 0, st, li.first, c->ne, sigma, c->d_fs2, c->d_fm, c->d_foff,
-                           c->d_soff, c->d_fnode_ptr, c->d_fnodes, c->d_leaf_elem_ptr, c->d_leaf_elems, c->d_epos, c->d_elem,
-                           c->d_front, c->d_schur, c->arena_doubles);
-      else
-        hipLaunchKernelGGL(k_leaf_assemble<0>, dim3(li.count), dim3(256), 0, st, li.first, c->ne, sigma, c->d_fs2, c->d_fm, c->d_foff,
-                           c->d_soff, c->d_fnode_ptr, c->d_fnodes, c->d_leaf_elem_ptr, c->d_leaf_elems, c->d_epos, c->d_elem,
-                           c->d_front, c->d_schur, c->arena_doubles);
+      with_constant<0, 1>(c->sh, [&](auto sh) {
+        hipLaunchKernelGGL(k_leaf_assemble<decltype(sh)::value>, dim3(li.count), dim3(256), 0, st, li.first, c->ne, sigma, c->d_fs2,
+                           c->d_fm, c->d_foff, c->d_soff, c->d_fnode_ptr, c->d_fnodes, c->d_leaf_elem_ptr, c->d_leaf_elems, c->d_epos,
+                           c->d_elem, c->d_front, c->d_schur, c->arena_doubles);
+      });
     } else if (li.gather_n > 0) {
-      if (c->sh)
-        hipLaunchKernelGGL(k_front_gather<1>, dim3(li.gather_n), dim3(256), 0, st, c->d_tiles + li.gather_off, c->d_fs2, c->d_fm,
-                           c->d_foff, c->d_soff, c->d_fnode_ptr, c->d_fnodes, c->d_cinv0, c->d_cinv1, c->d_front, c->d_schur,
-                           c->arena_doubles);
-      else
-        hipLaunchKernelGGL(k_front_gather<0>, dim3(li.gather_n), dim3(256), 0, st, c->d_tiles + li.gather_off, c->d_fs2, c->d_fm,
-                           c->d_foff, c->d_soff, c->d_fnode_ptr, c->d_fnodes, c->d_cinv0, c->d_cinv1, c->d_front, c->d_schur,
-                           c->arena_doubles);
+      with_constant<0, 1>(c->sh, [&](auto sh) {
+        hipLaunchKernelGGL(k_front_gather<decltype(sh)::value>, dim3(li.gather_n), dim3(256), 0, st, c->d_tiles + li.gather_off,
+                           c->d_fs2, c->d_fm, c->d_foff, c->d_soff, c->d_fnode_ptr, c->d_fnodes, c->d_cinv0, c->d_cinv1, c->d_front,
+                           c->d_schur, c->arena_doubles);
+      });
     }
     if (lev == stop_level && stop_stage == 0) return;
-    // Fronts of the level in order of decreasing s2 (c->forder): the fronts still active at block step kb are a
+    // Fronts of the level in order of decreasing s2 (plan.forder): the fronts still active at block step kb are a
     // prefix of that order, so every launch only covers them and is sized by the largest ACTIVE front.
     const int steps = (li.max_s2 + NB - 1) / NB;
     const int32_t* ford = c->d_forder + li.first;
     const FrontRec* frec = c->d_frec + li.first;
-    const int* hs2 = c->forder_s2.data() + li.first;          // s2 in that order (descending)
-    const int* hpm = c->forder_maxm.data() + li.first;        // running maximum of m in that order
+    const int* hs2 = plan.forder_s2.data() + li.first;          // s2 in that order (descending)
+    const int* hpm = plan.forder_maxm.data() + li.first;        // running maximum of m in that order
     for (int kb = 0; kb < steps; ++kb) {
       const bool stop_here = (lev == stop_level && kb == stop_step);
       const int k0 = kb * NB;
@@ -992,7 +987,7 @@ void launch_factor(plfem_ctx* c, double sigma, int stop_level, int stop_step, in
       // halves of dinv (see k_ldl_update)
       // (the kernels address these buffers by 2 fnode_ptr[f] NB: the pointers handed to them are shifted back by the
       // offset of the level's first front, so that the level in flight starts at the beginning of the buffer)
-      const size_t third = (size_t)2 * c->level_nodes_max * NB;
+      const size_t third = (size_t)2 * plan.level_nodes_max * NB;
       const int64_t base = 2 * c->S->fnode_ptr[li.first] * NB;
       double* wb0 = c->d_wbuf - base;
       double* rb0 = c->d_rbuf - base;
@@ -1019,9 +1014,9 @@ void launch_factor(plfem_ctx* c, double sigma, int stop_level, int stop_step, in
       if (stop_here && stop_stage >= 1 && stop_stage <= 2) return;
       // the step's launch: trailing update + triangular-inverse update + write-back of the pivot block, and for the
       // fronts with a next step its pivot block, its panel and the copy of its block row
-      const int un = c->upd_n[li.step0 + kb];                  // 64 x 64 blocks of this step's trailing updates
+      const int un = plan.upd_n[li.step0 + kb];                  // 64 x 64 blocks of this step's trailing updates
       const int n_inv = kb > 0 ? (k0 + 15) / 16 : 0;        // one workgroup per 16 columns of the block row
-      const int2* ut = c->d_tiles + c->upd_off[li.step0 + kb];
+      const int2* ut = c->d_tiles + plan.upd_off[li.step0 + kb];
       int n_look = 0;                                          // fronts with a next block step: s2 > k0 + NB (a prefix)
       {
         int lo = 0, hi = nact;
@@ -1033,14 +1028,13 @@ void launch_factor(plfem_ctx* c, double sigma, int stop_level, int stop_step, in
       const int cap = li.count >= 1024 ? 1 : 4;
       const int n_pan = n_look > 0 ? panel_wgs(hpm[n_look - 1] - (k0 + NB) - 16, cap) : 1;
       const unsigned gridB = (unsigned)(n_look * n_pan + un + nact * (n_inv + 1));
-      if ((kb & 1) == 0)
-        hipLaunchKernelGGL(k_ldl_update<0>, dim3(gridB), dim3(256), 0, st, un, n_inv, n_look, n_pan, ut, ford, frec, kb, c->d_fs2,
-                           c->d_fm, c->d_foff, c->d_soff, c->d_fnode_ptr, c->d_front, c->d_schur, c->arena_doubles, dinv_cur,
-                           dinv_nxt, c->d_delta, wb, rb, wb, rb, wb_next, rb_next, c->d_counters);
-      else
-        hipLaunchKernelGGL(k_ldl_update<1>, dim3(gridB), dim3(256), 0, st, un, n_inv, n_look, n_pan, ut, ford, frec, kb, c->d_fs2,
-                           c->d_fm, c->d_foff, c->d_soff, c->d_fnode_ptr, c->d_front, c->d_schur, c->arena_doubles, dinv_cur,
-                           dinv_nxt, c->d_delta, wb, rb, wb_prev, rb_prev, wb_next, rb_next, c->d_counters);
+      // (an even step gets its own panels in place of the previous step's)
+      with_constant<0, 1>(kb & 1, [&](auto mode) {
+        hipLaunchKernelGGL(k_ldl_update<decltype(mode)::value>, dim3(gridB), dim3(256), 0, st, un, n_inv, n_look, n_pan, ut, ford,
+                           frec, kb, c->d_fs2, c->d_fm, c->d_foff, c->d_soff, c->d_fnode_ptr, c->d_front, c->d_schur, c->arena_doubles,
+                           dinv_cur, dinv_nxt, c->d_delta, wb, rb, mode ? wb_prev : wb, mode ? rb_prev : rb, wb_next, rb_next,
+                           c->d_counters);
+      });
       if (stop_here && (stop_stage == 3 || stop_stage == 4)) return;
     }
     if (stop_level >= 0 && li.formz_n + li.mirrorx_n > 0)     // (debug run that stops after a level: its Z and lower(F11) now)
@@ -1050,9 +1044,9 @@ void launch_factor(plfem_ctx* c, double sigma, int stop_level, int stop_step, in
   }
   // Z = L21 L11^-1 (in place and transposed) and lower(F11) = the mirror of upper(F11), for every front at once: only the
   // solve sweeps read them (the two job lists are adjacent in d_tiles: Z blocks first)
-  if (stop_level < 0 && c->formz_all_n + c->mirrorx_all_n > 0)
-    hipLaunchKernelGGL(k_form_z_mirror, dim3(c->formz_all_n + c->mirrorx_all_n), dim3(256), 0, st, c->d_tiles + c->formz_all_off,
-                       c->formz_all_n, c->d_fs2, c->d_fm, c->d_foff, c->d_front);
+  if (stop_level < 0 && plan.formz_all_n + plan.mirrorx_all_n > 0)
+    hipLaunchKernelGGL(k_form_z_mirror, dim3(plan.formz_all_n + plan.mirrorx_all_n), dim3(256), 0, st, c->d_tiles + plan.formz_all_off,
+                       plan.formz_all_n, c->d_fs2, c->d_fm, c->d_foff, c->d_front);
 }
 
 }  // namespace plfem

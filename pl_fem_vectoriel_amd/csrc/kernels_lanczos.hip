@@ -161,7 +161,6 @@ __global__ __launch_bounds__(256) void k_panel_axpy_p(int64_t n, int ncols, cons
 // the sweeps' front-order result where k_permute_out would read it, written out in global order, and multiplied with the
 // up to 8 panel columns on the way); k_axpy_first sums the partials in its prologue (32 values x nseg partials, every
 // workgroup for itself in the same fixed order: the same bits everywhere) before it applies the update.
-constexpr int FIRST_ROWS = 1024;       // rows per workgroup of k_permute_dot_first = per partial sum (512 measured: 17.1 + 11.1 us against 15.8 + 9.5)
 template <int P>
 __global__ __launch_bounds__(256) void k_permute_dot_first(int64_t n2, int N, int nseg, int ncols, const int32_t* __restrict__ npos,
                                                            const double* __restrict__ xl, double* __restrict__ W, int64_t ldw,
@@ -431,7 +430,6 @@ __global__ __launch_bounds__(256) void k_core_mask(int N, const double* __restri
 
 // per (row chunk, mode) partial sums: [0] sum vx^2, [1] sum vy^2, [2] core vx^2, [3] core vy^2,
 // [4] vx.Dxx vx + 2 vx.Dxy vy + vy.Dyy vy.   8 lanes per row.
-constexpr int POST_ROWS = 256;   // rows per block
 // DPN = 1 (scalar solver, solver_fem.py:268-271): [0] sum v^2, [2] core v^2, [4] v.M v with M in the dxx argument
 // MB modes per workgroup (blockIdx.y = group of MB): the matrix entries and column indices of a row are read once for
 // MB vectors instead of once per vector (the 22 eigenvectors of C1 read the three D blocks 22 times: 167 us); each mode's
@@ -637,22 +635,19 @@ __global__ __launch_bounds__(64) void k_resid_finish(int nblocks, const double* 
 void resid_enqueue(plfem_ctx* c, int k, const double* lam_host, const double* evecs) {
   hipStream_t st = c->stream;
   const int N = c->N;
-  const int nblocks = (N + POST_ROWS - 1) / POST_ROWS;
+  const int nblocks = post_blocks(N);
   double* hs = c->h_pinned + PIN_RESID;
   for (int i = 0; i < k; ++i) hs[i] = lam_host[i];
   (void)hipMemcpyAsync(c->d_hacc, hs, sizeof(double) * k, hipMemcpyHostToDevice, st);
-  double* partial = c->d_post + c->post_doubles;     // second half of d_post: [k][nblocks][2], then the sums
-  double* sums = partial + (int64_t)k * nblocks * 2;
-  if (c->dpn == 1)
-    hipLaunchKernelGGL(k_resid_sums<1>, dim3(nblocks, (k + POST_MB - 1) / POST_MB), dim3(256), 0, st, N, k, nblocks, c->d_rowptr, c->d_colind, c->d_bmask,
-                       c->d_vals[PLFEM_BLK_AXX], c->d_vals[PLFEM_BLK_AXY], c->d_vals[PLFEM_BLK_AYX], c->d_vals[PLFEM_BLK_AYY],
-                       c->d_vals[PLFEM_BLK_MINV], c->d_hacc, evecs, partial);
-  else
-    hipLaunchKernelGGL(k_resid_sums<2>, dim3(nblocks, (k + POST_MB - 1) / POST_MB), dim3(256), 0, st, N, k, nblocks, c->d_rowptr, c->d_colind, c->d_bmask,
-                       c->d_vals[PLFEM_BLK_AXX], c->d_vals[PLFEM_BLK_AXY], c->d_vals[PLFEM_BLK_AYX], c->d_vals[PLFEM_BLK_AYY],
-                       c->d_vals[PLFEM_BLK_MINV], c->d_hacc, evecs, partial);
-  hipLaunchKernelGGL(k_resid_finish, dim3(2 * k), dim3(64), 0, st, nblocks, partial, sums);
-  (void)hipMemcpyAsync(hs + k, sums, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, st);
+  double* partial = c->d_post + c->post_doubles;     // second half of d_post: [k][nblocks][RESID_SUMS], then the sums
+  double* sums = partial + (int64_t)k * nblocks * RESID_SUMS;
+  with_constant<1, 2>(c->dpn, [&](auto dpn) {
+    hipLaunchKernelGGL(k_resid_sums<decltype(dpn)::value>, dim3(nblocks, (k + POST_MB - 1) / POST_MB), dim3(256), 0, st, N, k, nblocks,
+                       c->d_rowptr, c->d_colind, c->d_bmask, c->d_vals[PLFEM_BLK_AXX], c->d_vals[PLFEM_BLK_AXY],
+                       c->d_vals[PLFEM_BLK_AYX], c->d_vals[PLFEM_BLK_AYY], c->d_vals[PLFEM_BLK_MINV], c->d_hacc, evecs, partial);
+  });
+  hipLaunchKernelGGL(k_resid_finish, dim3(RESID_SUMS * k), dim3(64), 0, st, nblocks, partial, sums);
+  (void)hipMemcpyAsync(hs + k, sums, sizeof(double) * RESID_SUMS * k, hipMemcpyDeviceToHost, st);
 }
 
 // after the stream has been synchronised
@@ -680,44 +675,35 @@ void launch_scale_store(plfem_ctx* c, const double* w, const double* bw, const d
                      beta2, v, bv, beta_out);
 }
 
-namespace {
-template <int P, int CW>
-void panel_dot(plfem_ctx* c, const double* Pm, int ncols, const double* W, int64_t ldw, double* h, int ldh, double* hacc,
-               int ldacc) {
-  const int nchunks = c->npartial;
-  hipLaunchKernelGGL((k_panel_dot_p<P, CW>), dim3(nchunks, (ncols + 4 * CW - 1) / (4 * CW)), dim3(256), 0, c->stream, c->n2,
-                     ncols, nchunks, Pm, W, ldw, c->d_partial);
-  hipLaunchKernelGGL(k_panel_dot_finish_p, dim3(ncols * P), dim3(64), 0, c->stream, P, nchunks, c->d_partial, h, ldh,
-                     hacc, ldacc);
-}
-
-template <int P>
-void panel_axpy(plfem_ctx* c, const double* Pm, int ncols, const double* H, int ldh, double* W, int64_t ldw, double* wil) {
-  hipLaunchKernelGGL(k_panel_axpy_p<P>, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), sizeof(double) * ncols * P,
-                     c->stream, c->n2, ncols, Pm, H, ldh, W, ldw, wil, c->N, c->dpn);
-}
-}  // namespace
-
 void launch_panel_dot(plfem_ctx* c, int P, const double* Pm, int ncols, const double* W, int64_t ldw, double* h, int ldh,
                       double* hacc, int ldacc) {
-  if (P == 1) panel_dot<1, 1>(c, Pm, ncols, W, ldw, h, ldh, hacc, ldacc);
-  else panel_dot<BLOCK_P, 4>(c, Pm, ncols, W, ldw, h, ldh, hacc, ldacc);
+  const int nchunks = panel_chunks(c->n2);
+  with_constant<1, BLOCK_P>(P, [&](auto p) {
+    constexpr int PT = decltype(p)::value, CW = PT == 1 ? 1 : 4;   // columns per wave: nothing to share between them at P = 1
+    hipLaunchKernelGGL((k_panel_dot_p<PT, CW>), dim3(nchunks, (ncols + 4 * CW - 1) / (4 * CW)), dim3(256), 0, c->stream, c->n2,
+                       ncols, nchunks, Pm, W, ldw, c->d_partial);
+    hipLaunchKernelGGL(k_panel_dot_finish_p, dim3(ncols * PT), dim3(64), 0, c->stream, PT, nchunks, c->d_partial, h, ldh,
+                       hacc, ldacc);
+  });
 }
 
 void launch_panel_axpy(plfem_ctx* c, int P, const double* Pm, int ncols, const double* H, int ldh, double* W, int64_t ldw,
                        double* w_interleaved) {
-  if (P == 1) panel_axpy<1>(c, Pm, ncols, H, ldh, W, ldw, w_interleaved);
-  else panel_axpy<BLOCK_P>(c, Pm, ncols, H, ldh, W, ldw, w_interleaved);
+  with_constant<1, BLOCK_P>(P, [&](auto p) {
+    constexpr int PT = decltype(p)::value;
+    hipLaunchKernelGGL(k_panel_axpy_p<PT>, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), sizeof(double) * ncols * PT,
+                       c->stream, c->n2, ncols, Pm, H, ldh, W, ldw, w_interleaved, c->N, c->dpn);
+  });
 }
 
 void launch_dot(plfem_ctx* c, const double* a, const double* b, double* out) { launch_panel_dot(c, 1, a, 1, b, c->n2, out, 1); }
 
-// first Gram-Schmidt pass over ncols <= 8 columns, fused with the permutation of the sweeps' result (d_xl, front order)
+// first Gram-Schmidt pass over ncols <= FIRST_COLS columns, fused with the permutation of the sweeps' result (d_xl, front order)
 // into W (global order): h -> Hout, W -= Vm h.  (8 columns x P sums per thread: the two kernels are written for P = 4)
 void launch_first_pass_block(plfem_ctx* c, const double* BVm, const double* Vm, int ncols, double* W, int64_t ldw, double* Hout,
                              int ldh) {
   constexpr int P = BLOCK_P;
-  const int nseg = (int)((c->n2 + FIRST_ROWS - 1) / FIRST_ROWS);      // (= npartial: PANEL_CHUNK rows per partial sum)
+  const int nseg = first_pass_segments(c->n2);
   hipLaunchKernelGGL(k_permute_dot_first<P>, dim3(nseg), dim3(256), 0, c->stream, c->n2, c->N, nseg, ncols, c->d_npos, c->d_xl, W, ldw,
                      BVm, c->d_partial);
   hipLaunchKernelGGL(k_axpy_first<P>, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), 0, c->stream, c->n2, ncols, nseg, Vm,
@@ -795,22 +781,19 @@ void post_enqueue(plfem_ctx* c, int k, double* evecs, int ncore, double* modes_i
   (void)hipMemsetAsync(c->d_counters + 1, 0, sizeof(int32_t), st);
   hipLaunchKernelGGL(k_core_mask, dim3((N + 255) / 256), dim3(256), 0, st, N, c->d_doflocs, c->d_cores, ncore,
                      c->d_bmask, c->d_coremask, c->d_counters);
-  const int nblocks = (N + POST_ROWS - 1) / POST_ROWS;
+  const int nblocks = post_blocks(N);
   const int group = group_done ? POST_GROUP : k;
   for (int g0 = 0; g0 < k; g0 += group) {
     const int kg = std::min(group, k - g0);
     double* ev = evecs + (int64_t)g0 * c->n2;
-    double* partial = c->d_post + (int64_t)g0 * nblocks * 5;          // [k][nblocks][5]
-    double* sums = c->d_post + (int64_t)k * nblocks * 5 + (int64_t)g0 * 5;   // [k][5]
-    if (c->dpn == 1)      // scalar solver: v.M v with M = the MINV slot
-      hipLaunchKernelGGL(k_post_sums<1>, dim3(nblocks, (kg + POST_MB - 1) / POST_MB), dim3(256), 0, st, N, kg, nblocks, c->d_rowptr, c->d_colind,
-                         c->d_vals[PLFEM_BLK_MINV], c->d_vals[PLFEM_BLK_DXY], c->d_vals[PLFEM_BLK_DYY], c->d_coremask, ev,
-                         partial);
-    else
-      hipLaunchKernelGGL(k_post_sums<2>, dim3(nblocks, (kg + POST_MB - 1) / POST_MB), dim3(256), 0, st, N, kg, nblocks, c->d_rowptr, c->d_colind,
-                         c->d_vals[PLFEM_BLK_DXX], c->d_vals[PLFEM_BLK_DXY], c->d_vals[PLFEM_BLK_DYY], c->d_coremask, ev,
-                         partial);
-    hipLaunchKernelGGL(k_post_finish, dim3(kg * 5), dim3(64), 0, st, kg, nblocks, partial, sums);
+    double* partial = c->d_post + (int64_t)g0 * nblocks * POST_SUMS;          // [k][nblocks][POST_SUMS]
+    double* sums = c->d_post + (int64_t)k * nblocks * POST_SUMS + (int64_t)g0 * POST_SUMS;   // [k][POST_SUMS]
+    const double* dxx = c->d_vals[c->dpn == 1 ? PLFEM_BLK_MINV : PLFEM_BLK_DXX];   // scalar solver: v.M v with M = the MINV slot
+    with_constant<1, 2>(c->dpn, [&](auto dpn) {
+      hipLaunchKernelGGL(k_post_sums<decltype(dpn)::value>, dim3(nblocks, (kg + POST_MB - 1) / POST_MB), dim3(256), 0, st, N, kg, nblocks,
+                         c->d_rowptr, c->d_colind, dxx, c->d_vals[PLFEM_BLK_DXY], c->d_vals[PLFEM_BLK_DYY], c->d_coremask, ev, partial);
+    });
+    hipLaunchKernelGGL(k_post_finish, dim3(kg * POST_SUMS), dim3(64), 0, st, kg, nblocks, partial, sums);
     hipLaunchKernelGGL(k_post_scale, dim3((unsigned)((c->n2 + 255) / 256), kg), dim3(256), 0, st, N, c->dpn, sums, ev);
     if (modes_int)
       hipLaunchKernelGGL(k_gather_interior, dim3((unsigned)((c->dpn * (int64_t)c->nsolve + 255) / 256), kg), dim3(256), 0, st,
@@ -819,7 +802,7 @@ void post_enqueue(plfem_ctx* c, int k, double* evecs, int ncore, double* modes_i
   }
   // results to the host
   double* hs = c->h_pinned + PIN_POST;
-  (void)hipMemcpyAsync(hs, c->d_post + (int64_t)k * nblocks * 5, sizeof(double) * k * 5, hipMemcpyDeviceToHost, st);
+  (void)hipMemcpyAsync(hs, c->d_post + (int64_t)k * nblocks * POST_SUMS, sizeof(double) * k * POST_SUMS, hipMemcpyDeviceToHost, st);
   int32_t* hc = reinterpret_cast<int32_t*>(c->h_pinned + PIN_COUNTERS);
   (void)hipMemcpyAsync(hc, c->d_counters, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st);
 }
@@ -829,7 +812,7 @@ void post_finish(plfem_ctx* c, int k, double* out_host, double* frac_core) {
   const double* hs = c->h_pinned + PIN_POST;
   const int32_t* hc = reinterpret_cast<const int32_t*>(c->h_pinned + PIN_COUNTERS);
   for (int mode = 0; mode < k; ++mode) {
-    const double* s = hs + mode * 5;
+    const double* s = hs + mode * POST_SUMS;
     double nrm2 = c->dpn == 2 ? s[0] + s[1] : s[4];      // scalar solver: M-norm (solver_fem.py:268)
     double nrm = std::sqrt(nrm2) + 1e-30;
     double inv2 = 1.0 / (nrm * nrm);

@@ -629,8 +629,9 @@ void sweeps(plfem_ctx* c) {
   A.cinv0 = c->d_cinv0; A.cinv1 = c->d_cinv1; A.prow = c->d_prow;
   A.front = c->d_front; A.dinv2 = reinterpret_cast<const double2*>(c->d_delta);
   A.fr = c->d_fvec; A.u0 = c->d_u0; A.u1 = c->d_u1; A.ys = c->d_fvec2; A.xl = c->d_xl;
+  const std::vector<LevelInfo>& levels = c->plan->levels;
   double sweep_total = 0.0;                     // algorithmic bytes of one whole sweep (either direction)
-  for (const LevelInfo& li : c->levels) sweep_total += li.sweep_bytes + 8.0 * (P - 1) * li.sweep_vec_doubles;
+  for (const LevelInfo& li : levels) sweep_total += li.sweep_bytes + 8.0 * (P - 1) * li.sweep_vec_doubles;
   // Kernel form by level: fwd_block_rows / bwd_block_rows (device.h); workgroups come from the compact launch
   // lists of the context (no empty workgroups, large fronts first).
   // live timing (plfem_profile_*): event records around single launches lengthen the sweep they sit in (~8 us each), so
@@ -638,12 +639,12 @@ void sweeps(plfem_ctx* c) {
   const bool time_launches = c->prof_on && (c->prof_toggle++ & 1);
   const int pid_fwd = time_launches ? -1 : prof_open(c, PLFEM_PROF_FWD_SWEEP, sweep_total);
   for (int lev = c->L; lev >= 0; --lev) {
-    const LevelInfo& li = c->levels[lev];
+    const LevelInfo& li = levels[lev];
     if (li.fwd_n == 0) continue;
     A.leaf_level = lev == c->L ? 1 : 0;
     const SweepJob* blk = c->d_blk + li.fwd_off;
-    A.ldv = (li.max_s2 + 2) & ~1;                   // even: the row forms read the staged planes as double2
-    const size_t lds = sizeof(double) * P * A.ldv;
+    A.ldv = sweep_ldv(li.max_s2);
+    const size_t lds = sweep_dynamic_lds(P, li.max_s2);
     if (li.fwd_rows == 8) {
       hipLaunchKernelGGL((k_fwd_rows<P, 1, 4>), dim3(li.fwd_n), dim3(512), lds, st, blk, A);
     } else if (li.fwd_rows == 16) {
@@ -659,12 +660,12 @@ void sweeps(plfem_ctx* c) {
   prof_close(c, pid_fwd);
   const int pid_bwd = time_launches ? -1 : prof_open(c, PLFEM_PROF_BWD_SWEEP, sweep_total);
   for (int lev = 0; lev <= c->L; ++lev) {
-    const LevelInfo& li = c->levels[lev];
+    const LevelInfo& li = levels[lev];
     if (li.bwd_n == 0) continue;
     A.leaf_level = lev == c->L ? 1 : 0;
     const SweepJob* blk = c->d_blk + li.bwd_off;
-    A.ldv = (li.max_m + 2) & ~1;
-    const size_t lds = sizeof(double) * P * A.ldv;
+    A.ldv = sweep_ldv(li.max_m);
+    const size_t lds = sweep_dynamic_lds(P, li.max_m);   // (with the static tile of k_bwd: sweep_lds, checked by plfem_create)
     if (li.bwd_rows == 8)          // few large fronts: one row per wave, most blocks
       hipLaunchKernelGGL((k_bwd_rows<P, 1, 4>), dim3(li.bwd_n), dim3(512), lds, st, blk, A);
     else if (li.bwd_rows == 16)
@@ -677,23 +678,18 @@ void sweeps(plfem_ctx* c) {
 
 }  // namespace
 
-namespace {
-template <int P>
-void solve(plfem_ctx* c, const double* rhs, double* x, int64_t ldx, bool rhs_in_front_order) {
-  const unsigned grid = (unsigned)((c->n2 + 255) / 256);
-  if (!rhs_in_front_order)
-    hipLaunchKernelGGL(k_permute_in<P>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, rhs, ldx, c->d_fvec);
-  sweeps<P>(c);
-  if (x) hipLaunchKernelGGL(k_permute_out<P>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, c->d_xl, x, ldx);
-}
-}  // namespace
-
 // P (1 or BLOCK_P) right-hand sides given as columns (ldx apart); inside the sweeps the P values of a DOF are one 8 P-byte
 // access.  rhs_in_front_order: the caller's previous kernel (k_block_scale) already left the right-hand side in the
 // sweeps' layout (context buffer d_fvec)
 void launch_solve(plfem_ctx* c, int P, const double* rhs, double* x, int64_t ldx, bool rhs_in_front_order) {
-  if (P == 1) solve<1>(c, rhs, x, ldx, rhs_in_front_order);
-  else solve<BLOCK_P>(c, rhs, x, ldx, rhs_in_front_order);
+  const unsigned grid = (unsigned)((c->n2 + 255) / 256);
+  with_constant<1, BLOCK_P>(P, [&](auto p) {
+    constexpr int PT = decltype(p)::value;
+    if (!rhs_in_front_order)
+      hipLaunchKernelGGL(k_permute_in<PT>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, rhs, ldx, c->d_fvec);
+    sweeps<PT>(c);
+    if (x) hipLaunchKernelGGL(k_permute_out<PT>, dim3(grid), dim3(256), 0, c->stream, c->n2, c->N, c->d_npos, c->d_xl, x, ldx);
+  });
 }
 
 // y = K^-1 b followed by `steps` passes of iterative refinement against the ASSEMBLED K = A - sigma B:

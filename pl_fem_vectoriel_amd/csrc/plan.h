@@ -26,7 +26,13 @@ struct default_init_allocator : std::allocator<T> {
 
 constexpr int NB = 32;          // pivot-block width of the block LDL^T
 constexpr int PANEL_CHUNK = 1024; // rows per partial sum of the tall-skinny panel products
-// sweep kernel forms by level (launch_solve_p and the launch lists must agree)
+constexpr int FIRST_ROWS = 1024;  // rows per workgroup of k_permute_dot_first = per partial sum (512 measured: 17.1 + 11.1 us against 15.8 + 9.5)
+constexpr int FIRST_COLS = 8;     // panel columns of the fused first Gram-Schmidt pass (the last two blocks of the basis)
+constexpr int SPMV_WG_ROWS = 32;  // rows per workgroup of the sparse products: 8 lanes per row, 256 threads
+constexpr int POST_ROWS = 256;    // rows per workgroup of k_post_sums / k_resid_sums
+constexpr int POST_SUMS = 5;      // sums per mode of the post-processing; the residual check has RESID_SUMS
+constexpr int RESID_SUMS = 2;
+// sweep kernel forms by level (sweeps() of kernels_sweep.hip and the launch lists must agree)
 constexpr int ROW_FORM_MAX_FRONTS = 32;   // levels with at most this many fronts use the row-form kernels in both sweeps
 // 8 / 16: pure row form with that many rows per workgroup; 64: tile form (backward: leaf level only; forward: mixed
 // launch -- tiles of 64 rows, row-form workgroups of 16 rows for the fronts with more than MIX_BIG_S2 owned DOFs)
@@ -67,7 +73,7 @@ struct LevelInfo {
   // compact launch lists of the sweep kernels (d_blk): one entry per useful workgroup = (front, row block),
   // fronts in order of decreasing work so that the long ones start first
   // factorisation: 64 x 64 tile lists (d_tiles) of the extend-add, of Z, and (per block step: upd_off / upd_n of
-  // the context, index step0 + kb) of the trailing updates
+  // the plan, index step0 + kb) of the trailing updates
   int64_t gather_off = 0, formz_off = 0, mirrorx_off = 0;
   int gather_n = 0, formz_n = 0, mirrorx_n = 0, step0 = 0;
   int fwd_rows = 0, bwd_rows = 0;      // rows per workgroup of the forward / backward kernel of this level
