@@ -372,6 +372,32 @@ int plfem_mode_quartic(plfem_locator* loc, int32_t ncomp, int32_t k, const doubl
                        const double* cores_host, int32_t ncore, double w_core, double w_clad,
                        void* work_dev, int64_t work_bytes, double* out_host);
 
+/* Projection of k staged modes on a family of analytic fields that separate in x and y: plane waves (far field) and
+ * Gaussian beams of any centre, waist and tilt (launch maps).  A factor is a triple (c, s, kappa) of finite doubles,
+ * s >= 0:  phi(t; c, s, kappa) = exp(-s (t - c)^2) (cos(kappa t) - i sin(kappa t));  s = 0 is a plane wave (the Gaussian
+ * part is then exactly 1), a beam of 1/e field radius w has s = 1 / w^2.  With la x-factors and lb y-factors,
+ *   out_host[c][m][b][a] = sum over the elements e and the 16 points q of the degree-8 rule of
+ *                          |det J_e| w_q u_(c,m)(x_eq) phi(X_eq; xfac_a) phi(Y_eq; yfac_b)      (re, im),
+ * every component c < ncomp on its own; (X, Y) the physical quadrature point as the assembly forms it, u the P2 field
+ * of the element's six staged rows (a boundary DOF of an indexed record contributes 0), the phase argument the single
+ * rounded product kappa t, sincos and exp the full-precision double functions.  Defined on the discrete fields alone:
+ * nothing is assumed about the pencil the modes came from.  The reference has no counterpart (it turns no mode vector
+ * back into a field).
+ * modes_dev: staged by plfem_stage_modes ([ncomp][nrows][k]); indexed as in plfem_sample_fields.  xfac_host [la][3],
+ * yfac_host [lb][3] = (c, s, kappa) per factor; they travel to the device inside the work buffer.  Partial tiles per
+ * workgroup and a fixed-order second stage: the same bits on every run.  Runs on the locator's stream and
+ * synchronises it.
+ * work_dev: device scratch of plfem_project_work_bytes(ncomp, k, la, lb) bytes, 256-byte aligned: the result (16 ncomp k
+ * la lb bytes), the partial 16 x 16 tiles of every mode -- tiles of 8 x 8 factors, min(256, 1024 / tiles) element slices
+ * per tile, at least one, so at most 2 KB ncomp k max(1024, tiles) bytes -- and the two factor tables.
+ * Argument errors (ncomp not 1 or 2, k outside [1, 64], la or lb outside [1, 4096], a non-finite factor entry or
+ * s < 0, a null pointer, work_bytes too small) return PLFEM_EINVAL with the locator's last error set. */
+int plfem_project_work_bytes(int32_t ncomp, int32_t k, int32_t la, int32_t lb, int64_t* bytes);
+int plfem_mode_project(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                       int32_t la, const double* xfac_host /* [la][3] = c, s, kappa */,
+                       int32_t lb, const double* yfac_host /* [lb][3] */,
+                       void* work_dev, int64_t work_bytes, double* out_host /* [ncomp][k][lb][la][2] re, im */);
+
 #ifdef PLFEM_TEST_HOOKS
 /* ---------------------------------------------------------------------------------------------
  * TEST HOOKS -- NOT exported by libplfem_hip.so.  They live in the add-on libplfem_testhooks.so (csrc/api_debug.hip,

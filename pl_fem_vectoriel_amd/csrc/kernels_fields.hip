@@ -2,11 +2,15 @@
 // locator bound to a device, P2 evaluation of many modes at many points (k_sample_fields) and the overlap integral of
 // two mode sets living on two meshes (k_field_overlap + k_overlap_reduce), and the same-mesh Grams of a mode set under
 // the assembly's element forms, split by material region (k_mode_grams + k_overlap_reduce), and the quartic overlap of
-// products of four modes on a 16-point degree-8 rule (k_mode_quartic + k_quartic_reduce).
+// products of four modes on a 16-point degree-8 rule (k_mode_quartic + k_quartic_reduce), and the projection of a mode
+// set on a family of analytic fields that separate in x and y -- plane waves and Gaussian beams -- on the same rule
+// (k_mode_project + k_project_reduce).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
-// (reference solver_fem.py:126): the reference itself turns no mode vector back into a field.
+// (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
+// quartic overlap and the projection have no counterpart there.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -567,6 +571,159 @@ __global__ __launch_bounds__(256) void k_quartic_reduce(int npair, int ntile, in
   }
 }
 
+// Projection of the modes on separable analytic fields (plfem_mode_project): a factor (c, s, kappa) is
+// phi(t) = exp(-s (t - c)^2) (cos(kappa t) - i sin(kappa t)) -- s = 0: a plane wave, the Gaussian part exactly 1 -- and
+//   P[field][b][a] = sum over the elements and the 16 points of |det J| w_q u_field(x_q) phi(X_q; xfac_a) phi(Y_q; yfac_b),
+// field = (component, mode).  A real GEMM over the quadrature points whose operands are generated on the fly: rows
+// (field, x-factor, re | im) of value u phi_x, columns (y-factor, re | im) of value |det J| w phi_y.  One workgroup
+// owns, for ALL fields, the tile of PJ_X x-factors (blockIdx.x % ntx) against PJ_Y y-factors (blockIdx.x / ntx) and walks
+// the elements blockIdx.y, blockIdx.y + gridDim.y, ...  Per element: the six staged DOF rows of every field go to LDS
+// and u at the 16 points follows from one basis table, as in k_mode_quartic; thread (point, factor of the tile)
+// evaluates its factor at its point with the full-precision sincos / exp -- 16 (PJ_X + PJ_Y) = 256 evaluations, one per
+// thread, shared by all fields -- and stores re, im (the y-factors times the point's weight).  The 16 rows of one field
+// are then u[field][t] times the SAME 16 x-values (x-factor a, re: row a; im: row PJ_X + a), so a lane keeps its x-value
+// and its B operand in registers per K-step and forms the A operand of each field with one broadcast LDS read and
+// one product; wave w accumulates the 16 x 16 tiles of the fields w, w + 4, ... on v_mfma_f64_16x16x4_f64.  The factor
+// values are double-buffered, so two barriers per element suffice.  The workgroup's partial tiles
+// [field][row][column] go to its own slot (no atomics); k_project_reduce sums the slots in a fixed order and combines
+// the four real products: re = RR - II, im = RI + IR.
+constexpr int PJ_X = 8;          // x-factors per tile: 16 rows per field
+constexpr int PJ_Y = 8;          // y-factors per tile: 16 columns
+constexpr int PJ_KMAX = 64;      // most modes per call
+constexpr int PJ_LMAX = 4096;    // most x- or y-factors per call
+constexpr int PJ_SLICES = 256;   // most element slices (partial tiles) per tile
+constexpr int PJ_WG = 1024;      // workgroups aimed at: slices = min(PJ_SLICES, PJ_WG / tiles), at least 1
+constexpr int PJ_LD = 17;        // padded LDS row of the factor values
+
+template <int MAXT>              // most fields per wave: ncomp k <= 4 MAXT
+__global__ __launch_bounds__(256) void k_mode_project(LocArgs L, int ncomp, int k, int64_t nrows, const double* __restrict__ V,
+                                                      int la, const double* __restrict__ xfac, int lb,
+                                                      const double* __restrict__ yfac, int ntx, double* __restrict__ partial) {
+  constexpr int FMAX = 4 * MAXT;
+  __shared__ double s_v[6][FMAX];              // the element's DOF rows (0 for a boundary DOF of an indexed record)
+  __shared__ double s_u[16][FMAX + 1];
+  __shared__ double s_f[2][2][16][PJ_LD];      // [buffer][x | y][factor, re: + 0, im: + 8][point]
+  __shared__ double s_phi[16][6];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nf = ncomp * k;
+  const int ta = blockIdx.x % ntx, tb = blockIdx.x / ntx;
+  // this thread's factor of the tile and its point
+  const int pt = tid & 15, fj = tid >> 4;
+  const bool isy = fj >= PJ_X;
+  const int fi = isy ? tb * PJ_Y + (fj - PJ_X) : ta * PJ_X + fj;
+  const bool live = fi < (isy ? lb : la);      // past the table: the row / column is 0
+  const double* fp = (isy ? yfac : xfac) + 3 * (live ? fi : 0);
+  const double fc = fp[0], fs = fp[1], fk = fp[2];
+  const int frow = isy ? fj - PJ_X : fj;
+  if (tid < 96) s_phi[tid / 6][tid % 6] = p2_phi(tid % 6, c_q16x[tid / 6], c_q16y[tid / 6]);
+  for (int idx = tid; idx < 16 * (FMAX + 1); idx += 256) (&s_u[0][0])[idx] = 0.0;   // (the columns past nf stay 0)
+  const double* px = L.pxy;
+  const double* py = L.pxy + L.nv;
+  const int l16 = lane & 15, l4 = lane >> 4;
+  dbl4 acc[MAXT];
+#pragma unroll
+  for (int i = 0; i < MAXT; ++i) acc[i] = dbl4{0.0, 0.0, 0.0, 0.0};
+  // This thread's entries of the element's DOF rows and the element's map are fetched one element ahead: the dependent
+  // global loads (edof, int_index, the mode row; the vertices, their coordinates) then overlap the u and MFMA phases of the
+  // element before.  (blockIdx.y < ne: the host launches no more slices than elements.)
+  constexpr int NV = (6 * FMAX + 255) / 256;
+  double vn[NV];
+  auto fetch_rows = [&](int e) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int idx = tid + 256 * j;
+      vn[j] = 0.0;
+      if (idx < 6 * nf) {
+        const int f = idx % nf, r = dev_row(L, e, idx / nf);
+        if (r >= 0) vn[j] = V[((int64_t)(f / k) * nrows + r) * k + f % k];
+      }
+    }
+  };
+  fetch_rows(blockIdx.y);
+  P2Map Mn(L.edof, L.ne, px, py, blockIdx.y);
+  int buf = 0;
+  for (int e = blockIdx.y; e < L.ne; e += gridDim.y, buf ^= 1) {
+    const P2Map M = Mn;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int idx = tid + 256 * j;
+      if (idx < 6 * nf) s_v[idx / nf][idx % nf] = vn[j];
+    }
+    {
+      double X, Y, re = 0.0, im = 0.0;
+      M.point(c_q16x[pt], c_q16y[pt], X, Y);
+      if (live) {
+        const double t = isy ? Y : X;
+        double sn, cs, g = 1.0;
+        sincos(mul_rn(fk, t), &sn, &cs);        // the phase is the single rounded product
+        if (fs != 0.0) {
+          const double d = t - fc;
+          g = exp(-mul_rn(fs, mul_rn(d, d)));
+        }
+        if (isy) g *= fabs(M.det()) * c_q16w[pt];
+        re = g * cs;
+        im = -(g * sn);
+      }
+      s_f[buf][isy][frow][pt] = re;
+      s_f[buf][isy][8 + frow][pt] = im;
+    }
+    __syncthreads();
+    if (e + (int)gridDim.y < L.ne) {
+      fetch_rows(e + gridDim.y);
+      Mn = P2Map(L.edof, L.ne, px, py, e + gridDim.y);
+    }
+    for (int idx = tid; idx < 16 * nf; idx += 256) {
+      const int f = idx % nf, t = idx / nf;
+      double u = 0.0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) u += s_phi[t][a] * s_v[a][f];
+      s_u[t][f] = u;
+    }
+    __syncthreads();
+    // A[row][kk] = u[field][t = 4 ks + kk] x[row][t], B[kk][col] = y[col][t]; lane: row / col = lane & 15, kk = lane >> 4
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int t = 4 * ks + l4;
+      const double xv = s_f[buf][0][l16][t], bv = s_f[buf][1][l16][t];
+      // no branch on the field count here: a tile past nf multiplies the zero columns of s_u and is never stored, and
+      // the straight-line code lets the LDS reads run ahead of the MFMAs
+#pragma unroll
+      for (int i = 0; i < MAXT; ++i)
+        acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(s_u[t][wave + 4 * i] * xv, bv, acc[i], 0, 0, 0);
+    }
+    // (no barrier: the next element writes s_v and the other buffer of s_f, and s_u only behind its first barrier)
+  }
+  // D of v_mfma_f64_16x16x4_f64: entry g of a lane is (row (lane >> 4) + 4 g, col lane & 15)
+  double* out = partial + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * nf * 256;
+#pragma unroll
+  for (int i = 0; i < MAXT; ++i) {
+    const int f = wave + 4 * i;
+    if (f >= nf) continue;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) out[(int64_t)f * 256 + (l4 + 4 * g) * 16 + l16] = acc[i][g];
+  }
+}
+
+// Second stage of k_mode_project: one lane per complex entry (field, b, a) of O [nf][lb][la][2]; the nblk partial tiles
+// of its tile summed in slice order (the same bits on every run), each slice's four real products combined first.
+__global__ __launch_bounds__(256) void k_project_reduce(int nf, int la, int lb, int ntx, int nblk, const double* __restrict__ partial,
+                                                        double* __restrict__ O) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= (int64_t)nf * lb * la) return;
+  const int a = (int)(v % la), b = (int)((v / la) % lb), f = (int)(v / ((int64_t)la * lb));
+  const int64_t tile = (int64_t)(b / PJ_Y) * ntx + a / PJ_X;
+  const int ai = a % PJ_X, bi = b % PJ_Y;
+  const double* pp = partial + (tile * nblk * nf + f) * 256;
+  double re = 0.0, im = 0.0;
+  for (int s = 0; s < nblk; ++s) {
+    const double* q = pp + (int64_t)s * nf * 256;
+    re += q[ai * 16 + bi] - q[(8 + ai) * 16 + 8 + bi];
+    im += q[ai * 16 + 8 + bi] + q[(8 + ai) * 16 + bi];
+  }
+  O[2 * v] = re;
+  O[2 * v + 1] = im;
+}
+
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -855,6 +1012,91 @@ extern "C" int plfem_mode_quartic(plfem_locator* L, int32_t ncomp, int32_t k, co
   hipLaunchKernelGGL(k_quartic_reduce, dim3(ntp, 1, QP * QP / 256), dim3(256), 0, L->stream, np, nt, nblk, partial, O);
   TRY(check_launch(L, "k_quartic_reduce"));
   HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * np * np, hipMemcpyDeviceToHost, L->stream));
+  HIP_TRY(L, hipStreamSynchronize(L->stream));
+  return PLFEM_OK;
+} catch (...) { return host_failure(L); }
+
+namespace {
+// Tiles, element slices and work buffer of a projection: the result [nf][lb][la][2], then the partial tiles
+// [tile][slice][nf][16][16], then the two factor tables, each part 256-byte aligned
+struct ProjectPlan {
+  int nf, maxt, ntx, nty, slices;
+  int64_t tiles;
+  size_t off_partial, off_xfac, off_yfac, total;   // bytes
+};
+ProjectPlan project_plan(int ncomp, int k, int la, int lb) {
+  ProjectPlan p;
+  p.nf = ncomp * k;
+  p.maxt = (p.nf + 3) / 4;                                           // up to the next instance of k_mode_project
+  p.maxt += p.maxt <= 16 ? p.maxt % 2 : (4 - p.maxt % 4) % 4;
+  p.ntx = (la + PJ_X - 1) / PJ_X;
+  p.nty = (lb + PJ_Y - 1) / PJ_Y;
+  p.tiles = (int64_t)p.ntx * p.nty;
+  p.slices = (int)std::max<int64_t>(1, std::min<int64_t>(PJ_SLICES, PJ_WG / p.tiles));
+  size_t o = align256(sizeof(double) * 2 * p.nf * lb * la);
+  p.off_partial = o; o += align256(sizeof(double) * p.slices * p.tiles * p.nf * 256);
+  p.off_xfac = o;    o += align256(sizeof(double) * 3 * la);
+  p.off_yfac = o;    o += align256(sizeof(double) * 3 * lb);
+  p.total = o;
+  return p;
+}
+bool project_sizes_ok(int ncomp, int k, int la, int lb) {
+  return ncomp >= 1 && ncomp <= 2 && k >= 1 && k <= PJ_KMAX && la >= 1 && la <= PJ_LMAX && lb >= 1 && lb <= PJ_LMAX;
+}
+// every (c, s, kappa) finite and s >= 0
+bool factors_ok(const double* fac, int n) {
+  for (int i = 0; i < n; ++i) {
+    const double* f = fac + 3 * i;
+    if (!std::isfinite(f[0]) || !std::isfinite(f[1]) || !std::isfinite(f[2]) || f[1] < 0.0) return false;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int plfem_project_work_bytes(int32_t ncomp, int32_t k, int32_t la, int32_t lb, int64_t* bytes) {
+  if (!bytes || !project_sizes_ok(ncomp, k, la, lb)) return PLFEM_EINVAL;
+  *bytes = (int64_t)project_plan(ncomp, k, la, lb).total;
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_mode_project(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                  int32_t la, const double* xfac_host, int32_t lb, const double* yfac_host, void* work_dev,
+                                  int64_t work_bytes, double* out_host) try {
+  if (!L) return PLFEM_EINVAL;
+  if (!project_sizes_ok(ncomp, k, la, lb)) {
+    L->err = "plfem_mode_project: ncomp must be 1 or 2, 1 <= k <= 64 and 1 <= la, lb <= 4096";
+    return PLFEM_EINVAL;
+  }
+  if (!modes_dev || !xfac_host || !yfac_host || !work_dev || !out_host) {
+    L->err = "plfem_mode_project: null array";
+    return PLFEM_EINVAL;
+  }
+  if (!factors_ok(xfac_host, la) || !factors_ok(yfac_host, lb)) {
+    L->err = "plfem_mode_project: every factor (c, s, kappa) must be finite with s >= 0";
+    return PLFEM_EINVAL;
+  }
+  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_project: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  const ProjectPlan plan = project_plan(ncomp, k, la, lb);
+  TRY(check_work(L, "plfem_mode_project", "plfem_project_work_bytes", work_dev, work_bytes, (int64_t)plan.total));
+  HIP_TRY(L, hipSetDevice(L->device));
+  char* base = (char*)work_dev;
+  double *O = (double*)base, *partial = (double*)(base + plan.off_partial);
+  double *xfac = (double*)(base + plan.off_xfac), *yfac = (double*)(base + plan.off_yfac);
+  HIP_TRY(L, hipMemcpyAsync(xfac, xfac_host, sizeof(double) * 3 * la, hipMemcpyHostToDevice, L->stream));
+  HIP_TRY(L, hipMemcpyAsync(yfac, yfac_host, sizeof(double) * 3 * lb, hipMemcpyHostToDevice, L->stream));
+  const int nblk = std::max(1, std::min(plan.slices, L->ne));
+  const int64_t nrows = indexed ? L->nsolve : L->N;
+  const dim3 grid((unsigned)plan.tiles, nblk);
+  with_constant<2, 4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32>(plan.maxt, [&](auto mt) {
+    hipLaunchKernelGGL(k_mode_project<decltype(mt)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)ncomp,
+                       (int)k, nrows, modes_dev, (int)la, xfac, (int)lb, yfac, plan.ntx, partial);
+  });
+  TRY(check_launch(L, "k_mode_project"));
+  const int64_t entries = (int64_t)plan.nf * lb * la;
+  hipLaunchKernelGGL(k_project_reduce, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, L->stream, plan.nf, (int)la, (int)lb,
+                     plan.ntx, nblk, partial, O);
+  TRY(check_launch(L, "k_project_reduce"));
+  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * 2 * entries, hipMemcpyDeviceToHost, L->stream));
   HIP_TRY(L, hipStreamSynchronize(L->stream));
   return PLFEM_OK;
 } catch (...) { return host_failure(L); }

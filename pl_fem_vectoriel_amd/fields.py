@@ -12,7 +12,9 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
 * :meth:`ModeFields.grams` -- the k x k Grams of one mesh's modes under the assembly's element forms, split by material
   region (``plfem_mode_grams``): what :mod:`.dispersion` builds the group index and the k0-derivative coupling from;
 * :meth:`ModeFields.quartic` -- the packed overlap of products of four modes on a 16-point degree-8 rule
-  (``plfem_mode_quartic``): what :mod:`.nonlinear` builds the nonlinear coupling tensor, A_eff and gamma from.
+  (``plfem_mode_quartic``): what :mod:`.nonlinear` builds the nonlinear coupling tensor, A_eff and gamma from;
+* :meth:`ModeFields.project` -- the projection of the modes on plane waves and Gaussian beams, fields that separate in
+  x and y, on the same rule (``plfem_mode_project``): what :mod:`.launch` builds far fields and launch maps from.
 
 Containment (``PLFEM_LOC_TOL``): a point is inside an element when every barycentric coordinate is >= -1e-10 (minus
 that coordinate's floating-point rounding bound, which matters on sliver elements only); when
@@ -30,6 +32,8 @@ from .solver_fem import _core_table, mesh_key
 
 LOC_TOL = 1e-10                    # PLFEM_LOC_TOL of include/plfem.h
 GRAM_NAMES = {"vectorial": ("M_core", "M_clad", "K_core", "K_clad", "D"), "scalar": ("M_core", "M_clad", "S")}
+PROJECT_TILE = (8, 8)              # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
+PROJECT_MAX_FACTORS = 4096         # PJ_LMAX
 
 
 def _mesh_arrays(mesh):
@@ -38,6 +42,21 @@ def _mesh_arrays(mesh):
     if p.ndim != 2 or p.shape[0] != 2 or t.ndim != 2 or t.shape[0] != 3:
         raise ValueError("mesh must have p (2, nv) and t (3, ne)")
     return p, t
+
+
+def _factors(fac, name: str) -> np.ndarray:
+    """A factor table (l, 3) = (c, s, kappa) per row, 1 <= l <= 4096, finite, s >= 0, as contiguous float64."""
+    try:
+        f = np.ascontiguousarray(np.asarray(fac, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be an array of shape (l, 3): (c, s, kappa) per factor") from None
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"{name} must be an array of shape (l, 3): (c, s, kappa) per factor")
+    if not 1 <= f.shape[0] <= PROJECT_MAX_FACTORS:
+        raise ValueError(f"{name} must hold between 1 and {PROJECT_MAX_FACTORS} factors, got {f.shape[0]}")
+    if not np.all(np.isfinite(f)) or np.any(f[:, 1] < 0):
+        raise ValueError(f"every factor of {name} must be finite with s >= 0")
+    return f
 
 
 def _records(modes) -> tuple:
@@ -305,6 +324,47 @@ class ModeFields:
                                                  out.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_quartic")
         return out
 
+    def project(self, modes: Sequence[Dict], x_factors, y_factors) -> np.ndarray:
+        """Projection of the modes on separable analytic fields (``plfem_mode_project``), complex (ncomp, k, lb, la):
+        ``P[c, m, b, a] = sum over the elements and the 16-point degree-8 rule of |det J| w_q u_c,m(x_q)
+        phi(X_q; x_factors[a]) phi(Y_q; y_factors[b])`` with ``phi(t; c, s, kappa) = exp(-s (t - c)^2) exp(-i kappa t)``.
+        A factor table has shape (l, 3), a row (c, s, kappa) with s >= 0: s = 0 is a plane wave, a Gaussian beam of 1/e
+        field radius w has s = 1 / w^2.  Every component of a vectorial record (``Ex_dofs`` / ``Ey_dofs`` hold Hx / Hy) is
+        projected on its own; ncomp = 1 for scalar records.  At most 64 modes and 4096 factors per axis; the y-factors
+        are split into chunks so that one call's device result stays under ``CHUNK_BYTES``.  An empty mode list gives
+        an empty array."""
+        kind, vals, _ = self._check_records(modes)
+        xf, yf = _factors(x_factors, "x_factors"), _factors(y_factors, "y_factors")
+        la, lb = xf.shape[0], yf.shape[0]
+        if kind is None:
+            return np.zeros((0, 0, lb, la), dtype=np.complex128)
+        ncomp, k = vals.shape[0], vals.shape[1]
+        if k > 64:
+            raise ValueError(f"at most 64 modes per projection, got {k}")
+        self._ensure_locator()
+        import torch
+        chunk = int(max(1, min(lb, self.CHUNK_BYTES // (16 * ncomp * k * la))))
+        nbytes = 0
+        for n in {chunk, lb % chunk or chunk}:                  # the full chunks and a shorter last one
+            need = ctypes.c_int64(0)
+            if self._lib.plfem_project_work_bytes(ncomp, k, la, n, ctypes.byref(need)) != _native.PLFEM_OK:
+                raise ValueError(f"plfem_project_work_bytes rejected ncomp = {ncomp}, k = {k}, la = {la}, lb = {n}")
+            nbytes = max(nbytes, int(need.value))
+        staged, _src = self._stage(vals)
+        work = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.tdev)
+        aligned = (work.data_ptr() + 255) & ~255
+        out = np.empty((ncomp, k, lb, la), dtype=np.complex128)
+        for s in range(0, lb, chunk):
+            yc = np.ascontiguousarray(yf[s:s + chunk])
+            part = np.empty((ncomp, k, yc.shape[0], la), dtype=np.complex128)
+            self._check(self._lib.plfem_mode_project(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
+                                                     1 if kind == "vectorial" else 0, la, xf.ctypes.data_as(ctypes.c_void_p),
+                                                     yc.shape[0], yc.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(aligned),
+                                                     ctypes.c_int64(nbytes), part.ctypes.data_as(ctypes.c_void_p)),
+                        "plfem_mode_project")
+            out[:, :, s:s + chunk] = part
+        return out
+
     def close(self):
         if getattr(self, "_loc", None):
             self._lib.plfem_locator_destroy(self._loc)      # synchronises the stream before the memory goes back to torch
@@ -384,4 +444,4 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
     return O * O / (daa[:, None] * dbb[None, :])
 
 
-__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES"]
+__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES", "PROJECT_TILE", "PROJECT_MAX_FACTORS"]

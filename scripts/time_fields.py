@@ -1,11 +1,14 @@
 """Timing aid of the mode-field calls at C1 (vectorial, 22 modes): sampling on an nx x nx grid with Hx, Hy, Hz_im;
 mode_overlap C1 -> C1 refined (the C1 modes sampled at the DOF locations of mesh.refined(): ~1.1 M quadrature points of
-the finer mesh, 22 x 22); locator build times at C1 and L = 2; optionally the NumPy emulation of the same calls.
+the finer mesh, 22 x 22); locator build times at C1 and L = 2; the projection on a 1 x 1 Gaussian beam and on 64 x 64 and
+256 x 256 plane-wave grids up to k0 (``ModeFields.project``); optionally the NumPy emulation of the same calls (the
+projection up to ``--emulation-grid`` factors per axis: the 256 x 256 grid would take the host hours).
 
-    python scripts/time_fields.py [--grid 1024] [--reps 3] [--emulation] [--out FILE]
+    python scripts/time_fields.py [--grid 1024] [--reps 3] [--project-only] [--emulation] [--out FILE]
 
 Run it under ``rocprofv3 --kernel-trace --stats`` for the kernel times (k_sample_fields, k_field_overlap,
-k_overlap_reduce, k_stage_modes); the wall times printed here include the host-device copies."""
+k_overlap_reduce, k_stage_modes, k_mode_project, k_project_reduce; the projection leg dispatches k_mode_project ``--reps``
+times per grid, in the order of ``--project-grids``); the wall times printed here include the host-device copies."""
 from __future__ import annotations
 
 import argparse
@@ -27,6 +30,9 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--modes", type=int, default=22)
     ap.add_argument("--emulation", action="store_true", help="also time the NumPy emulation (minutes)")
+    ap.add_argument("--project-only", action="store_true", help="run the projection leg alone")
+    ap.add_argument("--project-grids", default="1,64,256", help="factors per axis of the projection leg (1: one Gaussian beam)")
+    ap.add_argument("--emulation-grid", type=int, default=64, help="largest projection grid the emulation is timed on")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -44,7 +50,7 @@ def main():
     res = {"k": len(modes), "ne_c1": int(mesh.t.shape[1]), "ne_l2": int(fine.t.shape[1])}
 
     # locator build (host) on fresh analyses
-    for name, m in (("c1", mesh), ("l2", fine)):
+    for name, m in () if args.project_only else (("c1", mesh), ("l2", fine)):
         sym = _native.Symbolic(m.p, m.t)
         t0 = time.perf_counter()
         st = sym.array("loc_stats")
@@ -65,6 +71,9 @@ def main():
             best = dt if best is None else min(best, dt)
         return out, best
 
+    project_leg(args, geom, mesh, mf, modes, timed, res)
+    if args.project_only:
+        return finish(args, res)
     img, dt = timed(lambda: mf.sample_grid(modes, args.grid, args.grid))
     out_bytes = 3 * len(modes) * args.grid * args.grid * 8
     res["sample_grid"] = {"nx": args.grid, "wall_ms": dt * 1e3, "output_bytes": out_bytes,
@@ -95,6 +104,38 @@ def main():
         Oe = overlap(em, vals, em1, vf, True)
         res["emulation_overlap_s"] = time.perf_counter() - t0
         res["emulation_overlap_rel_diff"] = float(np.abs(Oe - O).max() / np.abs(O).max())
+    finish(args, res)
+
+
+def project_factors(geom, n):
+    """The factor tables of one projection grid: n = 1 a w = 1.5 um beam on the central core, else n x n plane waves up to k0."""
+    if n == 1:
+        return np.array([[0.0, 1.0 / 1.5 ** 2, 0.0]]), np.array([[0.0, 1.0 / 1.5 ** 2, 0.0]])
+    kap = np.linspace(-geom.k0, geom.k0, n)
+    fac = np.stack([np.zeros(n), np.zeros(n), kap], 1)
+    return fac, fac
+
+
+def project_leg(args, geom, mesh, mf, modes, timed, res):
+    """``ModeFields.project`` per grid: wall time, and the 8 ncomp k la lb Q real multiply-adds counted as flop."""
+    nq = 16 * mesh.t.shape[1]
+    res["project"] = {}
+    for n in (int(v) for v in args.project_grids.split(",")):
+        xf, yf = project_factors(geom, n)
+        P, dt = timed(lambda: mf.project(modes, xf, yf))
+        entry = {"wall_ms": dt * 1e3, "flop": 8.0 * 2 * len(modes) * n * n * nq, "nq": nq, "max_abs": float(np.abs(P).max())}
+        if args.emulation and n <= args.emulation_grid:
+            from projection_emulation import ProjectionEmulation
+            em = ProjectionEmulation(mesh.p, mesh.t)
+            vals = np.stack([np.array([m["Ex_dofs"] for m in modes]), np.array([m["Ey_dofs"] for m in modes])])
+            t0 = time.perf_counter()
+            ref = em.project(vals, True, xf, yf)
+            entry["emulation_s"] = time.perf_counter() - t0
+            entry["emulation_excess"] = float((np.abs(P - ref) / em.tolerance(vals, True, xf, yf)).max())
+        res["project"][f"{n}x{n}"] = entry
+
+
+def finish(args, res):
     line = json.dumps(res)
     print(line)
     if args.out:
