@@ -74,10 +74,12 @@ class ArpackLikeNoConvergence(_ArpackNoConvergence, RuntimeError):
     """Raised when the Lanczos iteration does not converge.  The reference lets SciPy's
     ``ArpackNoConvergence`` propagate out of ``eigsh`` (``solver_fem.py:197``), so this IS one: a caller's
     ``except ArpackNoConvergence`` catches it, and ``.eigenvalues`` / ``.eigenvectors`` hold the current Ritz
-    pairs as SciPy's do (``.eigenvectors`` here is the device tensor, row c = vector c)."""
+    pairs as SciPy's do (``.eigenvectors`` here is the device tensor, row c = vector c); ``.stats`` is the stats
+    dictionary a converged call returns."""
 
-    def __init__(self, msg, eigenvalues=None, eigenvectors=None):
+    def __init__(self, msg, eigenvalues=None, eigenvectors=None, stats=None):
         _ArpackNoConvergence.__init__(self, msg, eigenvalues, eigenvectors)
+        self.stats = stats
 
 
 _lib = None
@@ -468,7 +470,7 @@ class Context:
         st = {"nconv": int(stats[0]), "n_opinv": int(stats[1]), "restarts": int(stats[2]), "max_rel_res": float(stats[3]),
               "n_block_solves": int(stats[4])}       # 0: single-vector recurrence was used
         if rc == PLFEM_ENOCONV:
-            raise ArpackLikeNoConvergence(self._lib.plfem_last_error(self._h).decode(), evals, evecs)
+            raise ArpackLikeNoConvergence(self._lib.plfem_last_error(self._h).decode(), evals, evecs, st)
         self._check(rc, "plfem_lanczos_shift_invert")
         return evals, evecs, st
 
@@ -494,7 +496,7 @@ class Context:
         st = {name: (float(stats[i]) if name.endswith("_us") or "res" in name else int(stats[i])) for i, name in enumerate(SOLVE_STATS)}
         st["refined"] = bool(st["refined"])
         if rc == PLFEM_ENOCONV:
-            raise ArpackLikeNoConvergence(self._lib.plfem_last_error(self._h).decode(), evals, self.modes_dev())
+            raise ArpackLikeNoConvergence(self._lib.plfem_last_error(self._h).decode(), evals, self.modes_dev(), st)
         self._check(rc, "plfem_solve_modes")
         return evals, post, float(frac.value), resid, st
 

@@ -669,13 +669,16 @@ struct ThickRestart {
   }
 
   // thick restart of mm columns: keep the k wanted pairs plus some of the next ones (ARPACK: kev + min(nconv, np/2)),
-  // followed by the residual block; pk = the columns kept
+  // followed by the residual block; pk = the columns kept.  The room left for two more blocks never costs a wanted pair:
+  // at least min(k, mm - P) columns stay (ncv = k + 1 on the single-vector driver would otherwise keep k - 1 columns at
+  // every restart and never converge; the block driver's dispatch has m >= k + 3 P, so its pk is unchanged)
   int restart(int mm, int& pk) {
     const int64_t n = c->n2;
     hipStream_t st = c->stream;
     pk = k + std::min(nconv, (mm - k) / 2);
     pk = std::max(pk, k + (mm - k) / 4);
     pk = std::min(pk, mm - 2 * P);
+    pk = std::max(pk, std::min(k, mm - P));
     for (int q = 0; q < pk; ++q) std::memcpy(hH + (size_t)q * mm, &Svec[(size_t)order[q] * mm], sizeof(double) * mm);
     HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * mm * pk, hipMemcpyHostToDevice, st));
     plfem::launch_rotate(c, c->d_V, mm, c->d_S, mm, pk, c->d_V2);
@@ -701,15 +704,31 @@ struct ThickRestart {
     std::vector<double> lam(mm);
     for (int i = 0; i < mm; ++i) lam[i] = sigma + 1.0 / theta[i];
     std::sort(want.begin(), want.end(), [&](int a, int b) { return lam[a] < lam[b]; });
+    // Converged pairs are purified as ARPACK purifies them in shift-invert mode: x + V[:, mm:mm+P] (R_m s[mm-P:mm]) / theta
+    // = OP x / theta, one step of inverse iteration at the cost of P more rows of the rotation.  The correction is of the
+    // size of tol and B-orthogonal to the basis; it damps the components of x far from sigma, which the stopping test on OP
+    // barely sees and which dominate the residual A x - lambda B x of the pencil (about 100 times smaller afterwards).
+    // An unconverged call returns the plain Ritz vectors; so does an exhausted Krylov space (a zero on the diagonal of R_m),
+    // whose residual block is no vector.
+    bool purify = nconv >= k;
+    for (int a = 0; a < P; ++a) purify = purify && T[(size_t)(mm - P + a) * ld + (mm + a)] > 0.0;
+    const int rows = purify ? mm + P : mm;
     for (int q = 0; q < k; ++q) {
-      evals_host[q] = lam[want[q]];
-      std::memcpy(hH + (size_t)q * mm, &Svec[(size_t)want[q] * mm], sizeof(double) * mm);
+      const int id = want[q];
+      evals_host[q] = lam[id];
+      double* s = hH + (size_t)q * rows;
+      std::memcpy(s, &Svec[(size_t)id * mm], sizeof(double) * mm);
+      for (int a = 0; a < rows - mm; ++a) {
+        double v = 0.0;
+        for (int b = a; b < P; ++b) v += T[(size_t)(mm - P + b) * ld + (mm + a)] * Svec[(size_t)id * mm + (mm - P + b)];
+        s[mm + a] = v / theta[id];
+      }
     }
-    HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * mm * k, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_S, hH, sizeof(double) * rows * k, hipMemcpyHostToDevice, st));
     if (!evecs_dev) evecs_dev = c->d_V2;            // (idle since the last restart, if any)
     c->modes_dev = evecs_dev;
     c->modes_k = k;
-    plfem::launch_rotate(c, c->d_V, mm, c->d_S, mm, k, evecs_dev);
+    plfem::launch_rotate(c, c->d_V, rows, c->d_S, rows, k, evecs_dev);
     HIP_TRY(c, phase_end(c, plfem::PH_LANCZOS));
     TRY(check_launch(c, "ritz rotation"));
     if (!c->defer_sync) HIP_TRY(c, hipStreamSynchronize(st));   // (plfem_solve_modes: its one synchronisation comes later)
@@ -906,6 +925,9 @@ static int lanczos_block(plfem_ctx* c, int k, int ncv, double tol, int maxiter, 
 
 // evecs_dev == nullptr: the vectors go into the context's own buffer (the idle restart double buffer d_V2; see
 // plfem_solve_modes / plfem_modes_dev)
+// The single-vector driver does not resolve eigenvalues closer together than its tolerance: a one-vector Krylov space holds
+// one direction of such a cluster, so the call can converge on a set that misses copies and holds pairs further from sigma
+// in their place (ARPACK shares this limit).  The block driver finds up to BLOCK_P copies.
 static int lanczos_run(plfem_ctx* c, int32_t k, int32_t ncv, double tol, int32_t maxiter,
                        double sigma, double* evals_host, double* evecs_dev, double* stats_host) {
   if (!c || !evals_host) return PLFEM_EINVAL;

@@ -1,6 +1,8 @@
 """Host references of the device kernels of the Lanczos drivers (csrc/kernels_lanczos.hip and the block SpMVs of
 csrc/kernels_assembly.hip), restated in np.longdouble from the kernels' definitions, with the error bounds the GPU tests
-hold them to and the mutation margins that show those tests would catch the cheapest plausible kernel mistakes.
+hold them to and the mutation margins that show those tests would catch the cheapest plausible kernel mistakes.  Below
+them, the two drivers themselves restated as one float64 function (lanczos_reference, with plantable driver mistakes), what
+the driver tests measure on the state after a restart (restart_state) and the dense references of a converged solve.
 
 Layouts (include/plfem.h): vectors have n2 = dpn N entries, component-major; a block of P vectors is an (n2, P) array;
 the interleaved copy of a block is wil[(node dpn + component) P + q]; the front order of the sweeps puts component c of
@@ -461,3 +463,281 @@ def residuals(pencil, lam, V):
     BV, _ = pencil.apply("B", V)
     R = AV - L(lam)[None, :] * BV
     return np.sqrt((R ** 2).sum(axis=0) / (AV ** 2).sum(axis=0))
+
+
+# ---- the two drivers as one float64 function ---------------------------------------------------------------------------
+RES_FLOOR = 3.7e-11         # floor of |theta| in the relative residual (ThickRestart::count_converged)
+MISTAKES = ("residual_at_pk_plus_1", "first_step_two_blocks", "rotation_unsorted", "theta_not_written", "keep_k_minus_1")
+# the first-cycle numbers of test_first_cycle_basis_and_projected_matrix: no post-restart tolerance goes below them
+# (bv_kept, bv_new: |BV - B V| in units of that test's bound 4 GAMMA u |B| |V| + 64 u |B V|, so 1)
+FIRST_CYCLE_TOL = {"orth": 1e-12, "relation": 1e-9, "symmetry": 1e-9, "outside_band": 1e-10, "bv_kept": 1.0, "bv_new": 1.0}
+STATE_KEYS = ("orth", "relation", "symmetry", "outside_band", "bv_kept", "bv_new")
+STATE_FACTOR = 10.0         # the GPU gets this many times what the float64 restatement shows (start block, summation orders)
+
+
+class ShiftInvert:
+    """OP = (A - sigma B)^-1 B on full-length vectors through SuperLU on the live rows (dead rows give 0)."""
+
+    def __init__(self, A, B, sigma, live=None):
+        import scipy.sparse as sp
+        import scipy.sparse.linalg as spla
+        self.B = sp.csr_matrix(B)
+        self.n = self.B.shape[0]
+        self.sigma = float(sigma)
+        self.live = np.ones(self.n, dtype=bool) if live is None else np.asarray(live, dtype=bool)
+        K = (sp.csr_matrix(A) - self.sigma * self.B).tocsc()[self.live][:, self.live]
+        self.lu = spla.splu(K.tocsc())
+
+    def __call__(self, X):
+        X = np.asarray(X, dtype=np.float64)
+        Y = np.zeros_like(X)
+        Y[self.live] = self.lu.solve(np.ascontiguousarray(np.asarray(self.B @ X)[self.live]))
+        return Y
+
+
+def restart_pk(P, k, mm, nconv, mistake=None):
+    """Columns ThickRestart::restart keeps: the k wanted pairs plus some of the next ones, leaving room for two blocks, but
+    never fewer than min(k, mm - P)."""
+    if mistake == "keep_k_minus_1":
+        return k - 1
+    pk = k + min(nconv, (mm - k) // 2)
+    pk = max(pk, k + (mm - k) // 4)
+    pk = min(pk, mm - 2 * P)
+    return max(pk, min(k, mm - P))
+
+
+def ritz_count(T, P, k, mm, tol):
+    """Ritz pairs of the first mm columns (upper triangle of T authoritative) by decreasing |theta|, and the converged
+    wanted ones: || R_m s[mm-P:mm] || <= tol max(|theta|, RES_FLOOR).  Returns theta, S, order, nconv, max_rel_res."""
+    Tm = np.triu(T[:mm, :mm])
+    Tm = Tm + np.triu(Tm, 1).T
+    theta, S = np.linalg.eigh(Tm)
+    order = np.argsort(-np.abs(theta), kind="stable")
+    Rm = np.triu(T[mm:mm + P, mm - P:mm])
+    nconv, worst = 0, 0.0
+    for q in range(min(k, mm)):
+        i = order[q]
+        rel = np.linalg.norm(Rm @ S[mm - P:mm, i]) / max(abs(theta[i]), RES_FLOOR)
+        worst = max(worst, rel)
+        nconv += rel <= tol
+    return theta, S, order, int(nconv), float(worst)
+
+
+def lanczos_reference(P, op, k, ncv, tol, maxiter, V0, mistake=None, max_ncv=None, purify=True):
+    """Thick-restart Lanczos of OP = op (a ShiftInvert) in the B inner product as csrc/api_device.hip runs it, in float64:
+    P = 1 the single-vector driver (m = ncv columns, tested for convergence when the basis is full), P = BLOCK_P the block
+    driver (m = ncv rounded up to a multiple of P, or down under max_ncv; tested after every step once mm >= k + P).
+    CGS2 over the whole basis, CholQR of the new block; the pipelining and the held step are scheduling and left out.
+    ``mistake`` plants one of MISTAKES.  V0: (n, P) start block (pushed through OP once, as the drivers do).
+    B V is kept as the drivers keep it: (B W) R^-1 for a new block, rotated with V at a restart, never recomputed.
+    The vectors of a converged run are purified as ThickRestart::finish purifies them (one step of inverse iteration:
+    x + V[:, mm:mm+P] (R_m s[mm-P:mm]) / theta = OP x / theta); purify=False returns the plain Ritz vectors.
+    Returns a dict: lam (the k wanted values, ascending), X (their vectors), V and BV (n, m + P + 1), T (the host's projected
+    matrix, ld = m + P), Hcols (what the device buffer holds: the columns before the last pk zero), pks, mm, nconv,
+    restarts, n_op, max_rel_res."""
+    assert mistake in (None,) + MISTAKES
+    B, n = op.B, op.n
+    m = ncv if P == 1 else -(-ncv // P) * P
+    if max_ncv is not None and m > max_ncv:
+        m = (max_ncv // P) * P
+    ld = m + P
+    V = np.zeros((n, ld + 1))
+    T = np.zeros((ld, ld))
+
+    BV = np.zeros((n, ld + 1))
+
+    def cholqr(W):
+        BW = np.asarray(B @ W)
+        R = np.linalg.cholesky(W.T @ BW).T
+        return np.linalg.solve(R.T, W.T).T, np.linalg.solve(R.T, BW.T).T, R
+
+    V[:, :P], BV[:, :P], _ = cholqr(op(np.asarray(V0, dtype=np.float64).reshape(n, P)))
+    n_op = P
+    c0, cycle_start, pks, restarts = 0, -1, [], 0
+    while True:
+        mm, done = c0, False
+        while c0 + P <= m:
+            nc = c0 + P
+            W = op(V[:, c0:nc])
+            n_op += P
+            lo = max(0, nc - 2 * P) if (mistake == "first_step_two_blocks" and c0 == cycle_start) else 0
+            H = np.zeros((nc, P))
+            for _ in range(2):
+                h = BV[:, lo:nc].T @ W
+                W = W - V[:, lo:nc] @ h
+                H[lo:] += h
+            T[:nc, c0:nc] = H
+            V[:, nc:nc + P], BV[:, nc:nc + P], T[nc:nc + P, c0:nc] = cholqr(W)
+            c0 = mm = nc
+            if P > 1 and mm >= k + P and c0 + P <= m:
+                theta, S, order, nconv, worst = ritz_count(T, P, k, mm, tol)
+                if nconv >= k:
+                    done = True
+                    break
+        if not done:
+            theta, S, order, nconv, worst = ritz_count(T, P, k, mm, tol)
+        if nconv >= k or restarts >= maxiter:
+            break
+        pk = restart_pk(P, k, mm, nconv, mistake)
+        keep = np.arange(pk) if mistake == "rotation_unsorted" else order[:pk]
+        at = pk + 1 if mistake == "residual_at_pk_plus_1" else pk
+        for X in (V, BV):
+            Xn = np.zeros_like(X)
+            Xn[:, :pk] = X[:, :mm] @ S[:, keep]
+            if at != pk:
+                Xn[:, pk] = X[:, pk]            # what the double buffer held there: a unit vector of an earlier basis
+            Xn[:, at:at + P] = X[:, mm:mm + P]
+            X[:] = Xn
+        T[:] = 0.0
+        if mistake != "theta_not_written":
+            T[np.arange(pk), np.arange(pk)] = theta[order[:pk]]
+        pks.append(pk)
+        restarts += 1
+        c0 = cycle_start = pk
+    want = order[:k]
+    lam = op.sigma + 1.0 / theta[want]
+    o = np.argsort(lam)
+    Hcols = T.copy()
+    if pks:
+        Hcols[:, :pks[-1]] = 0.0
+    X = V[:, :mm] @ S[:, want[o]]
+    Rm = np.triu(T[mm:mm + P, mm - P:mm])
+    if purify and nconv >= k and (np.diag(Rm) > 0).all():
+        X = X + V[:, mm:mm + P] @ ((Rm @ S[mm - P:mm, want[o]]) / theta[want[o]])
+    return {"lam": lam[o], "X": X, "V": V, "BV": BV, "T": T, "Hcols": Hcols, "pks": pks, "mm": mm, "m": m,
+            "nconv": nconv, "restarts": restarts, "n_op": n_op, "max_rel_res": worst}
+
+
+def restart_state(V, Hcols, P, k, m, op, BV=None):
+    """What the tests of the state after a restart measure on the basis V (n, >= m + P) and the device's projected columns
+    Hcols (ld, ld), ld = m + P, T[i, j] = Hcols[i, j]: a dict with
+    pk, mm        the first non-zero column and the columns the last cycle filled;
+    structure     names of the exact properties that fail (pk range, a gap in the written columns, an R block not upper
+                  triangular with a positive diagonal, a written entry below an R block, a zero in rows 0 .. pk of the
+                  first block after the restart);
+    orth          max |V^T B V - I| over the mm + P columns;
+    relation      || OP V_mm - V_{mm+P} T || / || OP V_mm ||, T completed in the kept columns by symmetry (rows pk .. pk + P)
+                  and the Rayleigh quotients v_q^T B OP v_q;
+    symmetry      max |T[c0-P:c0, c0:c0+P] - R^T| / max |T| over the blocks after the first;
+    outside_band  max |T[:c0-P, c0:c0+P]| / max |T| over the same blocks;
+    bv_kept, bv_new  (with BV) the largest |BV - B V| over the live rows in units of 4 GAMMA u |B| |V| + 64 u |B V|, the bound of
+                  the first-cycle test, over the kept columns (rotated with V, not recomputed: where a Ritz vector is small
+                  next to the basis vectors it was combined from, the rotation's own rounding u |BV| |S| exceeds a bound
+                  made of |B| |V| of the result) and over the columns from pk on (products of this and the last cycle)."""
+    ld = m + P
+    Hc = np.asarray(Hcols, dtype=np.float64)[:ld, :ld]
+    nzcol = np.nonzero(np.any(Hc != 0, axis=0))[0]
+    bad = []
+    pk = int(nzcol[0]) if nzcol.size else 0
+    if not (nzcol.size and k <= pk <= m - 2 * P):
+        return dict({q: np.inf for q in STATE_KEYS}, pk=pk, mm=0, structure=["pk_range"])
+    mm = pk + P * ((m - pk) // P)
+    if not np.array_equal(nzcol, np.arange(pk, mm)):
+        bad.append("written_columns")
+    B = op.B
+    Vc = np.asarray(V, dtype=np.float64)[:, :mm + P]
+    orth = float(np.abs(Vc.T @ (B @ Vc) - np.eye(mm + P)).max())
+    OPV = op(Vc[:, :mm])
+    T = Hc[:mm + P, :mm].copy()
+    T[pk:pk + P, :pk] = Hc[:pk, pk:pk + P].T
+    T[np.arange(pk), np.arange(pk)] = np.einsum("ij,ij->j", Vc[:, :pk], np.asarray(B @ OPV[:, :pk]))
+    relation = float(np.linalg.norm(OPV - Vc @ T) / np.linalg.norm(OPV))
+    Tn = float(np.abs(T).max())
+    if not (Hc[:pk + P, pk:pk + P] != 0).all():
+        bad.append("first_block_full")
+    sym = out = 0.0
+    for c0 in range(pk, mm, P):
+        R = Hc[c0 + P:c0 + 2 * P, c0:c0 + P]
+        if not (np.array_equal(R, np.triu(R)) and (np.diag(R) > 0).all()):
+            bad.append(f"R_upper_positive@{c0}")
+        if (Hc[c0 + 2 * P:, c0:c0 + P] != 0).any():
+            bad.append(f"below_R@{c0}")
+        if c0 > pk:
+            sym = max(sym, float(np.abs(Hc[c0 - P:c0, c0:c0 + P] - Hc[c0:c0 + P, c0 - P:c0].T).max()) / Tn)
+            out = max(out, float(np.abs(Hc[:c0 - P, c0:c0 + P]).max()) / Tn)
+    res = {"pk": pk, "mm": mm, "structure": bad, "orth": orth, "relation": relation, "symmetry": sym, "outside_band": out,
+           "bv_kept": 0.0, "bv_new": 0.0}
+    if BV is not None:
+        ref = np.asarray(B @ Vc)
+        bound = 4 * GAMMA * U * np.asarray(abs(B) @ np.abs(Vc)) + 64 * U * np.abs(ref)
+        d = np.abs(np.asarray(BV, dtype=np.float64)[:, :mm + P] - ref)[op.live]
+        if not np.isfinite(d).all():
+            bad.append("BV_finite")
+        ratio = np.where(d > 0, d / np.maximum(bound[op.live], 1e-300), 0.0)
+        res["bv_kept"], res["bv_new"] = float(ratio[:, :pk].max()), float(ratio[:, pk:].max())
+    return res
+
+
+def state_tolerances(ref_state):
+    """STATE_FACTOR times what the restatement shows on the same pencil, never below the first-cycle numbers."""
+    return {q: max(STATE_FACTOR * ref_state[q], FIRST_CYCLE_TOL[q]) for q in STATE_KEYS}
+
+
+def state_vector(st):
+    """The measured quantities and the count of failed exact properties as one vector (for margins / assert_margins; the
+    count has a zero bound: any failure is an infinite margin)."""
+    return np.array([min(st[q], 1e200) for q in STATE_KEYS] + [float(len(st["structure"]))])
+
+
+# ---- dense references of a converged solve -----------------------------------------------------------------------------
+def triple_mesh(p, t, cores, shifts=(0.0, 2.0, 4.0)):
+    """Copies of one mesh (p (2, nv), t (3, ne)) shifted in x, node numbers offset, the cores shifted along: a block
+    diagonal pencil whose every eigenvalue appears len(shifts) times up to the rounding of the shifted coordinates."""
+    p, t, cores = np.asarray(p, dtype=np.float64), np.asarray(t), np.asarray(cores, dtype=np.float64).reshape(-1, 3)
+    nv = p.shape[1]
+    ps = np.hstack([p + np.array([[s], [0.0]]) for s in shifts])
+    ts = np.hstack([t + i * nv for i in range(len(shifts))]).astype(t.dtype)
+    cs = np.vstack([cores + np.array([s, 0.0, 0.0]) for s in shifts])
+    return ps, ts, cs
+
+
+def dense_reference(A, B, live, sigma):
+    """All eigenpairs of the live rows of the pencil, one scipy.linalg.eigh per connected component of the pattern, sorted
+    by decreasing |1 / (lambda - sigma)|: (lam, X (n, nlive), ncomponents); X is B-orthonormal, dead rows 0."""
+    import scipy.linalg as sl
+    import scipy.sparse as sp
+    from scipy.sparse.csgraph import connected_components
+    live = np.nonzero(np.asarray(live, dtype=bool))[0]
+    Al = sp.csr_matrix(A)[live][:, live]
+    Bl = sp.csr_matrix(B)[live][:, live]
+    ncomp, lab = connected_components(abs(Al) + abs(Bl), directed=False)
+    lam, X = [], np.zeros((A.shape[0], live.size))
+    at = 0
+    for cpt in range(ncomp):
+        idx = np.nonzero(lab == cpt)[0]
+        a = Al[idx][:, idx].toarray()
+        b = Bl[idx][:, idx].toarray()
+        w, x = sl.eigh((a + a.T) / 2, (b + b.T) / 2)
+        lam.append(w)
+        X[live[idx], at:at + w.size] = x
+        at += w.size
+    lam = np.concatenate(lam)
+    o = np.argsort(-np.abs(1.0 / (lam - sigma)), kind="stable")
+    return lam[o], X[:, o], ncomp
+
+
+def theta_bound(theta_ref, tol):
+    """|theta - theta_ref| <= 2 tol |theta_ref| + 64 u max |theta|: the residual bounds a Ritz value's error for a symmetric
+    operator (the driver's contract, factor 2), plus rounding."""
+    theta_ref = np.asarray(theta_ref, dtype=np.float64)
+    return 2 * tol * np.abs(theta_ref) + 64 * U * np.abs(theta_ref).max()
+
+
+def wanted_interval(lam_sorted_all, lam_wanted_sorted):
+    """First index of the wanted values in the ascending spectrum (they are an interval of it: the nearest to sigma; equal
+    copies of a cut cluster at its lower end make the place of the smallest value ambiguous, so every candidate is tried)."""
+    lam, w = np.asarray(lam_sorted_all), np.asarray(lam_wanted_sorted)
+    for lo in range(int(np.searchsorted(lam, w[0], "left")), int(np.searchsorted(lam, w[0], "right"))):
+        if np.array_equal(lam[lo:lo + w.size], w):
+            return lo
+    raise AssertionError("the wanted values are no interval of the spectrum")
+
+
+def whole_clusters(lam_sorted_all, lo, hi, rel_gap):
+    """Boolean mask over [lo, hi) of an ascending spectrum: True where the cluster of the value (consecutive values closer
+    than rel_gap |lambda|, the rule of oracle/compare.py) lies wholly inside [lo, hi)."""
+    lam = np.asarray(lam_sorted_all)
+    close = np.abs(np.diff(lam)) < rel_gap * np.abs(lam[1:])         # close[i]: lam[i] and lam[i + 1] in one cluster
+    cid = np.concatenate([[0], np.cumsum(~close)])
+    inside = (cid >= (cid[lo - 1] + 1 if lo > 0 else 0)) & (cid <= (cid[hi] - 1 if hi < lam.size else cid[-1]))
+    return inside[lo:hi]

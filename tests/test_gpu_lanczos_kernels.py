@@ -6,109 +6,15 @@ rotation and its LDS chunking, k mod 4 of the per-mode kernels, and enough chunk
 test asserts its shape property and that its inputs make each cheap kernel mistake (a tail row dropped, the last chunk
 counted twice, columns shifted, coefficients transposed, ...) exceed the tolerance at least 100-fold.  A composed check
 reads back the basis and the projected matrix of one Lanczos cycle of each driver form."""
-import functools
-
 import numpy as np
 import pytest
 
 import lanczos_emulation as le
-from pl_fem_vectoriel_amd import _native
-from pl_fem_vectoriel_amd.mesh import generate_mesh, unit_square_mesh
-from pl_fem_vectoriel_amd.solver_fem import _core_table
+from lanczos_cases import CASES, K0, cases  # noqa: F401  (cases: the module-scoped fixture of the contexts)
 
 pytestmark = pytest.mark.gpu
 P = le.BLOCK_P
-SQUARE_CORES = np.array([[0.5, 0.5, 0.2937], [0.21, 0.77, 0.1113]])      # no DOF of the squares on a circle
-K0 = 2 * np.pi / 1.55
-NCOLS = (1, 2, 3, 4, 5, 15, 16, 17, 33, 129)            # + max_ncv + P
-NCOLS_LARGE = (1, 5, 17, 33)
 GAP = 37                                                # NaN-filled gap between the columns of a block
-
-
-class Case:
-    """A context whose n2 reaches a tail, its pencil and its shape property."""
-
-    def __init__(self, name, device, geometry):
-        import torch
-        self.torch, self.name = torch, name
-        if name == "c1":
-            mesh = generate_mesh(geometry, 1.0, 1)
-            self.sym = _native.Symbolic(mesh.p, mesh.t)
-            self.ctx = _native.Context(self.sym, device, max_ncv=65)
-            self.ctx.assemble(_core_table(geometry), geometry.n_core ** 2, geometry.n_clad ** 2, geometry.k0, 1.0)
-            self.cores = _core_table(geometry)
-        else:
-            n, dpn = {"sca16": (16, 1), "vec16": (16, 2), "sca255": (255, 1)}[name]
-            mesh = unit_square_mesh(n)
-            self.sym = _native.Symbolic(mesh.p, mesh.t, dofs_per_node=dpn, dirichlet=dpn == 2)
-            self.ctx = _native.Context(self.sym, device, max_ncv=65 if n == 255 else 160)
-            self.cores = SQUARE_CORES
-            if dpn == 2:
-                self.ctx.assemble(SQUARE_CORES, 1.535 ** 2, 1.0, K0, 1.0)
-            else:
-                self.ctx.assemble_scalar(SQUARE_CORES, 1.535 ** 2, 1.0, K0)
-        self.N, self.dpn, self.n2 = self.sym.N, self.sym.dofs_per_node, self.ctx.n2
-        self.pencil = le.Pencil(self.sym, self.ctx)
-        self.front = le.FrontOrder(self.sym)
-        self.ncols = (NCOLS if name in ("sca16", "vec16") else NCOLS_LARGE) + (self.ctx.max_ncv + P,)
-        self.rng = np.random.default_rng(CASES.index(name) + 11)
-        self.assert_shape()
-
-    def assert_shape(self):
-        n2, tail = self.n2, self.n2 % le.PANEL_CHUNK
-        bm = self.sym.array("bmask")
-        if self.name == "sca16":
-            assert n2 == 1089 and tail == 65 and 64 < tail < 128 and not bm.any()
-        elif self.name == "vec16":
-            assert n2 == 2178 and tail == 130 and bm.any()
-        elif self.name == "sca255":
-            assert n2 == 261121 == 255 * 1024 + 1 and tail == 1
-            assert -(-n2 // le.PANEL_CHUNK) > 56 and -(-self.N * 8 // 256) > 448     # both unrolled loops run
-        else:
-            assert n2 == 181278 and tail == 30 and -(-self.N * 8 // 256) == 2833 and bm.any()
-
-    # -- device buffers
-    def dev(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).ravel()).cuda(self.ctx.device)
-
-    @staticmethod
-    def host(t):
-        return t.cpu().numpy().astype(np.float64)
-
-    def block(self, X, ld):
-        """(n2, q) -> flat columns ld apart, gaps NaN."""
-        n, q = X.shape
-        buf = np.full((q, ld), np.nan)
-        buf[:, :n] = X.T
-        return self.dev(buf)
-
-    def unblock(self, t, q, ld):
-        """flat columns ld apart -> (n2, q); asserts the gaps are still NaN."""
-        buf = self.host(t).reshape(q, ld)
-        assert np.isnan(buf[:, self.n2:]).all(), "a gap between the columns was written"
-        return buf[:, :self.n2].T.copy()
-
-    def random(self, *shape, live=False):
-        """O(1) random data (every row matters); live = Dirichlet rows zero, as in a Lanczos vector."""
-        X = self.rng.uniform(0.5, 1.5, shape) * self.rng.choice((-1.0, 1.0), shape)
-        if live:
-            X[~self.live_rows()] = 0.0
-        return X
-
-    def live_rows(self):
-        bm = self.sym.array("bmask").astype(bool)
-        return ~np.tile(bm, self.dpn)
-
-
-@pytest.fixture(scope="module")
-def cases(c1_geometry, gpu_device, built_library):
-    @functools.lru_cache(maxsize=None)
-    def get(name):
-        return Case(name, gpu_device, c1_geometry)
-    return get
-
-
-CASES = ("sca16", "vec16", "sca255", "c1")
 
 
 def ok(gpu, ref, bound, what):
