@@ -426,6 +426,11 @@ int plfem_debug_symeig_band(int32_t n, int32_t b, const double* a_host, int32_t 
 /* fault injection for the a-posteriori guard: from the next plfem_factor on, D^-1 of the root front is scaled by
  * 1 + value after every factorisation (0 = off) */
 int plfem_debug_set_perturb(plfem_ctx* ctx, double value);
+/* the write counterpart of plfem_debug_copy("elem"): elem_host replaces the element matrices of the context (every slot
+ * of every element, [i][j] row-major), the product's CSR gather rebuilds the assembled blocks from them, and the context
+ * is assembled and not factored: plfem_factor, plfem_spmv and the refinement inside the solves all see this pencil.
+ * Synchronises. */
+int plfem_debug_set_elements(plfem_ctx* ctx, const double* elem_host /* [ne][PLFEM_BLK_COUNT][36] */);
 /* plfem_debug_solve_block: BLOCK_P (4) right-hand sides in global order, column u at rhs_dev + u ldx, through the block
  * sweeps the block Lanczos driver runs (k_permute_in / k_permute_out and the P = 4 sweep kernels); the solutions go to
  * the same columns of x_dev.  refine_steps passes of block iterative refinement against the assembled K = A - sigma B

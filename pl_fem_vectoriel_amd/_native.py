@@ -47,7 +47,7 @@ SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", 
 TEST_HOOK_EXPORTS = ("plfem_debug_factor_until", "plfem_debug_copy", "plfem_debug_symeig", "plfem_debug_symeig_band",
                      "plfem_debug_set_perturb", "plfem_debug_solve_block", "plfem_debug_level_plan", "plfem_debug_panel",
                      "plfem_debug_scale_store", "plfem_debug_first_pass", "plfem_debug_spmv_block", "plfem_debug_chol",
-                     "plfem_debug_block_scale", "plfem_debug_rotate", "plfem_debug_start_field")
+                     "plfem_debug_block_scale", "plfem_debug_rotate", "plfem_debug_start_field", "plfem_debug_set_elements")
 # forms of plfem_debug_panel and plfem_debug_spmv_block (PLFEM_DEBUG_PANEL_* / PLFEM_DEBUG_SPMV_* of include/plfem.h)
 PANEL_FORMS = ("dot", "axpy", "dot_block", "axpy_block")
 SPMV_BLOCK_FORMS = ("b_block", "b_block_il", "b_block_il_gram", "a_block")
@@ -241,6 +241,7 @@ def load_test_hooks() -> ctypes.CDLL:
     h.plfem_debug_factor_until.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     h.plfem_debug_copy.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
     h.plfem_debug_set_perturb.argtypes = [ctypes.c_void_p, ctypes.c_double]
+    h.plfem_debug_set_elements.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     h.plfem_debug_solve_block.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32]
     h.plfem_debug_level_plan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     h.plfem_debug_symeig.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
@@ -544,6 +545,14 @@ class Context:
     def debug_set_perturb(self, value: float):
         """Fault injection: D^-1 of the root front scaled by ``1 + value`` after every factorisation (0 = off)."""
         self._check(load_test_hooks().plfem_debug_set_perturb(self._h, float(value)), "plfem_debug_set_perturb")
+
+    def debug_set_elements(self, elem: np.ndarray):
+        """The element matrices ``[ne][8][6][6]`` (slots of ``BLOCK_NAMES``) in place of the assembled ones, and the CSR
+        blocks gathered from them: the context is assembled with this pencil and not factored."""
+        elem = np.ascontiguousarray(elem, dtype=np.float64)
+        if elem.size != self.sym.ne * 8 * 36:
+            raise ValueError("debug_set_elements: need ne x 8 x 36 doubles")
+        self._check(load_test_hooks().plfem_debug_set_elements(self._h, _ptr(elem)), "plfem_debug_set_elements")
 
     def debug_solve_block(self, rhs, x, ldx: int, refine_steps: int = 0):
         """BLOCK_P right-hand sides (columns ``ldx`` apart in the flat device tensor ``rhs``) through the block sweeps into

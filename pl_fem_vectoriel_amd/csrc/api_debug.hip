@@ -79,6 +79,22 @@ extern "C" int plfem_debug_copy(plfem_ctx* c, const char* name, int64_t offset, 
   return PLFEM_OK;
 } catch (...) { return host_failure(c); }
 
+// The write counterpart of plfem_debug_copy("elem"): the tests' own element matrices in place of the assembled ones, then
+// the product's CSR gather, so that plfem_spmv and the refinement inside the solves see the pencil the factorisation sees.
+extern "C" int plfem_debug_set_elements(plfem_ctx* c, const double* elem_host) try {
+  if (!c || !elem_host) return PLFEM_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  TRY(wait_for_upload(c));              // (as plfem_factor: the gather reads the uploaded adjacency)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(c->d_elem, elem_host, sizeof(double) * (size_t)c->ne * plfem::ELEM_STRIDE, hipMemcpyHostToDevice));
+  plfem::launch_csr_gather(c);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  TRY(check_launch(c, "debug set elements"));
+  c->assembled = true;
+  c->factored = false;
+  return PLFEM_OK;
+} catch (...) { return host_failure(c); }
+
 // BLOCK_P right-hand sides (global order, columns ldx apart) through the block sweeps, then refine_steps passes of block
 // iterative refinement against the assembled K = A - sigma B (the block SpMVs of the Lanczos driver's refined solve).
 // The refinement's scratch is the first 3 BLOCK_P columns (ldx apart) of d_V2, as in the block Lanczos driver.

@@ -113,29 +113,60 @@ def assemble_front(T: FrontTree, f, Ke, S):
     return Fm
 
 
-def ldl_partial(Fm, s2, kinds=None):
+MISTAKES = ("rep_positive", "rmax_block", "rep_thr", "no_det_guard", "d2_uncounted")
+
+
+def ldl_partial(Fm, s2, kinds=None, log=None, mistake=None):
     """Partial block LDL^T of the first s2 pivots, node pair by node pair in the static order (local DOFs 2q, 2q+1, no
     permutation; kernels_front.hip): two scalar pivots (a, then c - b^2 / a) or one 2 x 2 pivot, whichever amplifies rounding
     errors less ((b / a)^2 against max|E|^2 / |det|).  Returns the storage the HIP path leaves in F: lower(F11) = L11^-1,
     upper(F11) = L11^-T, F21 = Z = L21 L11^-1, F12 = Z^T, F22 = S; and D^-1 as (diagonal, off-diagonal) per row.
     The elimination runs in panels of NB columns (the update of the trailing matrix is one product per panel, as on the
     device), so that fronts of a few thousand rows stay cheap.
-    kinds (a list, optional): gets (is_2x2, margin) per pair, margin = |lhs - rhs| / max(lhs, rhs) of the kind test."""
+    A vanishing pivot is replaced, not permuted away (pair_step / ldl_pivot_block): with rmax the largest entry the pair's
+    own two rows have in the nbk x nbk pivot block -- both triangles, as the block arrives at its block step, i.e. after
+    the updates of all earlier block steps and before any elimination inside it; the identity padding of a partial block
+    adds nothing to the rows of a pair, a padding node is the unit diagonal entry the assembly gave it --
+    thr = max(1e-13 rmax, 1e-300), rep = max(1e-8 rmax, 1e-300), and
+      "a":   the first scalar pivot a,        |a| < thr       -> +-rep
+      "d2":  the second one, d2 = c - g b,    |d2| < thr      -> +-rep
+      "det": the determinant of the 2 x 2 form, |det| < thr s -> +-rep s      (s = max|E|)
+    each with the sign of the value it replaces (+ for zero).
+    kinds (a list, optional): gets (is_2x2, margin) per pair, margin = |lhs - rhs| / max(lhs, rhs) of the kind test.
+    log (a list, optional): gets (pair, site, value, rmax) per replacement; its length is what the device counts.
+    mistake (one of MISTAKES, optional): a deliberately wrong rule, for the host tests that show the GPU tests would see it."""
+    assert mistake is None or mistake in MISTAKES
     F = Fm.copy()
     Dinv = np.zeros((s2, 2), dtype=F.dtype)
+
+    def replaced(value, thr, rep, q, site, rm):
+        """value, or its replacement (logged) where it vanishes against thr."""
+        if abs(value) >= thr:
+            return value
+        if log is not None and not (mistake == "d2_uncounted" and site == "d2"):
+            log.append((q, site, value, rm))
+        return rep if mistake == "rep_positive" or not value < 0 else -rep
+
     for k0 in range(0, s2, NB):
         k1 = min(k0 + NB, s2)
         Cp = np.zeros((F.shape[0] - k1, k1 - k0), dtype=F.dtype)           # the panel's columns below it, as they were eliminated
+        rowmax = np.abs(F[k0:k1, k0:k1]).max(axis=1)                       # of the block on arrival
+        if mistake == "rmax_block":
+            rowmax[:] = rowmax.max()
         for k in range(k0, k1, 2):
             a, b, c = F[k, k], F[k + 1, k], F[k + 1, k + 1]
             det = a * c - b * b
             s = max(abs(a), abs(b), abs(c))
+            rm = max(rowmax[k - k0], rowmax[k + 1 - k0])
+            thr, rep = max(1e-13 * rm, 1e-300), max(1e-8 * rm, 1e-300)
+            if mistake == "rep_thr":
+                rep = thr
             lhs, rhs = b * b * abs(det), a * a * s * s
             if kinds is not None:
                 kinds.append((bool(lhs > rhs), abs(lhs - rhs) / max(lhs, rhs, 1e-300)))
             if lhs <= rhs:
                 for j in (k, k + 1):                         # two steps of the scalar LDL^T
-                    d = F[j, j]
+                    d = replaced(F[j, j], thr, rep, k // 2, "a" if j == k else "d2", rm)
                     col = F[j + 1:, j].copy()
                     l = col / d
                     F[j + 1:, j + 1:k1] -= np.outer(l, col[:k1 - j - 1])
@@ -143,6 +174,8 @@ def ldl_partial(Fm, s2, kinds=None):
                     Cp[:, j - k0] = col[k1 - j - 1:]
                     Dinv[j] = (1.0 / d, 0.0)
             else:
+                if mistake != "no_det_guard":
+                    det = replaced(det, thr * s, rep * s, k // 2, "det", rm)
                 e11, e12, e22 = c / det, -b / det, a / det
                 Dinv[k] = (e11, e12)
                 Dinv[k + 1] = (e22, e12)
@@ -168,8 +201,9 @@ def ldl_partial(Fm, s2, kinds=None):
     return out, Dinv
 
 
-def factor(T: FrontTree, Ke, kinds=None):
-    """Every front, leaves first.  kinds (a dict, optional): front -> ldl_partial's (is_2x2, margin) list."""
+def factor(T: FrontTree, Ke, kinds=None, logs=None, mistake=None):
+    """Every front, leaves first.  kinds (a dict, optional): front -> ldl_partial's (is_2x2, margin) list; logs (a dict,
+    optional): front -> ldl_partial's replacement log (fronts without a replacement have no entry)."""
     Fs = [None] * T.nf
     Ds = [None] * T.nf
     S = [None] * T.nf
@@ -177,9 +211,12 @@ def factor(T: FrontTree, Ke, kinds=None):
         Fm = assemble_front(T, f, Ke, S)
         s2 = T.s2(f)
         k = [] if kinds is not None else None
-        Fs[f], Ds[f] = ldl_partial(Fm, s2, k)
+        lg = []
+        Fs[f], Ds[f] = ldl_partial(Fm, s2, k, lg, mistake)
         if kinds is not None:
             kinds[f] = k
+        if logs is not None and lg:
+            logs[f] = lg
         S[f] = Fs[f][s2:, s2:]
     return Fs, Ds
 

@@ -10,24 +10,14 @@ import scipy.sparse.linalg as spla
 
 import front_emulation as fe
 import operator_cases as oc
+from front_checks import BERR_FLOOR, FACTOR_RATIO, FACTOR_TOL, FWD_TOL, backward_error  # noqa: F401
+from front_checks import front_check as _front_check, owned_dofs, right_hand_sides
 from oracle import hfield, scalar
 from oracle.p2 import MeshTriLite, P2Basis
 from pl_fem_vectoriel_amd import _native
 from pl_fem_vectoriel_amd.solver_fem import _core_table, shift_estimate
 
 pytestmark = pytest.mark.gpu
-FACTOR_TOL = 1e-8       # per front, relative to the largest entry of the block (test_fronts_match_numpy_emulation)
-# ... or this many times the double-precision emulation's own error, where that is larger: on the ill-conditioned fronts
-# of the sliver mesh (c1_h10) the GPU's factor, built from explicit inverses of the pivot blocks, is 10-12 times further
-# from the extended-precision reference than the sequential elimination (the solve's backward error: 9.3 times)
-FACTOR_RATIO = 30.0
-BERR_FLOOR = 1e-14
-FWD_TOL = 1e-9
-
-
-def backward_error(K, x, b):
-    """Componentwise backward error max|K x - b| / max(|K| |x| + |b|)."""
-    return float(np.abs(K @ x - b).max() / (abs(K) @ np.abs(x) + np.abs(b)).max())
 
 
 class Operator:
@@ -75,32 +65,10 @@ class Operator:
 
     def _owned_dofs(self, f):
         """Global DOFs owned by front f (component-major vectors of length dpn N)."""
-        T = self.T
-        nodes = T.nodes(f)[:int(T.fs[f])]
-        nodes = nodes[nodes >= 0]
-        return np.concatenate([c * self.N + nodes for c in range(self.dpn)])
+        return owned_dofs(self.T, f, self.N)
 
     def _right_hand_sides(self):
-        rng = np.random.default_rng(7)
-        out = {}
-        for name in ("random", "random2"):
-            b = np.zeros(self.n2)
-            b[self.idx] = rng.standard_normal(len(self.idx))
-            out[name] = b
-        # supported on the owned DOFs of one leaf (the one with the most) only: travels up through every level
-        leaves = range(self.T.leaf0, self.T.nf)
-        leaf = max(leaves, key=lambda f: int(self.T.fs[f]))
-        b = np.zeros(self.n2)
-        d = self._owned_dofs(leaf)
-        b[d] = rng.standard_normal(len(d))
-        out["leaf"] = b
-        # supported on the root separator only: travels down through every level
-        b = np.zeros(self.n2)
-        d = self._owned_dofs(0)
-        b[d] = rng.standard_normal(len(d))
-        out["root"] = b
-        assert all(np.count_nonzero(v) for v in out.values())
-        return out
+        return right_hand_sides(self.T, self.idx, self.N)
 
     def dev(self, a):
         return self.torch.from_numpy(np.ascontiguousarray(a)).cuda(self.ctx.device)
@@ -210,18 +178,6 @@ def test_block_solve(operators, name):
     with pytest.raises(ValueError):
         op.ctx.debug_solve_block(bd, xd, n2 - 1)
     print(f"\n{name} P=4: backward error {worst:.2e} (emulation {op.emul_berr:.2e})")
-
-
-def _front_check(got, dbl, xp, what):
-    """A block of the GPU's factor against the extended-precision emulation: within FACTOR_TOL of the block's largest
-    entry, or within FACTOR_RATIO times the error of the double-precision emulation (ill-conditioned fronts)."""
-    if not got.size:
-        return
-    xp = xp.astype(np.float64)
-    scale = max(np.abs(xp).max(), 1e-300)
-    err = np.abs(got - xp).max() / scale
-    ref = np.abs(dbl - xp).max() / scale
-    assert err <= max(FACTOR_TOL, FACTOR_RATIO * ref), (what, err, ref)
 
 
 @pytest.mark.parametrize("name", FACTOR_IDS)
