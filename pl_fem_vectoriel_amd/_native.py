@@ -85,6 +85,37 @@ class ArpackLikeNoConvergence(_ArpackNoConvergence, RuntimeError):
 _lib = None
 _hooks = None
 
+# Every byte of device memory the library works in comes from the two helpers below.  None: uninitialised
+# (``torch.empty``; nothing else runs).  A float64 value: every buffer is first filled with that bit pattern -- the
+# test-suite's way of showing that no result depends on what the memory held before (tests/test_gpu_workspace_contents.py).
+SCRATCH_FILL = None
+
+
+def device_scratch(nbytes: int, tdev):
+    """A uint8 device tensor of at least ``nbytes`` bytes for the library to work in (context slab, locator memory,
+    work buffers).  With ``SCRATCH_FILL`` set the size is rounded up to 8 bytes and the whole buffer filled, the fill complete
+    on return."""
+    import torch
+    if SCRATCH_FILL is None:
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=tdev)
+    buf = torch.empty((int(nbytes) + 7) & ~7, dtype=torch.uint8, device=tdev)
+    buf.view(torch.float64).fill_(float(SCRATCH_FILL))
+    # The fill runs on torch's current stream; plfem_create sends the front-level index arrays on a non-blocking copy stream
+    # of its own, which waits for nothing: the fill must have completed before the buffer is handed out, or it could land
+    # on top of an upload.
+    torch.cuda.current_stream(tdev).synchronize()
+    return buf
+
+
+def device_output(shape, dtype, tdev):
+    """A device tensor a kernel of the library writes its result into (uninitialised, or pre-filled as above)."""
+    import torch
+    if SCRATCH_FILL is None:
+        return torch.empty(shape, dtype=dtype, device=tdev)
+    shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+    nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
+    return device_scratch(nbytes, tdev)[:nbytes].view(dtype).view(shape)
+
 
 def _tune_host_allocator(_force: bool = False) -> None:
     """Keep the host analysis out of the kernel's memory-map lock.
@@ -385,7 +416,7 @@ class Context:
         if rc != PLFEM_OK:
             raise ValueError(f"plfem_workspace_bytes failed ({rc})")
         t0 = time.perf_counter()
-        self.workspace = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=self.tdev)
+        self.workspace = device_scratch(int(need.value) + 256, self.tdev)
         self.t_workspace = time.perf_counter() - t0      # ~0 when the caching allocator recycles a block, ms for a hipMalloc
         base = self.workspace.data_ptr()
         aligned = (base + 255) & ~255
@@ -415,7 +446,7 @@ class Context:
         return c, c.shape[0]
 
     def empty(self, *shape):
-        return self.torch.empty(*shape, dtype=self.torch.float64, device=self.tdev)
+        return device_output(shape, self.torch.float64, self.tdev)
 
     # -- C-ABI calls ------------------------------------------------------------------------------
     def assemble(self, cores, eps_core, eps_clad, k0, alpha_p=1.0):
@@ -509,7 +540,7 @@ class Context:
         self._check(self._lib.plfem_modes_dev(self._h, ctypes.byref(ptr), ctypes.byref(k)), "plfem_modes_dev")
 
         class _View:
-            __cuda_array_interface__ = {"shape": (int(k.value), int(self.n2)), "typestr": "<f8", "data": (int(ptr.value), True),
+            __cuda_array_interface__ = {"shape": (int(k.value), int(self.n2)), "typestr": "<f8", "data": (int(ptr.value), False),
                                         "version": 2, "strides": None}
         return self.torch.as_tensor(_View(), device=self.tdev).clone()
 

@@ -155,7 +155,7 @@ class ModeFields:
         rc = lib.plfem_locator_bytes(self.sym._h, ctypes.byref(need))
         if rc != _native.PLFEM_OK:
             raise RuntimeError(f"plfem_locator_bytes failed ({rc})")
-        self._mem = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=self.tdev)
+        self._mem = _native.device_scratch(int(need.value) + 256, self.tdev)
         aligned = (self._mem.data_ptr() + 255) & ~255
         h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)
@@ -178,7 +178,7 @@ class ModeFields:
         ncomp, k, n = vals.shape
         with torch.cuda.stream(self.stream):
             src = torch.from_numpy(vals).to(self.tdev)
-            dst = torch.empty((ncomp, n, k), dtype=torch.float64, device=self.tdev)
+            dst = _native.device_output((ncomp, n, k), torch.float64, self.tdev)
             self._check(self._lib.plfem_stage_modes(self._loc, ncomp, k, n, ctypes.c_void_p(src.data_ptr()),
                                                     ctypes.c_void_p(dst.data_ptr())), "plfem_stage_modes")
         return dst, src
@@ -216,8 +216,8 @@ class ModeFields:
                 e = min(npts, s + chunk)
                 n = e - s
                 pd = torch.from_numpy(np.ascontiguousarray(pts[:, s:e])).to(self.tdev)
-                od = torch.empty((max(nout, 1), k, n), dtype=torch.float64, device=self.tdev)
-                ed = torch.empty(n, dtype=torch.int32, device=self.tdev)
+                od = _native.device_output((max(nout, 1), k, n), torch.float64, self.tdev)
+                ed = _native.device_output((n,), torch.int32, self.tdev)
                 self._check(self._lib.plfem_sample_fields(
                     self._loc, max(ncomp, 1), k, ctypes.c_void_p(staged.data_ptr() if staged is not None else 0),
                     1 if kind == "vectorial" else 0, ctypes.c_void_p(beta_d.data_ptr() if beta_d is not None else 0), n,
@@ -271,7 +271,7 @@ class ModeFields:
         if self._lib.plfem_gram_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
             raise ValueError(f"plfem_gram_work_bytes rejected ncomp = {ncomp}, k = {k}")
         staged, _src = self._stage(vals)
-        work = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=self.tdev)
+        work = _native.device_scratch(int(need.value) + 256, self.tdev)
         aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((len(names), k, k), dtype=np.float64)
         self._check(self._lib.plfem_mode_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
@@ -314,7 +314,7 @@ class ModeFields:
         if self._lib.plfem_quartic_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
             raise ValueError(f"plfem_quartic_work_bytes rejected ncomp = {ncomp}, k = {k}")
         staged, _src = self._stage(vals)
-        work = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=self.tdev)
+        work = _native.device_scratch(int(need.value) + 256, self.tdev)
         aligned = (work.data_ptr() + 255) & ~255
         npair = k * (k + 1) // 2
         out = np.empty((npair, npair), dtype=np.float64)
@@ -351,7 +351,7 @@ class ModeFields:
                 raise ValueError(f"plfem_project_work_bytes rejected ncomp = {ncomp}, k = {k}, la = {la}, lb = {n}")
             nbytes = max(nbytes, int(need.value))
         staged, _src = self._stage(vals)
-        work = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.tdev)
+        work = _native.device_scratch(nbytes + 256, self.tdev)
         aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((ncomp, k, lb, la), dtype=np.complex128)
         for s in range(0, lb, chunk):
@@ -425,7 +425,7 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
         k1, k2 = v1.shape[1], v2.shape[1]
         need = ctypes.c_int64(0)
         lib.plfem_overlap_work_bytes(k1, k2, ctypes.byref(need))
-        work = torch.empty(int(need.value) + 256, dtype=torch.uint8, device=f1.tdev)
+        work = _native.device_scratch(int(need.value) + 256, f1.tdev)
         aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((k1, k2), dtype=np.float64)
         f2.stream.synchronize()                 # (B's staging ran on B's stream; the overlap runs on A's)

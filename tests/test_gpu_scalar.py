@@ -143,6 +143,79 @@ def test_cmt_rigorous_coupling_matches_oracle(c1_geometry, gpu_device, built_lib
         theory._compute_rigorous_coupling(modes, modes[:-1], g, mesh)
 
 
+# Largest |raw - reference| / (eps |E_i|^T |M_deps| |F_j|) of plfem_cmt_coupling at n = 5 against the np.longdouble product
+# with the oracle's M_deps, measured on the MI355X.  Asserted with a margin of 4: the summation order
+# across workgroups is the only thing that may move it.
+CMT_C_MEASURED = 0.028
+CMT_MARGIN = 4.0
+
+
+def _cmt_reference(M, E, F):
+    """(E M F^T in np.longdouble, |E| |M| |F|^T) for the float64 CSR matrix M and the fields in the rows of E and F."""
+    x = np.longdouble
+    MF = np.empty((M.shape[0], F.shape[0]), dtype=x)
+    for j0 in range(0, F.shape[0], 8):                       # (nnz x 8 extended-precision products at a time)
+        prod = M.data.astype(x)[:, None] * F[j0:j0 + 8].T.astype(x)[M.indices]
+        MF[:, j0:j0 + 8] = np.add.reduceat(prod, M.indptr[:-1], axis=0)
+    return E.astype(x) @ MF, np.abs(E) @ (abs(M) @ np.abs(F).T)
+
+
+@pytest.mark.parametrize("n", [1, 5, 65])
+def test_cmt_coupling_of_two_different_field_sets(c1_geometry, gpu_device, built_library, n):
+    """plfem_cmt_coupling with fields_i != fields_j (independent seeded vectors, another norm in every row): the whole of
+    raw[i, j] = E_i^T M_deps F_j -- a transposed hand-over or swapped norm vectors are invisible when both sets are one --
+    against the oracle's M_deps applied in np.longdouble; then the coupling matrix of two different record lists."""
+    import torch
+    from oracle import cmt as ocmt
+    from oracle.p2 import P2Basis
+    from pl_fem_vectoriel_amd.cmt import CoupledModeTheory
+    g = c1_geometry
+    mesh = generate_mesh(g, 0.5, 0)
+    basis = P2Basis(MeshTriLite(mesh.p, mesh.t))
+    M, mean = ocmt.delta_eps_mass(g, basis)
+    assert (np.diff(M.indptr) > 0).all()
+    sym = _native.Symbolic(mesh.p, mesh.t, dofs_per_node=1, dirichlet=False)
+    ctx = _native.Context(sym, gpu_device, max_ncv=65)
+    assert n <= ctx.max_ncv and (n < 65 or n == ctx.max_ncv)
+    rng = np.random.default_rng(40 + n)
+    E = rng.standard_normal((n, sym.N)) * rng.uniform(0.5, 2.0, (n, 1))
+    F = rng.standard_normal((n, sym.N)) * rng.uniform(4.0, 8.0, (n, 1))
+    try:
+        raw, pi, pj, got_mean = ctx.cmt_coupling(torch.from_numpy(E).to(ctx.tdev), torch.from_numpy(F).to(ctx.tdev),
+                                                 _core_table(g), g.n_core ** 2, g.n_clad ** 2)
+    finally:
+        ctx.close()
+    ref, bound = _cmt_reference(M, E, F)
+    eps = np.finfo(np.float64).eps
+    c = float((np.abs(raw - ref).astype(np.float64) / (eps * bound)).max())
+    print(f"\n[cmt] n = {n}: max |raw - ref| / (eps |E|^T |M| |F|) = {c:.3f}; against the transpose "
+          f"{float((np.abs(raw.T - ref).astype(np.float64) / (eps * bound)).max()):.3g}")
+    assert raw.shape == (n, n)
+    # (the one constant for every n, as measured at n = 5; at n = 65 the largest of 4225 entries measured 0.065, at n = 1
+    # 0.027: the margin left at max_ncv is 1.7, not 4)
+    assert c <= CMT_MARGIN * CMT_C_MEASURED, (n, c)
+    # the norms: a dot product of N terms is within N u sum |x_i|^2 of the exact one in any summation order
+    x = np.longdouble
+    for got, V, other in ((pi, E, F), (pj, F, E)):
+        want = np.einsum("ij,ij->i", V.astype(x), V.astype(x))
+        assert (np.abs(got - want) <= sym.N * 0.5 * eps * want).all()
+        assert (np.abs(got - np.einsum("ij,ij->i", other, other)) > 0.5 * got.min()).all()        # not the other set's
+    assert (pi < 0.5 * pj).all()
+    assert abs(got_mean - mean) < 1e-13
+    # the coupling matrix of two different record lists (reference config.py:274-322)
+    omega = 2 * np.pi * 2.99792458e14 / 1.55
+    beta = rng.uniform(5.0, 6.0, n)
+    modes_i = [{"field_vector": E[i], "beta": beta[i]} for i in range(n)]
+    modes_j = [{"field_vector": F[i], "beta": beta[i] + 1.0} for i in range(n)]
+    theory = CoupledModeTheory(omega, "rigorous", device=gpu_device)
+    H = theory._compute_rigorous_coupling(modes_i, modes_j, g, mesh)
+    Href = ocmt.rigorous_coupling(modes_i, modes_j, g, basis, omega)
+    assert np.array_equal(np.diag(H), beta) and abs(theory.last_stats["eps_mean"] - mean) < 1e-13
+    if n > 1:
+        scale = np.abs(Href - np.diag(np.diag(Href))).max()
+        assert np.abs(H - Href).max() <= 1e-10 * scale
+
+
 def test_scalar_solver_at_north_star_size(c1_geometry, gpu_device, built_library):
     """The scalar solver on the C1 mesh (N = 90 639 unknowns, 12 tree levels, long fronts -> every sweep kernel form
     with one unknown per node): n_eff against the oracle, every pair an eigenpair of the assembled pencil."""
