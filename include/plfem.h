@@ -355,6 +355,35 @@ int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes);
 int plfem_mode_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
                      const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host);
 
+/* Per-core Grams: the Grams of k staged modes (staged and indexed as for plfem_mode_grams) over the quadrature points of
+ * the mesh's own six-point rule that each core disc owns (ncore in [1, 64]; every sum is over the points of core c of
+ * |det J| w_q (...)):
+ *   ncomp = 2: out_host[c][0..2][k][k] = Mx, My, K with Mx[m][n] = sum_c hx_m hx_n, My[m][n] = sum_c hy_m hy_n and K the
+ *     form of K_r of plfem_mode_grams; ncomp = 1: out_host[c][0][k][k] = M, M[m][n] = sum_c u_m u_n.
+ * Ownership: a point belongs to the highest-index core whose closed disc holds it (the reference's epsilon lets later
+ * cores overwrite earlier ones), decided with the arithmetic of the core test of plfem_assemble_hfield, so a point has
+ * an owner exactly where that test puts it in the core: sum_c (Mx_c + My_c) = M_core and sum_c K_c = K_core of
+ * plfem_mode_grams up to summation order.  Both pencils are linear in a per-region material constant, so with core c at
+ * eps_c the projected pencil is V^T A V = sum_c K_c / eps_c + K_clad / eps_clad + alpha_p D - k0^2 M (vectorial; B
+ * likewise from Mx_c + My_c) or S - k0^2 (sum_c eps_c M_c + eps_clad M_clad) (scalar).  count_host[c]: the quadrature
+ * points core c owns; a core that owns none gives exact zeros.
+ * Three passes: the owner of every point, per-core ascending point lists (counts, exclusive offsets, a stable fill: no
+ * atomic decides a position), the Gram kernel over (slice, 32-mode chunk pair, core), then the fixed-order second stage
+ * of plfem_field_overlap: the same bits on every run, whatever the work buffer held before.  Synchronises the
+ * locator's stream.
+ * work_dev: device scratch of plfem_core_gram_work_bytes(loc, ncomp, k, ncore) bytes, 256-byte aligned.  The bound, with
+ * P = ceil(k / 32)^2 chunk pairs and nout = 3 or 1: slices = min(256, ceil(6 ne / 16), 1024 / ncore), at least 1 and the
+ * same for every k (so that a subset of the modes gives the same bits), so the Gram kernel runs at most 1024 P
+ * workgroups and the scratch is ncore nout k^2 doubles, at most 1024 nout P partial blocks of 8 KiB (24 MiB per chunk
+ * pair for ncomp = 2: 24 MiB up to k = 32, 216 MiB at k = 70), and 2 x 6 ne + 128 int32.
+ * Argument errors (ncomp not 1 or 2, k < 1, ncore outside [1, 64], a null pointer, work_bytes too small) return
+ * PLFEM_EINVAL with the locator's last error set. */
+int plfem_core_gram_work_bytes(const plfem_locator* loc, int32_t ncomp, int32_t k, int32_t ncore, int64_t* bytes);
+int plfem_core_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                     const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes,
+                     double* out_host   /* [ncore][NOUT][k][k], NOUT = 3 (Mx, My, K) or 1 (M) */,
+                     int64_t* count_host /* [ncore] quadrature points owned */);
+
 /* Quartic mode-overlap tensor of k staged modes over the locator's mesh (the input of multimode nonlinear propagation:
  * f_ijkl, A_eff, gamma), on the 16-point degree-8 rule (products of four P2 fields are of degree 8).  Pairs i <= j are
  * numbered p(i,j) = i k - i (i - 1) / 2 + (j - i), np = k (k + 1) / 2.

@@ -4,7 +4,8 @@
 // the assembly's element forms, split by material region (k_mode_grams + k_overlap_reduce), and the quartic overlap of
 // products of four modes on a 16-point degree-8 rule (k_mode_quartic + k_quartic_reduce), and the projection of a mode
 // set on a family of analytic fields that separate in x and y -- plane waves and Gaussian beams -- on the same rule
-// (k_mode_project + k_project_reduce).
+// (k_mode_project + k_project_reduce), and the Grams of a mode set restricted to each core disc (k_core_owner,
+// k_core_count + k_core_fill, k_core_grams + k_overlap_reduce).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
@@ -303,6 +304,88 @@ __global__ __launch_bounds__(256) void k_overlap_reduce(int ka, int kb, int nblk
 constexpr int GT = 16;          // quadrature points per tile
 constexpr int GRAM_BLOCKS = 768;
 
+// What k_mode_grams and k_core_grams share.  gram_stage_point: lane `lane` of a tile stages quadrature point g (element
+// g / 6, point g % 6 of the six-point rule) -- det J, J^-1, the physical basis gradients, the weight |det J| w_q, the
+// staged rows -- or, when not `live`, a point that contributes nothing (rows -1, weight 0).  at_point(X, Y) is called for
+// a live point with the physical point as the assembly forms it.
+template <typename AtPoint>
+__device__ __forceinline__ void gram_stage_point(const LocArgs& L, int64_t g, bool live, int lane, double (&s_gx)[6][GT],
+                                                 double (&s_gy)[6][GT], int (&s_r)[6][GT], double (&s_w)[GT], int (&s_q)[GT],
+                                                 AtPoint&& at_point) {
+  double w = 0.0;
+  int q = 0;
+  for (int a = 0; a < 6; ++a) { s_r[a][lane] = -1; s_gx[a][lane] = 0.0; s_gy[a][lane] = 0.0; }
+  if (live) {
+    const int e = (int)(g / 6);
+    q = (int)(g % 6);
+    const P2Map M(L.edof, L.ne, L.pxy, L.pxy + L.nv, e);
+    const double xi = c_qx[q], eta = c_qy[q];
+    double det = M.det(), inv[4], X, Y, gx[6], gy[6];
+    M.inverse(det, inv);
+    M.point(xi, eta, X, Y);
+    at_point(X, Y);
+    w = fabs(det) * c_qw[q];
+    p2_grad(inv, xi, eta, gx, gy);
+    for (int a = 0; a < 6; ++a) {
+      s_gx[a][lane] = gx[a];
+      s_gy[a][lane] = gy[a];
+      s_r[a][lane] = dev_row(L, e, a);
+    }
+  }
+  s_w[lane] = w;
+  s_q[lane] = q;
+}
+
+// gram_features: all 256 lanes evaluate the features of every (staged point, mode of the row chunk i0 / of the column
+// chunk j0) into s_f -- plain for the row chunk, times the point's weight for the column chunk.  Consecutive lanes read
+// consecutive modes of one staged row.
+template <int NCOMP>
+__device__ __forceinline__ void gram_features(int tid, int k, int64_t nrows, const double* __restrict__ V, int i0, int j0,
+                                              const double (&s_gx)[6][GT], const double (&s_gy)[6][GT], const int (&s_r)[6][GT],
+                                              const double (&s_w)[GT], const int (&s_q)[GT],
+                                              double (&s_f)[2][3 * NCOMP][GT][OC]) {
+  constexpr int NF = 3 * NCOMP;
+  for (int idx = tid; idx < 2 * GT * OC; idx += 256) {
+    const int i = idx % OC, t = (idx / OC) % GT, side = idx / (OC * GT);
+    const int m = (side ? j0 : i0) + i;
+    double f[NF];
+#pragma unroll
+    for (int c = 0; c < NF; ++c) f[c] = 0.0;
+    if (m < k) {
+      double phi[6];
+      p2_phi(c_qx[s_q[t]], c_qy[s_q[t]], phi);
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const int r = s_r[a][t];
+        if (r < 0) continue;
+        const double gx = s_gx[a][t], gy = s_gy[a][t];
+#pragma unroll
+        for (int c = 0; c < NCOMP; ++c) {
+          const double v = V[(int64_t)c * nrows * k + (int64_t)r * k + m];
+          f[c] += phi[a] * v;
+          f[NCOMP + 2 * c] += gx * v;
+          f[NCOMP + 2 * c + 1] += gy * v;
+        }
+      }
+      if (side) {
+        const double w = s_w[t];
+#pragma unroll
+        for (int c = 0; c < NF; ++c) f[c] *= w;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NF; ++c) s_f[side][c][t][i] = f[c];
+  }
+}
+
+// acc[o] += s x a[p] (x) b[q], s = +-1, on a lane's 2 x 2 block.  Explicit fused multiply-adds: left to contraction, a
+// product that both region branches of k_mode_grams share is hoisted above the branch, and the compiler then fuses it
+// into some of the four accumulators of the 2 x 2 block and not others, so that an entry's rounding would depend on its
+// place in the block
+#define GRAM_ACC(o, p, q, s)                                                                        \
+      acc[o][0][0] = fma((s) * a[p].x, b[q].x, acc[o][0][0]); acc[o][0][1] = fma((s) * a[p].x, b[q].y, acc[o][0][1]); \
+      acc[o][1][0] = fma((s) * a[p].y, b[q].x, acc[o][1][0]); acc[o][1][1] = fma((s) * a[p].y, b[q].y, acc[o][1][1]);
+
 template <int NCOMP>
 __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
                                                     CoreTable cores, int ncore, int nchunk, double* __restrict__ partial) {
@@ -322,68 +405,16 @@ __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nr
   double acc[NOUT][2][2];
 #pragma unroll
   for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
-  const double* px = L.pxy;
-  const double* py = L.pxy + L.nv;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (tid < GT) {
       const int64_t g = tile * GT + tid;
-      double w = 0.0;
-      int q = 0, core = 0;
-      for (int a = 0; a < 6; ++a) { s_r[a][tid] = -1; s_gx[a][tid] = 0.0; s_gy[a][tid] = 0.0; }
-      if (g < nq) {
-        const int e = (int)(g / 6);
-        q = (int)(g % 6);
-        const P2Map M(L.edof, L.ne, px, py, e);
-        const double xi = c_qx[q], eta = c_qy[q];
-        double det = M.det(), inv[4], X, Y, gx[6], gy[6];
-        M.inverse(det, inv);
-        M.point(xi, eta, X, Y);
-        core = in_any_core(X, Y, cores.c, ncore) ? 1 : 0;
-        w = fabs(det) * c_qw[q];
-        p2_grad(inv, xi, eta, gx, gy);
-        for (int a = 0; a < 6; ++a) {
-          s_gx[a][tid] = gx[a];
-          s_gy[a][tid] = gy[a];
-          s_r[a][tid] = dev_row(L, e, a);
-        }
-      }
-      s_w[tid] = w;
-      s_q[tid] = q;
+      int core = 0;
+      gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q,
+                       [&](double X, double Y) { core = in_any_core(X, Y, cores.c, ncore) ? 1 : 0; });
       s_core[tid] = core;
     }
     __syncthreads();
-    // features: consecutive lanes read consecutive modes of one staged row
-    for (int idx = tid; idx < 2 * GT * OC; idx += 256) {
-      const int i = idx % OC, t = (idx / OC) % GT, side = idx / (OC * GT);
-      const int m = (side ? j0 : i0) + i;
-      double f[NF];
-#pragma unroll
-      for (int c = 0; c < NF; ++c) f[c] = 0.0;
-      if (m < k) {
-        double phi[6];
-        p2_phi(c_qx[s_q[t]], c_qy[s_q[t]], phi);
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          const int r = s_r[a][t];
-          if (r < 0) continue;
-          const double gx = s_gx[a][t], gy = s_gy[a][t];
-#pragma unroll
-          for (int c = 0; c < NCOMP; ++c) {
-            const double v = V[(int64_t)c * nrows * k + (int64_t)r * k + m];
-            f[c] += phi[a] * v;
-            f[NCOMP + 2 * c] += gx * v;
-            f[NCOMP + 2 * c + 1] += gy * v;
-          }
-        }
-        if (side) {
-          const double w = s_w[t];
-#pragma unroll
-          for (int c = 0; c < NF; ++c) f[c] *= w;
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < NF; ++c) s_f[side][c][t][i] = f[c];
-    }
+    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
     __syncthreads();
 #pragma unroll 1
     for (int t = 0; t < GT; ++t) {
@@ -393,12 +424,6 @@ __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nr
         a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
         b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
       }
-      // acc[o] += s x a[p] (x) b[q], s = +-1.  Explicit fused multiply-adds: left to contraction, a product that both
-      // region branches share is hoisted above the branch, and the compiler then fuses it into some of the four
-      // accumulators of the 2 x 2 block and not others, so that an entry's rounding would depend on its place in the block
-#define GRAM_ACC(o, p, q, s)                                                                        \
-      acc[o][0][0] = fma((s) * a[p].x, b[q].x, acc[o][0][0]); acc[o][0][1] = fma((s) * a[p].x, b[q].y, acc[o][0][1]); \
-      acc[o][1][0] = fma((s) * a[p].y, b[q].x, acc[o][1][0]); acc[o][1][1] = fma((s) * a[p].y, b[q].y, acc[o][1][1]);
       const int r = s_core[t] ? 0 : 1;          // the same for every lane
       if (NCOMP == 2) {
         // M_r: hx hx + hy hy;  K_r: dy hx dy hx + dx hy dx hy - dx hx dy hy - dy hy dx hx;
@@ -416,7 +441,6 @@ __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nr
         if (r == 0) { GRAM_ACC(0, 0, 0, 1.0) } else { GRAM_ACC(1, 0, 0, 1.0) }
         GRAM_ACC(NOUT - 1, 1, 1, 1.0) GRAM_ACC(NOUT - 1, NF - 1, NF - 1, 1.0)
       }
-#undef GRAM_ACC
     }
     __syncthreads();
   }
@@ -428,6 +452,126 @@ __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nr
       for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
   }
 }
+
+// Per-core Grams (plfem_core_grams): the Grams of the modes restricted to each core disc, in three passes.
+//
+// Pass 1, k_core_owner: one lane per quadrature point of the six-point rule, element-major; the point formed as the
+// assembly forms it; owner[g] = core_owner (p2_element.h): the highest-index closed disc holding it, or -1.
+__global__ __launch_bounds__(256) void k_core_owner(LocArgs L, CoreTable cores, int ncore, int32_t* __restrict__ owner) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (int64_t)6 * L.ne) return;
+  const int e = (int)(g / 6), q = (int)(g % 6);
+  const P2Map M(L.edof, L.ne, L.pxy, L.pxy + L.nv, e);
+  double X, Y;
+  M.point(c_qx[q], c_qy[q], X, Y);
+  owner[g] = core_owner(X, Y, cores.c, ncore);
+}
+
+// Pass 2, compaction: per core the ascending list of the points it owns.  One workgroup per core walks the owner array
+// in order, first to count (k_core_count), then, with the exclusive offsets summed from the counts, to fill
+// (k_core_fill).  A point's place is its rank among the core's points -- ballot and popcount inside a wave, the four
+// wave totals in wave order, a running base across the 256-point steps -- so the lists do not depend on scheduling and
+// no atomic is involved.  meta = counts [MAX_CORES], then offsets [MAX_CORES].
+__global__ __launch_bounds__(256) void k_core_count(int64_t nq, const int32_t* __restrict__ owner, int32_t* __restrict__ meta) {
+  __shared__ int s_n[256];
+  const int tid = threadIdx.x, c = blockIdx.x;
+  int n = 0;
+  for (int64_t g = tid; g < nq; g += 256) n += owner[g] == c ? 1 : 0;
+  s_n[tid] = n;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) s_n[tid] += s_n[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) meta[c] = s_n[0];
+}
+
+__global__ __launch_bounds__(256) void k_core_fill(int64_t nq, const int32_t* __restrict__ owner, int32_t* __restrict__ meta,
+                                                   int32_t* __restrict__ list) {
+  __shared__ int s_wave[4];
+  const int tid = threadIdx.x, c = blockIdx.x, lane = tid & 63, wave = tid >> 6;
+  int base = 0;
+  for (int j = 0; j < c; ++j) base += meta[j];
+  if (tid == 0) meta[MAX_CORES + c] = base;
+  for (int64_t g0 = 0; g0 < nq; g0 += 256) {
+    const int64_t g = g0 + tid;
+    const bool mine = g < nq && owner[g] == c;
+    const unsigned long long votes = __ballot(mine);
+    if (lane == 0) s_wave[wave] = __popcll(votes);
+    __syncthreads();
+    int before = __popcll(votes & ((1ull << lane) - 1ull)), total = 0;
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) before += s_wave[w];
+      total += s_wave[w];
+    }
+    if (mine) list[base + before] = (int32_t)g;
+    base += total;
+    __syncthreads();
+  }
+}
+
+// Pass 3, k_core_grams: grid = (slice, chunk pair, core).  The workgroup walks tiles of GT points of its core's list --
+// tiles blockIdx.x, blockIdx.x + gridDim.x, ... of that core's ceil(count / GT), so the slices at work follow the core's
+// tile count and the others write zeros -- staging and features as in k_mode_grams (gram_stage_point, gram_features; a
+// list's last tile is padded with points that contribute nothing).  Every point of the walk is the core's: no region
+// branch.  Outputs (ncomp = 2): Mx = hx hx, My = hy hy, K (the form of K_r above); (ncomp = 1): M = u u.  Partials
+// [core][output][chunk pair][slice][OC * OC], every slot written: the layout k_overlap_reduce sums with blockIdx.y = core x
+// output.
+template <int NCOMP>
+__global__ __launch_bounds__(256) void k_core_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
+                                                    const int32_t* __restrict__ meta, const int32_t* __restrict__ list,
+                                                    int nchunk, double* __restrict__ partial) {
+  constexpr int NF = 3 * NCOMP;
+  constexpr int NOUT = NCOMP == 2 ? 3 : 1;
+  __shared__ double s_f[2][NF][GT][OC];
+  __shared__ double s_gx[6][GT], s_gy[6][GT];
+  __shared__ int s_r[6][GT];
+  __shared__ double s_w[GT];
+  __shared__ int s_q[GT];
+  const int tid = threadIdx.x, core = blockIdx.z;
+  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
+  const int i0 = ci * OC, j0 = cj * OC;
+  const int count = meta[core];
+  const int32_t* mine = list + meta[MAX_CORES + core];
+  const int ntiles = (count + GT - 1) / GT;
+  const int ti = tid >> 4, tj = tid & 15;
+  double acc[NOUT][2][2];
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < GT) {
+      const int p = tile * GT + tid;
+      const bool live = p < count;
+      gram_stage_point(L, live ? (int64_t)mine[p] : 0, live, tid, s_gx, s_gy, s_r, s_w, s_q, [](double, double) {});
+    }
+    __syncthreads();
+    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < GT; ++t) {
+      double2 a[NF], b[NF];
+#pragma unroll
+      for (int c = 0; c < NF; ++c) {
+        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
+        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
+      }
+      GRAM_ACC(0, 0, 0, 1.0)                    // Mx (M when ncomp = 1)
+      if constexpr (NCOMP == 2) {
+        GRAM_ACC(1, 1, 1, 1.0)
+        GRAM_ACC(2, 3, 3, 1.0) GRAM_ACC(2, 4, 4, 1.0) GRAM_ACC(2, 2, 5, -1.0) GRAM_ACC(2, 5, 2, -1.0)
+      }
+    }
+    __syncthreads();
+  }
+  const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) {
+    double* out = partial + ((((int64_t)core * NOUT + o) * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+    for (int r = 0; r < 2; ++r)
+      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
+  }
+}
+#undef GRAM_ACC
 
 // Quartic mode-overlap tensor (plfem_mode_quartic): Q[p(i,j)][p(l,m)] = sum over the points of the 16-point degree-8 rule
 // of |det J| w_q wt(x) (u_i . u_j)(u_l . u_m), i.e. Q = R^T diag(w) R with R[point][pair] = u_i . u_j.  R never reaches
@@ -959,6 +1103,84 @@ extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
   });
   TRY(check_launch(L, "k_mode_grams"));
   return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
+} catch (...) { return host_failure(L); }
+
+namespace {
+constexpr int CG_SLICES = 256;   // most slices (partial blocks) per core and chunk pair
+constexpr int CG_WG = 1024;      // workgroups of k_core_grams per chunk pair aimed at: slices = min(CG_SLICES, CG_WG / cores)
+int core_gram_outputs(int ncomp) { return ncomp == 2 ? 3 : 1; }
+// Work buffer of plfem_core_grams: the result [ncore][nout][k][k], the partials [ncore][nout][chunk pair][slice][OC * OC],
+// the owner of every quadrature point and the per-core point lists (6 ne int32 each), counts and offsets; every part
+// 256-byte aligned.  Slices: no more than the mesh has tiles, at least 1, and a function of the mesh and the core count
+// alone -- the tiles a slice sums, and so the bits of an entry, must not change with the number of modes.  k_core_grams
+// thus runs at most CG_WG workgroups per chunk pair and the partials take at most nout x CG_WG blocks of 8 KiB per chunk
+// pair.
+struct CoreGramLayout { int slices; size_t off_partial, off_owner, off_list, off_meta, total; };
+CoreGramLayout core_gram_layout(int ne, int ncomp, int k, int ncore) {
+  const size_t nout = core_gram_outputs(ncomp), nc = overlap_chunks(k), nq = (size_t)6 * ne;
+  const int64_t ntiles = ((int64_t)nq + GT - 1) / GT;
+  CoreGramLayout l;
+  l.slices = (int)std::max<int64_t>(1, std::min<int64_t>({CG_SLICES, ntiles, CG_WG / ncore}));
+  size_t o = align256((size_t)ncore * nout * k * k * sizeof(double));
+  l.off_partial = o; o += align256((size_t)ncore * nout * nc * nc * l.slices * OC * OC * sizeof(double));
+  l.off_owner = o;   o += align256(std::max<size_t>(1, nq) * sizeof(int32_t));
+  l.off_list = o;    o += align256(std::max<size_t>(1, nq) * sizeof(int32_t));
+  l.off_meta = o;    o += align256((size_t)2 * MAX_CORES * sizeof(int32_t));
+  l.total = o;
+  return l;
+}
+const char* core_gram_args(int ncomp, int k, int ncore) {
+  if (ncomp < 1 || ncomp > 2) return "ncomp must be 1 or 2";
+  if (k < 1) return "k must be >= 1";
+  if (ncore < 1 || ncore > MAX_CORES) return "ncore must be in [1, 64]";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int plfem_core_gram_work_bytes(const plfem_locator* L, int32_t ncomp, int32_t k, int32_t ncore, int64_t* bytes) try {
+  if (!L || !bytes || core_gram_args(ncomp, k, ncore)) return PLFEM_EINVAL;
+  *bytes = (int64_t)core_gram_layout(L->ne, ncomp, k, ncore).total;
+  return PLFEM_OK;
+} catch (...) { return host_failure(nullptr, 0); }
+
+extern "C" int plfem_core_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host,
+                                int64_t* count_host) try {
+  if (!L) return PLFEM_EINVAL;
+  if (const char* bad = core_gram_args(ncomp, k, ncore)) { L->err = std::string("plfem_core_grams: ") + bad; return PLFEM_EINVAL; }
+  if (!modes_dev || !cores_host || !work_dev || !out_host || !count_host) {
+    L->err = "plfem_core_grams: null array";
+    return PLFEM_EINVAL;
+  }
+  if (indexed && L->nsolve == 0) { L->err = "plfem_core_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  const CoreGramLayout lay = core_gram_layout(L->ne, ncomp, k, ncore);
+  TRY(check_work(L, "plfem_core_grams", "plfem_core_gram_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
+  HIP_TRY(L, hipSetDevice(L->device));
+  const CoreTable ct = pack_cores(cores_host, ncore);
+  const int nout = core_gram_outputs(ncomp), nc = overlap_chunks(k);
+  const int64_t nq = (int64_t)6 * L->ne, nrows = indexed ? L->nsolve : L->N;
+  char* base = (char*)work_dev;
+  double *O = (double*)base, *partial = (double*)(base + lay.off_partial);
+  int32_t *owner = (int32_t*)(base + lay.off_owner), *list = (int32_t*)(base + lay.off_list), *meta = (int32_t*)(base + lay.off_meta);
+  const LocArgs la = loc_args(L, indexed != 0);
+  if (nq > 0) {
+    hipLaunchKernelGGL(k_core_owner, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, L->stream, la, ct, (int)ncore, owner);
+    TRY(check_launch(L, "k_core_owner"));
+  }
+  hipLaunchKernelGGL(k_core_count, dim3(ncore), dim3(256), 0, L->stream, nq, owner, meta);
+  TRY(check_launch(L, "k_core_count"));
+  hipLaunchKernelGGL(k_core_fill, dim3(ncore), dim3(256), 0, L->stream, nq, owner, meta, list);
+  TRY(check_launch(L, "k_core_fill"));
+  with_constant<2, 1>(ncomp, [&](auto nco) {
+    hipLaunchKernelGGL(k_core_grams<decltype(nco)::value>, dim3(lay.slices, nc * nc, ncore), dim3(256), 0, L->stream, la, (int)k,
+                       nrows, modes_dev, meta, list, nc, partial);
+  });
+  TRY(check_launch(L, "k_core_grams"));
+  int32_t counts[MAX_CORES];
+  HIP_TRY(L, hipMemcpyAsync(counts, meta, sizeof(int32_t) * ncore, hipMemcpyDeviceToHost, L->stream));
+  TRY(reduce_to_host(L, dim3(nc * nc, ncore * nout, OC * OC / 256), (int)k, (int)k, lay.slices, nc, partial, O, out_host));
+  for (int c = 0; c < ncore; ++c) count_host[c] = counts[c];   // (the stream is synchronised)
+  return PLFEM_OK;
 } catch (...) { return host_failure(L); }
 
 namespace {

@@ -1,6 +1,6 @@
 // The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
 // integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
-// k_field_overlap, k_mode_grams, k_mode_quartic, k_mode_project).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// k_field_overlap, k_mode_grams, k_mode_quartic, k_mode_project, k_core_owner).  One definition, so that a quadrature point lands in the same region, and det J rounds
 // the same way, in the assembly and in every kernel that must reproduce it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -118,6 +118,18 @@ __device__ __forceinline__ bool in_any_core(double X, double Y, const double* co
     in |= (mul_rn(dx, dx) + mul_rn(dy, dy) <= mul_rn(r, r));
   }
   return in;
+}
+
+// which core: the highest index c whose closed disc holds the point, or -1 (the reference's epsilon writes the cores in
+// order, so a later disc overwrites an earlier one).  The comparison is that of in_any_core, operation for operation:
+// core_owner(...) >= 0 exactly where in_any_core(...), ties included
+__device__ __forceinline__ int core_owner(double X, double Y, const double* cores, int ncore) {
+  int owner = -1;
+  for (int c = 0; c < ncore; ++c) {
+    const double dx = X - cores[3 * c], dy = Y - cores[3 * c + 1], r = cores[3 * c + 2];
+    if (mul_rn(dx, dx) + mul_rn(dy, dy) <= mul_rn(r, r)) owner = c;
+  }
+  return owner;
 }
 
 }  // namespace

@@ -32,6 +32,7 @@ from .solver_fem import _core_table, mesh_key
 
 LOC_TOL = 1e-10                    # PLFEM_LOC_TOL of include/plfem.h
 GRAM_NAMES = {"vectorial": ("M_core", "M_clad", "K_core", "K_clad", "D"), "scalar": ("M_core", "M_clad", "S")}
+CORE_GRAM_NAMES = {"vectorial": ("Mx", "My", "K"), "scalar": ("M",)}
 PROJECT_TILE = (8, 8)              # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
 PROJECT_MAX_FACTORS = 4096         # PJ_LMAX
 
@@ -255,22 +256,31 @@ class ModeFields:
         alpha_p D - k0^2 (M_core + M_clad)`` and ``V^T B V = sum_r M_r / eps_r`` on the interior DOFs), scalar records
         ``M_core``, ``M_clad``, ``S`` (``V^T A V = S - k0^2 sum_r eps_r M_r``, ``V^T B V = M_core + M_clad``)."""
         kind, vals, _ = self._check_records(modes)
+        cores = self._cores(geometry)
+        k = 0 if kind is None else vals.shape[1]
+        if k == 0:
+            return {nm: np.zeros((0, 0)) for nm in GRAM_NAMES.get(kind, ())}
+        self._ensure_locator()
+        staged, _src = self._stage(vals)
+        return self._grams_staged(kind, staged, cores)
+
+    @staticmethod
+    def _cores(geometry) -> np.ndarray:
+        """The (ncore, 3) table (x, y, r) of a geometry's cores; ``ValueError`` without them or with more than 64."""
         if not all(hasattr(geometry, a) for a in ("positions", "core_radii")):
             raise ValueError("geometry must have positions and core_radii")
         cores = _core_table(geometry)
         if cores.shape[0] > 64:
             raise ValueError("at most 64 cores")
-        names = GRAM_NAMES.get(kind, ())
-        k = 0 if kind is None else vals.shape[1]
-        if k == 0:
-            return {nm: np.zeros((0, 0)) for nm in names}
-        self._ensure_locator()
-        import torch
-        ncomp = vals.shape[0]
+        return cores
+
+    def _grams_staged(self, kind, staged, cores) -> Dict[str, np.ndarray]:
+        """``plfem_mode_grams`` on modes already staged (ncomp, n, k) on the device."""
+        names = GRAM_NAMES[kind]
+        ncomp, _, k = staged.shape
         need = ctypes.c_int64(0)
         if self._lib.plfem_gram_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
             raise ValueError(f"plfem_gram_work_bytes rejected ncomp = {ncomp}, k = {k}")
-        staged, _src = self._stage(vals)
         work = _native.device_scratch(int(need.value) + 256, self.tdev)
         aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((len(names), k, k), dtype=np.float64)
@@ -279,6 +289,49 @@ class ModeFields:
                                                cores.shape[0], ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
                                                out.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_grams")
         return {nm: out[i] for i, nm in enumerate(names)}
+
+    def core_grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
+        """Grams of the modes restricted to each core disc (``plfem_core_grams``), each (ncore, k, k): vectorial records
+        ``Mx`` (sum over the core's quadrature points of hx_m hx_n), ``My`` and ``K`` (the form of ``K_core``), scalar
+        records ``M``; and ``points`` (ncore,) int64, the quadrature points each core owns.  A point belongs to the
+        highest-index core whose closed disc holds it, by the arithmetic of the assembly's core test, so summed over the
+        cores ``Mx + My`` is ``M_core`` and ``K`` is ``K_core`` of :meth:`grams`; a core that owns no point gives zeros.
+        With core c at eps_c instead of eps_core the pencils of :meth:`grams` become ``sum_c K_c / eps_c + ...``: these
+        are the exact projections of a pencil with unequal core indices on the span of the modes."""
+        kind, vals, _ = self._check_records(modes)
+        cores = self._cores(geometry)
+        ncore = cores.shape[0]
+        if ncore < 1:
+            raise ValueError("geometry has no cores")
+        k = 0 if kind is None else vals.shape[1]
+        if k == 0:
+            res = {nm: np.zeros((ncore, 0, 0)) for nm in CORE_GRAM_NAMES.get(kind, ())}
+            res["points"] = np.zeros(ncore, dtype=np.int64)
+            return res
+        self._ensure_locator()
+        staged, _src = self._stage(vals)
+        return self._core_grams_staged(kind, staged, cores)
+
+    def _core_grams_staged(self, kind, staged, cores) -> Dict[str, np.ndarray]:
+        """``plfem_core_grams`` on modes already staged (ncomp, n, k) on the device."""
+        names = CORE_GRAM_NAMES[kind]
+        ncomp, _, k = staged.shape
+        ncore = cores.shape[0]
+        need = ctypes.c_int64(0)
+        if self._lib.plfem_core_gram_work_bytes(self._loc, ncomp, k, ncore, ctypes.byref(need)) != _native.PLFEM_OK:
+            raise ValueError(f"plfem_core_gram_work_bytes rejected ncomp = {ncomp}, k = {k}, ncore = {ncore}")
+        work = _native.device_scratch(int(need.value) + 256, self.tdev)
+        aligned = (work.data_ptr() + 255) & ~255
+        out = np.empty((ncore, len(names), k, k), dtype=np.float64)
+        points = np.empty(ncore, dtype=np.int64)
+        self._check(self._lib.plfem_core_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
+                                               1 if kind == "vectorial" else 0, cores.ctypes.data_as(ctypes.c_void_p), ncore,
+                                               ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
+                                               out.ctypes.data_as(ctypes.c_void_p), points.ctypes.data_as(ctypes.c_void_p)),
+                    "plfem_core_grams")
+        res = {nm: np.ascontiguousarray(out[:, i]) for i, nm in enumerate(names)}
+        res["points"] = points
+        return res
 
     def quartic(self, modes: Sequence[Dict], geometry=None, weights=(1.0, 1.0)) -> np.ndarray:
         """Packed quartic overlap of the modes over this mesh (``plfem_mode_quartic``), np x np with np = k (k + 1) / 2:
@@ -444,4 +497,4 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
     return O * O / (daa[:, None] * dbb[None, :])
 
 
-__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES", "PROJECT_TILE", "PROJECT_MAX_FACTORS"]
+__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "PROJECT_TILE", "PROJECT_MAX_FACTORS"]
