@@ -384,6 +384,30 @@ int plfem_core_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double*
                      double* out_host   /* [ncore][NOUT][k][k], NOUT = 3 (Mx, My, K) or 1 (M) */,
                      int64_t* count_host /* [ncore] quadrature points owned */);
 
+/* Coordinate-weighted ("moment") Grams: the region Grams of plfem_mode_grams weighted by the coordinates of the
+ * quadrature point, X = x - origin_host[0], Y = y - origin_host[1], (x, y) the physical point exactly as the assembly
+ * forms it; modes, indexed, cores and regions as for plfem_mode_grams (ncore in [0, 64]); every sum is over the six-point
+ * rule with |det J| w_q:
+ *   ncomp = 1: out_host[0..6][k][k] = M_core_X, M_core_Y, M_clad_X, M_clad_Y, M_XX, M_XY, M_YY with
+ *     M_r_X[m][n] = sum_r X u_m u_n (likewise Y), M_XX[m][n] = sum X^2 u_m u_n over both regions (likewise XY, Y^2);
+ *   ncomp = 2: out_host[0..10][k][k] = M_core_X, M_core_Y, M_clad_X, M_clad_Y, K_core_X, K_core_Y, K_clad_X, K_clad_Y,
+ *     M_XX, M_XY, M_YY with M = hx hx' + hy hy' and K the form of K_r of plfem_mode_grams.
+ * A bend of curvature kappa along (c, s) enters both pencils linearly -- eps -> eps (1 + 2 kappa (c X + s Y)) in the
+ * scalar form, 1/eps -> (1 - 2 kappa (c X + s Y)) / eps in the vectorial form -- so these are the exact projections of
+ * the bent pencils on the span of the modes; the second moments give centroids and widths.
+ * The grid and tiling of plfem_mode_grams (the tile-to-workgroup map does not depend on k), partial blocks per
+ * workgroup, every one written by the call that reads it, and the fixed-order second stage: the same bits on every run,
+ * for a subset or a permutation of the modes, and whatever the work buffer held before.  Synchronises the locator's
+ * stream.
+ * work_dev: device scratch of plfem_moment_gram_work_bytes(ncomp, k) bytes, 256-byte aligned: nout k^2 doubles plus
+ * nout ceil(k / 32)^2 x 768 partial blocks of 8 KiB, nout = 7 or 11 (66 MiB for ncomp = 2 up to k = 32, 594 MiB at k = 70).
+ * Argument errors (ncomp not 1 or 2, k < 1, ncore outside [0, 64], a null pointer, a non-finite origin, work_bytes too
+ * small) return PLFEM_EINVAL with the locator's last error set. */
+int plfem_moment_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes);
+int plfem_moment_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                       const double* cores_host, int32_t ncore, const double origin_host[2], void* work_dev,
+                       int64_t work_bytes, double* out_host);
+
 /* Quartic mode-overlap tensor of k staged modes over the locator's mesh (the input of multimode nonlinear propagation:
  * f_ijkl, A_eff, gamma), on the 16-point degree-8 rule (products of four P2 fields are of degree 8).  Pairs i <= j are
  * numbered p(i,j) = i k - i (i - 1) / 2 + (j - i), np = k (k + 1) / 2.

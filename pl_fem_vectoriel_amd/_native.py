@@ -40,7 +40,7 @@ EXPORTS = (
     "plfem_locator_bytes", "plfem_locator_create", "plfem_locator_destroy", "plfem_locator_last_error", "plfem_stage_modes",
     "plfem_sample_fields", "plfem_overlap_work_bytes", "plfem_field_overlap", "plfem_gram_work_bytes", "plfem_mode_grams",
     "plfem_quartic_work_bytes", "plfem_mode_quartic", "plfem_project_work_bytes", "plfem_mode_project",
-    "plfem_core_gram_work_bytes", "plfem_core_grams",
+    "plfem_core_gram_work_bytes", "plfem_core_grams", "plfem_moment_gram_work_bytes", "plfem_moment_grams",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -227,6 +227,10 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_core_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                      ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                      ctypes.c_void_p]
+    lib.plfem_moment_gram_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
+    lib.plfem_moment_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.c_void_p]
     lib.plfem_quartic_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
     lib.plfem_mode_quartic.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,

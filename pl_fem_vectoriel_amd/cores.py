@@ -47,6 +47,22 @@ def _vector(v, n: int, name: str, positive: bool = False) -> np.ndarray:
     return a
 
 
+def _cluster_members(label: np.ndarray) -> list:
+    """The index sets of the clusters of :func:`.dispersion._clusters` labels, in label order."""
+    return [np.nonzero(label == c)[0] for c in range(int(label.max()) + 1 if label.size else 0)]
+
+
+def _directional_dmu(Ad: np.ndarray, Bd: np.ndarray, B: np.ndarray, mu: np.ndarray, members: list) -> np.ndarray:
+    """d mu of every B-normalised record along a direction in which the pencil moves by (Ad, Bd): Hellmann-Feynman for
+    a singleton; inside a cluster the generalised eigenvalues of the cluster block against ``B_SS``, handed out in
+    ascending order to the members in record order (shared with :mod:`.bend`)."""
+    dmu = np.diag(Ad) - mu * np.diag(Bd)
+    for S in members:
+        T = (Ad - float(mu[S].mean()) * Bd)[np.ix_(S, S)]
+        dmu[S] = scipy.linalg.eigh(0.5 * (T + T.T), B[np.ix_(S, S)], eigvals_only=True)
+    return dmu
+
+
 def core_quantities_from_grams(kind: str, core_grams: Dict[str, np.ndarray], grams: Dict[str, np.ndarray], beta, k0: float,
                                eps, n_cores=None, direction=None, cluster_rtol: float = 1e-10,
                                alpha_p: float = TrueVectorialMaxwellSolver.ALPHA_P) -> Dict:
@@ -121,16 +137,11 @@ def core_quantities_from_grams(kind: str, core_grams: Dict[str, np.ndarray], gra
     label = _clusters(mu, cluster_rtol * float(np.abs(mu).max()))
     res["cluster"] = label
     res["sensitivity"] = dA - mu[None, None, :] * dB
-    members = [np.nonzero(label == c)[0] for c in range(int(label.max()) + 1 if k else 0)]
+    members = _cluster_members(label)
 
     def along(d):
         """d mu of every mode along the direction d (ncore,)."""
-        Ad, Bd = np.tensordot(d, dA, 1), np.tensordot(d, dB, 1)
-        dmu = np.diag(Ad) - mu * np.diag(Bd)
-        for S in members:
-            T = (Ad - float(mu[S].mean()) * Bd)[np.ix_(S, S)]
-            dmu[S] = scipy.linalg.eigh(0.5 * (T + T.T), B[np.ix_(S, S)], eigvals_only=True)
-        return dmu
+        return _directional_dmu(np.tensordot(d, dA, 1), np.tensordot(d, dB, 1), B, mu, members)
 
     to_neff = sgn / (2.0 * beta * k0)
     res["dneff_dn"] = np.stack([along(e) for e in np.eye(ncore)], axis=1) * to_neff[:, None]

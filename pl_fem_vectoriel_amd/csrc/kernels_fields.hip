@@ -5,7 +5,8 @@
 // products of four modes on a 16-point degree-8 rule (k_mode_quartic + k_quartic_reduce), and the projection of a mode
 // set on a family of analytic fields that separate in x and y -- plane waves and Gaussian beams -- on the same rule
 // (k_mode_project + k_project_reduce), and the Grams of a mode set restricted to each core disc (k_core_owner,
-// k_core_count + k_core_fill, k_core_grams + k_overlap_reduce).
+// k_core_count + k_core_fill, k_core_grams + k_overlap_reduce), and the region Grams weighted by the coordinates of the
+// quadrature point (k_moment_grams + k_overlap_reduce).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
@@ -573,6 +574,108 @@ __global__ __launch_bounds__(256) void k_core_grams(LocArgs L, int k, int64_t nr
 }
 #undef GRAM_ACC
 
+// Coordinate-weighted Grams (plfem_moment_grams): the M_r (and K_r) of k_mode_grams weighted by the point's X = x - ox,
+// Y = y - oy, and the unweighted M by X^2, XY, Y^2.  Grid, tiling, staging and features as in k_mode_grams; the staging
+// lanes also put X, Y, X^2, XY, Y^2 of their point into LDS (0 for a padding point, whose weight is 0).  Per point every
+// lane forms the unweighted 2 x 2 products of its block once -- m = u u' (hx hx' + hy hy') or kk = the form of K_r -- and
+// adds them, times the point's coordinates, to the outputs of the point's region: the coordinates and the region are
+// the same for every lane.  Every product and sum is an explicit multiply or fused multiply-add in one written order,
+// the same for the four entries of the block, so an entry's bits do not depend on its place in the block or the chunk.
+// KPART = false: the seven outputs made of m (M_core_X, M_core_Y, M_clad_X, M_clad_Y, M_XX, M_XY, M_YY: all of the
+// scalar call); KPART = true (NCOMP = 2): the four made of kk (K_core_X, K_core_Y, K_clad_X, K_clad_Y).  The vectorial
+// call runs both instances: 11 outputs x 4 accumulators do not fit 128 VGPRs beside the features.  Partials
+// [output][chunk pair][workgroup][OC * OC] at the outputs' places in the call's list, every slot written.
+#define MOM_ACC(o, wgt, p)                                                                          \
+      acc[o][0][0] = fma(wgt, p[0][0], acc[o][0][0]); acc[o][0][1] = fma(wgt, p[0][1], acc[o][0][1]); \
+      acc[o][1][0] = fma(wgt, p[1][0], acc[o][1][0]); acc[o][1][1] = fma(wgt, p[1][1], acc[o][1][1]);
+
+template <int NCOMP, bool KPART>
+__global__ __launch_bounds__(256) void k_moment_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
+                                                      CoreTable cores, int ncore, double ox, double oy, int nchunk,
+                                                      double* __restrict__ partial) {
+  static_assert(NCOMP == 2 || !KPART, "the scalar call has no K");
+  constexpr int NF = 3 * NCOMP;
+  constexpr int NOUT = KPART ? 4 : 7;
+  __shared__ double s_f[2][NF][GT][OC];
+  __shared__ double s_gx[6][GT], s_gy[6][GT];
+  __shared__ int s_r[6][GT];
+  __shared__ double s_w[GT];
+  __shared__ double s_mx[5][GT];              // X, Y, X^2, XY, Y^2 of the tile's points
+  __shared__ int s_q[GT], s_core[GT];
+  const int tid = threadIdx.x;
+  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
+  const int i0 = ci * OC, j0 = cj * OC;
+  const int64_t nq = (int64_t)6 * L.ne;
+  const int64_t ntiles = (nq + GT - 1) / GT;
+  const int ti = tid >> 4, tj = tid & 15;
+  double acc[NOUT][2][2];
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < GT) {
+      const int64_t g = tile * GT + tid;
+      int core = 0;
+      double X = 0.0, Y = 0.0;
+      gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q, [&](double x, double y) {
+        core = in_any_core(x, y, cores.c, ncore) ? 1 : 0;
+        X = x - ox;
+        Y = y - oy;
+      });
+      s_core[tid] = core;
+      s_mx[0][tid] = X;
+      s_mx[1][tid] = Y;
+      s_mx[2][tid] = mul_rn(X, X);
+      s_mx[3][tid] = mul_rn(X, Y);
+      s_mx[4][tid] = mul_rn(Y, Y);
+    }
+    __syncthreads();
+    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < GT; ++t) {
+      constexpr int C0 = KPART ? 2 : 0, C1 = KPART ? NF : NCOMP;   // the features this instance reads
+      double2 a[NF], b[NF];
+#pragma unroll
+      for (int c = C0; c < C1; ++c) {
+        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
+        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
+      }
+      const double X = s_mx[0][t], Y = s_mx[1][t];
+      const bool core = s_core[t] != 0;         // the same for every lane
+      double p[2][2];
+      if constexpr (KPART) {
+        // dy hx dy hx' + dx hy dx hy' - dx hx dy hy' - dy hy dx hx'  (features 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy)
+#define MOM_K(r_, s_, ar, bs)                                                                       \
+        p[r_][s_] = a[3].ar * b[3].bs; p[r_][s_] = fma(a[4].ar, b[4].bs, p[r_][s_]);                  \
+        p[r_][s_] = fma(-a[2].ar, b[5].bs, p[r_][s_]); p[r_][s_] = fma(-a[5].ar, b[2].bs, p[r_][s_]);
+        MOM_K(0, 0, x, x) MOM_K(0, 1, x, y) MOM_K(1, 0, y, x) MOM_K(1, 1, y, y)
+#undef MOM_K
+      } else {
+        p[0][0] = a[0].x * b[0].x; p[0][1] = a[0].x * b[0].y; p[1][0] = a[0].y * b[0].x; p[1][1] = a[0].y * b[0].y;
+        if constexpr (NCOMP == 2) {
+          p[0][0] = fma(a[1].x, b[1].x, p[0][0]); p[0][1] = fma(a[1].x, b[1].y, p[0][1]);
+          p[1][0] = fma(a[1].y, b[1].x, p[1][0]); p[1][1] = fma(a[1].y, b[1].y, p[1][1]);
+        }
+      }
+      if (core) { MOM_ACC(0, X, p) MOM_ACC(1, Y, p) } else { MOM_ACC(2, X, p) MOM_ACC(3, Y, p) }
+      if constexpr (!KPART) {
+        const double XX = s_mx[2][t], XY = s_mx[3][t], YY = s_mx[4][t];
+        MOM_ACC(4, XX, p) MOM_ACC(5, XY, p) MOM_ACC(6, YY, p)
+      }
+    }
+    __syncthreads();
+  }
+  const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) {
+    const int og = KPART ? 4 + o : (o < 4 ? o : 4 * NCOMP + (o - 4));   // the output's place in the call's list
+    double* out = partial + (((int64_t)og * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+    for (int r = 0; r < 2; ++r)
+      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
+  }
+}
+#undef MOM_ACC
+
 // Quartic mode-overlap tensor (plfem_mode_quartic): Q[p(i,j)][p(l,m)] = sum over the points of the 16-point degree-8 rule
 // of |det J| w_q wt(x) (u_i . u_j)(u_l . u_m), i.e. Q = R^T diag(w) R with R[point][pair] = u_i . u_j.  R never reaches
 // HBM: one workgroup owns one 64 x 64 tile of Q on or above the diagonal (blockIdx.y, upper-triangle order) and walks
@@ -1069,6 +1172,12 @@ WorkLayout gram_layout(int ncomp, int k) {
   const size_t nout = gram_outputs(ncomp), nc = overlap_chunks(k);
   return work_layout(nout * k * k, nout * nc * nc * GRAM_BLOCKS * OC * OC);
 }
+// plfem_moment_grams: the same grid, 7 or 11 outputs
+int moment_gram_outputs(int ncomp) { return ncomp == 2 ? 11 : 7; }
+WorkLayout moment_gram_layout(int ncomp, int k) {
+  const size_t nout = moment_gram_outputs(ncomp), nc = overlap_chunks(k);
+  return work_layout(nout * k * k, nout * nc * nc * GRAM_BLOCKS * OC * OC);
+}
 }  // namespace
 
 extern "C" int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
@@ -1181,6 +1290,52 @@ extern "C" int plfem_core_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
   TRY(reduce_to_host(L, dim3(nc * nc, ncore * nout, OC * OC / 256), (int)k, (int)k, lay.slices, nc, partial, O, out_host));
   for (int c = 0; c < ncore; ++c) count_host[c] = counts[c];   // (the stream is synchronised)
   return PLFEM_OK;
+} catch (...) { return host_failure(L); }
+
+extern "C" int plfem_moment_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
+  if (!bytes || ncomp < 1 || ncomp > 2 || k < 1) return PLFEM_EINVAL;
+  *bytes = (int64_t)moment_gram_layout(ncomp, k).total;
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_moment_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                  const double* cores_host, int32_t ncore, const double* origin_host, void* work_dev,
+                                  int64_t work_bytes, double* out_host) try {
+  if (!L) return PLFEM_EINVAL;
+  if (ncomp < 1 || ncomp > 2 || k < 1) { L->err = "plfem_moment_grams: ncomp must be 1 or 2 and k >= 1"; return PLFEM_EINVAL; }
+  if (ncore < 0 || ncore > MAX_CORES) { L->err = "plfem_moment_grams: ncore must be in [0, 64]"; return PLFEM_EINVAL; }
+  if (!modes_dev || !work_dev || !out_host || !origin_host || (ncore > 0 && !cores_host)) {
+    L->err = "plfem_moment_grams: null array";
+    return PLFEM_EINVAL;
+  }
+  if (!std::isfinite(origin_host[0]) || !std::isfinite(origin_host[1])) {
+    L->err = "plfem_moment_grams: the origin must be finite";
+    return PLFEM_EINVAL;
+  }
+  if (indexed && L->nsolve == 0) { L->err = "plfem_moment_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  const WorkLayout lay = moment_gram_layout(ncomp, k);
+  TRY(check_work(L, "plfem_moment_grams", "plfem_moment_gram_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
+  HIP_TRY(L, hipSetDevice(L->device));
+  const CoreTable ct = pack_cores(cores_host, ncore);
+  const int nout = moment_gram_outputs(ncomp), nc = overlap_chunks(k);
+  const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
+  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ntiles));   // (no function of k)
+  const int64_t nrows = indexed ? L->nsolve : L->N;
+  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
+  const dim3 grid(nblk, nc * nc);
+  const LocArgs la = loc_args(L, indexed != 0);
+  const double ox = origin_host[0], oy = origin_host[1];
+  if (ncomp == 2) {                           // a second instance for the four outputs made of K
+    hipLaunchKernelGGL((k_moment_grams<2, true>), grid, dim3(256), 0, L->stream, la, (int)k, nrows, modes_dev, ct,
+                       (int)ncore, ox, oy, nc, partial);
+    TRY(check_launch(L, "k_moment_grams"));
+  }
+  with_constant<2, 1>(ncomp, [&](auto nco) {
+    hipLaunchKernelGGL((k_moment_grams<decltype(nco)::value, false>), grid, dim3(256), 0, L->stream, la, (int)k, nrows, modes_dev,
+                       ct, (int)ncore, ox, oy, nc, partial);
+  });
+  TRY(check_launch(L, "k_moment_grams"));
+  return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
 } catch (...) { return host_failure(L); }
 
 namespace {

@@ -11,6 +11,8 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
   values located and evaluated inside the kernel (``plfem_field_overlap``);
 * :meth:`ModeFields.grams` -- the k x k Grams of one mesh's modes under the assembly's element forms, split by material
   region (``plfem_mode_grams``): what :mod:`.dispersion` builds the group index and the k0-derivative coupling from;
+* :meth:`ModeFields.moment_grams` -- the region Grams weighted by the coordinates of the quadrature point
+  (``plfem_moment_grams``): what :mod:`.bend` builds bend-induced index shifts, mode mixing and beam widths from;
 * :meth:`ModeFields.quartic` -- the packed overlap of products of four modes on a 16-point degree-8 rule
   (``plfem_mode_quartic``): what :mod:`.nonlinear` builds the nonlinear coupling tensor, A_eff and gamma from;
 * :meth:`ModeFields.project` -- the projection of the modes on plane waves and Gaussian beams, fields that separate in
@@ -33,6 +35,9 @@ from .solver_fem import _core_table, mesh_key
 LOC_TOL = 1e-10                    # PLFEM_LOC_TOL of include/plfem.h
 GRAM_NAMES = {"vectorial": ("M_core", "M_clad", "K_core", "K_clad", "D"), "scalar": ("M_core", "M_clad", "S")}
 CORE_GRAM_NAMES = {"vectorial": ("Mx", "My", "K"), "scalar": ("M",)}
+MOMENT_GRAM_NAMES = {"vectorial": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "K_core_X", "K_core_Y", "K_clad_X",
+                                   "K_clad_Y", "M_XX", "M_XY", "M_YY"),
+                     "scalar": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "M_XX", "M_XY", "M_YY")}
 PROJECT_TILE = (8, 8)              # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
 PROJECT_MAX_FACTORS = 4096         # PJ_LMAX
 
@@ -333,6 +338,50 @@ class ModeFields:
         res["points"] = points
         return res
 
+    @staticmethod
+    def _origin(origin) -> np.ndarray:
+        """``origin`` as two finite float64; ``ValueError`` otherwise."""
+        try:
+            o = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(-1))
+        except (TypeError, ValueError):
+            raise ValueError("origin must be two finite numbers (x, y)") from None
+        if o.size != 2 or not np.all(np.isfinite(o)):
+            raise ValueError("origin must be two finite numbers (x, y)")
+        return o
+
+    def moment_grams(self, modes: Sequence[Dict], geometry, origin=(0.0, 0.0)) -> Dict[str, np.ndarray]:
+        """The region Grams of :meth:`grams` weighted by the coordinates ``X = x - origin[0]``, ``Y = y - origin[1]`` of
+        the quadrature point (``plfem_moment_grams``), each (k, k): ``M_core_X``, ``M_core_Y``, ``M_clad_X``, ``M_clad_Y``
+        (``M_r_X[m, n] = sum over region r of X u_m . u_n``), for vectorial records also ``K_core_X``, ``K_core_Y``,
+        ``K_clad_X``, ``K_clad_Y`` (the form of ``K_r``), and the second moments ``M_XX``, ``M_XY``, ``M_YY`` over both
+        regions.  A bend enters both pencils linearly in the curvature through exactly these (:mod:`.bend`)."""
+        kind, vals, _ = self._check_records(modes)
+        cores = self._cores(geometry)
+        o = self._origin(origin)
+        k = 0 if kind is None else vals.shape[1]
+        if k == 0:
+            return {nm: np.zeros((0, 0)) for nm in MOMENT_GRAM_NAMES.get(kind, ())}
+        self._ensure_locator()
+        staged, _src = self._stage(vals)
+        return self._moment_grams_staged(kind, staged, cores, o)
+
+    def _moment_grams_staged(self, kind, staged, cores, origin) -> Dict[str, np.ndarray]:
+        """``plfem_moment_grams`` on modes already staged (ncomp, n, k) on the device."""
+        names = MOMENT_GRAM_NAMES[kind]
+        ncomp, _, k = staged.shape
+        need = ctypes.c_int64(0)
+        if self._lib.plfem_moment_gram_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
+            raise ValueError(f"plfem_moment_gram_work_bytes rejected ncomp = {ncomp}, k = {k}")
+        work = _native.device_scratch(int(need.value) + 256, self.tdev)
+        aligned = (work.data_ptr() + 255) & ~255
+        out = np.empty((len(names), k, k), dtype=np.float64)
+        self._check(self._lib.plfem_moment_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
+                                                 1 if kind == "vectorial" else 0, cores.ctypes.data_as(ctypes.c_void_p),
+                                                 cores.shape[0], origin.ctypes.data_as(ctypes.c_void_p),
+                                                 ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
+                                                 out.ctypes.data_as(ctypes.c_void_p)), "plfem_moment_grams")
+        return {nm: out[i] for i, nm in enumerate(names)}
+
     def quartic(self, modes: Sequence[Dict], geometry=None, weights=(1.0, 1.0)) -> np.ndarray:
         """Packed quartic overlap of the modes over this mesh (``plfem_mode_quartic``), np x np with np = k (k + 1) / 2:
         ``Q[p(i,j), p(l,m)] = sum over the elements and the 16-point degree-8 rule of |det J| w_q wt(x_q) (u_i . u_j)
@@ -497,4 +546,5 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
     return O * O / (daa[:, None] * dbb[None, :])
 
 
-__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "PROJECT_TILE", "PROJECT_MAX_FACTORS"]
+__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES",
+           "PROJECT_TILE", "PROJECT_MAX_FACTORS"]
