@@ -146,6 +146,25 @@ int plfem_assemble_hfield(plfem_ctx* ctx, const double* cores_host, int32_t ncor
 int plfem_assemble_scalar(plfem_ctx* ctx, const double* cores_host, int32_t ncore, double eps_core,
                           double eps_clad, double k0);
 
+/* Index profile: a permittivity map beyond "discs of one eps_core on eps_clad" -- cladding plus jacket, trenches and
+ * rings, graded cores, cores of unequal index.  A profile is a background permittivity eps_bg and an ordered table of
+ * at most 64 layers of 8 doubles, layers_host[l][8] = (cx, cy, r_in, r_out, eps_a, eps_b, g, 0):
+ *   membership: with dx = x - cx, dy = y - cy and d2 = fl(dx dx) + fl(dy dy), the point is in the layer when
+ *     fl(r_in r_in) <= d2 <= fl(r_out r_out), every product rounded on its own (the arithmetic of the core test: a layer
+ *     with r_in = 0 is the closed disc of plfem_assemble_hfield, ties included);
+ *   value: g = 0: eps_a;  g > 0: eps_a + fl((eps_b - eps_a) t^g), t = (sqrt(d2) - r_in) / (r_out - r_in) clamped to
+ *     [0, 1] (the alpha-profile n^2(rho) = n0^2 + (n_edge^2 - n0^2) (rho / a)^alpha);
+ *   order: a later layer overwrites an earlier one; a point in no layer has eps_bg.
+ * While a profile is set (nlayer > 0), plfem_assemble_hfield, plfem_assemble_scalar and plfem_solve_modes on this context
+ * weigh every quadrature point with 1 / eps (the division made on the device, IEEE) -- eps in the scalar pencil -- of
+ * the profile at the point as the assembly forms it, and do not read their eps_core / eps_clad.  Their cores argument
+ * keeps its meaning: the discs the in-core sums of the post-processing count.  plfem_cmt_coupling does not read the
+ * profile.  nlayer = 0 clears the profile (layers_host and eps_bg are then not read).  The table is copied to a device
+ * buffer of the context; the call synchronises the context's stream.
+ * PLFEM_EINVAL, with the context's last error set: nlayer outside [0, 64]; a null table with nlayer > 0; a non-finite
+ * entry or eps_bg; r_in < 0; r_out <= r_in; eps_a, eps_b or eps_bg <= 0; g < 0. */
+int plfem_set_index_profile(plfem_ctx* ctx, const double* layers_host, int32_t nlayer, double eps_bg);
+
 /* Coupled-mode coupling integrals, scalar context only.
  * Replaces: the epsilon_product form + asm() and the E_i^H M_eps E_j loop of
  *           CoupledModeTheory._compute_rigorous_coupling                      reference config.py:296-320
@@ -354,6 +373,25 @@ int plfem_field_overlap(plfem_locator* loc_a, const double* modes_a_dev, int32_t
 int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes);
 int plfem_mode_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
                      const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host);
+
+/* Grams of a profile solve: the forms of plfem_mode_grams with the permittivity of an index profile (layers_host, nlayer,
+ * eps_bg as for plfem_set_index_profile; nlayer in [0, 64], eps_bg always read) in place of the two regions.  With
+ * w = 1 / eps (ncomp = 2) or w = eps (ncomp = 1) of the profile at the quadrature point as the assembly forms it, every
+ * sum over the six-point rule with |det J| w_q:
+ *   ncomp = 2: out_host[0..3][k][k] = M, M_w, K_w, D with M[m][n] = sum hx_m hx_n + hy_m hy_n, M_w the same under w, K_w
+ *     the form of K_r under w and D as in plfem_mode_grams, so that V^T A V = K_w + alpha_p D - k0^2 M, V^T B V = M_w;
+ *   ncomp = 1: out_host[0..2][k][k] = M, M_w, S, so that V^T A V = S - k0^2 M_w, V^T B V = M.
+ * Grid, tiling and second stage of plfem_mode_grams: the same bits on every run, for a subset or a permutation of the
+ * modes, and whatever the work buffer held before.  The table is copied to a device buffer of the locator; synchronises
+ * the locator's stream.
+ * work_dev: device scratch of plfem_profile_gram_work_bytes(ncomp, k) bytes, 256-byte aligned: nout k^2 doubles plus
+ * nout ceil(k / 32)^2 x 768 partial blocks of 8 KiB, nout = 4 or 3.
+ * Argument errors (ncomp not 1 or 2, k < 1, a table plfem_set_index_profile rejects, eps_bg not finite and positive, a
+ * null pointer, work_bytes too small) return PLFEM_EINVAL with the locator's last error set. */
+int plfem_profile_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes);
+int plfem_profile_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                        const double* layers_host, int32_t nlayer, double eps_bg, void* work_dev, int64_t work_bytes,
+                        double* out_host);
 
 /* Per-core Grams: the Grams of k staged modes (staged and indexed as for plfem_mode_grams) over the quadrature points of
  * the mesh's own six-point rule that each core disc owns (ncore in [1, 64]; every sum is over the points of core c of

@@ -7,7 +7,9 @@ from .nonlinear import mode_nonlinearity  # noqa: F401
 from .launch import encircled_na, far_field, gaussian_coupling  # noqa: F401
 from .cores import core_decomposition, core_quantities_from_grams  # noqa: F401
 from .bend import bend_propagate, bend_quantities_from_grams, bend_response  # noqa: F401
+from .profile import IndexProfile, ProfiledGeometry  # noqa: F401
 
 __all__ = ["MCFGeometry", "PhotonicLanternGeometry", "mcf_positions", "TriMesh", "generate_mesh", "ModeFields", "mode_overlap",
            "mode_dispersion", "mode_nonlinearity", "far_field", "encircled_na", "gaussian_coupling", "core_decomposition",
-           "core_quantities_from_grams", "bend_response", "bend_quantities_from_grams", "bend_propagate"]
+           "core_quantities_from_grams", "bend_response", "bend_quantities_from_grams", "bend_propagate", "IndexProfile",
+           "ProfiledGeometry"]

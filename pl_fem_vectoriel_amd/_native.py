@@ -41,6 +41,7 @@ EXPORTS = (
     "plfem_sample_fields", "plfem_overlap_work_bytes", "plfem_field_overlap", "plfem_gram_work_bytes", "plfem_mode_grams",
     "plfem_quartic_work_bytes", "plfem_mode_quartic", "plfem_project_work_bytes", "plfem_mode_project",
     "plfem_core_gram_work_bytes", "plfem_core_grams", "plfem_moment_gram_work_bytes", "plfem_moment_grams",
+    "plfem_set_index_profile", "plfem_profile_gram_work_bytes", "plfem_profile_grams",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -231,6 +232,11 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_moment_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]
+    lib.plfem_set_index_profile.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]
+    lib.plfem_profile_gram_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
+    lib.plfem_profile_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_void_p]
     lib.plfem_quartic_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
     lib.plfem_mode_quartic.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
@@ -459,6 +465,19 @@ class Context:
         return device_output(shape, self.torch.float64, self.tdev)
 
     # -- C-ABI calls ------------------------------------------------------------------------------
+    def set_index_profile(self, profile=None):
+        """``plfem_set_index_profile``: the assembly calls and ``solve_modes`` of this context take their permittivity
+        from ``profile`` (an object with ``table()`` (nlayer, 8) and ``eps_background``: ``profile.IndexProfile``) until the
+        next call; ``None``: back to their own ``eps_core`` / ``eps_clad``."""
+        if profile is None:
+            self._check(self._lib.plfem_set_index_profile(self._h, None, 0, 0.0), "plfem_set_index_profile")
+            return
+        t = np.ascontiguousarray(np.asarray(profile.table(), dtype=np.float64).reshape(-1, 8))
+        if t.shape[0] == 0:
+            raise ValueError("plfem_set_index_profile: the profile has no layers")
+        self._check(self._lib.plfem_set_index_profile(self._h, _ptr(t), t.shape[0], float(profile.eps_background)),
+                    "plfem_set_index_profile")
+
     def assemble(self, cores, eps_core, eps_clad, k0, alpha_p=1.0):
         c, n = self._cores(cores)
         self._check(self._lib.plfem_assemble_hfield(self._h, _ptr(c), n, float(eps_core), float(eps_clad),

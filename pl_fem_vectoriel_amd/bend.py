@@ -28,6 +28,7 @@ import scipy.linalg
 from .cores import _cluster_members, _directional_dmu, _sym
 from .dispersion import _clusters
 from .fields import ModeFields, _records
+from .profile import reject_profile
 from .solver_fem import TrueVectorialMaxwellSolver
 
 
@@ -177,6 +178,7 @@ def bend_response(modes: Sequence[Dict], mesh, geometry, radius=None, angle=0.0,
     ``grams`` and ``moment_grams``.  ``ValueError`` when ``2 |kappa| max |Xt|`` over the mesh's bounding box reaches 1: the
     first-order bent permittivity would change sign inside the section.  The records are not mutated.  Argument errors
     raise ``ValueError`` before any device call."""
+    reject_profile(geometry, "bend_response")
     kind, _, beta = _records(modes)
     if kind is None:
         raise ValueError("no mode records")

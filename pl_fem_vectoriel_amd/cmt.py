@@ -19,6 +19,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import _native
+from .profile import reject_profile
 from .solver_fem import _core_table
 
 
@@ -38,6 +39,7 @@ class CoupledModeTheory:
         reference passes the scikit-fem ``Basis`` of that mesh)."""
         import torch
 
+        reject_profile(geometry, "CoupledModeTheory._compute_rigorous_coupling")
         mesh = getattr(basis, "mesh", basis)
         n = len(modes_i)
         if len(modes_j) != n:
@@ -58,6 +60,7 @@ class CoupledModeTheory:
         try:
             di = torch.from_numpy(Ei.astype(np.float64)).to(ctx.tdev)
             dj = torch.from_numpy(Ej.astype(np.float64)).to(ctx.tdev)
+            ctx.set_index_profile(None)
             raw, Pi, Pj, mean = ctx.cmt_coupling(di, dj, _core_table(geometry), geometry.n_core ** 2, geometry.n_clad ** 2)
         finally:
             ctx.close()

@@ -29,6 +29,7 @@ import scipy.linalg
 
 from .dispersion import _clusters
 from .fields import ModeFields, _records
+from .profile import reject_profile
 from .solver_fem import TrueVectorialMaxwellSolver
 
 
@@ -175,6 +176,7 @@ def core_decomposition(modes: Sequence[Dict], mesh, geometry, n_cores=None, dire
     k x k host math.  Also returned: ``points`` (ncore,) the quadrature points each core owns (a point in several discs
     belongs to the highest-index one, as in the reference's ``epsilon``), ``grams`` and ``core_grams``.  The records are
     not mutated.  Argument errors raise ``ValueError`` before any device call."""
+    reject_profile(geometry, "core_decomposition")
     kind, _, beta = _records(modes)
     if kind is None:
         raise ValueError("no mode records")

@@ -340,6 +340,7 @@ int place_buffers(plfem_ctx* c, int max_ncv, Placement& pl) {
   // two halves of post_doubles each: the post-processing, and the residual check in flight beside it
   c->post_doubles = std::max(plfem::post_sum_doubles(S.N, (int)nc1), plfem::resid_sum_doubles(S.N, (int)nc1)) + 16;
   TRY(dalloc(c, &c->d_post, 2 * c->post_doubles));
+  TRY(dalloc(c, &c->d_layers, (size_t)plfem::MAX_LAYERS * plfem::LAYER_DOUBLES));   // (last: no other buffer moves)
   return PLFEM_OK;
 }
 
@@ -488,7 +489,8 @@ namespace {
 template <class ElementMatrices>
 int assemble(plfem_ctx* c, const double* cores_host, int ncore, double eps_core, double eps_clad, const char* what,
              ElementMatrices element_matrices) {
-  if (!(eps_core > 0) || !(eps_clad > 0)) { c->err = "permittivities must be positive"; return PLFEM_EINVAL; }
+  // (with an index profile set, eps_core and eps_clad are not read)
+  if (c->nlayer == 0 && (!(eps_core > 0) || !(eps_clad > 0))) { c->err = "permittivities must be positive"; return PLFEM_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(upload_cores(c, cores_host, ncore));
   HIP_TRY(c, phase_begin(c, plfem::PH_ASSEMBLE));
@@ -501,6 +503,26 @@ int assemble(plfem_ctx* c, const double* cores_host, int ncore, double eps_core,
   return PLFEM_OK;
 }
 }  // namespace
+
+extern "C" int plfem_set_index_profile(plfem_ctx* c, const double* layers_host, int32_t nlayer, double eps_bg) try {
+  if (!c) return PLFEM_EINVAL;
+  if (nlayer == 0) { c->nlayer = 0; return PLFEM_OK; }      // back to the step model of the assembly calls' own arguments
+  if (const char* bad = plfem::profile_table_error(layers_host, nlayer, eps_bg)) {
+    c->err = std::string("plfem_set_index_profile: ") + bad;
+    return PLFEM_EINVAL;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = sizeof(double) * plfem::LAYER_DOUBLES * nlayer;
+  double* pin = c->h_pinned + plfem::PIN_LAYERS;
+  // whatever was queued before may still read the old table, and the pinned block must be free for the next call:
+  // the copy goes behind that work on the context's stream and is waited for
+  std::memcpy(pin, layers_host, bytes);
+  HIP_TRY(c, hipMemcpyAsync(c->d_layers, pin, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->nlayer = nlayer;
+  c->eps_bg = eps_bg;
+  return PLFEM_OK;
+} catch (...) { return host_failure(c); }
 
 extern "C" int plfem_assemble_hfield(plfem_ctx* c, const double* cores_host, int32_t ncore, double eps_core,
                                      double eps_clad, double k0, double alpha_p) try {

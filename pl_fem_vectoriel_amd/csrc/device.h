@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <string>
@@ -24,13 +25,15 @@ constexpr size_t PIN_CORE_QP = 4000;   // one u64: quadrature points inside a co
 constexpr size_t PIN_COUNTERS = 4096;
 constexpr int PIN_COUNTERS_N = 2 * 4;  // int32 entries
 constexpr size_t PIN_CORES = 6144;     // core table, 3 MAX_CORES (upload_cores)
+constexpr size_t PIN_LAYERS = 6400;    // layer table of an index profile, LAYER_DOUBLES MAX_LAYERS (plfem_set_index_profile)
 // projected matrix (max_ncv + 2 + BLOCK_P)^2: d_Hcols mirror, restart / Ritz rotation matrices; h_slots behind it
 constexpr size_t PIN_PROJ = 8192;
 static_assert(PIN_POST + 5 * PLFEM_MAX_NCV <= PIN_RESID, "pinned layout: post-processing sums");
 static_assert(PIN_RESID + 3 * PLFEM_MAX_NCV <= PIN_CORE_QP, "pinned layout: residual check");
 static_assert(PIN_CORE_QP + 1 <= PIN_COUNTERS, "pinned layout: core-point counter");
 static_assert(PIN_COUNTERS + PIN_COUNTERS_N * sizeof(int32_t) / sizeof(double) <= PIN_CORES, "pinned layout: counters");
-static_assert(PIN_CORES + 3 * MAX_CORES <= PIN_PROJ, "pinned layout: core table");
+static_assert(PIN_CORES + 3 * MAX_CORES <= PIN_LAYERS, "pinned layout: core table");
+static_assert(PIN_LAYERS + LAYER_DOUBLES * MAX_LAYERS <= PIN_PROJ, "pinned layout: layer table");
 
 // Phases of a context timed on the device by an event pair each (plfem_timings, the *_us entries of plfem_solve_modes)
 enum Phase { PH_ASSEMBLE, PH_FACTOR, PH_LANCZOS, PH_POST, PH_UPLOAD, PH_RESIDUAL, PH_COUNT };
@@ -82,6 +85,9 @@ struct plfem_ctx {
   int32_t *d_epos = nullptr, *d_leaf_elem_ptr = nullptr, *d_leaf_elems = nullptr;
   // ---- numeric data
   double* d_cores = nullptr;      // [64][3]
+  double* d_layers = nullptr;     // [64][8] layer table of the index profile (plfem_set_index_profile)
+  int nlayer = 0;                 // > 0: the assembly takes its permittivity from the profile, not from eps_core / eps_clad
+  double eps_bg = 0.0;            // the profile's background permittivity
   double* d_elem = nullptr;       // [ne][8][36]
   double* d_vals[PLFEM_BLK_COUNT] = {nullptr};
   double* d_front = nullptr;      // what a front keeps: [F11; F21] (m x s2) and Z^T (s2 x b2), see symbolic.h
@@ -216,6 +222,24 @@ inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline int basis_cols(int max_ncv) { return max_ncv + 1 + BLOCK_P; }
 // column capacity of the projected-matrix blocks d_h, d_hacc, d_hblk and of one panel dot (its partials in d_partial)
 inline int proj_cols(int max_ncv) { return basis_cols(max_ncv) + 8; }
+
+// An index profile as the C ABI takes it (plfem_set_index_profile, plfem_profile_grams): nullptr if the table is
+// acceptable, otherwise what is wrong with it
+inline const char* profile_table_error(const double* layers, int nlayer, double eps_bg) {
+  if (nlayer < 0 || nlayer > MAX_LAYERS) return "nlayer must be in [0, 64]";
+  if (nlayer > 0 && !layers) return "null layer table";
+  if (!std::isfinite(eps_bg) || !(eps_bg > 0.0)) return "the background permittivity must be finite and positive";
+  for (int l = 0; l < nlayer; ++l) {
+    const double* p = layers + LAYER_DOUBLES * l;
+    for (int j = 0; j < LAYER_DOUBLES; ++j)
+      if (!std::isfinite(p[j])) return "every layer entry must be finite";
+    if (p[2] < 0.0) return "r_in must be >= 0";
+    if (!(p[3] > p[2])) return "r_out must be > r_in";
+    if (!(p[4] > 0.0) || !(p[5] > 0.0)) return "permittivities must be positive";
+    if (p[6] < 0.0) return "g must be >= 0";
+  }
+  return nullptr;
+}
 
 // kernels_assembly.hip
 void launch_element_matrices(plfem_ctx* c, int ncore, double eps_core, double eps_clad, double k0, double alpha_p);

@@ -15,6 +15,11 @@ constexpr int EPB = 7;   // elements per 256-thread block: 7*36 = 252 (i,j) pair
 // gradients of the six P2 basis functions and the two quadrature weights (plain and 1/eps) in LDS;
 // phase 2 (element, local pair) lanes reduce the six quadrature points into the eight element
 // matrices the pencil needs and store them as contiguous 288-B runs.
+// PROFILE = false: the step model, a point in a core disc weighs inv_eps_core and any other inv_eps_clad.  PROFILE = true
+// (plfem_set_index_profile): the same argument list carries the profile -- cores = the layer table, ncore = the number of
+// layers, inv_eps_clad = eps_bg (inv_eps_core is not read) -- and the weight is 1 / profile_eps (scalar: profile_eps)
+// at the point, the division made here.
+template <bool PROFILE>
 __global__ __launch_bounds__(256) void k_element_matrices(
     int ne, int N, const int32_t* __restrict__ tsorted, const double* __restrict__ doflocs,
     const double* __restrict__ cores, int ncore, double inv_eps_core, double inv_eps_clad, double k0sq,
@@ -41,7 +46,12 @@ __global__ __launch_bounds__(256) void k_element_matrices(
       M.point(xi, eta, X, Y);
       double w1 = fabs(det) * c_qw[q];
       s_w1[el][q] = w1;
-      s_we[el][q] = w1 * (in_any_core(X, Y, cores, ncore) ? inv_eps_core : inv_eps_clad);
+      if constexpr (PROFILE) {
+        const double eps = profile_eps(X, Y, cores, ncore, inv_eps_clad);
+        s_we[el][q] = w1 * (scalar ? eps : 1.0 / eps);
+      } else {
+        s_we[el][q] = w1 * (in_any_core(X, Y, cores, ncore) ? inv_eps_core : inv_eps_clad);
+      }
       p2_grad(inv, xi, eta, gx, gy);
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
@@ -415,15 +425,27 @@ __global__ __launch_bounds__(256) void k_spmv_a_block(int N, int64_t ld, const i
 
 }  // namespace
 
+// (with an index profile set on the context -- c->nlayer > 0 -- both take the profile instance and do not read
+// ncore, eps_core, eps_clad)
 void launch_element_matrices(plfem_ctx* c, int ncore, double eps_core, double eps_clad, double k0, double alpha_p) {
   int grid = (c->ne + EPB - 1) / EPB;
-  hipLaunchKernelGGL(k_element_matrices, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
+  if (c->nlayer > 0) {
+    hipLaunchKernelGGL(k_element_matrices<true>, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
+                       c->d_doflocs, c->d_layers, c->nlayer, 0.0, c->eps_bg, k0 * k0, alpha_p, 0, c->d_elem);
+    return;
+  }
+  hipLaunchKernelGGL(k_element_matrices<false>, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
                      c->d_doflocs, c->d_cores, ncore, 1.0 / eps_core, 1.0 / eps_clad, k0 * k0, alpha_p, 0, c->d_elem);
 }
 
 void launch_element_matrices_scalar(plfem_ctx* c, int ncore, double eps_core, double eps_clad, double k0) {
   int grid = (c->ne + EPB - 1) / EPB;
-  hipLaunchKernelGGL(k_element_matrices, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
+  if (c->nlayer > 0) {
+    hipLaunchKernelGGL(k_element_matrices<true>, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
+                       c->d_doflocs, c->d_layers, c->nlayer, 0.0, c->eps_bg, k0 * k0, 0.0, 1, c->d_elem);
+    return;
+  }
+  hipLaunchKernelGGL(k_element_matrices<false>, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
                      c->d_doflocs, c->d_cores, ncore, eps_core, eps_clad, k0 * k0, 0.0, 1, c->d_elem);
 }
 
@@ -440,7 +462,7 @@ double launch_delta_eps_mass(plfem_ctx* c, int ncore, double eps_core, double ep
   const double frac = (double)*h / (double)nq;
   const double mean = eps_clad + (eps_core - eps_clad) * frac;
   int grid = (c->ne + EPB - 1) / EPB;
-  hipLaunchKernelGGL(k_element_matrices, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
+  hipLaunchKernelGGL(k_element_matrices<false>, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
                      c->d_doflocs, c->d_cores, ncore, eps_core - mean, eps_clad - mean, 0.0, 0.0, 2, c->d_elem);
   launch_csr_gather(c);
   (void)hipMemsetAsync(cnt, 0, sizeof(unsigned long long), c->stream);     // counters[2] is the Lanczos rank flag

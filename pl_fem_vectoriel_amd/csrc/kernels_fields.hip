@@ -6,7 +6,8 @@
 // set on a family of analytic fields that separate in x and y -- plane waves and Gaussian beams -- on the same rule
 // (k_mode_project + k_project_reduce), and the Grams of a mode set restricted to each core disc (k_core_owner,
 // k_core_count + k_core_fill, k_core_grams + k_overlap_reduce), and the region Grams weighted by the coordinates of the
-// quadrature point (k_moment_grams + k_overlap_reduce).
+// quadrature point (k_moment_grams + k_overlap_reduce), and the Grams under the permittivity of an index profile
+// (k_profile_grams + k_overlap_reduce).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
@@ -30,6 +31,7 @@ struct plfem_locator {
   int nx = 0, ny = 0;
   int32_t *d_cell_ptr = nullptr, *d_cell_elems = nullptr, *d_edof = nullptr, *d_int_index = nullptr;
   double* d_pxy = nullptr;                     // [2][nv] vertex coordinates
+  double* d_layers = nullptr;                  // [64][8] layer table of the profile of the call in flight (plfem_profile_grams)
 };
 
 namespace plfem {
@@ -572,6 +574,80 @@ __global__ __launch_bounds__(256) void k_core_grams(LocArgs L, int k, int64_t nr
       for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
   }
 }
+
+// Grams of a profile solve (plfem_profile_grams): the forms of k_mode_grams with the permittivity of an index profile in
+// place of the two regions.  Grid, tiling, staging and features as in k_mode_grams; the staging lane evaluates
+// profile_eps (p2_element.h) at its point, as the profile instance of k_element_matrices does, and puts the point's
+// weight -- ncomp = 2: 1 / eps, the division made here; ncomp = 1: eps; 1 for a padding point, whose features are 0 --
+// into LDS.  The weight is the same for every lane and enters as GRAM_ACC's factor, so every product is written out:
+// (w a) b + acc, the same for the four entries of a lane's block.  Outputs (ncomp = 2): M, M_w, K_w, D; (ncomp = 1):
+// M, M_w, S, with M the unweighted u . u' and K, D, S the forms of k_mode_grams.  The layer table is read at indices
+// the workgroup shares (uniform loads) by the GT staging lanes only.
+template <int NCOMP>
+__global__ __launch_bounds__(256) void k_profile_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
+                                                       const double* __restrict__ layers, int nlayer, double eps_bg, int nchunk,
+                                                       double* __restrict__ partial) {
+  constexpr int NF = 3 * NCOMP;
+  constexpr int NOUT = NCOMP == 2 ? 4 : 3;
+  __shared__ double s_f[2][NF][GT][OC];
+  __shared__ double s_gx[6][GT], s_gy[6][GT];
+  __shared__ int s_r[6][GT];
+  __shared__ double s_w[GT], s_wt[GT];        // |det J| w_q, and the material weight of the point
+  __shared__ int s_q[GT];
+  const int tid = threadIdx.x;
+  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
+  const int i0 = ci * OC, j0 = cj * OC;
+  const int64_t nq = (int64_t)6 * L.ne;
+  const int64_t ntiles = (nq + GT - 1) / GT;
+  const int ti = tid >> 4, tj = tid & 15;
+  double acc[NOUT][2][2];
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < GT) {
+      const int64_t g = tile * GT + tid;
+      double wt = 1.0;
+      gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q, [&](double X, double Y) {
+        const double eps = profile_eps(X, Y, layers, nlayer, eps_bg);
+        wt = NCOMP == 2 ? 1.0 / eps : eps;
+      });
+      s_wt[tid] = wt;
+    }
+    __syncthreads();
+    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < GT; ++t) {
+      double2 a[NF], b[NF];
+#pragma unroll
+      for (int c = 0; c < NF; ++c) {
+        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
+        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
+      }
+      const double w = s_wt[t];                 // the same for every lane
+      if constexpr (NCOMP == 2) {
+        // features 0 hx, 1 hy, 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy
+        GRAM_ACC(0, 0, 0, 1.0) GRAM_ACC(0, 1, 1, 1.0)
+        GRAM_ACC(1, 0, 0, w) GRAM_ACC(1, 1, 1, w)
+        GRAM_ACC(2, 3, 3, w) GRAM_ACC(2, 4, 4, w) GRAM_ACC(2, 2, 5, -w) GRAM_ACC(2, 5, 2, -w)
+        GRAM_ACC(3, 2, 2, 1.0) GRAM_ACC(3, 5, 5, 1.0) GRAM_ACC(3, 3, 4, 1.0) GRAM_ACC(3, 4, 3, 1.0)
+      } else {
+        // features 0 u, 1 dx u, 2 dy u
+        GRAM_ACC(0, 0, 0, 1.0)
+        GRAM_ACC(1, 0, 0, w)
+        GRAM_ACC(2, 1, 1, 1.0) GRAM_ACC(2, 2, 2, 1.0)
+      }
+    }
+    __syncthreads();
+  }
+  const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) {
+    double* out = partial + (((int64_t)o * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+    for (int r = 0; r < 2; ++r)
+      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
+  }
+}
 #undef GRAM_ACC
 
 // Coordinate-weighted Grams (plfem_moment_grams): the M_r (and K_r) of k_mode_grams weighted by the point's X = x - ox,
@@ -979,7 +1055,7 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 using namespace plfem;
 
 namespace {
-struct LocLayout { size_t off_ptr, off_elems, off_edof, off_idx, off_pxy, total; };
+struct LocLayout { size_t off_ptr, off_elems, off_edof, off_idx, off_pxy, off_layers, total; };
 LocLayout loc_layout(const Symbolic& S) {
   LocLayout l;
   size_t o = 0;
@@ -988,6 +1064,7 @@ LocLayout loc_layout(const Symbolic& S) {
   l.off_edof = o;  o += align256((size_t)6 * S.ne * sizeof(int32_t));
   l.off_idx = o;   o += align256((size_t)S.N * sizeof(int32_t));
   l.off_pxy = o;   o += align256((size_t)2 * S.nv * sizeof(double));
+  l.off_layers = o; o += align256((size_t)MAX_LAYERS * LAYER_DOUBLES * sizeof(double));
   l.total = o;
   return l;
 }
@@ -1024,6 +1101,7 @@ extern "C" int plfem_locator_create(const plfem_symbolic* sym, int32_t device, v
   L->d_edof = (int32_t*)(base + lay.off_edof);
   L->d_int_index = (int32_t*)(base + lay.off_idx);
   L->d_pxy = (double*)(base + lay.off_pxy);
+  L->d_layers = (double*)(base + lay.off_layers);
   // vertex coordinates = the first nv entries of both doflocs rows
   std::vector<double> pxy((size_t)2 * S.nv);
   std::memcpy(pxy.data(), S.doflocs.data(), sizeof(double) * S.nv);
@@ -1172,6 +1250,12 @@ WorkLayout gram_layout(int ncomp, int k) {
   const size_t nout = gram_outputs(ncomp), nc = overlap_chunks(k);
   return work_layout(nout * k * k, nout * nc * nc * GRAM_BLOCKS * OC * OC);
 }
+// plfem_profile_grams: the same grid, 4 or 3 outputs
+int profile_gram_outputs(int ncomp) { return ncomp == 2 ? 4 : 3; }
+WorkLayout profile_gram_layout(int ncomp, int k) {
+  const size_t nout = profile_gram_outputs(ncomp), nc = overlap_chunks(k);
+  return work_layout(nout * k * k, nout * nc * nc * GRAM_BLOCKS * OC * OC);
+}
 // plfem_moment_grams: the same grid, 7 or 11 outputs
 int moment_gram_outputs(int ncomp) { return ncomp == 2 ? 11 : 7; }
 WorkLayout moment_gram_layout(int ncomp, int k) {
@@ -1211,6 +1295,43 @@ extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
                        modes_dev, ct, (int)ncore, nc, partial);
   });
   TRY(check_launch(L, "k_mode_grams"));
+  return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
+} catch (...) { return host_failure(L); }
+
+extern "C" int plfem_profile_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
+  if (!bytes || ncomp < 1 || ncomp > 2 || k <= 0) return PLFEM_EINVAL;
+  *bytes = (int64_t)profile_gram_layout(ncomp, k).total;
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_profile_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                   const double* layers_host, int32_t nlayer, double eps_bg, void* work_dev, int64_t work_bytes,
+                                   double* out_host) try {
+  if (!L) return PLFEM_EINVAL;
+  if (ncomp < 1 || ncomp > 2 || k <= 0) { L->err = "plfem_profile_grams: ncomp must be 1 or 2 and k > 0"; return PLFEM_EINVAL; }
+  if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) {
+    L->err = std::string("plfem_profile_grams: ") + bad;
+    return PLFEM_EINVAL;
+  }
+  if (!modes_dev || !work_dev || !out_host) { L->err = "plfem_profile_grams: null array"; return PLFEM_EINVAL; }
+  if (indexed && L->nsolve == 0) { L->err = "plfem_profile_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  const WorkLayout lay = profile_gram_layout(ncomp, k);
+  TRY(check_work(L, "plfem_profile_grams", "plfem_profile_gram_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
+  HIP_TRY(L, hipSetDevice(L->device));
+  // (every call of a locator that reads the table ends with a stream synchronisation: nothing in flight reads the old one)
+  if (nlayer > 0)
+    HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
+  const int nout = profile_gram_outputs(ncomp), nc = overlap_chunks(k);
+  const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
+  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ntiles));   // (no function of k)
+  const int64_t nrows = indexed ? L->nsolve : L->N;
+  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
+  const dim3 grid(nblk, nc * nc);
+  with_constant<2, 1>(ncomp, [&](auto nco) {
+    hipLaunchKernelGGL(k_profile_grams<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k,
+                       nrows, modes_dev, L->d_layers, (int)nlayer, eps_bg, nc, partial);
+  });
+  TRY(check_launch(L, "k_profile_grams"));
   return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
 } catch (...) { return host_failure(L); }
 

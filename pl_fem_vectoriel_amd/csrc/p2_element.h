@@ -1,11 +1,11 @@
 // The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
 // integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
-// k_field_overlap, k_mode_grams, k_mode_quartic, k_mode_project, k_core_owner).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// k_field_overlap, k_mode_grams, k_profile_grams, k_mode_quartic, k_mode_project, k_core_owner).  One definition, so that a quadrature point lands in the same region, and det J rounds
 // the same way, in the assembly and in every kernel that must reproduce it.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "plan.h"   // MAX_CORES
+#include "plan.h"   // MAX_CORES, LAYER_DOUBLES
 
 namespace plfem {
 
@@ -130,6 +130,32 @@ __device__ __forceinline__ int core_owner(double X, double Y, const double* core
     if (mul_rn(dx, dx) + mul_rn(dy, dy) <= mul_rn(r, r)) owner = c;
   }
   return owner;
+}
+
+// Permittivity of an index profile at a point: eps_bg overwritten by every layer that holds the point, in table order
+// (a later layer wins, as a later disc does above).  Layer l = layers[8 l .. 8 l + 7] = (cx, cy, r_in, r_out, eps_a,
+// eps_b, g, 0): the point is in the layer when r_in^2 <= d2 <= r_out^2, the squared distance and the squares formed as
+// in in_any_core, so a layer with r_in = 0 is that closed disc, ties included.  g = 0: the value is eps_a; g > 0: the
+// alpha-profile eps_a + (eps_b - eps_a) t^g, t = (sqrt(d2) - r_in) / (r_out - r_in) clamped to [0, 1], the product
+// rounded on its own (IndexProfile.epsilon of profile.py is this, operation for operation).  The table is read at
+// indices every lane shares: uniform loads.
+__device__ __forceinline__ double profile_eps(double X, double Y, const double* __restrict__ layers, int nlayer, double eps_bg) {
+  double eps = eps_bg;
+  for (int l = 0; l < nlayer; ++l) {
+    const double* p = layers + LAYER_DOUBLES * l;
+    const double dx = X - p[0], dy = Y - p[1], r_in = p[2], r_out = p[3];
+    const double d2 = mul_rn(dx, dx) + mul_rn(dy, dy);
+    if (mul_rn(r_in, r_in) <= d2 && d2 <= mul_rn(r_out, r_out)) {
+      const double eps_a = p[4], g = p[6];
+      if (g > 0.0) {
+        const double t = fmin(fmax((sqrt(d2) - r_in) / (r_out - r_in), 0.0), 1.0);
+        eps = eps_a + mul_rn(p[5] - eps_a, pow(t, g));
+      } else {
+        eps = eps_a;
+      }
+    }
+  }
+  return eps;
 }
 
 }  // namespace

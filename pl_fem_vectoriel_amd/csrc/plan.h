@@ -61,6 +61,10 @@ inline int bwd_block_rows(int count, bool leaf) { return leaf ? 64 : count <= RO
 // measured and dropped)
 constexpr int BLOCK_P = 4;
 constexpr int MAX_CORES = 64;   // capacity of the core tables (d_cores, CoreTable): 3 doubles (x, y, r) per core
+// index profile (plfem_set_index_profile, plfem_profile_grams): at most MAX_LAYERS layers of LAYER_DOUBLES doubles
+// (cx, cy, r_in, r_out, eps_a, eps_b, g, 0), read by profile_eps (p2_element.h)
+constexpr int MAX_LAYERS = 64;
+constexpr int LAYER_DOUBLES = 8;
 constexpr int ELEM_FORMS = 8;   // Axx Axy Ayx Ayy Minv Dxx Dxy Dyy
 constexpr int ELEM_STRIDE = ELEM_FORMS * 36;
 

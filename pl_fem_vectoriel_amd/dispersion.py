@@ -21,6 +21,7 @@ import numpy as np
 import scipy.linalg
 
 from .fields import ModeFields, _records
+from .profile import reject_profile
 from .solver_fem import TrueVectorialMaxwellSolver
 
 C_M_PER_S = 299792458.0
@@ -123,6 +124,7 @@ def mode_dispersion(modes: Sequence[Dict], mesh, geometry, dn_dlambda=(0.0, 0.0)
     members; in-cluster coupling is 0), ``rayleigh_defect`` |h^T A h - mu| / |mu| (mu = beta^2 or -beta^2; the check that
     regions and forms match the solver's pencil) and ``grams``.  The records are not mutated.  Argument errors raise
     ``ValueError`` before any device call."""
+    reject_profile(geometry, "mode_dispersion")
     kind, _, beta = _records(modes)
     if kind is None:
         raise ValueError("no mode records")

@@ -30,11 +30,13 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native
+from .profile import index_profile_of, reject_profile
 from .solver_fem import _core_table, mesh_key
 
 LOC_TOL = 1e-10                    # PLFEM_LOC_TOL of include/plfem.h
 GRAM_NAMES = {"vectorial": ("M_core", "M_clad", "K_core", "K_clad", "D"), "scalar": ("M_core", "M_clad", "S")}
 CORE_GRAM_NAMES = {"vectorial": ("Mx", "My", "K"), "scalar": ("M",)}
+PROFILE_GRAM_NAMES = {"vectorial": ("M", "M_w", "K_w", "D"), "scalar": ("M", "M_w", "S")}
 MOMENT_GRAM_NAMES = {"vectorial": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "K_core_X", "K_core_Y", "K_clad_X",
                                    "K_clad_Y", "M_XX", "M_XY", "M_YY"),
                      "scalar": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "M_XX", "M_XY", "M_YY")}
@@ -260,6 +262,7 @@ class ModeFields:
         vectorial records ``M_core``, ``M_clad``, ``K_core``, ``K_clad``, ``D`` (so that ``V^T A V = sum_r K_r / eps_r +
         alpha_p D - k0^2 (M_core + M_clad)`` and ``V^T B V = sum_r M_r / eps_r`` on the interior DOFs), scalar records
         ``M_core``, ``M_clad``, ``S`` (``V^T A V = S - k0^2 sum_r eps_r M_r``, ``V^T B V = M_core + M_clad``)."""
+        reject_profile(geometry, "ModeFields.grams")
         kind, vals, _ = self._check_records(modes)
         cores = self._cores(geometry)
         k = 0 if kind is None else vals.shape[1]
@@ -295,6 +298,46 @@ class ModeFields:
                                                out.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_grams")
         return {nm: out[i] for i, nm in enumerate(names)}
 
+    def profile_grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
+        """Grams of the modes of a profile solve (``plfem_profile_grams``): the forms of :meth:`grams` under the permittivity
+        of the index profile that ``geometry`` carries (``geometry.index_profile``), evaluated at every quadrature point
+        as the assembly evaluates it, each (k, k).  Vectorial records: ``M``, ``M_w``, ``K_w``, ``D`` with the weight
+        ``w = 1 / eps``, so that ``V^T A V = K_w + alpha_p D - k0^2 M`` and ``V^T B V = M_w`` on the interior DOFs; scalar
+        records: ``M``, ``M_w``, ``S`` with ``w = eps``, so that ``V^T A V = S - k0^2 M_w`` and ``V^T B V = M``."""
+        profile = index_profile_of(geometry)
+        if profile is None:
+            raise ValueError("profile_grams needs a geometry that carries an index profile (ProfiledGeometry); "
+                             "for core discs on a cladding use grams")
+        kind, vals, _ = self._check_records(modes)
+        k = 0 if kind is None else vals.shape[1]
+        if k == 0:
+            return {nm: np.zeros((0, 0)) for nm in PROFILE_GRAM_NAMES.get(kind, ())}
+        self._ensure_locator()
+        staged, _src = self._stage(vals)
+        return self._profile_grams_staged(kind, staged, profile.table(), profile.eps_background)
+
+    def _profile_grams_staged(self, kind, staged, table, eps_bg, work=None) -> Dict[str, np.ndarray]:
+        """``plfem_profile_grams`` on modes already staged (ncomp, n, k) on the device; ``work``: a uint8 device tensor to
+        use as the work buffer (at least the library's size + 256 bytes) instead of a fresh one."""
+        names = PROFILE_GRAM_NAMES[kind]
+        ncomp, _, k = staged.shape
+        table = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, 8))
+        need = ctypes.c_int64(0)
+        if self._lib.plfem_profile_gram_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
+            raise ValueError(f"plfem_profile_gram_work_bytes rejected ncomp = {ncomp}, k = {k}")
+        if work is None:
+            work = _native.device_scratch(int(need.value) + 256, self.tdev)
+        elif work.numel() < int(need.value) + 256:
+            raise ValueError("work buffer smaller than plfem_profile_gram_work_bytes + 256")
+        aligned = (work.data_ptr() + 255) & ~255
+        out = np.empty((len(names), k, k), dtype=np.float64)
+        self._check(self._lib.plfem_profile_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
+                                                  1 if kind == "vectorial" else 0, table.ctypes.data_as(ctypes.c_void_p),
+                                                  table.shape[0], float(eps_bg), ctypes.c_void_p(aligned),
+                                                  ctypes.c_int64(int(need.value)), out.ctypes.data_as(ctypes.c_void_p)),
+                    "plfem_profile_grams")
+        return {nm: out[i] for i, nm in enumerate(names)}
+
     def core_grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
         """Grams of the modes restricted to each core disc (``plfem_core_grams``), each (ncore, k, k): vectorial records
         ``Mx`` (sum over the core's quadrature points of hx_m hx_n), ``My`` and ``K`` (the form of ``K_core``), scalar
@@ -303,6 +346,7 @@ class ModeFields:
         cores ``Mx + My`` is ``M_core`` and ``K`` is ``K_core`` of :meth:`grams`; a core that owns no point gives zeros.
         With core c at eps_c instead of eps_core the pencils of :meth:`grams` become ``sum_c K_c / eps_c + ...``: these
         are the exact projections of a pencil with unequal core indices on the span of the modes."""
+        reject_profile(geometry, "ModeFields.core_grams")
         kind, vals, _ = self._check_records(modes)
         cores = self._cores(geometry)
         ncore = cores.shape[0]
@@ -355,6 +399,7 @@ class ModeFields:
         (``M_r_X[m, n] = sum over region r of X u_m . u_n``), for vectorial records also ``K_core_X``, ``K_core_Y``,
         ``K_clad_X``, ``K_clad_Y`` (the form of ``K_r``), and the second moments ``M_XX``, ``M_XY``, ``M_YY`` over both
         regions.  A bend enters both pencils linearly in the curvature through exactly these (:mod:`.bend`)."""
+        reject_profile(geometry, "ModeFields.moment_grams")
         kind, vals, _ = self._check_records(modes)
         cores = self._cores(geometry)
         o = self._origin(origin)
@@ -388,6 +433,7 @@ class ModeFields:
         (u_l . u_m)``, pairs i <= j numbered ``p(i,j) = i k - i (i - 1) / 2 + (j - i)`` (:func:`.nonlinear.pair_index`),
         transverse dot product for vectorial records.  ``geometry=None``: wt = 1; otherwise wt = ``weights[0]`` in the
         closed core discs of the assembly's core test and ``weights[1]`` outside.  At most 64 modes."""
+        reject_profile(geometry, "ModeFields.quartic with a geometry")
         kind, vals, _ = self._check_records(modes)
         if kind is None:
             return np.zeros((0, 0))
@@ -497,6 +543,7 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
         raise ValueError("vectorial and scalar mode records cannot be mixed")
     if weight is not None and not all(hasattr(weight, a) for a in ("positions", "core_radii", "n_core", "n_clad")):
         raise ValueError("weight must be None or a geometry (positions, core_radii, n_core, n_clad)")
+    reject_profile(weight, "mode_overlap with a weight")
     fa = _as_fields(mesh_a, device)
     fb = fa if (mesh_b is mesh_a or (not isinstance(mesh_b, ModeFields) and not isinstance(mesh_a, ModeFields)
                                      and mesh_key(mesh_b) == mesh_key(mesh_a))) else _as_fields(mesh_b, device)
@@ -546,5 +593,5 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
     return O * O / (daa[:, None] * dbb[None, :])
 
 
-__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES",
+__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES", "PROFILE_GRAM_NAMES",
            "PROJECT_TILE", "PROJECT_MAX_FACTORS"]

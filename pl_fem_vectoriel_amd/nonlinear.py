@@ -19,6 +19,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from .fields import ModeFields, _records
+from .profile import reject_profile
 
 # 16-point degree-8 rule on the reference triangle (0,0), (1,0), (0,1) (Dunavant 1985), digits polished on its moment
 # equations; weights sum to 1/2.  The device copy is c_q16x / c_q16y / c_q16w of csrc/p2_element.h.
@@ -117,6 +118,7 @@ def mode_nonlinearity(modes: Sequence[Dict], mesh, geometry=None, n2=None, devic
     if n2 is not None:
         if geometry is None:
             raise ValueError("n2 needs a geometry (the core test and k0)")
+        reject_profile(geometry, "mode_nonlinearity with n2")
         try:
             n2v = np.asarray(n2, dtype=np.float64).reshape(-1)
         except (TypeError, ValueError):

@@ -26,6 +26,7 @@ import numpy as np
 
 from . import _native
 from .mesh import TriMesh, generate_mesh
+from .profile import index_profile_of
 
 logger = logging.getLogger("pl_v18.solver_fem")   # same logger name as the reference (solver_fem.py:40)
 
@@ -98,6 +99,18 @@ def shift_estimate(geometry) -> float:
     return float((geometry.k0 * float(np.clip(n_eff_est, n_clad + 0.05, n_core - 0.005))) ** 2)
 
 
+def _n_eff_shift(n_eff_shift) -> Optional[float]:
+    if n_eff_shift is None:
+        return None
+    try:
+        n = float(n_eff_shift)
+    except (TypeError, ValueError):
+        raise ValueError("n_eff_shift must be a positive number") from None
+    if not (np.isfinite(n) and n > 0):
+        raise ValueError("n_eff_shift must be a positive number")
+    return n
+
+
 def _core_table(geometry) -> np.ndarray:
     pos = np.atleast_2d(np.asarray(geometry.positions, dtype=np.float64))
     rad = np.asarray(geometry.core_radii, dtype=np.float64).reshape(-1)
@@ -127,7 +140,10 @@ class TrueVectorialMaxwellSolver:
     fields then agree with ``eigsh`` to 3e-9, as they do at 1e-10, for two block steps less), ``leaf_elems`` (front-tree leaf
     size), ``reuse_symbolic`` (keep the mesh-only analysis and the device context between calls on
     the same mesh object — e.g. a wavelength sweep), ``mesh_levels`` / ``mesh_refinement`` for
-    ``solve()``.
+    ``solve()``; ``n_eff_shift``: the shift is ``(k0 n_eff_shift)^2`` instead of the LP01 estimate, which means nothing for
+    e.g. a jacketed low-contrast section.  A geometry that carries an index profile (``geometry.index_profile``,
+    :class:`.profile.ProfiledGeometry`) is assembled with it; every entry that assembles sets or clears the profile of
+    the cached context itself, so no solve inherits the previous one's.
     """
 
     ALPHA_P = 1.0            # solver_fem.py:158
@@ -141,9 +157,11 @@ class TrueVectorialMaxwellSolver:
 
     def __init__(self, geometry, use_pml: bool = False, n_modes: Optional[int] = None, device: Optional[int] = None,
                  eig_tol: float = 1e-8, leaf_elems: int = 0, reuse_symbolic: bool = True, mesh_refinement: float = 1.0,
-                 mesh_levels: int = 1, refine_steps: int = 0, profile_kernel: bool = False):
+                 mesh_levels: int = 1, refine_steps: int = 0, profile_kernel: bool = False,
+                 n_eff_shift: Optional[float] = None):
         _native.load_library()           # fail loudly: the reference raises RuntimeError when its backend is missing
         self.geometry = geometry
+        self.n_eff_shift = _n_eff_shift(n_eff_shift)
         self.k0 = geometry.k0
         self.use_pml = use_pml           # stored, never read — as in the reference
         self.n_modes = n_modes
@@ -202,6 +220,7 @@ class TrueVectorialMaxwellSolver:
 
     def _assemble_device(self, ctx):
         g = self.geometry
+        ctx.set_index_profile(index_profile_of(g))
         ctx.assemble(_core_table(g), g.n_core ** 2, g.n_clad ** 2, self.k0, self.ALPHA_P)
 
     # -- reference surface ---------------------------------------------------------------------------
@@ -247,7 +266,8 @@ class TrueVectorialMaxwellSolver:
             raise ValueError("mesh too small for the requested number of modes")
         ncv = min(self._basis_size(n_req, 2 * sym.N), 2 * N_solve, ctx.max_ncv)
         cores = _core_table(g)
-        sigma = shift_estimate(g)
+        sigma = shift_estimate(g) if self.n_eff_shift is None else float((self.k0 * self.n_eff_shift) ** 2)
+        ctx.set_index_profile(index_profile_of(g))
         import torch
         # (k, 2 N_solve) on the host: the caller owns NumPy arrays, as in the reference.  They live in pinned memory
         # from torch's caching host allocator, so a released mode list hands its 32 MB block to the next solve
@@ -346,7 +366,8 @@ class ScalarHelmholtzSolver:
     is_vectorial = False``), n_eff descending.  Optional keywords as for the vectorial class (``device``, ``eig_tol``:
     the reference passes ``tol=1e-6`` to eigsh; the default here stays at 1e-10 -- the shift of this pencil is far from
     its eigenvalues in relative terms, so a Ritz residual of 1e-8 |theta| already is an eigen-residual of 5e-7 against
-    the assembled pencil, above the bound of the a-posteriori check; ``leaf_elems``)."""
+    the assembled pencil, above the bound of the a-posteriori check; ``leaf_elems``; ``n_eff_shift``: ``sigma =
+    -(k0 n_eff_shift)^2``).  A geometry with an index profile is assembled with it, as in the vectorial class."""
 
     REF_TOL = 1e-6           # solver_fem.py:261
     MAXITER = 6000           # solver_fem.py:261
@@ -354,9 +375,11 @@ class ScalarHelmholtzSolver:
     RESIDUAL_TOL = 1e-7
     BASIS_FACTOR, BASIS_MAX, BASIS_BYTES = TrueVectorialMaxwellSolver.BASIS_FACTOR, TrueVectorialMaxwellSolver.BASIS_MAX, TrueVectorialMaxwellSolver.BASIS_BYTES
 
-    def __init__(self, geometry, device: Optional[int] = None, eig_tol: float = 1e-10, leaf_elems: int = 0):
+    def __init__(self, geometry, device: Optional[int] = None, eig_tol: float = 1e-10, leaf_elems: int = 0,
+                 n_eff_shift: Optional[float] = None):
         _native.load_library()
         self.geometry = geometry
+        self.n_eff_shift = _n_eff_shift(n_eff_shift)
         self.k0 = geometry.k0
         self.device = device
         self.eig_tol = float(eig_tol)
@@ -394,7 +417,8 @@ class ScalarHelmholtzSolver:
             ent["ctx"] = _native.Context(sym, self.device, max_ncv=max(ncv, 65))
         ctx = ent["ctx"]
         cores = _core_table(g)
-        sigma = float(-(self.k0 * (g.n_core - 0.008)) ** 2)                  # solver_fem.py:260
+        sigma = float(-(self.k0 * (g.n_core - 0.008 if self.n_eff_shift is None else self.n_eff_shift)) ** 2)   # solver_fem.py:260
+        ctx.set_index_profile(index_profile_of(g))
         import torch
         host = torch.empty((n_req, N), dtype=torch.float64, pin_memory=True)
         # one call (plfem_solve_modes on a scalar context): K - k0^2 M_eps and M, factorisation, eigen-solve, the

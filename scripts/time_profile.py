@@ -1,0 +1,95 @@
+"""Timing aid of the index-profile path at C1: the assembly with a profile of ``--layers`` layers beside the step
+assembly, and ``ModeFields.profile_grams`` beside ``ModeFields.grams`` for 22 vectorial and scalar modes.
+
+    python scripts/time_profile.py [--layers 7] [--modes 22] [--reps 10] [--out FILE]
+
+Run it under ``rocprofv3 --kernel-trace --stats``, in a run of its own and once per ``--layers`` (both profile assemblies
+are the one instance k_element_matrices<true>), for the kernel times of k_element_matrices<true> / <false> and of
+k_profile_grams next to k_mode_grams; the wall times printed here include the copies and the launches."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def c1_profile(geom, layers: int):
+    """A cladding disc in air, a trench ring and a graded centre core (3 layers), then the outer cores as step discs at
+    unequal indices while ``layers`` allows (4 of the 6 at the default 7; all 6 from 9 on), then thin rings round the
+    outer cores up to ``layers``."""
+    from pl_fem_vectoriel_amd import IndexProfile
+    pos = np.atleast_2d(geom.positions)
+    prof = IndexProfile(1.0).disc((0.0, 0.0), 14.0, 1.45).ring(pos[1], 1.5, 2.4, 1.44).graded(pos[0], 1.5, 1.535, 1.50, 2)
+    for i, p in enumerate(pos[1:]):
+        if len(prof) < layers:
+            prof.disc(p, 1.5, 1.530 + 1e-3 * i)
+    i = 0
+    while len(prof) < layers:
+        prof.ring(pos[1 + i % 6], 1.6 + 0.05 * (i // 6), 1.64 + 0.05 * (i // 6), 1.445)
+        i += 1
+    return prof
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=7)
+    ap.add_argument("--modes", type=int, default=22)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from pl_fem_vectoriel_amd import MCFGeometry, ModeFields, ProfiledGeometry, _native, generate_mesh
+    from pl_fem_vectoriel_amd.solver_fem import ScalarHelmholtzSolver, TrueVectorialMaxwellSolver, _core_table
+
+    if not torch.cuda.is_available():
+        raise SystemExit("time_profile.py needs a GPU")
+    geom = MCFGeometry(7, 8.0, 1.5, 1.535, 1.0, wavelength_um=1.55)
+    mesh = generate_mesh(geom, 1.0, 1)
+    prof = c1_profile(geom, args.layers)
+    pg = ProfiledGeometry(geom, prof)
+    res = {"ne": int(mesh.t.shape[1]), "layers": len(prof)}
+
+    def timed(f):
+        best = None
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            best = dt if best is None else min(best, dt)
+        return best * 1e3
+
+    ctx = _native.Context(_native.Symbolic(mesh.p, mesh.t), 0, max_ncv=65)
+    cores = _core_table(geom)
+    asm = lambda: ctx.assemble(cores, geom.n_core ** 2, geom.n_clad ** 2, geom.k0, 1.0)
+    ctx.set_index_profile(None)
+    res["assemble_step_wall_ms"] = timed(asm)
+    ctx.set_index_profile(prof)
+    res["assemble_profile_wall_ms"] = timed(asm)
+    ctx.close()
+
+    solver = TrueVectorialMaxwellSolver(geom, device=0)
+    vec = solver.solve_vectorial_modes(mesh, args.modes)[:args.modes]
+    scal = ScalarHelmholtzSolver(geom, device=0).solve(mesh, args.modes)[:args.modes]
+    mf = ModeFields(mesh, device=0, solver=solver)
+    for kind, modes in (("vectorial", vec), ("scalar", scal)):
+        res[kind] = {"k": len(modes), "grams_wall_ms": timed(lambda: mf.grams(modes, geom)),
+                     "profile_grams_wall_ms": timed(lambda: mf.profile_grams(modes, pg))}
+    mf.close()
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
