@@ -356,6 +356,35 @@ int plfem_field_overlap(plfem_locator* loc_a, const double* modes_a_dev, int32_t
                         plfem_locator* loc_b, const double* modes_b_dev, int32_t kb, int32_t indexed_b, int32_t ncomp,
                         const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
                         void* work_dev, int64_t work_bytes, double* out_host);
+/* plfem_field_overlap under nposes poses of mesh A relative to mesh B, in one call.  A pose row is five doubles (tx, ty,
+ * c, s, m): a point xi of mesh A appears in B's frame at x = t + m R xi, R = [[c, -s], [s, c]] (a shift, a rotation
+ * and a magnification).  For B's quadrature point (X, Y), formed as the assembly forms it, A is located and evaluated at
+ *   xa = (fl(c dx) + fl(s dy)) / m,  ya = (fl(c dy) - fl(s dx)) / m,  dx = X - tx, dy = Y - ty
+ * (every product rounded on its own, the division IEEE: the identity pose (0, 0, 1, 0, 1) gives (X, Y) bit for bit and
+ * the location decisions of plfem_field_overlap), and for ncomp = 2 A's value is turned into B's frame, (c ua_x - s ua_y,
+ * s ua_x + c ua_y), before the dot product.  There is no amplitude factor for m: the self-overlap of the posed A is m^2
+ * times its own.  out_host[p][i][j] = sum over the elements of B and B's six-point rule of |det J| w_q wt(x_q)
+ * ua'_i(xa, ya) . ub_j(x_q); wt as in plfem_field_overlap, in B's frame; a point that lands in no element of A
+ * contributes 0.
+ * One workgroup per (slice of B's 64-point tiles, pair of 32-mode chunks, pose) writes its partial block to its own
+ * slot, slices = min(128, tiles of B) whatever nposes, ka and kb are, and the fixed-order second stage of
+ * plfem_field_overlap sums them: the bits of out_host[p] depend on pose p, the modes and the two meshes only -- not on
+ * the other poses, on p's place in the table, on what the work buffer held or on the run.
+ * The poses are worked off in batches of
+ *   batch = max(1, min(nposes, 4096, (512 MiB - 768) / (8 (ka kb + 1024 pairs slices + 5)))) poses,
+ * pairs = ceil(ka / 32) ceil(kb / 32) <= 256, and work_dev holds one batch: its results, its partial blocks and its
+ * pose rows, each part 256-byte aligned, so plfem_overlap_posed_work_bytes(loc_b, ka, kb, nposes) never exceeds 512 MiB.
+ * The pose rows travel to the device inside the work buffer.  Runs on loc_a's stream and synchronises it once, at the
+ * end; both locators on one device.
+ * Argument errors (nposes < 1, ka or kb < 1, more than 256 chunk pairs, ncomp not 1 or 2, ncore > 64, a null pointer,
+ * work_bytes too small, a non-finite pose entry, m <= 0, |c^2 + s^2 - 1| > 1e-12) return PLFEM_EINVAL with loc_a's last
+ * error set, before any launch. */
+int plfem_overlap_posed_work_bytes(const plfem_locator* loc_b, int32_t ka, int32_t kb, int32_t nposes, int64_t* bytes);
+int plfem_field_overlap_posed(plfem_locator* loc_a, const double* modes_a_dev, int32_t ka, int32_t indexed_a,
+                              plfem_locator* loc_b, const double* modes_b_dev, int32_t kb, int32_t indexed_b, int32_t ncomp,
+                              const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                              int32_t nposes, const double* poses_host /* [nposes][5] = tx, ty, c, s, m */,
+                              void* work_dev, int64_t work_bytes, double* out_host /* [nposes][ka][kb] */);
 /* Same-mesh Grams of k staged modes (indexed as for plfem_sample_fields) under the element forms of the assembly, over
  * the mesh's own six-point rule, split by the closed-disc core test of plfem_assemble_hfield (ncore in [0, 64]; r = core,
  * clad; every sum is over the points of region r of |det J| w_q (...)):

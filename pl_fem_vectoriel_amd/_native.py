@@ -39,6 +39,7 @@ EXPORTS = (
     "plfem_solve_modes", "plfem_modes_dev",
     "plfem_locator_bytes", "plfem_locator_create", "plfem_locator_destroy", "plfem_locator_last_error", "plfem_stage_modes",
     "plfem_sample_fields", "plfem_overlap_work_bytes", "plfem_field_overlap", "plfem_gram_work_bytes", "plfem_mode_grams",
+    "plfem_overlap_posed_work_bytes", "plfem_field_overlap_posed",
     "plfem_quartic_work_bytes", "plfem_mode_quartic", "plfem_project_work_bytes", "plfem_mode_project",
     "plfem_core_gram_work_bytes", "plfem_core_grams", "plfem_moment_gram_work_bytes", "plfem_moment_grams",
     "plfem_set_index_profile", "plfem_profile_gram_work_bytes", "plfem_profile_grams",
@@ -220,6 +221,11 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_field_overlap.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] * 2 +
                                         [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p])
+    lib.plfem_overlap_posed_work_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.POINTER(ctypes.c_int64)]
+    lib.plfem_field_overlap_posed.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] * 2 +
+                                              [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p])
     lib.plfem_gram_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
     lib.plfem_mode_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                      ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]

@@ -1,6 +1,7 @@
 // gfx950 kernels and C-ABI of the mode-field calls (include/plfem.h, "Mode fields at arbitrary points"): the point
 // locator bound to a device, P2 evaluation of many modes at many points (k_sample_fields) and the overlap integral of
-// two mode sets living on two meshes (k_field_overlap + k_overlap_reduce), and the same-mesh Grams of a mode set under
+// two mode sets living on two meshes (k_field_overlap + k_overlap_reduce), alone or under a table of poses of one mesh
+// relative to the other (k_field_overlap_posed + k_overlap_reduce), and the same-mesh Grams of a mode set under
 // the assembly's element forms, split by material region (k_mode_grams + k_overlap_reduce), and the quartic overlap of
 // products of four modes on a 16-point degree-8 rule (k_mode_quartic + k_quartic_reduce), and the projection of a mode
 // set on a family of analytic fields that separate in x and y -- plane waves and Gaussian beams -- on the same rule
@@ -274,6 +275,118 @@ __global__ __launch_bounds__(256) void k_field_overlap(LocArgs A, LocArgs B, int
     __syncthreads();
   }
   double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (OC * OC);
+  for (int r = 0; r < 2; ++r)
+    for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[r][s];
+}
+
+// Posed overlap (plfem_field_overlap_posed): the contract of k_field_overlap with a pose between B's quadrature point
+// and its location in A.  A pose row is (tx, ty, c, s, m): a point xi of mesh A appears in B's frame at x = t + m R xi,
+// R = [[c, -s], [s, c]], so B's point (X, Y) is looked up in A at R^T (x - t) / m -- every product rounded on its own,
+// the division IEEE, which gives (X, Y) back bit for bit under the identity pose -- and A's value there is turned by R
+// when the record is vectorial.  The core test and B's own values stay in B's frame.  Grid = (slice of B's tiles, chunk
+// pair, pose of the batch); tiles blockIdx.x, blockIdx.x + gridDim.x, ... as in k_field_overlap, and gridDim.x follows
+// B's element count alone, so the sum order of an entry depends on neither the other poses nor the mode counts.
+// Partials [pose][chunk pair][slice][OC * OC], every slot written: what k_overlap_reduce sums with blockIdx.y = pose.
+constexpr int POSE_SLICES = 128;    // most slices (partial blocks) per pose and chunk pair
+constexpr int POSE_DOUBLES = 5;
+
+__global__ __launch_bounds__(256) void k_field_overlap_posed(LocArgs A, LocArgs B, int ncomp, int ka, int64_t nrows_a,
+                                                             const double* __restrict__ Va, int kb, int64_t nrows_b,
+                                                             const double* __restrict__ Vb, CoreTable cores, int ncore,
+                                                             double inv_eps_core, double inv_eps_clad, int nchunk_b,
+                                                             const double* __restrict__ poses, double* __restrict__ partial) {
+  __shared__ double s_phi[6][OT];
+  __shared__ int s_ra[6][OT], s_rb[6][OT];
+  __shared__ double s_w[OT];
+  __shared__ int s_q[OT];
+  __shared__ double s_ua[2][OT][OC];
+  __shared__ double s_ub[2][OT][OC];
+  const int tid = threadIdx.x;
+  const int ca = blockIdx.y / nchunk_b, cb = blockIdx.y % nchunk_b;
+  const int ia0 = ca * OC, jb0 = cb * OC;
+  const double* pose = poses + (int64_t)blockIdx.z * POSE_DOUBLES;     // the same for every lane
+  const double tx = pose[0], ty = pose[1], pc = pose[2], ps = pose[3], pm = pose[4];
+  const int64_t nq = (int64_t)6 * B.ne;
+  const int64_t ntiles = (nq + OT - 1) / OT;
+  const int ti = tid >> 4, tj = tid & 15;
+  double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+  const double* pbx = B.pxy;
+  const double* pby = B.pxy + B.nv;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < OT) {
+      const int64_t g = tile * OT + tid;
+      double w = 0.0;
+      int q = 0;
+      for (int a = 0; a < 6; ++a) { s_ra[a][tid] = -1; s_rb[a][tid] = -1; s_phi[a][tid] = 0.0; }
+      if (g < nq) {
+        const int e = (int)(g / 6);
+        q = (int)(g % 6);
+        const P2Map M(B.edof, B.ne, pbx, pby, e);
+        double X, Y;
+        M.point(c_qx[q], c_qy[q], X, Y);
+        w = fabs(M.det()) * c_qw[q];
+        if (ncore >= 0) w *= in_any_core(X, Y, cores.c, ncore) ? inv_eps_core : inv_eps_clad;
+        const double dx = X - tx, dy = Y - ty;
+        const double xa = (mul_rn(pc, dx) + mul_rn(ps, dy)) / pm;
+        const double ya = (mul_rn(pc, dy) - mul_rn(ps, dx)) / pm;
+        double axi, aeta, inv[4];
+        const int ea = dev_locate(A, xa, ya, axi, aeta, inv);
+        if (ea >= 0) {
+          double phi[6];
+          p2_phi(axi, aeta, phi);
+          for (int a = 0; a < 6; ++a) {
+            s_phi[a][tid] = phi[a];
+            s_ra[a][tid] = dev_row(A, ea, a);
+            s_rb[a][tid] = dev_row(B, e, a);
+          }
+        } else {
+          w = 0.0;
+        }
+      }
+      s_w[tid] = w;
+      s_q[tid] = q;
+    }
+    __syncthreads();
+    // ua'[c][t][i] and w ub[c][t][j]: a lane holds both components of its (point, mode), so that it can turn A's value
+    for (int idx = tid; idx < OT * OC; idx += 256) {
+      const int i = idx % OC, t = idx / OC;
+      const int q = s_q[t];
+      const double w = s_w[t];
+      double ua[2] = {0.0, 0.0}, ub[2] = {0.0, 0.0};
+      for (int c = 0; c < ncomp; ++c) {
+        const double* va = Va + c * nrows_a * ka;
+        const double* vb = Vb + c * nrows_b * kb;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          const int ra = s_ra[a][t], rb = s_rb[a][t];
+          if (ia0 + i < ka && ra >= 0) ua[c] += s_phi[a][t] * va[(int64_t)ra * ka + ia0 + i];
+          if (jb0 + i < kb && rb >= 0) {
+            const double ph = p2_phi(a, c_qx[q], c_qy[q]);   // B's basis at its own quadrature point q
+            ub[c] += ph * vb[(int64_t)rb * kb + jb0 + i];
+          }
+        }
+        ub[c] *= w;
+      }
+      if (ncomp == 2) {
+        const double ux = ua[0], uy = ua[1];
+        ua[0] = mul_rn(pc, ux) - mul_rn(ps, uy);
+        ua[1] = mul_rn(ps, ux) + mul_rn(pc, uy);
+      }
+      s_ua[0][t][i] = ua[0]; s_ua[1][t][i] = ua[1];
+      s_ub[0][t][i] = ub[0]; s_ub[1][t][i] = ub[1];
+    }
+    __syncthreads();
+    for (int c = 0; c < ncomp; ++c) {
+      for (int t = 0; t < OT; ++t) {
+        const double2 a = *reinterpret_cast<const double2*>(&s_ua[c][t][2 * ti]);
+        const double2 b = *reinterpret_cast<const double2*>(&s_ub[c][t][2 * tj]);
+        acc[0][0] += a.x * b.x; acc[0][1] += a.x * b.y;
+        acc[1][0] += a.y * b.x; acc[1][1] += a.y * b.y;
+      }
+    }
+    __syncthreads();
+  }
+  double* out = partial + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
   for (int r = 0; r < 2; ++r)
     for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[r][s];
 }
@@ -1242,6 +1355,103 @@ extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev,
                      ncore < 0 ? -1 : (int)ncore, 1.0 / eps_core, 1.0 / eps_clad, ncb, partial);
   TRY(check_launch(La, "k_field_overlap"));
   return reduce_to_host(La, dim3(nca * ncb), (int)ka, (int)kb, nblk, ncb, partial, O, out_host);
+} catch (...) { return host_failure(La); }
+
+namespace {
+constexpr int POSE_BATCH = 4096;                       // most poses per internal batch
+constexpr int POSE_MAX_PAIRS = 256;                    // most chunk pairs of a posed call
+constexpr int64_t POSE_SCRATCH = (int64_t)512 << 20;   // what the work buffer never exceeds
+// Batches, slices and work buffer of a posed overlap: the results of a batch [batch][ka][kb], then its partials
+// [batch][chunk pair][slice][OC * OC], then its pose rows, each part 256-byte aligned
+struct PosedPlan {
+  int nca, ncb, slices, batch;
+  size_t off_partial, off_poses, total;   // bytes
+};
+PosedPlan posed_plan(int ne_b, int ka, int kb, int nposes) {
+  PosedPlan p;
+  p.nca = overlap_chunks(ka);
+  p.ncb = overlap_chunks(kb);
+  const int64_t ntiles = ((int64_t)6 * ne_b + OT - 1) / OT;
+  p.slices = (int)std::max<int64_t>(1, std::min<int64_t>(POSE_SLICES, ntiles));
+  const int64_t per_pose = (int64_t)sizeof(double) * ((int64_t)ka * kb + (int64_t)p.nca * p.ncb * p.slices * OC * OC + POSE_DOUBLES);
+  p.batch = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(nposes, POSE_BATCH), (POSE_SCRATCH - 768) / per_pose));
+  size_t o = align256(sizeof(double) * p.batch * ka * kb);
+  p.off_partial = o; o += align256(sizeof(double) * p.batch * p.nca * p.ncb * p.slices * OC * OC);
+  p.off_poses = o;   o += align256(sizeof(double) * p.batch * POSE_DOUBLES);
+  p.total = o;
+  return p;
+}
+const char* posed_sizes(int ka, int kb, int nposes) {
+  if (ka < 1 || kb < 1) return "ka and kb must be >= 1";
+  if (nposes < 1) return "nposes must be >= 1";
+  if ((int64_t)overlap_chunks(ka) * overlap_chunks(kb) > POSE_MAX_PAIRS) return "at most 256 pairs of 32-mode chunks";
+  return nullptr;
+}
+// every entry finite, m > 0, |c^2 + s^2 - 1| <= 1e-12
+bool poses_ok(const double* poses, int n) {
+  for (int i = 0; i < n; ++i) {
+    const double* p = poses + (size_t)POSE_DOUBLES * i;
+    for (int j = 0; j < POSE_DOUBLES; ++j)
+      if (!std::isfinite(p[j])) return false;
+    if (!(p[4] > 0.0) || !(std::fabs(p[2] * p[2] + p[3] * p[3] - 1.0) <= 1e-12)) return false;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int plfem_overlap_posed_work_bytes(const plfem_locator* Lb, int32_t ka, int32_t kb, int32_t nposes, int64_t* bytes) try {
+  if (!Lb || !bytes || posed_sizes(ka, kb, nposes)) return PLFEM_EINVAL;
+  *bytes = (int64_t)posed_plan(Lb->ne, ka, kb, nposes).total;
+  return PLFEM_OK;
+} catch (...) { return host_failure(nullptr, 0); }
+
+extern "C" int plfem_field_overlap_posed(plfem_locator* La, const double* modes_a_dev, int32_t ka, int32_t indexed_a,
+                                         plfem_locator* Lb, const double* modes_b_dev, int32_t kb, int32_t indexed_b, int32_t ncomp,
+                                         const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                                         int32_t nposes, const double* poses_host, void* work_dev, int64_t work_bytes,
+                                         double* out_host) try {
+  if (!La) return PLFEM_EINVAL;
+  if (!Lb || La->device != Lb->device) { La->err = "plfem_field_overlap_posed: the two locators must be on one device"; return PLFEM_EINVAL; }
+  if (ncomp < 1 || ncomp > 2) { La->err = "plfem_field_overlap_posed: ncomp must be 1 or 2"; return PLFEM_EINVAL; }
+  if (const char* bad = posed_sizes(ka, kb, nposes)) { La->err = std::string("plfem_field_overlap_posed: ") + bad; return PLFEM_EINVAL; }
+  if (!modes_a_dev || !modes_b_dev || !poses_host || !work_dev || !out_host) {
+    La->err = "plfem_field_overlap_posed: null array";
+    return PLFEM_EINVAL;
+  }
+  if (ncore > MAX_CORES || (ncore > 0 && !cores_host)) { La->err = "plfem_field_overlap_posed: at most 64 cores"; return PLFEM_EINVAL; }
+  if ((indexed_a && La->nsolve == 0) || (indexed_b && Lb->nsolve == 0)) {
+    La->err = "plfem_field_overlap_posed: the analysis has no interior DOFs";
+    return PLFEM_EINVAL;
+  }
+  if (!poses_ok(poses_host, nposes)) {
+    La->err = "plfem_field_overlap_posed: every pose (tx, ty, c, s, m) must be finite with m > 0 and |c^2 + s^2 - 1| <= 1e-12";
+    return PLFEM_EINVAL;
+  }
+  const PosedPlan plan = posed_plan(Lb->ne, ka, kb, nposes);
+  TRY(check_work(La, "plfem_field_overlap_posed", "plfem_overlap_posed_work_bytes", work_dev, work_bytes, (int64_t)plan.total));
+  HIP_TRY(La, hipSetDevice(La->device));
+  char* base = (char*)work_dev;
+  double *O = (double*)base, *partial = (double*)(base + plan.off_partial), *poses = (double*)(base + plan.off_poses);
+  const LocArgs la = loc_args(La, indexed_a != 0), lb = loc_args(Lb, indexed_b != 0);
+  const CoreTable ct = pack_cores(cores_host, ncore);
+  const int npair = plan.nca * plan.ncb;
+  // the batches follow each other on one stream: a batch's pose rows, partials and results are read before the next
+  // batch's copies and kernels overwrite them
+  for (int p0 = 0; p0 < nposes; p0 += plan.batch) {
+    const int nb = std::min(plan.batch, nposes - p0);
+    HIP_TRY(La, hipMemcpyAsync(poses, poses_host + (size_t)POSE_DOUBLES * p0, sizeof(double) * POSE_DOUBLES * nb,
+                               hipMemcpyHostToDevice, La->stream));
+    hipLaunchKernelGGL(k_field_overlap_posed, dim3(plan.slices, npair, nb), dim3(256), 0, La->stream, la, lb, (int)ncomp, (int)ka,
+                       (int64_t)(indexed_a ? La->nsolve : La->N), modes_a_dev, (int)kb, (int64_t)(indexed_b ? Lb->nsolve : Lb->N),
+                       modes_b_dev, ct, ncore < 0 ? -1 : (int)ncore, 1.0 / eps_core, 1.0 / eps_clad, plan.ncb, poses, partial);
+    TRY(check_launch(La, "k_field_overlap_posed"));
+    hipLaunchKernelGGL(k_overlap_reduce, dim3(npair, nb, OC * OC / 256), dim3(256), 0, La->stream, (int)ka, (int)kb, plan.slices,
+                       plan.ncb, partial, O);
+    TRY(check_launch(La, "k_overlap_reduce"));
+    HIP_TRY(La, hipMemcpyAsync(out_host + (size_t)p0 * ka * kb, O, sizeof(double) * nb * ka * kb, hipMemcpyDeviceToHost, La->stream));
+  }
+  HIP_TRY(La, hipStreamSynchronize(La->stream));
+  return PLFEM_OK;
 } catch (...) { return host_failure(La); }
 
 namespace {

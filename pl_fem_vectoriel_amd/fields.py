@@ -9,6 +9,9 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
   evaluation of many modes at many points in one kernel (``plfem_sample_fields``);
 * :func:`mode_overlap` -- ``O[i, j] = integral over mesh B of w(x) u_a,i . u_b,j`` with mesh B's six-point rule, A's
   values located and evaluated inside the kernel (``plfem_field_overlap``);
+* :func:`mode_overlap_poses` -- the same under a table of poses (shift, rotation, magnification) of mesh A relative to
+  mesh B, applied to B's quadrature points inside the kernel, the modes staged once (``plfem_field_overlap_posed``):
+  what :mod:`.splice` builds splice maps and taper steps from;
 * :meth:`ModeFields.grams` -- the k x k Grams of one mesh's modes under the assembly's element forms, split by material
   region (``plfem_mode_grams``): what :mod:`.dispersion` builds the group index and the k0-derivative coupling from;
 * :meth:`ModeFields.moment_grams` -- the region Grams weighted by the coordinates of the quadrature point
@@ -593,5 +596,108 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
     return O * O / (daa[:, None] * dbb[None, :])
 
 
-__all__ = ["ModeFields", "mode_overlap", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES", "PROFILE_GRAM_NAMES",
+def pose_table(dx=0.0, dy=0.0, angle=0.0, scale=1.0) -> np.ndarray:
+    """The (T, 5) pose table ``(tx, ty, c, s, m)`` of :func:`mode_overlap_poses` from shifts ``dx``, ``dy`` (um), rotation
+    ``angle`` (rad; ``c = cos(angle)``, ``s = sin(angle)``) and magnification ``scale`` > 0, broadcast against each other
+    and flattened in C order.  A point xi of mesh A appears in B's frame at ``(dx, dy) + scale R(angle) xi``."""
+    try:
+        a = [np.asarray(v, dtype=np.float64) for v in (dx, dy, angle, scale)]
+        tx, ty, ang, m = np.broadcast_arrays(*a)
+    except (TypeError, ValueError):
+        raise ValueError("dx, dy, angle and scale must be numbers or arrays that broadcast against each other") from None
+    tab = np.stack([tx.ravel(), ty.ravel(), np.cos(ang).ravel(), np.sin(ang).ravel(), m.ravel()], axis=1)
+    return _poses(tab)
+
+
+def _poses(poses) -> np.ndarray:
+    """A pose table (T, 5), T >= 1, every entry finite, m > 0, |c^2 + s^2 - 1| <= 1e-12, as contiguous float64."""
+    try:
+        p = np.ascontiguousarray(np.asarray(poses, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError("poses must be an array of shape (T, 5): (tx, ty, c, s, m) per pose") from None
+    if p.ndim != 2 or p.shape[1] != 5 or p.shape[0] < 1:
+        raise ValueError("poses must be an array of shape (T, 5) with T >= 1: (tx, ty, c, s, m) per pose")
+    if not np.all(np.isfinite(p)):
+        raise ValueError("every pose entry must be finite")
+    if np.any(p[:, 4] <= 0):
+        raise ValueError("the magnification m of every pose must be > 0")
+    if np.any(np.abs(p[:, 2] ** 2 + p[:, 3] ** 2 - 1.0) > 1e-12):
+        raise ValueError("(c, s) of every pose must be a rotation: |c^2 + s^2 - 1| <= 1e-12")
+    return p
+
+
+POSE_MAX_CHUNK_PAIRS = 256         # POSE_MAX_PAIRS of csrc/kernels_fields.hip: pairs of 32-mode chunks per posed call
+
+
+def mode_overlap_poses(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_b, poses, weight=None,
+                       normalize: bool = False, device: Optional[int] = None) -> np.ndarray:
+    """:func:`mode_overlap` under T poses of mesh A relative to mesh B in one call (``plfem_field_overlap_posed``), (T, ka,
+    kb).  ``poses`` is a (T, 5) table of rows ``(tx, ty, c, s, m)`` (:func:`pose_table` builds one from shifts, angles and
+    magnifications; a caller may also write exact rotations such as ``c = 0, s = 1``): a point xi of mesh A appears in
+    B's frame at ``x = t + m R xi``, ``R = [[c, -s], [s, c]]``.  The sum runs over mesh B's six-point rule; each point is
+    taken back into A's frame inside the kernel, located there, and A's value is turned by R for vectorial records.  A
+    point outside the posed A contributes 0.  ``weight`` as in :func:`mode_overlap`, in B's frame.  The modes are staged
+    once for all poses, and the bits of ``O[p]`` do not depend on the other poses.
+
+    There is no amplitude factor for m: the self-overlap of the posed A is ``m^2`` times A's own.  ``normalize=True``
+    (``weight=None`` only) gives the power coupling ``|O_ij|^2 / (m^2 O^aa_ii O^bb_jj)``.  Argument errors raise
+    ``ValueError`` before anything touches the device."""
+    ka_kind, va, _ = _records(modes_a)
+    kb_kind, vb, _ = _records(modes_b)
+    if ka_kind is not None and kb_kind is not None and ka_kind != kb_kind:
+        raise ValueError("vectorial and scalar mode records cannot be mixed")
+    P = _poses(poses)
+    if weight is not None and not all(hasattr(weight, a) for a in ("positions", "core_radii", "n_core", "n_clad")):
+        raise ValueError("weight must be None or a geometry (positions, core_radii, n_core, n_clad)")
+    reject_profile(weight, "mode_overlap_poses with a weight")
+    if normalize and weight is not None:
+        raise ValueError("normalize=True is defined for weight=None only")
+    fa = _as_fields(mesh_a, device)
+    fb = fa if (mesh_b is mesh_a or (not isinstance(mesh_b, ModeFields) and not isinstance(mesh_a, ModeFields)
+                                     and mesh_key(mesh_b) == mesh_key(mesh_a))) else _as_fields(mesh_b, device)
+    _, va, _ = fa._check_records(modes_a)
+    _, vb, _ = fb._check_records(modes_b)
+    ka = 0 if va is None else va.shape[1]
+    kb = 0 if vb is None else vb.shape[1]
+    T = P.shape[0]
+    if ka == 0 or kb == 0:
+        return np.zeros((T, ka, kb), dtype=np.float64)
+    if ((ka + 31) // 32) * ((kb + 31) // 32) > POSE_MAX_CHUNK_PAIRS:
+        raise ValueError(f"at most {POSE_MAX_CHUNK_PAIRS} pairs of 32-mode chunks per posed overlap, got ka = {ka}, kb = {kb}")
+    indexed = 1 if ka_kind == "vectorial" else 0
+    if weight is None:
+        cores, ncore, ec, el = None, -1, 1.0, 1.0
+    else:
+        cores = _core_table(weight)
+        ncore, ec, el = cores.shape[0], float(weight.n_core) ** 2, float(weight.n_clad) ** 2
+        if ncore > 64:
+            raise ValueError("at most 64 cores")
+    fa._ensure_locator()
+    fb._ensure_locator()
+    if fa.device != fb.device:
+        raise ValueError("both meshes must be evaluated on one device")
+    lib = fa._lib
+    sa, _ = fa._stage(va)
+    sb, _ = fb._stage(vb)
+    need = ctypes.c_int64(0)
+    if lib.plfem_overlap_posed_work_bytes(fb._loc, ka, kb, T, ctypes.byref(need)) != _native.PLFEM_OK:
+        raise ValueError(f"plfem_overlap_posed_work_bytes rejected ka = {ka}, kb = {kb}, nposes = {T}")
+    work = _native.device_scratch(int(need.value) + 256, fa.tdev)
+    aligned = (work.data_ptr() + 255) & ~255
+    out = np.empty((T, ka, kb), dtype=np.float64)
+    fb.stream.synchronize()                     # (B's staging ran on B's stream; the overlap runs on A's)
+    fa._check(lib.plfem_field_overlap_posed(fa._loc, ctypes.c_void_p(sa.data_ptr()), ka, indexed,
+                                            fb._loc, ctypes.c_void_p(sb.data_ptr()), kb, indexed, va.shape[0],
+                                            cores.ctypes.data_as(ctypes.c_void_p) if cores is not None else None, ncore,
+                                            ec, el, T, P.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(aligned),
+                                            ctypes.c_int64(int(need.value)), out.ctypes.data_as(ctypes.c_void_p)),
+              "plfem_field_overlap_posed")
+    if not normalize:
+        return out
+    daa = np.diag(mode_overlap(modes_a, fa, modes_a, fa)).copy()
+    dbb = np.diag(mode_overlap(modes_b, fb, modes_b, fb)).copy()
+    return out * out / (P[:, 4, None, None] ** 2 * daa[None, :, None] * dbb[None, None, :])
+
+
+__all__ = ["ModeFields", "mode_overlap", "mode_overlap_poses", "pose_table", "POSE_MAX_CHUNK_PAIRS", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES", "PROFILE_GRAM_NAMES",
            "PROJECT_TILE", "PROJECT_MAX_FACTORS"]
