@@ -518,6 +518,42 @@ int plfem_mode_project(plfem_locator* loc, int32_t ncomp, int32_t k, const doubl
                        int32_t lb, const double* yfac_host /* [lb][3] */,
                        void* work_dev, int64_t work_bytes, double* out_host /* [ncomp][k][lb][la][2] re, im */);
 
+/* Projection of k staged modes on a batch of sampled complex fields ("frames": an aberrated PSF, a speckle pattern, a
+ * measured near field, the output of a beam-propagation run): what each mode receives from each input field.  Frame f
+ * holds complex samples on the node grid x_i = x0 + i dx (i < nx), y_j = y0 + j dy (j < ny), dx, dy > 0, and
+ *   out_host[c][m][f] = sum over the elements e and the 16 points q of the degree-8 rule of
+ *                       |det J_e| w_q u_(c,m)(x_eq) F_f(x_eq)                                  (re, im, no conjugation),
+ * every component c < ncomp on its own; (X, Y) = x_eq the physical quadrature point as the assembly forms it, u the P2
+ * field of the element's six staged rows (a boundary DOF of an indexed record contributes 0), both exactly as in
+ * plfem_mode_project.  F_f is the bilinear interpolant of frame f:
+ *   tx = (X - x0) * (1 / dx), 1 / dx formed once on the host, the difference and the product each rounded on their own
+ *   (no fused multiply-add); ty likewise.  A point with tx < 0, tx > nx - 1, ty < 0 or ty > ny - 1 contributes 0 (the
+ *   extent is closed).  Otherwise i0 = min(floor(tx), nx - 2), a = tx - i0, j0 and b likewise, and
+ *   F = ((1 - a) F[j0][i0] + a F[j0][i0+1]) (1 - b) + ((1 - a) F[j0+1][i0] + a F[j0+1][i0+1]) b    for re and im each,
+ *   every product rounded on its own; the point's term is (|det J_e| w_q) F.
+ * The interpolant is continuous, so the cell a point on a pixel edge falls in does not matter beyond rounding; only the
+ * outer edge is a discontinuity.  Frame values are the caller's: a NaN pixel gives NaN results for its frame only.
+ * Defined on the discrete fields alone; the reference has no counterpart.
+ * modes_dev: staged by plfem_stage_modes ([ncomp][nrows][k]); indexed as in plfem_sample_fields.  frames_dev: device,
+ * pixel-major and frame-minor, [ny][nx][nf][2] (re, im): the columns of a workgroup's tile at one pixel corner are one
+ * contiguous run; offsets into it are 64-bit (ny nx nf 2 may pass 2^31).  Partial tiles per workgroup and a fixed-order
+ * second stage whose slice count depends on the mesh alone: the same bits on every run, and the bits of a frame do not
+ * depend on the frames it is batched with.  Runs on the locator's stream and synchronises it.
+ * Limits: ncomp 1 or 2, 1 <= k <= 64, 2 <= nx, ny <= 8192, 1 <= nf <= 4096; x0, y0, dx, dy, 1 / dx, 1 / dy finite.
+ * work_dev: device scratch of plfem_project_sampled_work_bytes(ncomp, k, nf) bytes, 256-byte aligned: the result (16 ncomp k
+ * nf bytes) plus the partial tiles of one launch -- tiles of 32 frames (512 ncomp k bytes each), at most 16 tiles per
+ * launch, 128 element slices per tile -- so at most 1 MiB ncomp k more (128 MiB at ncomp k = 128, 44 MiB for 22
+ * vectorial modes).
+ * Argument errors (ncomp not 1 or 2, k outside [1, 64], nx or ny outside [2, 8192], nf outside [1, 4096], dx or dy not
+ * positive or any of x0, y0, dx, dy, 1 / dx, 1 / dy not finite, a null pointer, work_bytes too small, an indexed record
+ * on an analysis without interior DOFs) return PLFEM_EINVAL with the locator's last error set, starting
+ * "plfem_mode_project_sampled: "; they write nothing and leave the locator usable. */
+int plfem_project_sampled_work_bytes(int32_t ncomp, int32_t k, int32_t nf, int64_t* bytes);
+int plfem_mode_project_sampled(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                               int32_t nx, int32_t ny, double x0, double y0, double dx, double dy,
+                               int32_t nf, const double* frames_dev /* [ny][nx][nf][2] re, im */,
+                               void* work_dev, int64_t work_bytes, double* out_host /* [ncomp][k][nf][2] */);
+
 #ifdef PLFEM_TEST_HOOKS
 /* ---------------------------------------------------------------------------------------------
  * TEST HOOKS -- NOT exported by libplfem_hip.so.  They live in the add-on libplfem_testhooks.so (csrc/api_debug.hip,

@@ -4,14 +4,14 @@ from .mesh import TriMesh, generate_mesh  # noqa: F401
 from .fields import ModeFields, mode_overlap, mode_overlap_poses, pose_table  # noqa: F401
 from .dispersion import mode_dispersion  # noqa: F401
 from .nonlinear import mode_nonlinearity  # noqa: F401
-from .launch import encircled_na, far_field, gaussian_coupling  # noqa: F401
+from .launch import encircled_na, far_field, field_coupling, gaussian_coupling  # noqa: F401
 from .cores import core_decomposition, core_quantities_from_grams  # noqa: F401
 from .bend import bend_propagate, bend_quantities_from_grams, bend_response  # noqa: F401
 from .profile import IndexProfile, ProfiledGeometry  # noqa: F401
 from .splice import splice_map, splice_quantities_from_overlaps, taper_from_interfaces, taper_transfer  # noqa: F401
 
 __all__ = ["MCFGeometry", "PhotonicLanternGeometry", "mcf_positions", "TriMesh", "generate_mesh", "ModeFields", "mode_overlap",
-           "mode_dispersion", "mode_nonlinearity", "far_field", "encircled_na", "gaussian_coupling", "core_decomposition",
+           "mode_dispersion", "mode_nonlinearity", "far_field", "encircled_na", "gaussian_coupling", "field_coupling", "core_decomposition",
            "core_quantities_from_grams", "bend_response", "bend_quantities_from_grams", "bend_propagate", "IndexProfile",
            "ProfiledGeometry", "mode_overlap_poses", "pose_table", "splice_map", "splice_quantities_from_overlaps",
            "taper_from_interfaces", "taper_transfer"]

@@ -43,6 +43,7 @@ EXPORTS = (
     "plfem_quartic_work_bytes", "plfem_mode_quartic", "plfem_project_work_bytes", "plfem_mode_project",
     "plfem_core_gram_work_bytes", "plfem_core_grams", "plfem_moment_gram_work_bytes", "plfem_moment_grams",
     "plfem_set_index_profile", "plfem_profile_gram_work_bytes", "plfem_profile_grams",
+    "plfem_project_sampled_work_bytes", "plfem_mode_project_sampled",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -251,6 +252,11 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_mode_project.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_int64, ctypes.c_void_p]
+    lib.plfem_project_sampled_work_bytes.argtypes = [ctypes.c_int32] * 3 + [ctypes.POINTER(ctypes.c_int64)]
+    lib.plfem_mode_project_sampled.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_void_p]
     _lib = lib
     return lib
 

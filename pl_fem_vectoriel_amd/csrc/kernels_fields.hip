@@ -5,7 +5,8 @@
 // the assembly's element forms, split by material region (k_mode_grams + k_overlap_reduce), and the quartic overlap of
 // products of four modes on a 16-point degree-8 rule (k_mode_quartic + k_quartic_reduce), and the projection of a mode
 // set on a family of analytic fields that separate in x and y -- plane waves and Gaussian beams -- on the same rule
-// (k_mode_project + k_project_reduce), and the Grams of a mode set restricted to each core disc (k_core_owner,
+// (k_mode_project + k_project_reduce) and on a batch of sampled complex fields, images on a pixel grid interpolated
+// bilinearly (k_mode_project_sampled + k_project_sampled_reduce), and the Grams of a mode set restricted to each core disc (k_core_owner,
 // k_core_count + k_core_fill, k_core_grams + k_overlap_reduce), and the region Grams weighted by the coordinates of the
 // quadrature point (k_moment_grams + k_overlap_reduce), and the Grams under the permittivity of an index profile
 // (k_profile_grams + k_overlap_reduce).
@@ -1160,6 +1161,179 @@ __global__ __launch_bounds__(256) void k_project_reduce(int nf, int la, int lb, 
   O[2 * v + 1] = im;
 }
 
+// Projection of the modes on sampled complex fields (plfem_mode_project_sampled): frame f is a complex image on the node
+// grid x_i = x0 + i dx, y_j = y0 + j dy, F_f its bilinear interpolant (0 outside the closed extent), and
+//   P[field][f] = sum over the elements and the 16 points of |det J| w_q u_field(x_q) F_f(x_q),
+// field = (component, mode).  The GEMM of k_mode_project with the B operand gathered instead of evaluated: rows = fields
+// (A[row][kk] = u[field][t], 16 fields per MFMA tile), columns = (frame, re | im) of value |det J| w F.  The frames lie
+// pixel-major, frame-minor ([ny][nx][nf][2]), so the PS_COLS columns of a workgroup's tile at one pixel corner are one
+// contiguous 512-byte run: wave w gathers the points w, w + 4, w + 8, w + 12, lane = column, four coalesced loads per
+// point, fetched one element ahead (with the DOF rows and the element map) and interpolated into the other LDS buffer
+// at the top of the next element.  Wave w then accumulates the 16-column tile w of every field tile on
+// v_mfma_f64_16x16x4_f64.  A workgroup owns the frame tile blockIdx.x for ALL fields and walks the elements blockIdx.y,
+// blockIdx.y + gridDim.y, ...; its partial tiles [field][column] go to its own slot (no atomics) and
+// k_project_sampled_reduce sums the slots in slice order.  The slice count depends on the mesh alone, never on the
+// frame count, and a column's arithmetic never on its neighbours: the bits of a frame do not depend on the frames it is
+// batched with.
+constexpr int PS_F = 32;             // frames per workgroup tile
+constexpr int PS_COLS = 2 * PS_F;    // its columns: one 16-column MFMA tile per wave
+constexpr int PS_NMAX = 8192;        // most pixels per axis
+constexpr int PS_FRAMES = 4096;      // most frames per call
+constexpr int PS_SLICES = 128;       // element slices (partial tiles) per frame tile, fewer only on a mesh with fewer elements
+constexpr int PS_GROUP = 16;         // frame tiles per launch: the partial tiles of one group share the work buffer
+constexpr int PS_LDB = PS_COLS + 16; // padded LDS row of the B operand: the four K-rows of a read 32 banks apart
+
+struct SampledGrid {
+  double x0, y0, inv_dx, inv_dy;
+  int nx, ny;
+};
+
+// Cell (i0, j0) and weights (a, b) of the bilinear interpolant at (X, Y); false outside the closed extent (and for a NaN).
+// tx = (X - x0) (1 / dx), the difference and the product each rounded on their own.
+__device__ __forceinline__ bool sampled_cell(const SampledGrid& G, double X, double Y, int& i0, int& j0, double& a, double& b) {
+  const double tx = mul_rn(X - G.x0, G.inv_dx), ty = mul_rn(Y - G.y0, G.inv_dy);
+  if (!(tx >= 0.0 && tx <= (double)(G.nx - 1) && ty >= 0.0 && ty <= (double)(G.ny - 1))) return false;
+  i0 = min((int)floor(tx), G.nx - 2);
+  j0 = min((int)floor(ty), G.ny - 2);
+  a = tx - (double)i0;
+  b = ty - (double)j0;
+  return true;
+}
+
+template <int NFT>                   // field tiles: ncomp k <= 16 NFT
+__global__ __launch_bounds__(256) void k_mode_project_sampled(LocArgs L, int ncomp, int k, int64_t nrows, const double* __restrict__ V,
+                                                              SampledGrid G, int nfr, int tile0, const double* __restrict__ F,
+                                                              double* __restrict__ partial) {
+  constexpr int FMAX = 16 * NFT;
+  constexpr int LDU = FMAX % 32 == 0 ? FMAX + 16 : FMAX;   // the four K-rows of an A read 32 banks apart
+  __shared__ double s_v[6][FMAX];              // the element's DOF rows (0 for a boundary DOF of an indexed record)
+  __shared__ double s_u[16][LDU];
+  __shared__ double s_b[2][16][PS_LDB];        // [buffer][point][column]
+  __shared__ double s_phi[16][6];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nf = ncomp * k;
+  const int f0 = (tile0 + (int)blockIdx.x) * PS_F;
+  const int ncol = 2 * min(PS_F, nfr - f0);    // live columns of the tile (the host launches no tile past the frames)
+  const bool live = lane < ncol;
+  const int64_t pix = 2 * (int64_t)nfr;        // doubles per pixel
+  const double* Fc = F + 2 * (int64_t)f0 + lane;   // this lane's column at pixel (0, 0)
+  if (tid < 96) s_phi[tid / 6][tid % 6] = p2_phi(tid % 6, c_q16x[tid / 6], c_q16y[tid / 6]);
+  for (int idx = tid; idx < 16 * LDU; idx += 256) (&s_u[0][0])[idx] = 0.0;   // (the columns past nf stay 0)
+  const double* px = L.pxy;
+  const double* py = L.pxy + L.nv;
+  const int l16 = lane & 15, l4 = lane >> 4;
+  dbl4 acc[NFT];
+#pragma unroll
+  for (int i = 0; i < NFT; ++i) acc[i] = dbl4{0.0, 0.0, 0.0, 0.0};
+  // Fetched one element ahead, as in k_mode_project: this thread's entries of the DOF rows, the element's map, and the
+  // four pixel corners of this lane's column at the wave's four points (zeros with zero weights outside the extent).
+  constexpr int NV = (6 * FMAX + 255) / 256;
+  double vn[NV];
+  auto fetch_rows = [&](int e) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int idx = tid + 256 * j;
+      vn[j] = 0.0;
+      if (idx < 6 * nf) {
+        const int f = idx % nf, r = dev_row(L, e, idx / nf);
+        if (r >= 0) vn[j] = V[((int64_t)(f / k) * nrows + r) * k + f % k];
+      }
+    }
+  };
+  double c00[4], c01[4], c10[4], c11[4], wa[4], wb[4];
+  auto fetch_corners = [&](const P2Map& M) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int pt = wave + 4 * j;
+      double X, Y;
+      M.point(c_q16x[pt], c_q16y[pt], X, Y);
+      int i0 = 0, j0 = 0;
+      wa[j] = wb[j] = 0.0;
+      c00[j] = c01[j] = c10[j] = c11[j] = 0.0;
+      if (sampled_cell(G, X, Y, i0, j0, wa[j], wb[j]) && live) {
+        const double* p = Fc + ((int64_t)j0 * G.nx + i0) * pix;
+        const int64_t up = (int64_t)G.nx * pix;
+        c00[j] = p[0];
+        c01[j] = p[pix];
+        c10[j] = p[up];
+        c11[j] = p[up + pix];
+      }
+    }
+  };
+  fetch_rows(blockIdx.y);
+  P2Map Mn(L.edof, L.ne, px, py, blockIdx.y);
+  fetch_corners(Mn);
+  int buf = 0;
+  for (int e = blockIdx.y; e < L.ne; e += gridDim.y, buf ^= 1) {
+    const P2Map M = Mn;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int idx = tid + 256 * j;
+      if (idx < 6 * nf) s_v[idx / nf][idx % nf] = vn[j];
+    }
+    {
+      const double adet = fabs(M.det());
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int pt = wave + 4 * j;
+        const double a = wa[j], b = wb[j], a1 = 1.0 - a, b1 = 1.0 - b;
+        const double lo = mul_rn(a1, c00[j]) + mul_rn(a, c01[j]), hi = mul_rn(a1, c10[j]) + mul_rn(a, c11[j]);
+        s_b[buf][pt][lane] = mul_rn(adet * c_q16w[pt], mul_rn(lo, b1) + mul_rn(hi, b));
+      }
+    }
+    __syncthreads();
+    if (e + (int)gridDim.y < L.ne) {
+      Mn = P2Map(L.edof, L.ne, px, py, e + gridDim.y);
+      fetch_rows(e + gridDim.y);
+      fetch_corners(Mn);
+    }
+    for (int idx = tid; idx < 16 * nf; idx += 256) {
+      const int f = idx % nf, t = idx / nf;
+      double u = 0.0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) u += s_phi[t][a] * s_v[a][f];
+      s_u[t][f] = u;
+    }
+    __syncthreads();
+    // A[row][kk] = u[field 16 i + row][t = 4 ks + kk], B[kk][col] = s_b[t][16 wave + col]; lane: row / col = lane & 15,
+    // kk = lane >> 4.  A wave whose 16 columns are all past the frames has nothing to add.
+    if (16 * wave < ncol) {
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int t = 4 * ks + l4;
+        const double bv = s_b[buf][t][16 * wave + l16];
+#pragma unroll
+        for (int i = 0; i < NFT; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(s_u[t][16 * i + l16], bv, acc[i], 0, 0, 0);
+      }
+    }
+    // (no barrier: the next element writes s_v and the other buffer of s_b, and s_u only behind its first barrier)
+  }
+  // D of v_mfma_f64_16x16x4_f64: entry g of a lane is (row (lane >> 4) + 4 g, col lane & 15)
+  double* out = partial + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * nf * PS_COLS;
+#pragma unroll
+  for (int i = 0; i < NFT; ++i) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int f = 16 * i + l4 + 4 * g;
+      if (f < nf) out[(int64_t)f * PS_COLS + 16 * wave + l16] = acc[i][g];
+    }
+  }
+}
+
+// Second stage of k_mode_project_sampled: one lane per double (field, column) of the launch's frame tiles, columns
+// [c0, c1) of O [nf][nfr][2]; the nblk partial tiles of its tile summed in slice order (the same bits on every run).
+__global__ __launch_bounds__(256) void k_project_sampled_reduce(int nf, int nfr, int c0, int c1, int nblk,
+                                                                const double* __restrict__ partial, double* __restrict__ O) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int w = c1 - c0;
+  if (v >= (int64_t)nf * w) return;
+  const int c = (int)(v % w), f = (int)(v / w);
+  const double* pp = partial + ((int64_t)(c / PS_COLS) * nblk * nf + f) * PS_COLS + c % PS_COLS;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += pp[(int64_t)b * nf * PS_COLS];
+  O[(int64_t)f * 2 * nfr + c0 + c] = s;
+}
+
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -1805,6 +1979,80 @@ extern "C" int plfem_mode_project(plfem_locator* L, int32_t ncomp, int32_t k, co
                      plan.ntx, nblk, partial, O);
   TRY(check_launch(L, "k_project_reduce"));
   HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * 2 * entries, hipMemcpyDeviceToHost, L->stream));
+  HIP_TRY(L, hipStreamSynchronize(L->stream));
+  return PLFEM_OK;
+} catch (...) { return host_failure(L); }
+
+namespace {
+// Work buffer of a sampled projection: the result [nf][frames][2], then the partial tiles [tile of a launch][slice][nf][PS_COLS]
+// of one launch's group of frame tiles, each part 256-byte aligned.  Sized for PS_SLICES slices: a mesh with fewer elements
+// uses fewer.
+struct SampledPlan {
+  int nf, nft, tiles;
+  size_t off_partial, total;   // bytes
+};
+SampledPlan sampled_plan(int ncomp, int k, int nfr) {
+  SampledPlan p;
+  p.nf = ncomp * k;
+  p.nft = (p.nf + 15) / 16;                                          // up to the next instance of k_mode_project_sampled
+  if (p.nft == 5) p.nft = 6;
+  if (p.nft == 7) p.nft = 8;
+  p.tiles = (nfr + PS_F - 1) / PS_F;
+  size_t o = align256(sizeof(double) * 2 * p.nf * nfr);
+  p.off_partial = o; o += align256(sizeof(double) * std::min(p.tiles, PS_GROUP) * PS_SLICES * p.nf * PS_COLS);
+  p.total = o;
+  return p;
+}
+bool sampled_sizes_ok(int ncomp, int k, int nfr) {
+  return ncomp >= 1 && ncomp <= 2 && k >= 1 && k <= PJ_KMAX && nfr >= 1 && nfr <= PS_FRAMES;
+}
+}  // namespace
+
+extern "C" int plfem_project_sampled_work_bytes(int32_t ncomp, int32_t k, int32_t nf, int64_t* bytes) {
+  if (!bytes || !sampled_sizes_ok(ncomp, k, nf)) return PLFEM_EINVAL;
+  *bytes = (int64_t)sampled_plan(ncomp, k, nf).total;
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_mode_project_sampled(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                          int32_t nx, int32_t ny, double x0, double y0, double dx, double dy, int32_t nf,
+                                          const double* frames_dev, void* work_dev, int64_t work_bytes, double* out_host) try {
+  if (!L) return PLFEM_EINVAL;
+  if (!sampled_sizes_ok(ncomp, k, nf) || nx < 2 || nx > PS_NMAX || ny < 2 || ny > PS_NMAX) {
+    L->err = "plfem_mode_project_sampled: ncomp must be 1 or 2, 1 <= k <= 64, 2 <= nx, ny <= 8192 and 1 <= nf <= 4096";
+    return PLFEM_EINVAL;
+  }
+  const SampledGrid grid{x0, y0, 1.0 / dx, 1.0 / dy, nx, ny};
+  if (!(dx > 0.0) || !(dy > 0.0) || !std::isfinite(dx) || !std::isfinite(dy) || !std::isfinite(x0) || !std::isfinite(y0) ||
+      !std::isfinite(grid.inv_dx) || !std::isfinite(grid.inv_dy)) {
+    L->err = "plfem_mode_project_sampled: x0, y0, dx, dy, 1 / dx and 1 / dy must be finite with dx, dy > 0";
+    return PLFEM_EINVAL;
+  }
+  if (!modes_dev || !frames_dev || !work_dev || !out_host) {
+    L->err = "plfem_mode_project_sampled: null array";
+    return PLFEM_EINVAL;
+  }
+  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_project_sampled: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  const SampledPlan plan = sampled_plan(ncomp, k, nf);
+  TRY(check_work(L, "plfem_mode_project_sampled", "plfem_project_sampled_work_bytes", work_dev, work_bytes, (int64_t)plan.total));
+  HIP_TRY(L, hipSetDevice(L->device));
+  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + plan.off_partial);
+  const int nblk = std::max(1, std::min(PS_SLICES, L->ne));           // the mesh alone decides: a frame's bits do not depend on nf
+  const int64_t nrows = indexed ? L->nsolve : L->N;
+  for (int t0 = 0; t0 < plan.tiles; t0 += PS_GROUP) {                 // (stream order keeps a group's partial tiles until its reduce)
+    const int nt = std::min(PS_GROUP, plan.tiles - t0);
+    with_constant<1, 2, 3, 4, 6, 8>(plan.nft, [&](auto nft) {
+      hipLaunchKernelGGL(k_mode_project_sampled<decltype(nft)::value>, dim3(nt, nblk), dim3(256), 0, L->stream,
+                         loc_args(L, indexed != 0), (int)ncomp, (int)k, nrows, modes_dev, grid, (int)nf, t0, frames_dev, partial);
+    });
+    TRY(check_launch(L, "k_mode_project_sampled"));
+    const int c0 = t0 * PS_COLS, c1 = std::min(2 * (int)nf, (t0 + nt) * PS_COLS);
+    const int64_t entries = (int64_t)plan.nf * (c1 - c0);
+    hipLaunchKernelGGL(k_project_sampled_reduce, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, L->stream, plan.nf, (int)nf,
+                       c0, c1, nblk, partial, O);
+    TRY(check_launch(L, "k_project_sampled_reduce"));
+  }
+  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * 2 * plan.nf * nf, hipMemcpyDeviceToHost, L->stream));
   HIP_TRY(L, hipStreamSynchronize(L->stream));
   return PLFEM_OK;
 } catch (...) { return host_failure(L); }

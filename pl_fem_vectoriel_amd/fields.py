@@ -19,7 +19,10 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
 * :meth:`ModeFields.quartic` -- the packed overlap of products of four modes on a 16-point degree-8 rule
   (``plfem_mode_quartic``): what :mod:`.nonlinear` builds the nonlinear coupling tensor, A_eff and gamma from;
 * :meth:`ModeFields.project` -- the projection of the modes on plane waves and Gaussian beams, fields that separate in
-  x and y, on the same rule (``plfem_mode_project``): what :mod:`.launch` builds far fields and launch maps from.
+  x and y, on the same rule (``plfem_mode_project``): what :mod:`.launch` builds far fields and launch maps from;
+* :meth:`ModeFields.project_sampled` -- the projection of the modes on a batch of complex images on a pixel grid (PSF
+  frames, speckle, measured near fields, beam-propagation output), interpolated bilinearly at the points of the same
+  rule (``plfem_mode_project_sampled``): what :func:`.launch.field_coupling` builds response maps from.
 
 Containment (``PLFEM_LOC_TOL``): a point is inside an element when every barycentric coordinate is >= -1e-10 (minus
 that coordinate's floating-point rounding bound, which matters on sliver elements only); when
@@ -45,6 +48,43 @@ MOMENT_GRAM_NAMES = {"vectorial": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y
                      "scalar": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "M_XX", "M_XY", "M_YY")}
 PROJECT_TILE = (8, 8)              # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
 PROJECT_MAX_FACTORS = 4096         # PJ_LMAX
+PROJECT_SAMPLED_TILE = 32          # PS_F: frames per workgroup tile of the sampled projection
+PROJECT_SAMPLED_MAX_FRAMES = 4096  # PS_FRAMES: frames per call of plfem_mode_project_sampled
+PROJECT_SAMPLED_MAX_PIXELS = 8192  # PS_NMAX: pixels per axis
+
+
+def _grid_axis(v, name: str) -> tuple:
+    """A pixel axis: 2 .. 8192 finite, ascending, uniformly spaced numbers (every step within 1e-12 of the span of the
+    mean step).  Returns (axis, step) with ``step = (v[-1] - v[0]) / (n - 1)``."""
+    try:
+        a = np.asarray(v, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a 1-D array of finite numbers") from None
+    if a.ndim != 1 or not 2 <= a.size <= PROJECT_SAMPLED_MAX_PIXELS or not np.all(np.isfinite(a)):
+        raise ValueError(f"{name} must be a 1-D array of 2 to {PROJECT_SAMPLED_MAX_PIXELS} finite numbers")
+    span = float(a[-1] - a[0])
+    step = span / (a.size - 1)
+    if not (np.isfinite(span) and step > 0 and np.isfinite(1.0 / step)):
+        raise ValueError(f"{name} must be ascending with a finite step whose inverse is finite")
+    if np.any(np.abs(np.diff(a) - step) > 1e-12 * span):
+        raise ValueError(f"{name} must be uniformly spaced and ascending: every step within 1e-12 (x[-1] - x[0]) of the mean step")
+    return a, step
+
+
+def _frames(frames, nx: int, ny: int) -> np.ndarray:
+    """Sampled fields as complex128 (nf, ny, nx); a single (ny, nx) image is one frame."""
+    try:
+        f = np.asarray(frames)
+        if f.dtype.kind not in "biufc":
+            raise TypeError
+        f = f.astype(np.complex128, copy=False)
+    except (TypeError, ValueError):
+        raise ValueError("frames must be a real or complex array of shape (nf, ny, nx) or (ny, nx)") from None
+    if f.ndim == 2:
+        f = f[None]
+    if f.ndim != 3 or f.shape[1:] != (ny, nx):
+        raise ValueError(f"frames must have shape (nf, {ny}, {nx}) or ({ny}, {nx}) for these axes, got {np.shape(frames)}")
+    return f
 
 
 def _mesh_arrays(mesh):
@@ -516,6 +556,55 @@ class ModeFields:
             out[:, :, s:s + chunk] = part
         return out
 
+    def project_sampled(self, modes: Sequence[Dict], frames, x, y) -> np.ndarray:
+        """Projection of the modes on sampled complex fields (``plfem_mode_project_sampled``), complex (ncomp, k, nf):
+        ``P[c, m, f] = sum over the elements and the 16-point degree-8 rule of |det J| w_q u_c,m(x_q) F_f(x_q)`` (no
+        conjugation), ``F_f`` the bilinear interpolant of ``frames[f]`` on the pixel grid ``x`` (nx,) x ``y`` (ny,) and 0
+        outside its closed extent.  ``frames`` is complex or real, (nf, ny, nx) or one image (ny, nx); ``x`` and ``y``
+        are ascending, uniformly spaced axes (every step within ``1e-12 (x[-1] - x[0])`` of the mean step; the ``"x"`` /
+        ``"y"`` of :meth:`sample_grid` are such axes) of 2 to 8192 pixels; the grid step is ``(x[-1] - x[0]) / (nx - 1)``.
+        Every component of a vectorial record is projected on its own.  The modes are staged once; the frames go to the
+        device in chunks of at most ``CHUNK_BYTES`` and 4096 frames, and the bits of a frame's result do not depend on
+        the chunking.  A NaN pixel gives NaN for its frame only.  At most 64 modes; an empty mode list gives an empty
+        array, ``nf = 0`` gives (ncomp, k, 0).  Argument errors raise ``ValueError`` before any device call."""
+        kind, vals, _ = self._check_records(modes)
+        xa, dx = _grid_axis(x, "x")
+        ya, dy = _grid_axis(y, "y")
+        nx, ny = xa.size, ya.size
+        fr = _frames(frames, nx, ny)
+        nf = fr.shape[0]
+        if kind is None:
+            return np.zeros((0, 0, nf), dtype=np.complex128)
+        ncomp, k = vals.shape[0], vals.shape[1]
+        if k > 64:
+            raise ValueError(f"at most 64 modes per projection, got {k}")
+        out = np.empty((ncomp, k, nf), dtype=np.complex128)
+        if nf == 0:
+            return out
+        self._ensure_locator()
+        import torch
+        chunk = int(max(1, min(nf, PROJECT_SAMPLED_MAX_FRAMES, self.CHUNK_BYTES // (16 * ny * nx))))
+        need = ctypes.c_int64(0)
+        if self._lib.plfem_project_sampled_work_bytes(ncomp, k, chunk, ctypes.byref(need)) != _native.PLFEM_OK:
+            raise ValueError(f"plfem_project_sampled_work_bytes rejected ncomp = {ncomp}, k = {k}, nf = {chunk}")
+        nbytes = int(need.value)                                  # (a shorter last chunk needs no more)
+        staged, _src = self._stage(vals)
+        work = _native.device_scratch(nbytes + 256, self.tdev)
+        aligned = (work.data_ptr() + 255) & ~255
+        with torch.cuda.stream(self.stream):
+            for s in range(0, nf, chunk):
+                src = torch.from_numpy(np.ascontiguousarray(fr[s:s + chunk])).to(self.tdev)       # (n, ny, nx) complex
+                n = src.shape[0]
+                dev = torch.view_as_real(src).permute(1, 2, 0, 3).contiguous()                    # [ny][nx][n][2]
+                del src
+                part = np.empty((ncomp, k, n), dtype=np.complex128)
+                self._check(self._lib.plfem_mode_project_sampled(
+                    self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()), 1 if kind == "vectorial" else 0, nx, ny,
+                    float(xa[0]), float(ya[0]), dx, dy, n, ctypes.c_void_p(dev.data_ptr()), ctypes.c_void_p(aligned),
+                    ctypes.c_int64(nbytes), part.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_project_sampled")
+                out[:, :, s:s + chunk] = part
+        return out
+
     def close(self):
         if getattr(self, "_loc", None):
             self._lib.plfem_locator_destroy(self._loc)      # synchronises the stream before the memory goes back to torch
@@ -700,4 +789,5 @@ def mode_overlap_poses(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict],
 
 
 __all__ = ["ModeFields", "mode_overlap", "mode_overlap_poses", "pose_table", "POSE_MAX_CHUNK_PAIRS", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES", "PROFILE_GRAM_NAMES",
-           "PROJECT_TILE", "PROJECT_MAX_FACTORS"]
+           "PROJECT_TILE", "PROJECT_MAX_FACTORS", "PROJECT_SAMPLED_TILE", "PROJECT_SAMPLED_MAX_FRAMES",
+           "PROJECT_SAMPLED_MAX_PIXELS"]

@@ -11,6 +11,13 @@ the GPU over the mesh the modes live on with the 16-point degree-8 rule (:meth:`
 every component of a vectorial record (``Ex_dofs`` / ``Ey_dofs`` hold Hx / Hy) is projected on its own, and nothing is
 assumed about the pencil the modes came from.  The reference has no counterpart: it turns no mode vector back into a
 field.
+
+What a lantern meets in practice is neither separable nor analytic -- an aberrated PSF, a speckle pattern, a measured
+near field, the output of a beam-propagation run: complex images on a pixel grid.  :func:`field_coupling` takes a batch
+of them: the overlap of every mode with the bilinear interpolant of every image, on the same
+16-point rule and on the GPU (:meth:`ModeFields.project_sampled`, ``plfem_mode_project_sampled``), with the coupling
+efficiency per mode, the power fraction the span of the modes captures, and the images' own power
+(:func:`sampled_power`, exact for the interpolant, on the host).
 """
 from __future__ import annotations
 
@@ -18,7 +25,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from .fields import PROJECT_MAX_FACTORS, ModeFields, _records, mode_overlap
+from .fields import PROJECT_MAX_FACTORS, ModeFields, _frames, _grid_axis, _records, mode_overlap
 
 
 def _axis(v, name: str) -> np.ndarray:
@@ -141,4 +148,76 @@ def gaussian_coupling(modes: Sequence[Dict], mesh, waist: float, cx, cy, tilt=(0
     return {"amplitude": amp, "efficiency": eff, "cx": cx, "cy": cy}
 
 
-__all__ = ["far_field", "encircled_na", "gaussian_coupling"]
+def _mass_1d(f: np.ndarray, h: float, axis: int) -> np.ndarray:
+    """The 1-D piecewise-linear mass matrix of step ``h`` (cells of ``(h / 6) [[2, 1], [1, 2]]``) applied along ``axis``."""
+    f = np.moveaxis(f, axis, -1)
+    out = 4.0 * f
+    out[..., 0] = 2.0 * f[..., 0]
+    out[..., -1] = 2.0 * f[..., -1]
+    out[..., 1:] += f[..., :-1]
+    out[..., :-1] += f[..., 1:]
+    return np.moveaxis(out * (h / 6.0), -1, axis)
+
+
+def sampled_power(fields, x, y) -> np.ndarray:
+    """``P_f`` (nf,): the exact integral of ``|bilinear interpolant of fields[f]|^2`` over the whole pixel grid ``x`` (nx,) x
+    ``y`` (ny,) (host only).  On a cell the interpolant is a tensor product of linear functions, so the integral is the
+    quadratic form of the tensor product of the two 1-D mass matrices, cells of ``(h / 6) [[2, 1], [1, 2]]``.  ``fields``
+    and the axes are those of :meth:`ModeFields.project_sampled`."""
+    xa, dx = _grid_axis(x, "x")
+    ya, dy = _grid_axis(y, "y")
+    f = _frames(fields, xa.size, ya.size)
+    out = np.empty(f.shape[0])
+    for s in range(0, f.shape[0], 64):                              # (bounded temporaries)
+        c = f[s:s + 64]
+        m = _mass_1d(_mass_1d(c, dx, 2), dy, 1)
+        out[s:s + 64] = (c.real * m.real + c.imag * m.imag).sum(axis=(1, 2))
+    return out
+
+
+def field_coupling(modes: Sequence[Dict], mesh, fields, x, y, polarization=(1.0, 0.0), power=None,
+                   device: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """Coupling of the modes (at most 64) to a batch of sampled input fields -- PSF frames of an aberrated telescope,
+    speckle, a measured near field, the output of a beam-propagation run: ``fields`` complex or real (nf, ny, nx) or
+    (ny, nx) on the pixel grid ``x`` (nx,) x ``y`` (ny,) (ascending, uniformly spaced), taken between the pixels as their
+    bilinear interpolant and as 0 outside the grid (:meth:`ModeFields.project_sampled`).
+
+    * ``amplitude`` complex (ncomp, k, nf): ``A = integral u F dA`` of every component (no conjugation);
+    * ``efficiency`` (k, nf) = ``|sum_c p_c A_c|^2 / (N_m P_f)``, with ``N_m`` as in :func:`gaussian_coupling` and ``p`` the
+      unit vector along ``polarization`` (ignored for scalar records);
+    * ``captured`` (nf,) = ``c^H G^-1 c / P_f`` with ``G = mode_overlap(modes, mesh, modes, mesh)`` and ``c = sum_c p_c
+      A_c``: the power fraction the span of the given modes takes, also for modes that are not orthonormal;
+    * ``power`` (nf,) = ``P_f``: by default :func:`sampled_power`, the exact integral of the interpolant's modulus
+      squared over the whole grid, so power outside the mesh counts as lost, as in :func:`gaussian_coupling`;
+      ``power=`` takes the caller's own (nf,) finite, non-negative numbers instead.  A field without power gives NaN
+      or inf.
+
+    ``mesh`` is the mesh the modes were solved on, or its :class:`ModeFields`.  Argument errors raise ``ValueError``
+    before any device call."""
+    xa, dx = _grid_axis(x, "x")
+    ya, dy = _grid_axis(y, "y")
+    fr = _frames(fields, xa.size, ya.size)
+    pol = _pair(polarization, "polarization")
+    if not np.hypot(pol[0], pol[1]) > 0:
+        raise ValueError("polarization must not be the zero vector")
+    pol = pol / np.hypot(pol[0], pol[1])
+    if power is None:
+        pw = sampled_power(fr, xa, ya)
+    else:
+        try:
+            pw = np.asarray(power, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"power must be an array of {fr.shape[0]} numbers") from None
+        if pw.shape != (fr.shape[0],) or not np.all(np.isfinite(pw)) or np.any(pw < 0):
+            raise ValueError(f"power must have shape ({fr.shape[0]},), finite and >= 0")
+    mf = _fields_of(modes, mesh, device)
+    amp = mf.project_sampled(modes, fr, xa, ya)
+    G = mode_overlap(modes, mf, modes, mf)
+    c = amp[0] if amp.shape[0] == 1 else pol[0] * amp[0] + pol[1] * amp[1]                # (k, nf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        eff = (c.real ** 2 + c.imag ** 2) / (np.diag(G)[:, None] * pw[None, :])
+        cap = np.real(np.sum(np.conj(c) * np.linalg.solve(G, c), axis=0)) / pw
+    return {"amplitude": amp, "efficiency": eff, "captured": cap, "power": pw}
+
+
+__all__ = ["far_field", "encircled_na", "gaussian_coupling", "field_coupling", "sampled_power"]
