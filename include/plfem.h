@@ -82,7 +82,8 @@ int plfem_symbolic_info(const plfem_symbolic* sym, int64_t* info /* [PLFEM_INFO_
  * "leaf_of_elem"[ne] i32, "owner"[N] i32, "fs","fb"[nfronts] i32, "fnode_ptr","foff"[nfronts+1] i64, "soff"[nfronts] i64
  * (foff: kept part of a front = [F11; F21] m x s2 then Z^T s2 x b2; soff: its Schur complement inside the level's arena),
  * "fnodes","cinv0","cinv1"[fnode_ptr[nfronts]] i32, "epos"[6][ne] i32 (by element id), "epos_leaf"[ne][6] i32 (in the order of
- * "leaf_elems": what the device reads).
+ * "leaf_elems": what the device reads), "elem_nbr"[3][ne] i32 (the element across local edge (0,1), (1,2), (0,2), -1 on the
+ * outer boundary; built on first request).
  * plfem_symbolic_array_bytes returns the size in bytes or a negative error. */
 int64_t plfem_symbolic_array_bytes(const plfem_symbolic* sym, const char* name);
 int plfem_symbolic_get(const plfem_symbolic* sym, const char* name, void* out_host, int64_t nbytes);
@@ -98,6 +99,23 @@ int plfem_mesh_edge_count(int32_t nv, int32_t ne, const double* p_host, const in
                           int32_t* nedges, char* err, int32_t errlen);
 int plfem_mesh_refine(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
                       double* p_out, int32_t* t_out, char* err, int32_t errlen);
+
+/* Marked refinement: longest-edge bisection with a conformity closure (host, stateless, deterministic); what an adaptive
+ * loop refines the elements with that plfem_mode_indicators singles out.  marked_host[ne]: non-zero = refine this element.
+ *   1. every marked element marks its longest edge -- squared lengths dx dx + dy dy from the sorted vertex pair of the
+ *      edge (one value per edge, whichever element asks), ties to the smallest edge id;
+ *   2. closure: an element with a marked edge also marks its own longest edge, until nothing changes;
+ *   3. an element with 1 / 2 / 3 marked edges is bisected at its longest edge, then each child that holds another marked
+ *      edge is bisected at that edge: 2 / 3 / 4 children.  The result is conforming.
+ * Old vertices keep their ids; new vertex id = nv + the rank of its edge among the marked edges in edge-id order, at the
+ * midpoint 0.5 (p_lo + p_hi); elements come out in the order of their parents, columns sorted; parent_out[ne_out] names
+ * the parent.  plfem_mesh_refine_marked_count gives the sizes: p_out [2][nv_out], t_out [3][ne_out].
+ * PLFEM_EINVAL (a null pointer) and PLFEM_EMESH (a mesh the numbering rejects) write their message to err. */
+int plfem_mesh_refine_marked_count(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
+                                   const uint8_t* marked_host, int32_t* nv_out, int32_t* ne_out, char* err, int32_t errlen);
+int plfem_mesh_refine_marked(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
+                             const uint8_t* marked_host, double* p_out, int32_t* t_out, int32_t* parent_out,
+                             char* err, int32_t errlen);
 
 /* ---------------------------------------------------------------------------------------------
  * Context: binds a symbolic analysis to a device and stream, uploads the index structures and
@@ -553,6 +571,45 @@ int plfem_mode_project_sampled(plfem_locator* loc, int32_t ncomp, int32_t k, con
                                int32_t nx, int32_t ny, double x0, double y0, double dx, double dy,
                                int32_t nf, const double* frames_dev /* [ny][nx][nf][2] re, im */,
                                void* work_dev, int64_t work_bytes, double* out_host /* [ncomp][k][nf][2] */);
+
+/* A-posteriori error indicators of k staged modes: where the mesh limits the eigenvalues a solve returned.  For mode m
+ * with pencil eigenvalue lambda_host[m] (vectorial: beta^2; scalar: -beta^2), element T and its three edges e,
+ *   out_host[m][T] = |det J_T| sum_q |det J_T| w_q |r(x_q)|^2 + sum_e c_e |e| int_e |[F . n]|^2 ds,
+ * the first sum over the assembly's six-point rule, the edge integral by the two-point Gauss rule s = 1/2 -+ 1/(2 sqrt 3)
+ * (exact: the jump of the flux of a P2 field is linear along an edge).  c_e = 1/2 on an interior edge; on an edge of the
+ * outer boundary 1 for the scalar pencil (natural boundary: the flux itself is the residual) and 0 for the vectorial one
+ * (Dirichlet).  Edges run from the lower to the higher vertex id and the edge point is x_lo + fl(s (x_hi - x_lo)): both
+ * neighbours form it identically and see the same permittivity.
+ *   ncomp = 1, (K - k0^2 M_eps) u = lambda M u:  F = grad u,  r = -lap u - (k0^2 eps + lambda) u;
+ *   ncomp = 2, A = K + alpha_p D - k0^2 M, B = M_(1/eps) with the forms as listed for plfem_mode_grams, w = 1 / eps:
+ *     F_x = (-w dy hy + alpha_p dx hx,  w dy hx + alpha_p dx hy),  F_y = (w dx hy + alpha_p dy hx,  -w dx hx + alpha_p dy hy),
+ *     r_x = -div F_x - (k0^2 + lambda w) hx,  r_y = -div F_y - (k0^2 + lambda w) hy,
+ *     div F taken with w frozen at the point (the second derivatives of a P2 field are constant per element).
+ *   Summed against a basis function, int r phi_i over the elements plus the outward fluxes int F . n phi_i over all their
+ *   edges reproduce ((A - lambda B) h)_i of the unrestricted matrices: the indicator is the residual of the assembled
+ *   pencil, localised.
+ * Permittivity: nlayer > 0: the index profile (layers_host, nlayer, eps_bg as for plfem_set_index_profile) and the cores
+ * arguments are not read; nlayer = 0: eps_core inside the closed discs of cores_host (ncore in [0, 64], the core test of
+ * plfem_assemble_hfield) and eps_clad outside.  Either way a point is decided by the helpers the assembly uses.
+ * modes_dev: staged by plfem_stage_modes ([ncomp][nrows][k]); indexed as in plfem_sample_fields (a boundary DOF of an
+ * indexed record contributes 0).  The element neighbours ("elem_nbr" [3][ne] i32 of plfem_symbolic_get: the element across
+ * local edge (0,1), (1,2), (0,2), -1 on the outer boundary; built on the host on first request) and the eigenvalues travel
+ * to the device inside the work buffer.  A workgroup owns 16 consecutive elements and stages their geometry and that of
+ * their neighbours once; one lane then forms one (element, mode) value in a fixed operation order, nothing is summed
+ * across lanes: the bits of out_host[m][T] depend on mode m, its eigenvalue, the mesh and the material table only -- not on
+ * k, on the other modes, on what the work buffer held or on the run.  Runs on the locator's stream and synchronises it.
+ * work_dev: device scratch of plfem_indicator_work_bytes(loc, ncomp, k) bytes, 256-byte aligned: k ne doubles, 3 ne int32
+ * and k doubles, each part rounded up to 256 bytes.
+ * Argument errors (ncomp not 1 or 2, k < 1, a null pointer, a non-finite eigenvalue, k0 or alpha_p, a table
+ * plfem_set_index_profile rejects, with nlayer = 0 ncore outside [0, 64] or eps_core / eps_clad not finite and positive,
+ * work_bytes too small, an indexed record on an analysis without interior DOFs) return PLFEM_EINVAL with the locator's
+ * last error set, before any launch. */
+int plfem_indicator_work_bytes(const plfem_locator* loc, int32_t ncomp, int32_t k, int64_t* bytes);
+int plfem_mode_indicators(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                          const double* lambda_host /* [k] */, double k0, double alpha_p,
+                          const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                          const double* layers_host, int32_t nlayer, double eps_bg,
+                          void* work_dev, int64_t work_bytes, double* out_host /* [k][ne] */);
 
 #ifdef PLFEM_TEST_HOOKS
 /* ---------------------------------------------------------------------------------------------

@@ -44,6 +44,7 @@ EXPORTS = (
     "plfem_core_gram_work_bytes", "plfem_core_grams", "plfem_moment_gram_work_bytes", "plfem_moment_grams",
     "plfem_set_index_profile", "plfem_profile_gram_work_bytes", "plfem_profile_grams",
     "plfem_project_sampled_work_bytes", "plfem_mode_project_sampled",
+    "plfem_indicator_work_bytes", "plfem_mode_indicators", "plfem_mesh_refine_marked_count", "plfem_mesh_refine_marked",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -68,6 +69,7 @@ _ARRAY_DTYPES = {
     "owner": np.int32, "fs": np.int32, "fb": np.int32, "fs_true": np.int32, "fb_true": np.int32,
     "fnode_ptr": np.int64, "fnodes": np.int32, "cinv0": np.int32, "cinv1": np.int32, "foff": np.int64, "soff": np.int64, "prow": np.int32, "npos": np.int32,
     "loc_grid": np.float64, "loc_cell_ptr": np.int32, "loc_cell_elems": np.int32, "loc_stats": np.float64,
+    "elem_nbr": np.int32,
 }
 
 
@@ -257,6 +259,16 @@ def load_library() -> ctypes.CDLL:
                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.c_void_p]
+    lib.plfem_indicator_work_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
+    lib.plfem_mode_indicators.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double,
+                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    lib.plfem_mesh_refine_marked_count.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_int32]
+    lib.plfem_mesh_refine_marked.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32]
     _lib = lib
     return lib
 
@@ -284,6 +296,39 @@ def mesh_refine(p, t):
     if rc != PLFEM_OK:
         raise ValueError(f"plfem_mesh_refine failed ({rc}): {err.value.decode()}")
     return p2, t2
+
+
+def mesh_refine_marked(p, t, marked):
+    """Longest-edge bisection of the marked elements with a conformity closure (``plfem_mesh_refine_marked``): returns
+    ``(p2 (2, nv2) float64, t2 (3, ne2) int32, parent (ne2,) int32)``; ``marked`` is one flag per element."""
+    lib = load_library()
+    p = np.ascontiguousarray(np.asarray(p, dtype=np.float64))
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.int32))
+    if p.ndim != 2 or p.shape[0] != 2 or t.ndim != 2 or t.shape[0] != 3:
+        raise ValueError("mesh.p must be (2, nv) and mesh.t (3, ne)")
+    try:
+        mk = np.asarray(marked)
+        if mk.dtype.kind not in "biu":
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("marked must be an array of one flag (bool or integer) per element") from None
+    if mk.shape != (t.shape[1],):
+        raise ValueError(f"marked must have one flag per element ({t.shape[1]}), got shape {mk.shape}")
+    mk = np.ascontiguousarray(mk != 0, dtype=np.uint8)
+    err = ctypes.create_string_buffer(512)
+    nv2, ne2 = ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = lib.plfem_mesh_refine_marked_count(p.shape[1], t.shape[1], _ptr(p), _ptr(t), _ptr(mk), ctypes.byref(nv2),
+                                            ctypes.byref(ne2), err, 512)
+    if rc != PLFEM_OK:
+        raise ValueError(f"plfem_mesh_refine_marked_count failed ({rc}): {err.value.decode()}")
+    p2 = np.empty((2, nv2.value), dtype=np.float64)
+    t2 = np.empty((3, ne2.value), dtype=np.int32)
+    parent = np.empty(ne2.value, dtype=np.int32)
+    rc = lib.plfem_mesh_refine_marked(p.shape[1], t.shape[1], _ptr(p), _ptr(t), _ptr(mk), _ptr(p2), _ptr(t2), _ptr(parent),
+                                      err, 512)
+    if rc != PLFEM_OK:
+        raise ValueError(f"plfem_mesh_refine_marked failed ({rc}): {err.value.decode()}")
+    return p2, t2, parent
 
 
 def load_test_hooks() -> ctypes.CDLL:

@@ -117,6 +117,7 @@ bool lookup(const Symbolic& S, const char* name, ArrayRef& r) {
   else if (n == "loc_cell_ptr") { plfem::ensure_locator(S); r = aref(S.loc_cell_ptr); }
   else if (n == "loc_cell_elems") { plfem::ensure_locator(S); r = aref(S.loc_cell_elems); }
   else if (n == "loc_stats") { plfem::ensure_locator(S); r = aref(S.loc_stats); }
+  else if (n == "elem_nbr") { plfem::ensure_elem_nbr(S); r = aref(S.elem_nbr); }
   else return false;
   return true;
 }
@@ -175,6 +176,136 @@ extern "C" int plfem_mesh_refine(int32_t nv, int32_t ne, const double* p_host, c
       t_out[col] = a;
       t_out[n4 + col] = b;
       t_out[2 * n4 + col] = cc;
+    }
+  }
+  return PLFEM_OK;
+} catch (...) { return host_failure(err, errlen); }
+
+// ---------------------------------------------------------------------------------------------
+// Marked refinement: longest-edge bisection with a conformity closure (include/plfem.h, "Marked refinement").
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr int EDGE_A[3] = {0, 1, 0}, EDGE_B[3] = {1, 2, 2}, EDGE_OPP[3] = {2, 0, 1};   // local edges (0,1), (1,2), (0,2)
+inline int local_edge(int i, int j) { return i + j == 1 ? 0 : (i + j == 3 ? 1 : 2); }
+
+// What both entry points derive from the mesh and the marks: the longest local edge of every element, the new vertex
+// of every marked edge (-1: not marked) and the sizes of the refined mesh.
+struct MarkedPlan {
+  std::vector<int8_t> longest;     // [ne]
+  std::vector<int32_t> mid;        // [nedges]
+  int32_t nv_out = 0, ne_out = 0;
+};
+
+std::string marked_plan(int nv, int ne, const double* p, const int32_t* t, const uint8_t* marked, Symbolic& S, MarkedPlan& P) {
+  std::string msg = plfem::numbering_only(nv, ne, p, t, S);
+  if (!msg.empty()) return msg;
+  const int nedges = S.nedges;
+  const int32_t* t2f = S.edof.data() + (size_t)3 * ne;             // [3][ne], edge DOF = nv + edge id
+  // squared lengths from the sorted vertex pair: one value per edge, the same for both neighbours
+  std::vector<double> len2(nedges);
+  for (int f = 0; f < nedges; ++f) {
+    const int32_t lo = S.edges[f], hi = S.edges[(size_t)nedges + f];
+    const double dx = p[hi] - p[lo], dy = p[(size_t)nv + hi] - p[(size_t)nv + lo];
+    len2[f] = dx * dx + dy * dy;
+  }
+  P.longest.resize(ne);
+  std::vector<int32_t> edge_elems((size_t)2 * nedges, -1);
+  for (int e = 0; e < ne; ++e) {
+    int best = 0;
+    for (int l = 0; l < 3; ++l) {
+      const int32_t f = t2f[(size_t)l * ne + e] - nv, fb = t2f[(size_t)best * ne + e] - nv;
+      if (len2[f] > len2[fb] || (len2[f] == len2[fb] && f < fb)) best = l;     // ties: the smallest edge id
+      edge_elems[(size_t)2 * f + (edge_elems[(size_t)2 * f] < 0 ? 0 : 1)] = e;
+    }
+    P.longest[e] = (int8_t)best;
+  }
+  // marks and closure: an element with a marked edge has its own longest edge marked
+  std::vector<uint8_t> me(nedges, 0);
+  std::vector<int32_t> stack;
+  auto mark_longest = [&](int e) {
+    const int32_t f = t2f[(size_t)P.longest[e] * ne + e] - nv;
+    if (!me[f]) { me[f] = 1; stack.push_back(f); }
+  };
+  for (int e = 0; e < ne; ++e)
+    if (marked[e]) mark_longest(e);
+  while (!stack.empty()) {
+    const int32_t f = stack.back();
+    stack.pop_back();
+    for (int s = 0; s < 2; ++s)
+      if (edge_elems[(size_t)2 * f + s] >= 0) mark_longest(edge_elems[(size_t)2 * f + s]);
+  }
+  P.mid.assign(nedges, -1);
+  int32_t rank = 0;
+  for (int f = 0; f < nedges; ++f)
+    if (me[f]) P.mid[f] = nv + rank++;
+  int64_t ne_out = ne;
+  for (int e = 0; e < ne; ++e)
+    for (int l = 0; l < 3; ++l) ne_out += P.mid[t2f[(size_t)l * ne + e] - nv] >= 0;
+  if ((int64_t)nv + rank > INT32_MAX || ne_out > INT32_MAX) return "refined mesh too large for 32-bit ids";
+  P.nv_out = nv + rank;
+  P.ne_out = (int32_t)ne_out;
+  return "";
+}
+}  // namespace
+
+extern "C" int plfem_mesh_refine_marked_count(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
+                                              const uint8_t* marked_host, int32_t* nv_out, int32_t* ne_out,
+                                              char* err, int32_t errlen) try {
+  if (!p_host || !t_host || !marked_host || !nv_out || !ne_out)
+    return write_err(err, errlen, "plfem_mesh_refine_marked_count: null pointer", PLFEM_EINVAL);
+  plfem::Symbolic S;
+  MarkedPlan P;
+  std::string msg = marked_plan(nv, ne, p_host, t_host, marked_host, S, P);
+  if (!msg.empty()) return write_err(err, errlen, msg, PLFEM_EMESH);
+  *nv_out = P.nv_out;
+  *ne_out = P.ne_out;
+  return PLFEM_OK;
+} catch (...) { return host_failure(err, errlen); }
+
+extern "C" int plfem_mesh_refine_marked(int32_t nv, int32_t ne, const double* p_host, const int32_t* t_host,
+                                        const uint8_t* marked_host, double* p_out, int32_t* t_out, int32_t* parent_out,
+                                        char* err, int32_t errlen) try {
+  if (!p_host || !t_host || !marked_host || !p_out || !t_out || !parent_out)
+    return write_err(err, errlen, "plfem_mesh_refine_marked: null pointer", PLFEM_EINVAL);
+  plfem::Symbolic S;
+  MarkedPlan P;
+  std::string msg = marked_plan(nv, ne, p_host, t_host, marked_host, S, P);
+  if (!msg.empty()) return write_err(err, errlen, msg, PLFEM_EMESH);
+  const size_t nvo = (size_t)P.nv_out, neo = (size_t)P.ne_out;
+  const int nedges = S.nedges;
+  std::memcpy(p_out, p_host, sizeof(double) * nv);
+  std::memcpy(p_out + nvo, p_host + nv, sizeof(double) * nv);
+  for (int f = 0; f < nedges; ++f) {
+    const int32_t m = P.mid[f];
+    if (m < 0) continue;
+    const int32_t lo = S.edges[f], hi = S.edges[(size_t)nedges + f];
+    p_out[m] = 0.5 * (p_host[lo] + p_host[hi]);
+    p_out[nvo + m] = 0.5 * (p_host[(size_t)nv + lo] + p_host[(size_t)nv + hi]);
+  }
+  const int32_t* d = S.edof.data();
+  size_t col = 0;
+  auto emit = [&](int32_t a, int32_t b, int32_t c, int32_t parent) {
+    if (a > b) std::swap(a, b);
+    if (b > c) std::swap(b, c);
+    if (a > b) std::swap(a, b);
+    t_out[col] = a;
+    t_out[neo + col] = b;
+    t_out[2 * neo + col] = c;
+    parent_out[col++] = parent;
+  };
+  for (int e = 0; e < ne; ++e) {
+    const int32_t v[3] = {d[e], d[(size_t)ne + e], d[(size_t)2 * ne + e]};
+    int32_t m[3];
+    for (int l = 0; l < 3; ++l) m[l] = P.mid[d[(size_t)(3 + l) * ne + e] - nv];
+    if (m[0] < 0 && m[1] < 0 && m[2] < 0) { emit(v[0], v[1], v[2], e); continue; }
+    // bisect at the longest edge (a, b) with midpoint M; the child at x has the other edge (x, c): bisect it there if marked
+    const int L = P.longest[e], c = EDGE_OPP[L];
+    const int32_t M = m[L];
+    const int ends[2] = {EDGE_A[L], EDGE_B[L]};
+    for (int x : ends) {
+      const int32_t mm = m[local_edge(std::min(x, c), std::max(x, c))];
+      if (mm < 0) emit(v[x], M, v[c], e);
+      else { emit(v[x], M, mm, e); emit(mm, M, v[c], e); }
     }
   }
   return PLFEM_OK;

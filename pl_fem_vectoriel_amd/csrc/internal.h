@@ -35,7 +35,7 @@ using Owned = std::unique_ptr<T, Delete<T>>;
 // The functions left outside cannot throw: plfem_destroy, plfem_symbolic_destroy, plfem_locator_destroy,
 // plfem_last_error, plfem_locator_last_error, plfem_symbolic_info and the sizers plfem_overlap_work_bytes,
 // plfem_gram_work_bytes, plfem_profile_gram_work_bytes, plfem_quartic_work_bytes, plfem_project_work_bytes,
-// plfem_project_sampled_work_bytes.  (plfem_symbolic_create returns through
+// plfem_project_sampled_work_bytes, plfem_indicator_work_bytes.  (plfem_symbolic_create returns through
 // plfem_symbolic_create_ex.)
 // Call it inside a catch handler only: the exception in flight stays alive until that handler exits.
 int host_failure(char* err, int32_t errlen) noexcept {

@@ -9,7 +9,8 @@
 // bilinearly (k_mode_project_sampled + k_project_sampled_reduce), and the Grams of a mode set restricted to each core disc (k_core_owner,
 // k_core_count + k_core_fill, k_core_grams + k_overlap_reduce), and the region Grams weighted by the coordinates of the
 // quadrature point (k_moment_grams + k_overlap_reduce), and the Grams under the permittivity of an index profile
-// (k_profile_grams + k_overlap_reduce).
+// (k_profile_grams + k_overlap_reduce), and the per-element a-posteriori error indicators of a mode set: element residual
+// plus flux jumps across the edges (k_mode_indicators).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
@@ -1334,6 +1335,201 @@ __global__ __launch_bounds__(256) void k_project_sampled_reduce(int nf, int nfr,
   O[(int64_t)f * 2 * nfr + c0 + c] = s;
 }
 
+
+// A-posteriori error indicators of k staged modes (plfem_mode_indicators): per element T and mode m
+//   eta2[m][T] = |det J| sum_q |det J| w_q |r(x_q)|^2 + sum_e c_e |e| int_e |[F . n]|^2 ds,
+// the strong residual r of the pencil on the assembly's six-point rule and the jump of the flux F across the three edges
+// on a two-point Gauss rule (exact: the jump is linear along an edge); c_e = 1/2 inside, on the outer boundary 1 for the
+// scalar pencil (natural boundary) and 0 for the vectorial one (Dirichlet).  With t = x_hi - x_lo the edge vector and
+// n = (t_y, -t_x) / |e|, c_e |e| int_e (F . n)^2 ds = (c_e / 2) sum_g (F_g . (t_y, -t_x))^2: no square root is taken.
+// A workgroup owns IND_E consecutive elements.  Stage: 4 IND_E lanes form J^-1 and the six staged rows of every element
+// and of its three neighbours, and find the local edge each neighbour shares (by the id of the edge DOF); 12 IND_E lanes
+// evaluate the permittivity at the six quadrature points (P2Map::point, the assembly's) and at the 3 x 2 edge points
+// x_lo + fl(s (x_hi - x_lo)), which both neighbours of an edge form identically from the sorted vertex pair.  Compute:
+// lane (element, mode) = (tid / IND_M, tid % IND_M), IND_M modes per pass, so the 16 lanes of an element read 16
+// consecutive doubles of each staged row; one lane forms one value in one fixed operation order -- nothing is summed
+// across lanes, so the bits of eta2[m][T] do not depend on k or on the other modes -- and the pass is written out through
+// LDS, 16 consecutive elements per mode.  Every out[m][T] is written.
+constexpr int IND_E = 16;          // elements per workgroup
+constexpr int IND_M = 16;          // modes per pass
+constexpr double IND_G0 = 0.21132486540518708, IND_G1 = 0.7886751345948129;   // 1/2 -+ 1/(2 sqrt 3), as NumPy forms them
+
+// reference coordinates of the point at parameter s (from the lower to the higher vertex) of local edge l
+__device__ __forceinline__ void ind_edge_point(int l, double s, double& xi, double& eta) {
+  xi = l == 0 ? s : (l == 1 ? 1.0 - s : 0.0);
+  eta = l == 0 ? 0.0 : s;
+}
+
+template <int NCOMP>
+__global__ __launch_bounds__(256) void k_mode_indicators(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
+                                                         const int32_t* __restrict__ nbr, const double* __restrict__ lam,
+                                                         double k0sq, double alpha, CoreTable cores, int ncore, double eps_core,
+                                                         double eps_clad, const double* __restrict__ layers, int nlayer,
+                                                         double eps_bg, double* __restrict__ out) {
+  __shared__ double s_inv[IND_E][4][4];      // J^-1 of the element (slot 0) and of its neighbours (slots 1-3)
+  __shared__ int s_row[IND_E][4][6];         // their staged rows, -1 = contributes nothing
+  __shared__ int s_nl[IND_E][3];             // the neighbour's local index of the shared edge, -1 = outer boundary
+  __shared__ double s_det[IND_E];            // |det J|
+  __shared__ double s_tx[IND_E][3], s_ty[IND_E][3];
+  __shared__ double s_eps[IND_E][12];        // permittivity at the 6 quadrature and the 3 x 2 edge points
+  __shared__ double s_phi[6][6];             // [q][i] basis values at the quadrature points
+  __shared__ double s_out[IND_M][IND_E + 1];
+  const int tid = threadIdx.x;
+  const int ne = L.ne;
+  const int e0 = blockIdx.x * IND_E;
+  const double* px = L.pxy;
+  const double* py = L.pxy + L.nv;
+  if (tid < 36) s_phi[tid / 6][tid % 6] = p2_phi(tid % 6, c_qx[tid / 6], c_qy[tid / 6]);
+  if (tid < 4 * IND_E) {
+    const int el = tid >> 2, slot = tid & 3, e = e0 + el;
+    int id = -1;
+    if (e < ne) id = slot == 0 ? e : nbr[(int64_t)(slot - 1) * ne + e];
+    if (id >= 0) {
+      const P2Map M(L.edof, ne, px, py, id);
+      const double det = M.det();
+      M.inverse(det, s_inv[el][slot]);
+#pragma unroll
+      for (int a = 0; a < 6; ++a) s_row[el][slot][a] = dev_row(L, id, a);
+      if (slot == 0) {
+        s_det[el] = fabs(det);
+      } else {
+        const int node = L.edof[(int64_t)(2 + slot) * ne + e];
+        int nl = 0;
+#pragma unroll
+        for (int l = 1; l < 3; ++l)
+          if (L.edof[(int64_t)(3 + l) * ne + id] == node) nl = l;
+        s_nl[el][slot - 1] = nl;
+      }
+    } else if (slot > 0) {
+      s_nl[el][slot - 1] = -1;
+    }
+  } else {
+    const int idx = tid - 4 * IND_E, el = idx / 12, pt = idx % 12, e = e0 + el;
+    if (e < ne) {
+      double X, Y;
+      if (pt < 6) {
+        const P2Map M(L.edof, ne, px, py, e);
+        M.point(c_qx[pt], c_qy[pt], X, Y);
+      } else {
+        const int l = (pt - 6) >> 1;
+        const int va = L.edof[(int64_t)(l == 1 ? 1 : 0) * ne + e], vb = L.edof[(int64_t)(l == 0 ? 1 : 2) * ne + e];
+        const double tx = px[vb] - px[va], ty = py[vb] - py[va];
+        const double s = (pt & 1) ? IND_G1 : IND_G0;
+        X = px[va] + mul_rn(s, tx);
+        Y = py[va] + mul_rn(s, ty);
+        if (!(pt & 1)) { s_tx[el][l] = tx; s_ty[el][l] = ty; }
+      }
+      s_eps[el][pt] = nlayer > 0 ? profile_eps(X, Y, layers, nlayer, eps_bg)
+                                 : (in_any_core(X, Y, cores.c, ncore) ? eps_core : eps_clad);
+    }
+  }
+  __syncthreads();
+  const int el = tid / IND_M, ml = tid % IND_M, e = e0 + el;
+  const int64_t plane = nrows * k;
+  for (int m0 = 0; m0 < k; m0 += IND_M) {
+    const int m = m0 + ml;
+    if (m < k && e < ne) {
+      double u[NCOMP][6], uxx[NCOMP], uxy[NCOMP], uyy[NCOMP];
+#pragma unroll
+      for (int c = 0; c < NCOMP; ++c) {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          const int r = s_row[el][0][a];
+          u[c][a] = r < 0 ? 0.0 : V[c * plane + (int64_t)r * k + m];
+        }
+        p2_hess(s_inv[el][0], u[c], uxx[c], uxy[c], uyy[c]);
+      }
+      const double lm = lam[m];
+      // the element residual on the six-point rule
+      double acc = 0.0;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) {
+        double uq[NCOMP];
+#pragma unroll
+        for (int c = 0; c < NCOMP; ++c) {
+          uq[c] = 0.0;
+#pragma unroll
+          for (int a = 0; a < 6; ++a) uq[c] += s_phi[q][a] * u[c][a];
+        }
+        const double eps = s_eps[el][q];
+        double r2;
+        if constexpr (NCOMP == 2) {
+          const double w = 1.0 / eps;
+          const double dfx = -w * uxy[1] + alpha * uxx[0] + w * uyy[0] + alpha * uxy[1];
+          const double dfy = w * uxx[1] + alpha * uxy[0] - w * uxy[0] + alpha * uyy[1];
+          const double rx = -dfx - (k0sq + lm * w) * uq[0], ry = -dfy - (k0sq + lm * w) * uq[1];
+          r2 = rx * rx + ry * ry;
+        } else {
+          const double r = -(uxx[0] + uyy[0]) - (k0sq * eps + lm) * uq[0];
+          r2 = r * r;
+        }
+        acc += c_qw[q] * r2;
+      }
+      const double det = s_det[el];
+      double eta = det * (det * acc);
+      // the flux jumps across the three edges
+#pragma unroll 1
+      for (int l = 0; l < 3; ++l) {
+        const int nl = s_nl[el][l];
+        if (NCOMP == 2 && nl < 0) continue;        // Dirichlet boundary: no term
+        double un[NCOMP][6];
+#pragma unroll
+        for (int c = 0; c < NCOMP; ++c)
+#pragma unroll
+          for (int a = 0; a < 6; ++a) {
+            const int r = nl < 0 ? -1 : s_row[el][1 + l][a];
+            un[c][a] = r < 0 ? 0.0 : V[c * plane + (int64_t)r * k + m];
+          }
+        const double tx = s_tx[el][l], ty = s_ty[el][l];
+        double j2 = 0.0;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          const double s = g ? IND_G1 : IND_G0;
+          double f[2][NCOMP];                       // F . (t_y, -t_x) of every component, this side and the other
+#pragma unroll
+          for (int side = 0; side < 2; ++side) {
+            double xi, eta_r, gx[6], gy[6], ux[NCOMP], uy[NCOMP];
+            ind_edge_point(side == 0 ? l : (nl < 0 ? 0 : nl), s, xi, eta_r);
+            p2_grad(s_inv[el][side == 0 ? 0 : 1 + l], xi, eta_r, gx, gy);
+#pragma unroll
+            for (int c = 0; c < NCOMP; ++c) {
+              ux[c] = uy[c] = 0.0;
+#pragma unroll
+              for (int a = 0; a < 6; ++a) {
+                const double v = side == 0 ? u[c][a] : un[c][a];
+                ux[c] += gx[a] * v;
+                uy[c] += gy[a] * v;
+              }
+            }
+            if constexpr (NCOMP == 2) {
+              const double w = 1.0 / s_eps[el][6 + 2 * l + g];
+              const double fxx = -w * uy[1] + alpha * ux[0], fxy = w * uy[0] + alpha * ux[1];
+              const double fyx = w * ux[1] + alpha * uy[0], fyy = -w * ux[0] + alpha * uy[1];
+              f[side][0] = fxx * ty - fxy * tx;
+              f[side][1] = fyx * ty - fyy * tx;
+            } else {
+              f[side][0] = ux[0] * ty - uy[0] * tx;
+            }
+          }
+#pragma unroll
+          for (int c = 0; c < NCOMP; ++c) {
+            const double j = nl < 0 ? f[0][c] : f[0][c] - f[1][c];
+            j2 += j * j;
+          }
+        }
+        eta += (nl < 0 ? 0.5 : 0.25) * j2;
+      }
+      s_out[ml][el] = eta;
+    }
+    __syncthreads();
+    {
+      const int mo = tid / IND_E, eo = tid % IND_E;
+      if (m0 + mo < k && e0 + eo < ne) out[(int64_t)(m0 + mo) * ne + e0 + eo] = s_out[mo][eo];
+    }
+    __syncthreads();
+  }
+}
+
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -1717,6 +1913,77 @@ extern "C" int plfem_profile_grams(plfem_locator* L, int32_t ncomp, int32_t k, c
   });
   TRY(check_launch(L, "k_profile_grams"));
   return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
+} catch (...) { return host_failure(L); }
+
+namespace {
+// plfem_mode_indicators: the result [k][ne], then the element-neighbour table [3][ne] int32, then the k eigenvalues
+struct IndicatorLayout { size_t off_nbr, off_lam, total; };
+IndicatorLayout indicator_layout(int ne, int k) {
+  IndicatorLayout l;
+  l.off_nbr = align256((size_t)k * ne * sizeof(double));
+  l.off_lam = l.off_nbr + align256((size_t)3 * ne * sizeof(int32_t));
+  l.total = l.off_lam + align256((size_t)k * sizeof(double));
+  return l;
+}
+}  // namespace
+
+extern "C" int plfem_indicator_work_bytes(const plfem_locator* L, int32_t ncomp, int32_t k, int64_t* bytes) {
+  if (!L || !bytes || ncomp < 1 || ncomp > 2 || k <= 0) return PLFEM_EINVAL;
+  *bytes = (int64_t)indicator_layout(L->ne, k).total;
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_mode_indicators(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                     const double* lambda_host, double k0, double alpha_p, const double* cores_host,
+                                     int32_t ncore, double eps_core, double eps_clad, const double* layers_host,
+                                     int32_t nlayer, double eps_bg, void* work_dev, int64_t work_bytes, double* out_host) try {
+  if (!L) return PLFEM_EINVAL;
+  if (ncomp < 1 || ncomp > 2 || k <= 0) { L->err = "plfem_mode_indicators: ncomp must be 1 or 2 and k > 0"; return PLFEM_EINVAL; }
+  if (!modes_dev || !lambda_host || !work_dev || !out_host) { L->err = "plfem_mode_indicators: null array"; return PLFEM_EINVAL; }
+  if (!std::isfinite(k0) || !std::isfinite(alpha_p)) { L->err = "plfem_mode_indicators: k0 and alpha_p must be finite"; return PLFEM_EINVAL; }
+  for (int m = 0; m < k; ++m)
+    if (!std::isfinite(lambda_host[m])) { L->err = "plfem_mode_indicators: every eigenvalue must be finite"; return PLFEM_EINVAL; }
+  if (nlayer != 0) {
+    if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) {
+      L->err = std::string("plfem_mode_indicators: ") + bad;
+      return PLFEM_EINVAL;
+    }
+  } else {
+    if (ncore < 0 || ncore > MAX_CORES || (ncore > 0 && !cores_host)) {
+      L->err = "plfem_mode_indicators: ncore must be in [0, 64], with a core table";
+      return PLFEM_EINVAL;
+    }
+    if (!std::isfinite(eps_core) || !std::isfinite(eps_clad) || !(eps_core > 0.0) || !(eps_clad > 0.0)) {
+      L->err = "plfem_mode_indicators: eps_core and eps_clad must be finite and positive";
+      return PLFEM_EINVAL;
+    }
+  }
+  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_indicators: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  const IndicatorLayout lay = indicator_layout(L->ne, k);
+  TRY(check_work(L, "plfem_mode_indicators", "plfem_indicator_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
+  ensure_elem_nbr(*L->S);
+  HIP_TRY(L, hipSetDevice(L->device));
+  double* O = (double*)work_dev;
+  int32_t* d_nbr = (int32_t*)((char*)work_dev + lay.off_nbr);
+  double* d_lam = (double*)((char*)work_dev + lay.off_lam);
+  // (the call ends with a stream synchronisation: the host arrays outlive the copies, and nothing in flight reads the
+  // locator's layer table of an earlier call)
+  HIP_TRY(L, hipMemcpyAsync(d_nbr, L->S->elem_nbr.data(), sizeof(int32_t) * 3 * (size_t)L->ne, hipMemcpyHostToDevice, L->stream));
+  HIP_TRY(L, hipMemcpyAsync(d_lam, lambda_host, sizeof(double) * k, hipMemcpyHostToDevice, L->stream));
+  if (nlayer > 0)
+    HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
+  const CoreTable ct = pack_cores(cores_host, nlayer > 0 ? 0 : ncore);
+  const int64_t nrows = indexed ? L->nsolve : L->N;
+  const dim3 grid((L->ne + IND_E - 1) / IND_E);
+  with_constant<2, 1>(ncomp, [&](auto nco) {
+    hipLaunchKernelGGL(k_mode_indicators<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k,
+                       nrows, modes_dev, d_nbr, d_lam, k0 * k0, alpha_p, ct, nlayer > 0 ? 0 : (int)ncore, eps_core, eps_clad,
+                       L->d_layers, (int)nlayer, eps_bg, O);
+  });
+  TRY(check_launch(L, "k_mode_indicators"));
+  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * (size_t)k * L->ne, hipMemcpyDeviceToHost, L->stream));
+  HIP_TRY(L, hipStreamSynchronize(L->stream));
+  return PLFEM_OK;
 } catch (...) { return host_failure(L); }
 
 namespace {

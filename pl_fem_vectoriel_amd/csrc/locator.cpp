@@ -70,4 +70,19 @@ void ensure_locator(const Symbolic& S) {
   S.loc_cell_ptr.swap(cnt);
 }
 
+// An edge node has one adjacent element (outer boundary) or two (the analysis rejects a non-manifold mesh): the neighbour
+// across the edge is the one that is not the element itself.
+void ensure_elem_nbr(const Symbolic& S) {
+  if (!S.elem_nbr.empty()) return;
+  const int ne = S.ne;
+  std::vector<int32_t> nbr((size_t)3 * ne, -1);
+  for (int l = 0; l < 3; ++l)
+    for (int e = 0; e < ne; ++e) {
+      const int32_t node = S.edof[(size_t)(3 + l) * ne + e];
+      for (int32_t q = S.nptr[node]; q < S.nptr[node + 1]; ++q)
+        if (S.nadj[q] != e) nbr[(size_t)l * ne + e] = S.nadj[q];
+    }
+  S.elem_nbr.swap(nbr);
+}
+
 }  // namespace plfem

@@ -1,6 +1,7 @@
 // The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
 // integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
-// k_field_overlap, k_mode_grams, k_profile_grams, k_mode_quartic, k_mode_project, k_mode_project_sampled, k_core_owner).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// k_field_overlap, k_mode_grams, k_profile_grams, k_mode_quartic, k_mode_project, k_mode_project_sampled, k_core_owner,
+// k_mode_indicators).  One definition, so that a quadrature point lands in the same region, and det J rounds
 // the same way, in the assembly and in every kernel that must reproduce it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -77,6 +78,18 @@ __device__ __forceinline__ void p2_grad(const double inv[4], double xi, double e
     gx[i] = inv[0] * dxh[i] + inv[2] * dyh[i];
     gy[i] = inv[1] * dxh[i] + inv[3] * dyh[i];
   }
+}
+
+// physical second derivatives of the P2 field with nodal values u: constant over the element.  The reference Hessians of
+// the six basis functions are (4, 4, 0, -8, 0, 0) for xi xi, (4, 0, 4, 0, 0, -8) for eta eta and (4, 0, 0, -4, 4, -4) for
+// xi eta; with d/dx = inv[0] d_xi + inv[2] d_eta and d/dy = inv[1] d_xi + inv[3] d_eta (p2_grad) they transform as below
+__device__ __forceinline__ void p2_hess(const double inv[4], const double u[6], double& uxx, double& uxy, double& uyy) {
+  const double h00 = 4.0 * (u[0] + u[1]) - 8.0 * u[3];
+  const double h11 = 4.0 * (u[0] + u[2]) - 8.0 * u[5];
+  const double h01 = 4.0 * (u[0] - u[3] + u[4] - u[5]);
+  uxx = inv[0] * inv[0] * h00 + 2.0 * (inv[0] * inv[2]) * h01 + inv[2] * inv[2] * h11;
+  uxy = inv[0] * inv[1] * h00 + (inv[0] * inv[3] + inv[2] * inv[1]) * h01 + inv[2] * inv[3] * h11;
+  uyy = inv[1] * inv[1] * h00 + 2.0 * (inv[1] * inv[3]) * h01 + inv[3] * inv[3] * h11;
 }
 
 // Affine map of element e: vertices = rows 0-2 of vrow ([3+][ne], sorted), coordinates x[v], y[v].  The type of ne is

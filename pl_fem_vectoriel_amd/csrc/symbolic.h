@@ -86,6 +86,10 @@ struct Symbolic {
   mutable std::vector<int32_t> loc_cell_ptr;   // [nx ny + 1], cell id = iy nx + ix
   mutable std::vector<int32_t> loc_cell_elems; // [loc_cell_ptr[nx ny]]
   mutable std::vector<double> loc_stats;       // [4] cells, mean candidates per cell, max candidates per cell, build seconds
+  // ---- element neighbours (locator.cpp, ensure_elem_nbr): the element across local edge l (0,1), (1,2), (0,2) of
+  // element e at elem_nbr[l ne + e], -1 on the outer boundary; built on first request only (plfem_mode_indicators,
+  // plfem_symbolic_get("elem_nbr"))
+  mutable std::vector<int32_t> elem_nbr;       // [3][ne]
 };
 
 // p: [2][nv] (x row then y row), t: [3][ne].  leaf_elems: target elements per leaf front.
@@ -101,6 +105,10 @@ void ensure_pattern(const Symbolic& S);
 // against concurrent first calls on the same Symbolic.
 constexpr int LOC_CELLS_PER_ELEM = 2;
 void ensure_locator(const Symbolic& S);
+
+// The element-neighbour table of S (elem_nbr above) from the node -> element lists of the edge nodes; no-op if already
+// built.  Not thread-safe against concurrent first calls on the same Symbolic.
+void ensure_elem_nbr(const Symbolic& S);
 
 // One step of a spin wait on another host thread.  The waits of the analysis pool are short (its regions are 10-500 us
 // apart): spin on the cache line with a pause instruction first -- a yield costs a system call and several microseconds

@@ -16,6 +16,8 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
   region (``plfem_mode_grams``): what :mod:`.dispersion` builds the group index and the k0-derivative coupling from;
 * :meth:`ModeFields.moment_grams` -- the region Grams weighted by the coordinates of the quadrature point
   (``plfem_moment_grams``): what :mod:`.bend` builds bend-induced index shifts, mode mixing and beam widths from;
+* :meth:`ModeFields.indicators` -- per-element a-posteriori error indicators of the modes, element residual plus flux
+  jumps (``plfem_mode_indicators``): what :mod:`.adapt` marks and refines a mesh with;
 * :meth:`ModeFields.quartic` -- the packed overlap of products of four modes on a 16-point degree-8 rule
   (``plfem_mode_quartic``): what :mod:`.nonlinear` builds the nonlinear coupling tensor, A_eff and gamma from;
 * :meth:`ModeFields.project` -- the projection of the modes on plane waves and Gaussian beams, fields that separate in
@@ -380,6 +382,65 @@ class ModeFields:
                                                   ctypes.c_int64(int(need.value)), out.ctypes.data_as(ctypes.c_void_p)),
                     "plfem_profile_grams")
         return {nm: out[i] for i, nm in enumerate(names)}
+
+    def indicators(self, modes: Sequence[Dict], geometry, alpha_p: float = 1.0) -> Dict[str, np.ndarray]:
+        """A-posteriori error indicators of the modes on this mesh (``plfem_mode_indicators``): ``{"eta2": (k, ne),
+        "total": (k,)}`` with ``eta2[m, T]`` = element residual plus flux jumps of mode m on element T under the pencil the
+        mode was solved with -- the eigenvalue is taken from the record (``beta**2`` for vectorial records, ``-beta**2``
+        for scalar ones), ``k0`` and the material map from ``geometry`` (its index profile if it carries one, otherwise
+        its core discs at ``n_core`` on ``n_clad``), ``alpha_p`` the divergence penalty of the vectorial solve -- and
+        ``total[m] = eta2[m].sum()``.  :mod:`.adapt` marks and refines with them."""
+        kind, vals, beta = self._check_records(modes)
+        try:
+            alpha_p = float(alpha_p)
+            k0 = float(geometry.k0)
+        except (AttributeError, TypeError, ValueError):
+            raise ValueError("geometry must have k0, and alpha_p must be a number") from None
+        if not (np.isfinite(alpha_p) and np.isfinite(k0)):
+            raise ValueError("k0 and alpha_p must be finite")
+        profile = index_profile_of(geometry)
+        if profile is None:
+            if not all(hasattr(geometry, a) for a in ("n_core", "n_clad")):
+                raise ValueError("geometry must have n_core and n_clad (or carry an index profile)")
+            cores = self._cores(geometry)
+            table, eps = np.zeros((0, 8)), (float(geometry.n_core) ** 2, float(geometry.n_clad) ** 2, 1.0)
+        else:
+            cores = np.zeros((0, 3))
+            table, eps = profile.table(), (1.0, 1.0, float(profile.eps_background))
+        k = 0 if kind is None else vals.shape[1]
+        if k == 0:
+            return {"eta2": np.zeros((0, self.ne)), "total": np.zeros(0)}
+        if not np.all(np.isfinite(beta)):
+            raise ValueError("every mode record needs a finite 'beta': the indicator is that of the eigenpair")
+        lam = np.ascontiguousarray(beta * beta if kind == "vectorial" else -(beta * beta))
+        self._ensure_locator()
+        staged, _src = self._stage(vals)
+        eta2 = self._indicators_staged(kind, staged, lam, k0, alpha_p, cores, eps, table)
+        return {"eta2": eta2, "total": eta2.sum(axis=1)}
+
+    def _indicators_staged(self, kind, staged, lam, k0, alpha_p, cores, eps, table, work=None) -> np.ndarray:
+        """``plfem_mode_indicators`` on modes already staged (ncomp, n, k) on the device: (k, ne).  ``eps`` = (eps_core,
+        eps_clad, eps_bg); ``work``: a uint8 device tensor to use as the work buffer instead of a fresh one."""
+        ncomp, _, k = staged.shape
+        table = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, 8))
+        cores = np.ascontiguousarray(np.asarray(cores, dtype=np.float64).reshape(-1, 3))
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        need = ctypes.c_int64(0)
+        if self._lib.plfem_indicator_work_bytes(self._loc, ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
+            raise ValueError(f"plfem_indicator_work_bytes rejected ncomp = {ncomp}, k = {k}")
+        if work is None:
+            work = _native.device_scratch(int(need.value) + 256, self.tdev)
+        elif work.numel() < int(need.value) + 256:
+            raise ValueError("work buffer smaller than plfem_indicator_work_bytes + 256")
+        aligned = (work.data_ptr() + 255) & ~255
+        out = np.empty((k, self.ne), dtype=np.float64)
+        self._check(self._lib.plfem_mode_indicators(
+            self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()), 1 if kind == "vectorial" else 0,
+            lam.ctypes.data_as(ctypes.c_void_p), float(k0), float(alpha_p), cores.ctypes.data_as(ctypes.c_void_p),
+            cores.shape[0], float(eps[0]), float(eps[1]), table.ctypes.data_as(ctypes.c_void_p), table.shape[0], float(eps[2]),
+            ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)), out.ctypes.data_as(ctypes.c_void_p)),
+            "plfem_mode_indicators")
+        return out
 
     def core_grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
         """Grams of the modes restricted to each core disc (``plfem_core_grams``), each (ncore, k, k): vectorial records

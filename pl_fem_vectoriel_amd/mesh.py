@@ -75,6 +75,15 @@ class TriMesh:
             m = TriMesh(p2, t2)
         return m
 
+    def refined_marked(self, marked):
+        """Longest-edge bisection of the elements flagged in ``marked`` (ne,) with a conformity closure
+        (``plfem_mesh_refine_marked``): ``(TriMesh, parent)``, ``parent`` (ne2,) int32 the element each new one came from.
+        Old vertices keep their ids; no flag set gives the mesh back."""
+        from . import _native
+
+        p2, t2, parent = _native.mesh_refine_marked(self.p, self.t, marked)
+        return TriMesh(p2, t2), parent
+
 
 def lantern_point_cloud(geometry, refinement: float = 1.0) -> np.ndarray:
     """Point recipe of ``MeshGenerator._generate_mesh`` (reference ``mesh.py:232-297``) -> (2, npts)."""
