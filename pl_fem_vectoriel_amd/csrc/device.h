@@ -215,6 +215,48 @@ inline void with_constant(int v, F&& f) {
   else with_constant<Rest...>(v, f);
 }
 
+// Sums V (a power of two <= 64) per-lane values over the 64 lanes with V - 1 + log2(64 / V) shuffles instead of
+// 6 V: each butterfly step halves the values a lane still carries.  On return a[0] of lane l is the complete sum
+// of value multi_reduce_index<V>(l); lanes 0 .. V-1 cover every value once.  Fixed order, so deterministic.
+// DESC = false pairs lanes 1, 2, 4, .. apart (the sweeps' order).  DESC = true pairs them 32, 16, .. apart: every value
+// is then summed in exactly the order of the plain six-step reduction `for (off = 32; off >= 1; off >>= 1) v += shfl_xor(v, off)`
+// -- the same bits -- and value multi_reduce_index<V, true>(l) ends up in lane l (each value in 64 / V neighbouring lanes).
+template <int V, bool DESC = false>
+__device__ __forceinline__ int multi_reduce_index(int lane) {
+  int idx = 0;
+#pragma unroll
+  for (int h = V / 2, s = 0; h >= 1; h >>= 1, ++s) idx += ((DESC ? lane >> (5 - s) : lane >> s) & 1) ? h : 0;
+  return idx;
+}
+
+// (the butterfly steps are a compile-time recursion: as a loop over h = V/2, V/4, .. the V = 32 instance was not unrolled
+// and its array went to scratch, and the sweeps' instances indexed theirs through chains of v_cndmask: DESIGN section 25)
+template <int H, int BIT, bool DESC, int V>
+__device__ __forceinline__ void multi_reduce_step(double (&a)[V], int lane) {
+  if constexpr (H >= 1) {
+    const bool up = (lane & BIT) != 0;
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+      const double send = up ? a[k] : a[k + H];
+      const double keep = up ? a[k + H] : a[k];
+      a[k] = keep + __shfl_xor(send, BIT);
+    }
+    multi_reduce_step<H / 2, DESC ? BIT / 2 : 2 * BIT, DESC>(a, lane);
+  }
+}
+
+template <int V, bool DESC = false>
+__device__ __forceinline__ void multi_reduce(double (&a)[V], int lane) {
+  multi_reduce_step<V / 2, DESC ? 32 : 1, DESC>(a, lane);
+  if constexpr (DESC) {
+#pragma unroll
+    for (int off = 32 / V; off >= 1; off >>= 1) a[0] += __shfl_xor(a[0], off);
+  } else {
+#pragma unroll
+    for (int off = V; off < 64; off <<= 1) a[0] += __shfl_xor(a[0], off);
+  }
+}
+
 // Below, beside every launch function: the grid and scratch numbers it is shaped by (constants: plan.h).  Whoever else
 // needs one -- create_impl for the buffer sizes, the test hooks for their bounds -- calls these.
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -151,38 +151,44 @@ __global__ __launch_bounds__(256) void k_panel_axpy_p(int64_t n, int ncols, cons
 
 // (Round 4 measured 16-byte variants of the two panel products -- two rows per lane, W staged in LDS, 8 columns per wave,
 // double-buffered column batches: scripts/micro/panel_bench.hip.  At 72-96 columns k_panel_axpy_p already streams at
-// 5.6-5.9 TB/s, what a plain streaming read of the same panel reaches on this chip (5.4-5.9), and k_panel_dot_p at 4.2;
-// every variant was equal or slower, so the kernels above stay.  Below ~24 columns both are at their launch-latency floor.)
+// 5.5-5.9 TB/s, what a plain streaming read of the same panel reaches on this chip (5.4-6.0), and k_panel_dot_p at 4.2;
+// every variant was equal or slower, so the kernels above stay.  Below ~24 columns both are at their launch-latency floor.
+// A dot on v_mfma_f64_16x16x4_f64 (k_panel_dot_mfma, kept in that file) was measured later: 466 against 555 us per C1 solve.
+// It sums in another order, and the sign of a mode as the solver returns it turns on the last bits of the projected matrix,
+// so it is not in the library: DESIGN section 25.)
 
 // ---- first Gram-Schmidt pass of a block step in TWO launches instead of four (round 4) ----------------------------
 // The first pass runs over the last two blocks of the basis only (8 columns): its four launches -- the permutation of the
 // sweeps' result into global order, the panel dot, the sum of its partials, the panel axpy -- are each at their 5-8 us
 // latency floor.  k_permute_dot_first does the permutation and the dot in one pass over the rows (the block is read from
 // the sweeps' front-order result where k_permute_out would read it, written out in global order, and multiplied with the
-// up to 8 panel columns on the way); k_axpy_first sums the partials in its prologue (32 values x nseg partials, every
-// workgroup for itself in the same fixed order: the same bits everywhere) before it applies the update.
+// up to 8 panel columns on the way; a wave's 32 sums by the sweeps' butterfly, multi_reduce of device.h, then the waves meet
+// in LDS in a fixed order: the sums and their order are those of the 32 six-step reductions this replaced); k_axpy_first
+// sums the partials in its prologue (32 values x nseg partials, every workgroup for itself in the same fixed order: the
+// same bits everywhere) before it applies the update.
 template <int P>
-__global__ __launch_bounds__(256) void k_permute_dot_first(int64_t n2, int N, int nseg, int ncols, const int32_t* __restrict__ npos,
-                                                           const double* __restrict__ xl, double* __restrict__ W, int64_t ldw,
-                                                           const double* __restrict__ Pm, double* __restrict__ partial) {
-  constexpr int CW = 8;
-  __shared__ double red[4][CW * P];
+__global__ __launch_bounds__(FIRST_THREADS) void k_permute_dot_first(int64_t n2, int N, int nseg, int ncols, const int32_t* __restrict__ npos,
+                                                          const double* __restrict__ xl, double* __restrict__ W, int64_t ldw,
+                                                          const double* __restrict__ Pm, double* __restrict__ partial) {
+  constexpr int CW = FIRST_COLS, V = CW * P, NT = FIRST_THREADS, NW = NT / 64;
+  static_assert(V <= 64 && (V & (V - 1)) == 0 && FIRST_ROWS % NT == 0 && NW == 4, "multi_reduce<V>; whole rows per thread; four waves meet");
+  __shared__ double red[NW][V];
   const int seg = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  double acc[CW * P];
+  double acc[V];
 #pragma unroll
-  for (int v = 0; v < CW * P; ++v) acc[v] = 0.0;
+  for (int v = 0; v < V; ++v) acc[v] = 0.0;
   const double* col[CW];
 #pragma unroll
   for (int t = 0; t < CW; ++t) col[t] = Pm + (int64_t)min(t, ncols - 1) * n2;      // (clamped: the result is dropped)
-  // the thread's four rows: every load that does not depend on another is requested first (the index of a row's
-  // front-order slot and its 8 panel entries), then the 16 gathers; a row-by-row loop was a chain of 8 memory round trips
-  constexpr int RPT = FIRST_ROWS / 256;
+  // the thread's rows: every load that does not depend on another is requested first (the index of a row's front-order
+  // slot and its 8 panel entries), then the gathers; a row-by-row loop was a chain of memory round trips
+  constexpr int RPT = FIRST_ROWS / NT;
   int64_t g[RPT];
   int pos[RPT];
   double a[RPT][CW], w[RPT][P];
 #pragma unroll
   for (int j = 0; j < RPT; ++j) {
-    g[j] = (int64_t)seg * FIRST_ROWS + j * 256 + threadIdx.x;
+    g[j] = (int64_t)seg * FIRST_ROWS + j * NT + threadIdx.x;
     const bool on = g[j] < n2;
     const int c = on && g[j] >= N;
     pos[j] = on ? npos[(int)(g[j] - (int64_t)c * N)] : -1;
@@ -206,14 +212,12 @@ __global__ __launch_bounds__(256) void k_permute_dot_first(int64_t n2, int N, in
 #pragma unroll
       for (int q = 0; q < P; ++q) acc[t * P + q] = fma(a[j][t], w[j][q], acc[t * P + q]);
   }
-#pragma unroll
-  for (int v = 0; v < CW * P; ++v) {
-    double x = acc[v];
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    if (lane == 0) red[wave][v] = x;
-  }
+  // the wave's V sums by the sweeps' butterfly in descending lane distance: V shuffles instead of 6 V, and every sum in the
+  // order of the six-step reduction it replaces (the same bits); then the four waves meet in LDS in a fixed order
+  multi_reduce<V, true>(acc, lane);
+  if ((lane & (64 / V - 1)) == 0) red[wave][multi_reduce_index<V, true>(lane)] = acc[0];
   __syncthreads();
-  if ((int)threadIdx.x < CW * P) {
+  if ((int)threadIdx.x < V) {
     const int v = threadIdx.x, t = v / P;
     if (t < ncols) partial[(int64_t)v * nseg + seg] = (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]);
   }
@@ -704,7 +708,7 @@ void launch_first_pass_block(plfem_ctx* c, const double* BVm, const double* Vm, 
                              int ldh) {
   constexpr int P = BLOCK_P;
   const int nseg = first_pass_segments(c->n2);
-  hipLaunchKernelGGL(k_permute_dot_first<P>, dim3(nseg), dim3(256), 0, c->stream, c->n2, c->N, nseg, ncols, c->d_npos, c->d_xl, W, ldw,
+  hipLaunchKernelGGL(k_permute_dot_first<P>, dim3(nseg), dim3(FIRST_THREADS), 0, c->stream, c->n2, c->N, nseg, ncols, c->d_npos, c->d_xl, W, ldw,
                      BVm, c->d_partial);
   hipLaunchKernelGGL(k_axpy_first<P>, dim3((unsigned)((c->n2 + 255) / 256)), dim3(256), 0, c->stream, c->n2, ncols, nseg, Vm,
                      c->d_partial, Hout, ldh, W, ldw);

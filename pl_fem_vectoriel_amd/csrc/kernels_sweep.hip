@@ -24,7 +24,7 @@
 // Forward "tile" form (levels with many fronts): lane = output row, the waves split the columns, partial sums
 // meet in LDS in a fixed order; "row" form (at most 32 fronts): a wave owns R rows of [L11^-1 ; Z] and runs along
 // their columns in the mirrored upper storage.  Backward: row form (contiguous columns of the lower storage)
-// except at the leaf level.  The cross-lane sums of the row forms use multi_reduce.  Deterministic throughout.
+// except at the leaf level.  The cross-lane sums of the row forms use multi_reduce (device.h).  Deterministic throughout.
 #include <algorithm>
 
 #include "device.h"
@@ -41,33 +41,6 @@ struct SweepArgs {
   const double2* dinv2;             // D^-1 of every front row: (diagonal, off-diagonal entry of the row's node pair)
   double *fr, *u0, *u1, *ys, *xl;
 };
-
-// Sums V (a power of two <= 64) per-lane values over the 64 lanes with V - 1 + log2(64 / V) shuffles instead of
-// 6 V: each butterfly step halves the values a lane still carries.  On return a[0] of lane l is the complete sum
-// of value multi_reduce_index<V>(l); lanes 0 .. V-1 cover every value once.  Fixed order, so deterministic.
-template <int V>
-__device__ __forceinline__ int multi_reduce_index(int lane) {
-  int idx = 0;
-#pragma unroll
-  for (int h = V / 2, s = 0; h >= 1; h >>= 1, ++s) idx += ((lane >> s) & 1) ? h : 0;
-  return idx;
-}
-
-template <int V>
-__device__ __forceinline__ void multi_reduce(double (&a)[V], int lane) {
-#pragma unroll
-  for (int h = V / 2, bit = 1; h >= 1; h >>= 1, bit <<= 1) {
-    const bool up = (lane & bit) != 0;
-#pragma unroll
-    for (int k = 0; k < h; ++k) {
-      const double send = up ? a[k] : a[k + h];
-      const double keep = up ? a[k + h] : a[k];
-      a[k] = keep + __shfl_xor(send, bit);
-    }
-  }
-#pragma unroll
-  for (int off = V; off < 64; off <<= 1) a[0] += __shfl_xor(a[0], off);
-}
 
 // LDS layout of the staged vector: tile forms read one entry for all lanes (broadcast) and keep the P values of a DOF
 // together ([i][P]: two 16-byte reads); row forms read a different DOF per lane, where [i][P] is a 32-byte lane stride

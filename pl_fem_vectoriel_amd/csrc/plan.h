@@ -27,6 +27,12 @@ struct default_init_allocator : std::allocator<T> {
 constexpr int NB = 32;          // pivot-block width of the block LDL^T
 constexpr int PANEL_CHUNK = 1024; // rows per partial sum of the tall-skinny panel products
 constexpr int FIRST_ROWS = 1024;  // rows per workgroup of k_permute_dot_first = per partial sum (512 measured: 17.1 + 11.1 us against 15.8 + 9.5)
+// threads per workgroup of k_permute_dot_first: a segment's rows go four to a thread.  With the 32 sums of a wave reduced by
+// multi_reduce (32 shuffles instead of 192) the kernel takes 9.7 us per launch in the C1 solve (15.5 before).  256 / 512 /
+// 1024 threads per segment were measured with it (ascending pairing) at 9.4 / 9.8 / 11.1 us: every further wave repeats
+// the butterfly, and the chain index -> gather -> FMA is as long for one row as for four
+// (profiles/mfma_dot_block_step_kernels.txt)
+constexpr int FIRST_THREADS = 256;
 constexpr int FIRST_COLS = 8;     // panel columns of the fused first Gram-Schmidt pass (the last two blocks of the basis)
 constexpr int SPMV_WG_ROWS = 32;  // rows per workgroup of the sparse products: 8 lanes per row, 256 threads
 constexpr int POST_ROWS = 256;    // rows per workgroup of k_post_sums / k_resid_sums

@@ -1,44 +1,114 @@
 // Times the tall-skinny panel products of the block Lanczos step in isolation (C1 sizes: n = 181 278, P = 4): the library's
-// kernels and candidate variants, plus a plain streaming read as the yardstick.  Prints us and GB/s of panel bytes.
+// kernels and candidate variants, plus a plain streaming read as the yardstick.  Prints us per launch (fastest and slowest
+// of five windows of 20 launches) and GB/s of panel bytes at the fastest.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/micro/panel_bench.hip -o scripts/micro/build/panel_bench
 #include "../../pl_fem_vectoriel_amd/csrc/kernels_lanczos.hip"
 
+#include <algorithm>
 #include <cstdio>
 #include <vector>
 
 namespace plfem {
 namespace {
 
-// ---- 16-byte variants measured in round 4 and NOT adopted by the library (see kernels_lanczos.hip) ----
+// ---- the block driver's dot on the matrix cores: measured, faster (profiles/mfma_dot_panel_bench.txt; 466 against 555 us
+// per C1 solve) and NOT adopted: it sums in another order than k_panel_dot_p, and the sign of a mode as the solver returns
+// it turns on the last bits of the projected matrix ----
+// v_mfma_f64_16x16x4_f64 (operand map: kernels_front.hip, ldl_update_tile).  A workgroup owns 16 panel columns of one chunk:
+// A[i = lane&15][k = lane>>4] takes the panel, B[k][j = lane&15] takes W in the columns j < P and zero elsewhere, so that
+// D[(lane>>4) + 4 r][lane&15] of the lanes with (lane&15) < P is sum_rows Pm[row, c0 + i] W[row, q]: no cross-lane
+// reduction, and W is read once per 16 columns.  The k index of a sum is free: lane (i, kq) loads the FOUR consecutive rows
+// r0 + 4 kq .. + 3 of its column (two 16-byte loads: n even, the panel 16-byte aligned), and MFMA t = 0..3 of a tile takes
+// element t of every lane for A and B alike -- a 16 x 16 tile is read as sixteen 128-byte runs.  Rows past n, columns past
+// ncols and the columns j >= P of B are zero in BOTH operands.  The four waves split the chunk's rows and meet in LDS in a
+// fixed order, so that every wave has work at any column count (four column groups per workgroup, and four tiles per
+// request group, were measured too and lose or tie).  WA: W is read 16 bytes at a time as well (ldw even, W aligned).
+typedef double v2d __attribute__((ext_vector_type(2)));
+template <int P, bool WA>
+__global__ __launch_bounds__(256) void k_panel_dot_mfma(int64_t n, int ncols, int nchunks, const double* __restrict__ Pm,
+                                                        const double* __restrict__ W, int64_t ldw,
+                                                        double* __restrict__ partial) {
+  constexpr int ROWS = CHUNK / 4;       // rows of a wave
+  constexpr int U = 2;                  // tiles per request group (2 + 2 16-byte loads per lane and tile), two groups in flight
+  static_assert(P <= 16 && ROWS % (16 * U) == 0, "whole groups of tiles per wave");
+  __shared__ double red[4][16 * P];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // (scalar: a uniform row loop)
+  const int li = lane & 15, kq = lane >> 4;
+  const int c0 = blockIdx.y * 16;
+  const bool acol = c0 + li < ncols, bcol = li < P;
+  const double* ap = Pm + (int64_t)(acol ? c0 + li : 0) * n + 4 * kq;
+  const double* bp = W + (int64_t)(bcol ? li : 0) * ldw + 4 * kq;
+  const int64_t rb = (int64_t)blockIdx.x * CHUNK + wave * ROWS;
+  const int64_t r1 = min(n, rb + ROWS);
+  v4d acc = (v4d){0.0, 0.0, 0.0, 0.0};
+  // whole groups of tiles: only the column masks.  The next group is requested before the MFMAs of this one.
+  struct Group { v2d a[U][2], b[U][2]; };
+  auto request = [&](Group& g, int64_t r0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) g.a[u][0] = g.a[u][1] = g.b[u][0] = g.b[u][1] = (v2d){0.0, 0.0};
+    if (acol) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        g.a[u][0] = *reinterpret_cast<const v2d*>(ap + r0 + 16 * u);
+        g.a[u][1] = *reinterpret_cast<const v2d*>(ap + r0 + 16 * u + 2);
+      }
+    }
+    if (bcol) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const double* pb = bp + r0 + 16 * u;
+        if (WA) {
+          g.b[u][0] = *reinterpret_cast<const v2d*>(pb);
+          g.b[u][1] = *reinterpret_cast<const v2d*>(pb + 2);
+        } else {
+          g.b[u][0] = (v2d){pb[0], pb[1]};
+          g.b[u][1] = (v2d){pb[2], pb[3]};
+        }
+      }
+    }
+  };
+  auto multiply = [&](const Group& g) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(g.a[u][t >> 1][t & 1], g.b[u][t >> 1][t & 1], acc, 0, 0, 0);
+  };
+  const int ngroups = r1 > rb ? (int)((r1 - rb) / (16 * U)) : 0;
+  Group g0, g1;
+  if (ngroups > 0) request(g0, rb);
+  for (int k = 0; k < ngroups; k += 2) {
+    if (k + 1 < ngroups) request(g1, rb + (k + 1) * (16 * U));
+    multiply(g0);
+    if (k + 1 < ngroups) {
+      if (k + 2 < ngroups) request(g0, rb + (k + 2) * (16 * U));
+      multiply(g1);
+    }
+  }
+  for (int64_t r = rb + (int64_t)ngroups * (16 * U); r < r1; r += 16) {   // the tiles of the tail, row by row
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const bool on = r + 4 * kq + t < r1;
+      const double a = acol && on ? ap[r + t] : 0.0;
+      const double b = bcol && on ? bp[r + t] : 0.0;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+    }
+  }
+  if (bcol) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[wave][(kq + 4 * j) * P + li] = acc[j];
+  }
+  __syncthreads();
+  const int v = threadIdx.x, i = v / P;            // v = i P + q
+  if (v < 16 * P && c0 + i < ncols)
+    partial[((int64_t)c0 * P + v) * nchunks + blockIdx.x] = (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]);
+}
+
+// ---- vector-unit variants measured in round 4 and NOT adopted by the library (see kernels_lanczos.hip) ----
 // ---- the same two panel products with 16-byte accesses (n even: every column starts 16-byte aligned) -------------
 // An 8-byte access per lane streams at 0.54-0.70 of the rate of a 16-byte one on this chip (MI355X_MICROARCH.md, cache
 // policy table) -- the round-3 kernels above sat at 3.1 TB/s for exactly that reason -- so a lane takes TWO consecutive
 // rows per load.
-// Sums V (a power of two <= 64) per-lane values over the 64 lanes with V - 1 + log2(64 / V) shuffles instead of 6 V (the
-// butterfly of the solve sweeps); on return a[0] of lane l is the complete sum of value multi_reduce_index<V>(l).
-template <int V>
-__device__ __forceinline__ int multi_reduce_index(int lane) {
-  int idx = 0;
-#pragma unroll
-  for (int h = V / 2, s = 0; h >= 1; h >>= 1, ++s) idx += ((lane >> s) & 1) ? h : 0;
-  return idx;
-}
-template <int V>
-__device__ __forceinline__ void multi_reduce(double (&a)[V], int lane) {
-#pragma unroll
-  for (int h = V / 2, bit = 1; h >= 1; h >>= 1, bit <<= 1) {
-    const bool up = (lane & bit) != 0;
-#pragma unroll
-    for (int k = 0; k < h; ++k) {
-      const double send = up ? a[k] : a[k + h];
-      const double keep = up ? a[k + h] : a[k];
-      a[k] = keep + __shfl_xor(send, bit);
-    }
-  }
-#pragma unroll
-  for (int off = V; off < 64; off <<= 1) a[0] += __shfl_xor(a[0], off);
-}
-
+// (the epilogue is multi_reduce of device.h, the butterfly of the solve sweeps)
 // partial[(c P + q) nseg + seg] = sum over the rows of segment seg of Pm[i, c] W[i, q].  One WAVE per (row segment of
 // DOT_SEG rows, group of 4 columns), the waves of a workgroup on consecutive column groups of one segment (they share
 // the segment's rows of W in L1 / L2).  Two trips of (4 + P) 16-byte loads per lane in flight = 16 KB per wave.
@@ -293,24 +363,33 @@ __global__ __launch_bounds__(256) void k_axpy_db(int64_t n, int ncols, const dou
 
 using namespace plfem;
 
+struct Timing { double lo, hi; };
+// REPS windows of `reps` launches each: the fastest and the slowest window, in us per launch (the spread between them is
+// what a difference between two kernels has to exceed)
 template <class F>
-static double time_us(F&& launch, int reps = 20) {
+static Timing time_us(F&& launch, int reps = 20, int windows = 5) {
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   for (int r = 0; r < 3; ++r) launch();
-  hipEventRecord(e0, 0);
-  for (int r = 0; r < reps; ++r) launch();
-  hipEventRecord(e1, 0);
-  hipEventSynchronize(e1);
-  float ms = 0;
-  hipEventElapsedTime(&ms, e0, e1);
-  return 1e3 * ms / reps;
+  Timing t{1e30, 0.0};
+  for (int w = 0; w < windows; ++w) {
+    hipEventRecord(e0, 0);
+    for (int r = 0; r < reps; ++r) launch();
+    hipEventRecord(e1, 0);
+    hipEventSynchronize(e1);
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    t.lo = std::min(t.lo, 1e3 * ms / reps);
+    t.hi = std::max(t.hi, 1e3 * ms / reps);
+  }
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  return t;
 }
 
 int main() {
   constexpr int P = 4;
   const int64_t n = 181278;
-  const int maxc = 96;
+  const int maxc = 132;
   double *V, *BV, *W, *H, *partial, *out;
   hipMalloc(&V, sizeof(double) * n * (maxc + 8));
   hipMalloc(&BV, sizeof(double) * n * (maxc + 8));
@@ -323,14 +402,17 @@ int main() {
   hipMemset(W, 0, sizeof(double) * n * P);
   hipMemset(H, 0, sizeof(double) * (maxc + 8) * P);
   const int nchunks = (int)((n + 1023) / 1024);
-  for (int ncols : {8, 24, 48, 72, 96}) {
+  for (int ncols : {8, 24, 48, 72, 96, 132}) {
     const double mb = 8.0 * n * ncols / 1e6;
     printf("== ncols %d: panel %.1f MB\n", ncols, mb);
-    auto rep = [&](const char* name, double us) { printf("  %-44s %7.1f us  %6.0f GB/s\n", name, us, mb / us * 1e3); };
+    auto rep = [&](const char* name, Timing t) { printf("  %-44s %7.1f .. %5.1f us  %6.0f GB/s\n", name, t.lo, t.hi, mb / t.lo * 1e3); };
     rep("stream sum, 8-byte loads, 2048 WGs", time_us([&] { hipLaunchKernelGGL(k_stream_sum<1>, dim3(2048), dim3(256), 0, 0, n * ncols, BV, out); }));
     rep("stream sum, 16-byte loads, 2048 WGs", time_us([&] { hipLaunchKernelGGL(k_stream_sum<2>, dim3(2048), dim3(256), 0, 0, n * ncols, BV, out); }));
     rep("stream sum, 16-byte loads, 1024 WGs", time_us([&] { hipLaunchKernelGGL(k_stream_sum<2>, dim3(1024), dim3(256), 0, 0, n * ncols, BV, out); }));
-    rep("dot: k_panel_dot_p<4> (round 3, 8 B)", time_us([&] { hipLaunchKernelGGL(k_panel_dot_p<P>, dim3(nchunks, (ncols + 15) / 16), dim3(256), 0, 0, n, ncols, nchunks, BV, W, n, partial); }));
+    rep("dot: k_panel_dot_p<4, 4> (8 B, vector units)", time_us([&] { hipLaunchKernelGGL((k_panel_dot_p<P, 4>), dim3(nchunks, (ncols + 15) / 16), dim3(256), 0, 0, n, ncols, nchunks, BV, W, n, partial); }));
+    // the matrix-core dot (not adopted, see above)
+    rep("dot: k_panel_dot_mfma<4> (MFMA, 16 B)", time_us([&] { hipLaunchKernelGGL((k_panel_dot_mfma<P, true>), dim3(nchunks, (ncols + 15) / 16), dim3(256), 0, 0, n, ncols, nchunks, BV, W, n, partial); }));
+    rep("dot: k_panel_dot_mfma<4>, 8-byte W loads", time_us([&] { hipLaunchKernelGGL((k_panel_dot_mfma<P, false>), dim3(nchunks, (ncols + 15) / 16), dim3(256), 0, 0, n, ncols, nchunks, BV, W, n, partial); }));
     {
       const int nseg = nchunks, ncg = (ncols + 3) / 4;
       rep("dot: k_panel_dot_p16<4> (16 B, CW 4)", time_us([&] { hipLaunchKernelGGL(k_panel_dot_p16<P>, dim3((nseg * ncg + 3) / 4), dim3(256), 0, 0, n, ncols, ncg, nseg, BV, W, n, partial); }));
