@@ -177,11 +177,37 @@ int plfem_assemble_scalar(plfem_ctx* ctx, const double* cores_host, int32_t ncor
  * weigh every quadrature point with 1 / eps (the division made on the device, IEEE) -- eps in the scalar pencil -- of
  * the profile at the point as the assembly forms it, and do not read their eps_core / eps_clad.  Their cores argument
  * keeps its meaning: the discs the in-core sums of the post-processing count.  plfem_cmt_coupling does not read the
- * profile.  nlayer = 0 clears the profile (layers_host and eps_bg are then not read).  The table is copied to a device
+ * profile.  nlayer = 0 clears the profile: layers_host is not read, and eps_bg is kept as the background of an index map
+(plfem_set_index_map) if it is finite and positive and is otherwise ignored, without an error.  The table is copied to a device
  * buffer of the context; the call synchronises the context's stream.
  * PLFEM_EINVAL, with the context's last error set: nlayer outside [0, 64]; a null table with nlayer > 0; a non-finite
  * entry or eps_bg; r_in < 0; r_out <= r_in; eps_a, eps_b or eps_bg <= 0; g < 0. */
 int plfem_set_index_profile(plfem_ctx* ctx, const double* layers_host, int32_t nlayer, double eps_bg);
+
+/* Sampled index map: the background of the profile as a pixel grid.  eps_host[j][i] (row-major, nx ny doubles) are
+ * relative permittivities (n^2) on the uniform node grid x_i = x0 + i dx, y_j = y0 + j dy, 2 <= nx, ny <= 8192,
+ * nx ny <= 2^24.  While a map is set, the permittivity of a point is
+ *   inside the closed extent, 0 <= tx <= nx - 1 and 0 <= ty <= ny - 1 with tx = fl(fl(x - x0) fl(1 / dx)), ty likewise
+ *     (false for a NaN): the bilinear interpolant of the map, formed as
+ *       i0 = min(floor(tx), nx - 2), a = tx - i0, a1 = 1 - a;  j0, b, b1 likewise;
+ *       lo = fl(a1 E[j0][i0]) + fl(a E[j0][i0+1]),  hi = fl(a1 E[j0+1][i0]) + fl(a E[j0+1][i0+1]),
+ *       eps = fl(lo b1) + fl(hi b), every product rounded on its own (no fused multiply-add);
+ *   outside it: eps_bg;
+ * and the layers of plfem_set_index_profile are painted over that in their order.  The interpolant is bilinear in
+ * eps = n^2, not in n.
+ * While a map is set, plfem_assemble_hfield, plfem_assemble_scalar and plfem_solve_modes take the profile path even with
+ * no layer set.  eps_bg is the one plfem_set_index_profile was last given: for a map without layers call
+ * plfem_set_index_profile(ctx, NULL, 0, eps_bg), which sets no layer and keeps eps_bg (if it is finite and positive; any
+ * other value is ignored, as before).  An assembly under a map with no such eps_bg is PLFEM_EINVAL.
+ * A null map with nx = ny = 0 clears (the other arguments are not read).  The map is copied to a device buffer of the
+ * context's own, outside its workspace, which is reused while it is large enough and freed by a clear and by
+ * plfem_destroy; the call synchronises the context's stream.  With no map set every entry behaves, bit for bit, as it
+ * did before this entry existed.
+ * PLFEM_EINVAL, with the context's last error set and the context left as it was: nx or ny outside the limits; a null
+ * map with non-zero sizes; a permittivity that is not finite or is <= 0; a non-finite origin; a step that is not finite,
+ * is <= 0, or whose inverse is not finite. */
+int plfem_set_index_map(plfem_ctx* ctx, const double* eps_host, int32_t nx, int32_t ny, double x0, double y0, double dx,
+                        double dy);
 
 /* Coupled-mode coupling integrals, scalar context only.
  * Replaces: the epsilon_product form + asm() and the E_i^H M_eps E_j loop of
@@ -439,6 +465,16 @@ int plfem_profile_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes);
 int plfem_profile_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
                         const double* layers_host, int32_t nlayer, double eps_bg, void* work_dev, int64_t work_bytes,
                         double* out_host);
+
+/* The sampled index map of plfem_set_index_map on a locator: while one is set, plfem_profile_grams evaluates its profile
+ * over the map (eps_bg outside the extent, its layers painted over both), and plfem_mode_indicators takes its profile
+ * path (layers_host, nlayer, eps_bg; the cores, eps_core and eps_clad are not read) even with nlayer = 0.  Both read
+ * eps_bg from their own arguments, as before.  Arguments, model, clearing (a null map with nx = ny = 0) and argument
+ * errors as for plfem_set_index_map, with the locator's last error set.  The map is copied to a device buffer of the
+ * locator's own, outside the caller's memory, reused while it is large enough and freed by a clear and by
+ * plfem_locator_destroy; the call synchronises the locator's stream. */
+int plfem_locator_set_index_map(plfem_locator* loc, const double* eps_host, int32_t nx, int32_t ny, double x0, double y0,
+                                double dx, double dy);
 
 /* Per-core Grams: the Grams of k staged modes (staged and indexed as for plfem_mode_grams) over the quadrature points of
  * the mesh's own six-point rule that each core disc owns (ncore in [1, 64]; every sum is over the points of core c of

@@ -45,6 +45,7 @@ EXPORTS = (
     "plfem_set_index_profile", "plfem_profile_gram_work_bytes", "plfem_profile_grams",
     "plfem_project_sampled_work_bytes", "plfem_mode_project_sampled",
     "plfem_indicator_work_bytes", "plfem_mode_indicators", "plfem_mesh_refine_marked_count", "plfem_mesh_refine_marked",
+    "plfem_set_index_map", "plfem_locator_set_index_map",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -74,6 +75,19 @@ _ARRAY_DTYPES = {
 
 
 from scipy.sparse.linalg import ArpackNoConvergence as _ArpackNoConvergence
+
+
+def set_index_map_call(entry, handle, index_map):
+    """``plfem_set_index_map`` / ``plfem_locator_set_index_map`` (``entry``) on ``handle`` with ``index_map`` =
+    ``(eps (ny, nx), x0, y0, dx, dy)``, or None: clear.  Returns the status."""
+    if index_map is None:
+        return entry(handle, None, 0, 0, 0.0, 0.0, 0.0, 0.0)
+    eps, x0, y0, dx, dy = index_map
+    eps = np.ascontiguousarray(eps, dtype=np.float64)
+    if eps.ndim != 2:
+        raise ValueError("the index map must be a (ny, nx) array")
+    return entry(handle, eps.ctypes.data_as(ctypes.c_void_p), eps.shape[1], eps.shape[0], float(x0), float(y0), float(dx),
+                 float(dy))
 
 
 class ArpackLikeNoConvergence(_ArpackNoConvergence, RuntimeError):
@@ -242,6 +256,8 @@ def load_library() -> ctypes.CDLL:
                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]
     lib.plfem_set_index_profile.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]
+    lib.plfem_set_index_map.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_double] * 4
+    lib.plfem_locator_set_index_map.argtypes = lib.plfem_set_index_map.argtypes
     lib.plfem_profile_gram_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
     lib.plfem_profile_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int64,
@@ -524,16 +540,26 @@ class Context:
     # -- C-ABI calls ------------------------------------------------------------------------------
     def set_index_profile(self, profile=None):
         """``plfem_set_index_profile``: the assembly calls and ``solve_modes`` of this context take their permittivity
-        from ``profile`` (an object with ``table()`` (nlayer, 8) and ``eps_background``: ``profile.IndexProfile``) until the
-        next call; ``None``: back to their own ``eps_core`` / ``eps_clad``."""
+        from ``profile`` (an object with ``table()`` (nlayer, 8) and ``eps_background``, and optionally ``index_map``:
+        ``profile.IndexProfile``) until the next call; ``None``: back to their own ``eps_core`` / ``eps_clad``.  The map
+        of the profile (``plfem_set_index_map``) is set, or the context's cleared, on every call: a cached context never
+        carries one into the next solve."""
         if profile is None:
             self._check(self._lib.plfem_set_index_profile(self._h, None, 0, 0.0), "plfem_set_index_profile")
+            self.set_index_map(None)
             return
         t = np.ascontiguousarray(np.asarray(profile.table(), dtype=np.float64).reshape(-1, 8))
-        if t.shape[0] == 0:
+        index_map = getattr(profile, "index_map", None)
+        if t.shape[0] == 0 and index_map is None:
             raise ValueError("plfem_set_index_profile: the profile has no layers")
-        self._check(self._lib.plfem_set_index_profile(self._h, _ptr(t), t.shape[0], float(profile.eps_background)),
-                    "plfem_set_index_profile")
+        self._check(self._lib.plfem_set_index_profile(self._h, _ptr(t) if t.shape[0] else None, t.shape[0],
+                                                      float(profile.eps_background)), "plfem_set_index_profile")
+        self.set_index_map(index_map)
+
+    def set_index_map(self, index_map=None):
+        """``plfem_set_index_map``: ``index_map`` = ``(eps (ny, nx), x0, y0, dx, dy)`` (``IndexProfile.index_map``), or
+        ``None`` to clear."""
+        self._check(set_index_map_call(self._lib.plfem_set_index_map, self._h, index_map), "plfem_set_index_map")
 
     def assemble(self, cores, eps_core, eps_clad, k0, alpha_p=1.0):
         c, n = self._cores(cores)

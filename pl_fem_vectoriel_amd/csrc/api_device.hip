@@ -222,6 +222,7 @@ int flush_uploads(plfem_ctx* c, const std::vector<UploadItem>& items, size_t spa
 void free_all(plfem_ctx* c) {
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);   // (the tail of the index upload reads the staging block)
   if (c->own_slab && c->slab) (void)hipFree(c->slab);
+  plfem::free_index_map(c->map);
   if (c->h_pinned) pinned_release(c->h_pinned, c->h_pinned_bytes);
   if (c->h_staging) {
     (void)hipStreamSynchronize(c->stream);              // (the upload out of the block has long completed)
@@ -489,8 +490,13 @@ namespace {
 template <class ElementMatrices>
 int assemble(plfem_ctx* c, const double* cores_host, int ncore, double eps_core, double eps_clad, const char* what,
              ElementMatrices element_matrices) {
-  // (with an index profile set, eps_core and eps_clad are not read)
-  if (c->nlayer == 0 && (!(eps_core > 0) || !(eps_clad > 0))) { c->err = "permittivities must be positive"; return PLFEM_EINVAL; }
+  // (with an index profile set -- layers, a map or both -- eps_core and eps_clad are not read)
+  const bool profile = c->nlayer > 0 || c->map.set();
+  if (!profile && (!(eps_core > 0) || !(eps_clad > 0))) { c->err = "permittivities must be positive"; return PLFEM_EINVAL; }
+  if (profile && !(c->eps_bg > 0)) {
+    c->err = std::string(what) + ": an index map is set without a background permittivity (plfem_set_index_profile(ctx, NULL, 0, eps_bg))";
+    return PLFEM_EINVAL;
+  }
   HIP_TRY(c, hipSetDevice(c->device));
   TRY(upload_cores(c, cores_host, ncore));
   HIP_TRY(c, phase_begin(c, plfem::PH_ASSEMBLE));
@@ -506,7 +512,13 @@ int assemble(plfem_ctx* c, const double* cores_host, int ncore, double eps_core,
 
 extern "C" int plfem_set_index_profile(plfem_ctx* c, const double* layers_host, int32_t nlayer, double eps_bg) try {
   if (!c) return PLFEM_EINVAL;
-  if (nlayer == 0) { c->nlayer = 0; return PLFEM_OK; }      // back to the step model of the assembly calls' own arguments
+  // no layers: back to the step model of the assembly calls' own arguments -- or, under an index map, to the map alone
+  // over eps_bg, which is kept for that if it is one (anything else is not an error here: nothing else reads it)
+  if (nlayer == 0) {
+    c->nlayer = 0;
+    c->eps_bg = (std::isfinite(eps_bg) && eps_bg > 0.0) ? eps_bg : 0.0;
+    return PLFEM_OK;
+  }
   if (const char* bad = plfem::profile_table_error(layers_host, nlayer, eps_bg)) {
     c->err = std::string("plfem_set_index_profile: ") + bad;
     return PLFEM_EINVAL;
@@ -522,6 +534,12 @@ extern "C" int plfem_set_index_profile(plfem_ctx* c, const double* layers_host, 
   c->nlayer = nlayer;
   c->eps_bg = eps_bg;
   return PLFEM_OK;
+} catch (...) { return host_failure(c); }
+
+extern "C" int plfem_set_index_map(plfem_ctx* c, const double* eps_host, int32_t nx, int32_t ny, double x0, double y0,
+                                   double dx, double dy) try {
+  if (!c) return PLFEM_EINVAL;
+  return plfem::set_index_map(c, "plfem_set_index_map", eps_host, nx, ny, x0, y0, dx, dy);
 } catch (...) { return host_failure(c); }
 
 extern "C" int plfem_assemble_hfield(plfem_ctx* c, const double* cores_host, int32_t ncore, double eps_core,

@@ -58,6 +58,25 @@ static_assert(PLFEM_SOLVE_T_ASSEMBLE_US + PH_RESIDUAL == PLFEM_SOLVE_T_RESIDUAL_
     if (rc__ != PLFEM_OK) return rc__; \
   } while (0)
 
+namespace plfem {
+// The sampled map of an index profile as a handle keeps it (plfem_set_index_map, plfem_locator_set_index_map): a device
+// buffer of the handle's own -- not part of the context's slab or of the locator's memory, so no other buffer moves --
+// that is reused while it is large enough and freed on clear and destroy, and the grid of the map in it.
+struct IndexMap {
+  double* d = nullptr;            // MAP_HEADER doubles that hold the grid as the kernels read it, then [ny][nx] permittivities
+  size_t cap = 0;                 // permittivities the buffer has room for
+  int nx = 0, ny = 0;             // 0: no map set
+  double x0 = 0, y0 = 0, inv_dx = 0, inv_dy = 0;
+  bool set() const { return nx > 0; }
+};
+// the grid as the first bytes of the buffer hold it: SampledGrid of p2_element.h, field for field
+struct IndexMapHeader {
+  double x0, y0, inv_dx, inv_dy;
+  int nx, ny;
+};
+static_assert(sizeof(IndexMapHeader) <= MAP_HEADER * sizeof(double), "the grid fits the map buffer's header");
+}  // namespace plfem
+
 struct plfem_ctx {
   const plfem::Symbolic* S = nullptr;
   const plfem::LaunchPlan* plan = nullptr;   // S->plan: kernel forms by level, launch order, workgroup lists (plan.h)
@@ -87,7 +106,8 @@ struct plfem_ctx {
   double* d_cores = nullptr;      // [64][3]
   double* d_layers = nullptr;     // [64][8] layer table of the index profile (plfem_set_index_profile)
   int nlayer = 0;                 // > 0: the assembly takes its permittivity from the profile, not from eps_core / eps_clad
-  double eps_bg = 0.0;            // the profile's background permittivity
+  double eps_bg = 0.0;            // the profile's background permittivity (0: none given)
+  plfem::IndexMap map;            // the sampled map under the layers (plfem_set_index_map); set: the profile path, layers or not
   double* d_elem = nullptr;       // [ne][8][36]
   double* d_vals[PLFEM_BLK_COUNT] = {nullptr};
   double* d_front = nullptr;      // what a front keeps: [F11; F21] (m x s2) and Z^T (s2 x b2), see symbolic.h
@@ -281,6 +301,60 @@ inline const char* profile_table_error(const double* layers, int nlayer, double 
     if (p[6] < 0.0) return "g must be >= 0";
   }
   return nullptr;
+}
+
+// A sampled map as the C ABI takes it (plfem_set_index_map, plfem_locator_set_index_map): nullptr if it is acceptable,
+// otherwise what is wrong with it
+inline const char* index_map_error(const double* eps, int nx, int ny, double x0, double y0, double dx, double dy) {
+  if (nx < 2 || ny < 2 || nx > MAP_NMAX || ny > MAP_NMAX || (int64_t)nx * ny > MAP_SAMPLES)
+    return "nx and ny must be in [2, 8192] with nx ny <= 2^24 (a null map with nx = ny = 0 clears)";
+  if (!eps) return "null map";
+  if (!std::isfinite(x0) || !std::isfinite(y0)) return "the origin must be finite";
+  if (!std::isfinite(dx) || !std::isfinite(dy) || !(dx > 0.0) || !(dy > 0.0) || !std::isfinite(1.0 / dx) ||
+      !std::isfinite(1.0 / dy))
+    return "the steps must be finite and positive, with finite inverses";
+  for (int64_t i = 0, n = (int64_t)nx * ny; i < n; ++i)
+    if (!std::isfinite(eps[i]) || !(eps[i] > 0.0)) return "every permittivity must be finite and positive";
+  return nullptr;
+}
+
+// What both entries do on a handle with `err`, `device`, `stream` and `map`.  A null map with nx = ny = 0 clears: the
+// buffer is freed.  A rejected map leaves the handle as it was.  The copy goes behind whatever the handle's stream still
+// runs on the old map and is waited for: the caller's array is free on return.
+template <class Owner>
+int set_index_map(Owner* o, const char* entry, const double* eps, int nx, int ny, double x0, double y0, double dx, double dy) {
+  IndexMap& m = o->map;
+  const bool clear = !eps && nx == 0 && ny == 0;
+  if (!clear) {
+    if (const char* bad = index_map_error(eps, nx, ny, x0, y0, dx, dy)) {
+      o->err = std::string(entry) + ": " + bad;
+      return PLFEM_EINVAL;
+    }
+  }
+  if (clear && !m.d) return PLFEM_OK;                // (nothing to free: no device call)
+  HIP_TRY(o, hipSetDevice(o->device));
+  const size_t n = clear ? 0 : (size_t)nx * ny;
+  if (clear || m.cap < n) {
+    HIP_TRY(o, hipStreamSynchronize(o->stream));     // nothing in flight may still read the old buffer
+    double* old = m.d;
+    m = IndexMap();
+    if (old) HIP_TRY(o, hipFree(old));
+    if (clear) return PLFEM_OK;
+    HIP_TRY(o, hipMalloc((void**)&m.d, sizeof(double) * (MAP_HEADER + n)));
+    m.cap = n;
+  }
+  m.nx = 0;                                          // (no map while a copy can still fail)
+  const IndexMapHeader head{x0, y0, 1.0 / dx, 1.0 / dy, nx, ny};
+  HIP_TRY(o, hipMemcpyAsync(m.d, &head, sizeof(head), hipMemcpyHostToDevice, o->stream));
+  HIP_TRY(o, hipMemcpyAsync(m.d + MAP_HEADER, eps, sizeof(double) * n, hipMemcpyHostToDevice, o->stream));
+  HIP_TRY(o, hipStreamSynchronize(o->stream));
+  m.x0 = head.x0; m.y0 = head.y0; m.inv_dx = head.inv_dx; m.inv_dy = head.inv_dy;
+  m.nx = nx; m.ny = ny;
+  return PLFEM_OK;
+}
+inline void free_index_map(IndexMap& m) {
+  if (m.d) (void)hipFree(m.d);
+  m = IndexMap();
 }
 
 // kernels_assembly.hip

@@ -18,12 +18,15 @@ constexpr int EPB = 7;   // elements per 256-thread block: 7*36 = 252 (i,j) pair
 // PROFILE = false: the step model, a point in a core disc weighs inv_eps_core and any other inv_eps_clad.  PROFILE = true
 // (plfem_set_index_profile): the same argument list carries the profile -- cores = the layer table, ncore = the number of
 // layers, inv_eps_clad = eps_bg (inv_eps_core is not read) -- and the weight is 1 / profile_eps (scalar: profile_eps)
-// at the point, the division made here.
-template <bool PROFILE>
+// at the point, the division made here.  Map...: nothing, or one EpsMap (plfem_set_index_map; PROFILE = true only): the
+// sampled map under the layers, whose four corners the staging lane of a quadrature point gathers itself.  The step
+// and the layer-only instances have no such argument: their argument lists and their code are what they were.
+template <bool PROFILE, typename... Map>
 __global__ __launch_bounds__(256) void k_element_matrices(
     int ne, int N, const int32_t* __restrict__ tsorted, const double* __restrict__ doflocs,
     const double* __restrict__ cores, int ncore, double inv_eps_core, double inv_eps_clad, double k0sq,
-    double alpha_p, int scalar, double* __restrict__ elem) {
+    double alpha_p, int scalar, double* __restrict__ elem, Map... map) {
+  static_assert(PROFILE || sizeof...(Map) == 0, "a map belongs to the profile instance");
   __shared__ double s_phi[6][6];            // [basis][qp]
   __shared__ double s_gx[EPB][6][6];        // [el][basis][qp]
   __shared__ double s_gy[EPB][6][6];
@@ -47,7 +50,7 @@ __global__ __launch_bounds__(256) void k_element_matrices(
       double w1 = fabs(det) * c_qw[q];
       s_w1[el][q] = w1;
       if constexpr (PROFILE) {
-        const double eps = profile_eps(X, Y, cores, ncore, inv_eps_clad);
+        const double eps = profile_eps(X, Y, cores, ncore, inv_eps_clad, map...);
         s_we[el][q] = w1 * (scalar ? eps : 1.0 / eps);
       } else {
         s_we[el][q] = w1 * (in_any_core(X, Y, cores, ncore) ? inv_eps_core : inv_eps_clad);
@@ -425,10 +428,19 @@ __global__ __launch_bounds__(256) void k_spmv_a_block(int N, int64_t ld, const i
 
 }  // namespace
 
-// (with an index profile set on the context -- c->nlayer > 0 -- both take the profile instance and do not read
-// ncore, eps_core, eps_clad)
+// (with an index profile set on the context -- c->nlayer > 0, or an index map -- both take a profile instance and do not
+// read ncore, eps_core, eps_clad)
+namespace {
+EpsMap eps_map(const IndexMap& m) { return {m.d}; }
+}  // namespace
+
 void launch_element_matrices(plfem_ctx* c, int ncore, double eps_core, double eps_clad, double k0, double alpha_p) {
   int grid = (c->ne + EPB - 1) / EPB;
+  if (c->map.set()) {
+    hipLaunchKernelGGL((k_element_matrices<true, EpsMap>), dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
+                       c->d_doflocs, c->d_layers, c->nlayer, 0.0, c->eps_bg, k0 * k0, alpha_p, 0, c->d_elem, eps_map(c->map));
+    return;
+  }
   if (c->nlayer > 0) {
     hipLaunchKernelGGL(k_element_matrices<true>, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
                        c->d_doflocs, c->d_layers, c->nlayer, 0.0, c->eps_bg, k0 * k0, alpha_p, 0, c->d_elem);
@@ -440,6 +452,11 @@ void launch_element_matrices(plfem_ctx* c, int ncore, double eps_core, double ep
 
 void launch_element_matrices_scalar(plfem_ctx* c, int ncore, double eps_core, double eps_clad, double k0) {
   int grid = (c->ne + EPB - 1) / EPB;
+  if (c->map.set()) {
+    hipLaunchKernelGGL((k_element_matrices<true, EpsMap>), dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
+                       c->d_doflocs, c->d_layers, c->nlayer, 0.0, c->eps_bg, k0 * k0, 0.0, 1, c->d_elem, eps_map(c->map));
+    return;
+  }
   if (c->nlayer > 0) {
     hipLaunchKernelGGL(k_element_matrices<true>, dim3(grid), dim3(256), 0, c->stream, c->ne, c->N, c->d_tsorted,
                        c->d_doflocs, c->d_layers, c->nlayer, 0.0, c->eps_bg, k0 * k0, 0.0, 1, c->d_elem);

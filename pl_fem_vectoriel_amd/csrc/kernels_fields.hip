@@ -35,6 +35,7 @@ struct plfem_locator {
   int32_t *d_cell_ptr = nullptr, *d_cell_elems = nullptr, *d_edof = nullptr, *d_int_index = nullptr;
   double* d_pxy = nullptr;                     // [2][nv] vertex coordinates
   double* d_layers = nullptr;                  // [64][8] layer table of the profile of the call in flight (plfem_profile_grams)
+  plfem::IndexMap map;                         // the sampled map under the layers (plfem_locator_set_index_map)
 };
 
 namespace plfem {
@@ -53,6 +54,8 @@ struct LocArgs {
 struct CoreTable {
   double c[MAX_CORES * 3];
 };
+
+EpsMap eps_map(const IndexMap& m) { return {m.d}; }
 
 LocArgs loc_args(const plfem_locator* L, bool indexed) {
   return {L->x0, L->y0, L->inv_hx, L->inv_hy, L->nx, L->ny, L->nv, L->ne, L->d_cell_ptr, L->d_cell_elems, L->d_pxy,
@@ -698,10 +701,12 @@ __global__ __launch_bounds__(256) void k_core_grams(LocArgs L, int k, int64_t nr
 // (w a) b + acc, the same for the four entries of a lane's block.  Outputs (ncomp = 2): M, M_w, K_w, D; (ncomp = 1):
 // M, M_w, S, with M the unweighted u . u' and K, D, S the forms of k_mode_grams.  The layer table is read at indices
 // the workgroup shares (uniform loads) by the GT staging lanes only.
-template <int NCOMP>
+// Map...: nothing, or one EpsMap (a sampled map under the layers, plfem_locator_set_index_map): the instances without a
+// map keep their argument list and their code.
+template <int NCOMP, typename... Map>
 __global__ __launch_bounds__(256) void k_profile_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
                                                        const double* __restrict__ layers, int nlayer, double eps_bg, int nchunk,
-                                                       double* __restrict__ partial) {
+                                                       double* __restrict__ partial, Map... map) {
   constexpr int NF = 3 * NCOMP;
   constexpr int NOUT = NCOMP == 2 ? 4 : 3;
   __shared__ double s_f[2][NF][GT][OC];
@@ -723,7 +728,7 @@ __global__ __launch_bounds__(256) void k_profile_grams(LocArgs L, int k, int64_t
       const int64_t g = tile * GT + tid;
       double wt = 1.0;
       gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q, [&](double X, double Y) {
-        const double eps = profile_eps(X, Y, layers, nlayer, eps_bg);
+        const double eps = profile_eps(X, Y, layers, nlayer, eps_bg, map...);
         wt = NCOMP == 2 ? 1.0 / eps : eps;
       });
       s_wt[tid] = wt;
@@ -1184,23 +1189,7 @@ constexpr int PS_SLICES = 128;       // element slices (partial tiles) per frame
 constexpr int PS_GROUP = 16;         // frame tiles per launch: the partial tiles of one group share the work buffer
 constexpr int PS_LDB = PS_COLS + 16; // padded LDS row of the B operand: the four K-rows of a read 32 banks apart
 
-struct SampledGrid {
-  double x0, y0, inv_dx, inv_dy;
-  int nx, ny;
-};
-
-// Cell (i0, j0) and weights (a, b) of the bilinear interpolant at (X, Y); false outside the closed extent (and for a NaN).
-// tx = (X - x0) (1 / dx), the difference and the product each rounded on their own.
-__device__ __forceinline__ bool sampled_cell(const SampledGrid& G, double X, double Y, int& i0, int& j0, double& a, double& b) {
-  const double tx = mul_rn(X - G.x0, G.inv_dx), ty = mul_rn(Y - G.y0, G.inv_dy);
-  if (!(tx >= 0.0 && tx <= (double)(G.nx - 1) && ty >= 0.0 && ty <= (double)(G.ny - 1))) return false;
-  i0 = min((int)floor(tx), G.nx - 2);
-  j0 = min((int)floor(ty), G.ny - 2);
-  a = tx - (double)i0;
-  b = ty - (double)j0;
-  return true;
-}
-
+// (SampledGrid and sampled_cell, the pixel grid and its cell: p2_element.h)
 template <int NFT>                   // field tiles: ncomp k <= 16 NFT
 __global__ __launch_bounds__(256) void k_mode_project_sampled(LocArgs L, int ncomp, int k, int64_t nrows, const double* __restrict__ V,
                                                               SampledGrid G, int nfr, int tile0, const double* __restrict__ F,
@@ -1360,12 +1349,14 @@ __device__ __forceinline__ void ind_edge_point(int l, double s, double& xi, doub
   eta = l == 0 ? 0.0 : s;
 }
 
-template <int NCOMP>
+// Map...: nothing, or one EpsMap: the point's permittivity is then the profile's over that map, whatever nlayer is
+// (the instances without a map keep their argument list and their code).
+template <int NCOMP, typename... Map>
 __global__ __launch_bounds__(256) void k_mode_indicators(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
                                                          const int32_t* __restrict__ nbr, const double* __restrict__ lam,
                                                          double k0sq, double alpha, CoreTable cores, int ncore, double eps_core,
                                                          double eps_clad, const double* __restrict__ layers, int nlayer,
-                                                         double eps_bg, double* __restrict__ out) {
+                                                         double eps_bg, double* __restrict__ out, Map... map) {
   __shared__ double s_inv[IND_E][4][4];      // J^-1 of the element (slot 0) and of its neighbours (slots 1-3)
   __shared__ int s_row[IND_E][4][6];         // their staged rows, -1 = contributes nothing
   __shared__ int s_nl[IND_E][3];             // the neighbour's local index of the shared edge, -1 = outer boundary
@@ -1419,8 +1410,11 @@ __global__ __launch_bounds__(256) void k_mode_indicators(LocArgs L, int k, int64
         Y = py[va] + mul_rn(s, ty);
         if (!(pt & 1)) { s_tx[el][l] = tx; s_ty[el][l] = ty; }
       }
-      s_eps[el][pt] = nlayer > 0 ? profile_eps(X, Y, layers, nlayer, eps_bg)
-                                 : (in_any_core(X, Y, cores.c, ncore) ? eps_core : eps_clad);
+      if constexpr (sizeof...(Map) > 0)
+        s_eps[el][pt] = profile_eps(X, Y, layers, nlayer, eps_bg, map...);
+      else
+        s_eps[el][pt] = nlayer > 0 ? profile_eps(X, Y, layers, nlayer, eps_bg)
+                                   : (in_any_core(X, Y, cores.c, ncore) ? eps_core : eps_clad);
     }
   }
   __syncthreads();
@@ -1612,8 +1606,15 @@ extern "C" void plfem_locator_destroy(plfem_locator* loc) {
   if (!loc) return;
   (void)hipSetDevice(loc->device);
   (void)hipStreamSynchronize(loc->stream);     // nothing in flight may still read the caller's memory
+  free_index_map(loc->map);
   delete loc;
 }
+
+extern "C" int plfem_locator_set_index_map(plfem_locator* L, const double* eps_host, int32_t nx, int32_t ny, double x0,
+                                           double y0, double dx, double dy) try {
+  if (!L) return PLFEM_EINVAL;
+  return set_index_map(L, "plfem_locator_set_index_map", eps_host, nx, ny, x0, y0, dx, dy);
+} catch (...) { return host_failure(L); }
 
 extern "C" const char* plfem_locator_last_error(const plfem_locator* loc) { return loc ? loc->err.c_str() : "null locator"; }
 
@@ -1908,8 +1909,12 @@ extern "C" int plfem_profile_grams(plfem_locator* L, int32_t ncomp, int32_t k, c
   double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
   const dim3 grid(nblk, nc * nc);
   with_constant<2, 1>(ncomp, [&](auto nco) {
-    hipLaunchKernelGGL(k_profile_grams<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k,
-                       nrows, modes_dev, L->d_layers, (int)nlayer, eps_bg, nc, partial);
+    if (L->map.set())
+      hipLaunchKernelGGL((k_profile_grams<decltype(nco)::value, EpsMap>), grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0),
+                         (int)k, nrows, modes_dev, L->d_layers, (int)nlayer, eps_bg, nc, partial, eps_map(L->map));
+    else
+      hipLaunchKernelGGL(k_profile_grams<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k,
+                         nrows, modes_dev, L->d_layers, (int)nlayer, eps_bg, nc, partial);
   });
   TRY(check_launch(L, "k_profile_grams"));
   return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
@@ -1943,7 +1948,7 @@ extern "C" int plfem_mode_indicators(plfem_locator* L, int32_t ncomp, int32_t k,
   if (!std::isfinite(k0) || !std::isfinite(alpha_p)) { L->err = "plfem_mode_indicators: k0 and alpha_p must be finite"; return PLFEM_EINVAL; }
   for (int m = 0; m < k; ++m)
     if (!std::isfinite(lambda_host[m])) { L->err = "plfem_mode_indicators: every eigenvalue must be finite"; return PLFEM_EINVAL; }
-  if (nlayer != 0) {
+  if (nlayer != 0 || L->map.set()) {              // the profile path: layers, a map (plfem_locator_set_index_map) or both
     if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) {
       L->err = std::string("plfem_mode_indicators: ") + bad;
       return PLFEM_EINVAL;
@@ -1972,13 +1977,19 @@ extern "C" int plfem_mode_indicators(plfem_locator* L, int32_t ncomp, int32_t k,
   HIP_TRY(L, hipMemcpyAsync(d_lam, lambda_host, sizeof(double) * k, hipMemcpyHostToDevice, L->stream));
   if (nlayer > 0)
     HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
-  const CoreTable ct = pack_cores(cores_host, nlayer > 0 ? 0 : ncore);
+  const bool profile = nlayer > 0 || L->map.set();
+  const CoreTable ct = pack_cores(cores_host, profile ? 0 : ncore);
   const int64_t nrows = indexed ? L->nsolve : L->N;
   const dim3 grid((L->ne + IND_E - 1) / IND_E);
   with_constant<2, 1>(ncomp, [&](auto nco) {
-    hipLaunchKernelGGL(k_mode_indicators<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k,
-                       nrows, modes_dev, d_nbr, d_lam, k0 * k0, alpha_p, ct, nlayer > 0 ? 0 : (int)ncore, eps_core, eps_clad,
-                       L->d_layers, (int)nlayer, eps_bg, O);
+    if (L->map.set())
+      hipLaunchKernelGGL((k_mode_indicators<decltype(nco)::value, EpsMap>), grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0),
+                         (int)k, nrows, modes_dev, d_nbr, d_lam, k0 * k0, alpha_p, ct, 0, eps_core, eps_clad, L->d_layers,
+                         (int)nlayer, eps_bg, O, eps_map(L->map));
+    else
+      hipLaunchKernelGGL(k_mode_indicators<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k,
+                         nrows, modes_dev, d_nbr, d_lam, k0 * k0, alpha_p, ct, profile ? 0 : (int)ncore, eps_core, eps_clad,
+                         L->d_layers, (int)nlayer, eps_bg, O);
   });
   TRY(check_launch(L, "k_mode_indicators"));
   HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * (size_t)k * L->ne, hipMemcpyDeviceToHost, L->stream));

@@ -171,5 +171,55 @@ __device__ __forceinline__ double profile_eps(double X, double Y, const double* 
   return eps;
 }
 
+// A uniform node grid x_i = x0 + i dx, y_j = y0 + j dy of nx x ny samples (k_mode_project_sampled: fields; the map of an
+// index profile below: permittivities).  inv_dx = fl(1 / dx) is formed once on the host.
+struct SampledGrid {
+  double x0, y0, inv_dx, inv_dy;
+  int nx, ny;
+};
+
+// Cell (i0, j0) and weights (a, b) of the bilinear interpolant at (X, Y); false outside the closed extent (and for a NaN).
+// tx = (X - x0) (1 / dx), the difference and the product each rounded on their own.
+__device__ __forceinline__ bool sampled_cell(const SampledGrid& G, double X, double Y, int& i0, int& j0, double& a, double& b) {
+  const double tx = mul_rn(X - G.x0, G.inv_dx), ty = mul_rn(Y - G.y0, G.inv_dy);
+  if (!(tx >= 0.0 && tx <= (double)(G.nx - 1) && ty >= 0.0 && ty <= (double)(G.ny - 1))) return false;
+  i0 = min((int)floor(tx), G.nx - 2);
+  j0 = min((int)floor(ty), G.ny - 2);
+  a = tx - (double)i0;
+  b = ty - (double)j0;
+  return true;
+}
+
+// The sampled map of an index profile (plfem_set_index_map, plfem_locator_set_index_map) as a kernel takes it: one
+// pointer to the handle's map buffer (IndexMap of device.h), which holds the grid in its first MAP_HEADER doubles and
+// behind it the permittivities E[j][i], row-major, nx ny <= 2^24 of them.  The grid is read where a point needs it
+// (uniform loads), not carried in twelve scalar registers through a kernel that has none to spare.
+struct EpsMap {
+  const double* buf;
+  __device__ __forceinline__ const SampledGrid& grid() const { return *reinterpret_cast<const SampledGrid*>(buf); }
+  __device__ __forceinline__ const double* eps() const { return buf + MAP_HEADER; }
+};
+static_assert(sizeof(SampledGrid) <= MAP_HEADER * sizeof(double), "the grid fits the map buffer's header");
+
+// The profile over a map: inside the closed extent of the grid the background is the bilinear interpolant of E -- the
+// cell of sampled_cell, the interpolation order of k_mode_project_sampled (along x in both rows, then along y), every
+// product through mul_rn so that no fused multiply-add decides a value -- and eps_bg outside it; the layers are painted
+// over that as above (IndexProfile.epsilon of profile.py, operation for operation).  The four corners are ordinary
+// vector loads at i0 <= nx - 2, j0 <= ny - 2: inside the map for every point, NaN included (outside: nothing is read).
+__device__ __forceinline__ double profile_eps(double X, double Y, const double* __restrict__ layers, int nlayer, double eps_bg,
+                                              const EpsMap& map) {
+  int i0, j0;
+  double a, b;
+  const SampledGrid G = map.grid();
+  if (sampled_cell(G, X, Y, i0, j0, a, b)) {
+    const double* p = map.eps() + ((int64_t)j0 * G.nx + i0);
+    const double e00 = p[0], e01 = p[1], e10 = p[G.nx], e11 = p[G.nx + 1];
+    const double a1 = 1.0 - a, b1 = 1.0 - b;
+    const double lo = mul_rn(a1, e00) + mul_rn(a, e01), hi = mul_rn(a1, e10) + mul_rn(a, e11);
+    eps_bg = mul_rn(lo, b1) + mul_rn(hi, b);
+  }
+  return profile_eps(X, Y, layers, nlayer, eps_bg);
+}
+
 }  // namespace
 }  // namespace plfem

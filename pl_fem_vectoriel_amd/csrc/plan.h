@@ -68,7 +68,12 @@ inline int bwd_block_rows(int count, bool leaf) { return leaf ? 64 : count <= RO
 constexpr int BLOCK_P = 4;
 constexpr int MAX_CORES = 64;   // capacity of the core tables (d_cores, CoreTable): 3 doubles (x, y, r) per core
 // index profile (plfem_set_index_profile, plfem_profile_grams): at most MAX_LAYERS layers of LAYER_DOUBLES doubles
-// (cx, cy, r_in, r_out, eps_a, eps_b, g, 0), read by profile_eps (p2_element.h)
+// (cx, cy, r_in, r_out, eps_a, eps_b, g, 0), read by profile_eps (p2_element.h); a sampled map under them
+// (plfem_set_index_map): at most MAP_NMAX samples per axis and MAP_SAMPLES in all, in a buffer whose first MAP_HEADER
+// doubles hold the grid (SampledGrid of p2_element.h)
+constexpr int MAP_NMAX = 8192;
+constexpr int64_t MAP_SAMPLES = 1 << 24;
+constexpr int MAP_HEADER = 8;
 constexpr int MAX_LAYERS = 64;
 constexpr int LAYER_DOUBLES = 8;
 constexpr int ELEM_FORMS = 8;   // Axx Axy Ayx Ayy Minv Dxx Dxy Dyy

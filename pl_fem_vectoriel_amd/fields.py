@@ -359,11 +359,19 @@ class ModeFields:
             return {nm: np.zeros((0, 0)) for nm in PROFILE_GRAM_NAMES.get(kind, ())}
         self._ensure_locator()
         staged, _src = self._stage(vals)
-        return self._profile_grams_staged(kind, staged, profile.table(), profile.eps_background)
+        return self._profile_grams_staged(kind, staged, profile.table(), profile.eps_background, index_map=profile.index_map)
 
-    def _profile_grams_staged(self, kind, staged, table, eps_bg, work=None) -> Dict[str, np.ndarray]:
+    def _set_index_map(self, index_map) -> None:
+        """``plfem_locator_set_index_map``: the map of the profile of the call in flight, or None: clear.  Every profile
+        branch sets or clears it, so a cached locator never carries a map into the next call."""
+        self._check(_native.set_index_map_call(self._lib.plfem_locator_set_index_map, self._loc, index_map),
+                    "plfem_locator_set_index_map")
+
+    def _profile_grams_staged(self, kind, staged, table, eps_bg, work=None, index_map=None) -> Dict[str, np.ndarray]:
         """``plfem_profile_grams`` on modes already staged (ncomp, n, k) on the device; ``work``: a uint8 device tensor to
-        use as the work buffer (at least the library's size + 256 bytes) instead of a fresh one."""
+        use as the work buffer (at least the library's size + 256 bytes) instead of a fresh one; ``index_map``: the
+        profile's map (``IndexProfile.index_map``) or None."""
+        self._set_index_map(index_map)
         names = PROFILE_GRAM_NAMES[kind]
         ncomp, _, k = staged.shape
         table = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, 8))
@@ -403,10 +411,10 @@ class ModeFields:
             if not all(hasattr(geometry, a) for a in ("n_core", "n_clad")):
                 raise ValueError("geometry must have n_core and n_clad (or carry an index profile)")
             cores = self._cores(geometry)
-            table, eps = np.zeros((0, 8)), (float(geometry.n_core) ** 2, float(geometry.n_clad) ** 2, 1.0)
+            table, eps, index_map = np.zeros((0, 8)), (float(geometry.n_core) ** 2, float(geometry.n_clad) ** 2, 1.0), None
         else:
             cores = np.zeros((0, 3))
-            table, eps = profile.table(), (1.0, 1.0, float(profile.eps_background))
+            table, eps, index_map = profile.table(), (1.0, 1.0, float(profile.eps_background)), profile.index_map
         k = 0 if kind is None else vals.shape[1]
         if k == 0:
             return {"eta2": np.zeros((0, self.ne)), "total": np.zeros(0)}
@@ -415,12 +423,14 @@ class ModeFields:
         lam = np.ascontiguousarray(beta * beta if kind == "vectorial" else -(beta * beta))
         self._ensure_locator()
         staged, _src = self._stage(vals)
-        eta2 = self._indicators_staged(kind, staged, lam, k0, alpha_p, cores, eps, table)
+        eta2 = self._indicators_staged(kind, staged, lam, k0, alpha_p, cores, eps, table, index_map=index_map)
         return {"eta2": eta2, "total": eta2.sum(axis=1)}
 
-    def _indicators_staged(self, kind, staged, lam, k0, alpha_p, cores, eps, table, work=None) -> np.ndarray:
+    def _indicators_staged(self, kind, staged, lam, k0, alpha_p, cores, eps, table, work=None, index_map=None) -> np.ndarray:
         """``plfem_mode_indicators`` on modes already staged (ncomp, n, k) on the device: (k, ne).  ``eps`` = (eps_core,
-        eps_clad, eps_bg); ``work``: a uint8 device tensor to use as the work buffer instead of a fresh one."""
+        eps_clad, eps_bg); ``work``: a uint8 device tensor to use as the work buffer instead of a fresh one; ``index_map``:
+        the profile's map (``IndexProfile.index_map``) or None."""
+        self._set_index_map(index_map)
         ncomp, _, k = staged.shape
         table = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, 8))
         cores = np.ascontiguousarray(np.asarray(cores, dtype=np.float64).reshape(-1, 3))

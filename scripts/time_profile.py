@@ -1,11 +1,15 @@
 """Timing aid of the index-profile path at C1: the assembly with a profile of ``--layers`` layers beside the step
 assembly, and ``ModeFields.profile_grams`` beside ``ModeFields.grams`` for 22 vectorial and scalar modes.
 
-    python scripts/time_profile.py [--layers 7] [--modes 22] [--reps 10] [--out FILE]
+    python scripts/time_profile.py [--layers 7] [--map NX NY] [--modes 22] [--reps 10] [--out FILE]
 
-Run it under ``rocprofv3 --kernel-trace --stats``, in a run of its own and once per ``--layers`` (both profile assemblies
-are the one instance k_element_matrices<true>), for the kernel times of k_element_matrices<true> / <false> and of
-k_profile_grams next to k_mode_grams; the wall times printed here include the copies and the launches."""
+``--map NX NY`` puts a sampled index map of NX x NY pixels over the bounding box of the mesh under the layers
+(``IndexProfile.sampled``): the profile kernels are then their map instances (k_element_matrices<true, EpsMap>,
+k_profile_grams<.., EpsMap>).
+
+Run it under ``rocprofv3 --kernel-trace --stats``, in a run of its own and once per ``--layers`` / ``--map`` (the profile
+assemblies without a map are the one instance k_element_matrices<true>), for the kernel times of k_element_matrices and
+of k_profile_grams next to k_mode_grams; the wall times printed here include the copies and the launches."""
 from __future__ import annotations
 
 import argparse
@@ -37,9 +41,19 @@ def c1_profile(geom, layers: int):
     return prof
 
 
+def add_map(prof, mesh, nx: int, ny: int):
+    """A smooth index image under the layers: a super-Gaussian plateau of 1.45 in air with a slow tilt, sampled on
+    nx x ny pixels over the bounding box of the mesh."""
+    x = np.linspace(mesh.p[0].min(), mesh.p[0].max(), nx)
+    y = np.linspace(mesh.p[1].min(), mesh.p[1].max(), ny)
+    X, Y = np.meshgrid(x, y)
+    return prof.sampled(x, y, 1.0 + 0.45 * np.exp(-(((X * X + Y * Y) / 196.0) ** 4)) * (1.0 + 1e-3 * X))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=7)
+    ap.add_argument("--map", type=int, nargs=2, metavar=("NX", "NY"), default=None)
     ap.add_argument("--modes", type=int, default=22)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)
@@ -53,8 +67,10 @@ def main():
     geom = MCFGeometry(7, 8.0, 1.5, 1.535, 1.0, wavelength_um=1.55)
     mesh = generate_mesh(geom, 1.0, 1)
     prof = c1_profile(geom, args.layers)
+    if args.map:
+        add_map(prof, mesh, *args.map)
     pg = ProfiledGeometry(geom, prof)
-    res = {"ne": int(mesh.t.shape[1]), "layers": len(prof)}
+    res = {"ne": int(mesh.t.shape[1]), "layers": len(prof), "map": args.map}
 
     def timed(f):
         best = None
