@@ -42,9 +42,15 @@ def owned_dofs(T, f, N):
     return np.concatenate([c * N + nodes for c in range(T.dpn)])
 
 
+def shallowest_owner(T, N):
+    """The shallowest front that owns DOFs: lowest level, then lowest index (heap order is level order).  The root,
+    unless the first cut of the dissection runs through a gap of the mesh and owns nothing."""
+    return next(f for f in range(T.nf) if owned_dofs(T, f, N).size)
+
+
 def right_hand_sides(T, idx, N):
     """The four right-hand sides of a case (full length dpn N, zero outside the unknowns idx): two random ones, one
-    supported on the owned DOFs of one leaf, one on the root separator."""
+    supported on the owned DOFs of one leaf, one ("root") on the topmost separator that owns DOFs."""
     n2 = T.dpn * N
     rng = np.random.default_rng(7)
     out = {}
@@ -59,10 +65,55 @@ def right_hand_sides(T, idx, N):
     d = owned_dofs(T, leaf, N)
     b[d] = rng.standard_normal(len(d))
     out["leaf"] = b
-    # supported on the root separator only: travels down through every level
+    # supported on the topmost separator only (the root of every tree whose root owns DOFs): travels down through every
+    # level below it
     b = np.zeros(n2)
-    d = owned_dofs(T, 0, N)
+    d = owned_dofs(T, shallowest_owner(T, N), N)
     b[d] = rng.standard_normal(len(d))
     out["root"] = b
     assert all(np.count_nonzero(v) for v in out.values())
     return out
+
+
+def check_tree_invariants(sym):
+    """The front tree of an analysis is a valid elimination structure: every unknown node is owned by exactly one front
+    (a Dirichlet node by none), the boundary nodes of a front are owned by proper ancestors, the root has no boundary,
+    front sizes are multiples of 8, and every element sits in one leaf with all its unknown nodes in that front.  Every
+    front, boundary node and element is checked.  Returns the FrontTree."""
+    import front_emulation as fe
+    T = fe.FrontTree(sym)
+    owner = sym.array("owner")
+    bmask = sym.array("bmask").astype(bool)
+    assert (owner[bmask] == -1).all() and (owner[~bmask] >= 0).all()
+    seen = np.zeros(sym.N, dtype=int)
+    for f in range(T.nf):
+        fn = T.nodes(f)
+        own = fn[:T.fs[f]]
+        own = own[own >= 0]
+        assert (owner[own] == f).all()
+        seen[own] += 1
+        bnd = fn[T.fs[f]:]
+        bnd = bnd[bnd >= 0]
+        for v in bnd:
+            a = owner[v]
+            g = f
+            while g > a:
+                g = (g - 1) // 2
+            assert g == a and a != f, (f, v, a)
+        assert T.fs[f] % 8 == 0 and T.fb[f] % 8 == 0
+    assert (seen[~bmask] == 1).all() and (seen[bmask] == 0).all()
+    assert T.fb[0] == 0                                            # the root has no boundary
+    epos = T.epos
+    edof = sym.array("edof").reshape(6, -1)
+    leaf = sym.array("leaf_of_elem")
+    count = np.zeros(sym.ne, dtype=int)
+    np.add.at(count, T.lel, 1)
+    assert (count == 1).all()                                      # every element in exactly one leaf's list
+    for e in range(sym.ne):
+        fn = T.nodes(T.leaf0 + leaf[e])
+        for a in range(6):
+            if bmask[edof[a, e]]:
+                assert epos[a, e] == -1
+            else:
+                assert fn[epos[a, e]] == edof[a, e]
+    return T

@@ -290,7 +290,8 @@ def bwd_block_rows(count, leaf):
 
 def level_forms(sym):
     """Per tree level (root first) the record plfem_debug_level_plan returns (_native.PLAN_FIELDS), from the symbolic
-    arrays and the rules of plan.cpp, plus the kernel names of the two sweeps ("fwd", "bwd") and "leaf"."""
+    arrays and the rules of plan.cpp, plus the kernel names of the two sweeps ("fwd", "bwd"), "leaf" and the number of
+    fronts of the level that have rows at all ("fronts_m") and owned DOFs ("fronts_s2")."""
     dpn = int(sym.dofs_per_node)
     fs, fb = sym.array("fs").astype(np.int64), sym.array("fb").astype(np.int64)
     L = sym.info["levels"]
@@ -312,5 +313,6 @@ def level_forms(sym):
         bwd = {8: "k_bwd_rows<P,1,4>", 16: "k_bwd_rows<P,2,4>"}.get(br, "k_bwd")
         out.append({"count": count, "fwd_rows": fr, "bwd_rows": br, "fwd_mixed": int(mixed), "max_s2": int(s2.max()),
                     "max_m": int(m.max()), "fwd_n": fwd_n, "bwd_n": bwd_n, "steps": cdiv(int(s2.max()), NB),
-                    "max_block_p": max_block_p, "fwd": fwd, "bwd": bwd, "leaf": leaf})
+                    "max_block_p": max_block_p, "fwd": fwd, "bwd": bwd, "leaf": leaf,
+                    "fronts_m": int((m > 0).sum()), "fronts_s2": int((s2 > 0).sum())})   # fronts with rows / with owned DOFs
     return out

@@ -28,6 +28,10 @@ def c1_l0(c1_geometry, gpu_device, built_library):
     torch.cuda.empty_cache()
 
 
+OWN_DOF_TOL = 1e-13     # a DOF location sampled in an element of that DOF, of the largest DOF value
+ANY_DOF_TOL = 1e-8      # ... in a neighbouring element (slivers)
+
+
 def _stack(modes, key):
     return np.array([m[key] for m in modes])
 
@@ -52,13 +56,13 @@ def test_sampling_at_own_doflocs_returns_dof_values(c1_l0):
         w = int(np.argmax(err))
         print(f"{comp}: worst relative error {err[w]:.2e} at DOF {w} (boundary {w in set(bnd.tolist())}, element {e[w]}, "
               f"own element {own[w]}, |det J| {det[w]:.2e}); DOFs above 1e-13: {int((err > 1e-13).sum())} of {mf.N}")
-        assert (err[own] <= 1e-13).all()
-        assert err.max() <= 1e-8
+        assert (err[own] <= OWN_DOF_TOL).all()
+        assert err.max() <= ANY_DOF_TOL
     u = mf.sample(scal, dl)["u"]
     ref = _stack(scal, "field_vector")
     err = np.abs(u - ref).max(0) / np.abs(ref).max()
     print(f"u: worst relative error {err.max():.2e}; DOFs above 1e-13: {int((err > 1e-13).sum())}")
-    assert (err[own] <= 1e-13).all() and err.max() <= 1e-8
+    assert (err[own] <= OWN_DOF_TOL).all() and err.max() <= ANY_DOF_TOL
 
 
 def _compare(out, ref, elem_gpu, elem_em, near, comps):

@@ -3,10 +3,10 @@ meshes.  Tolerances: north_star asks |dn_eff| < 5e-5 and field L2 < 1e-6; the ma
 compared to 1e-13 of the assembled magnitude."""
 import numpy as np
 import pytest
-import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 import front_emulation as fe
+from assembly_checks import check_blocks, vectorial_refs
 from oracle import hfield
 from oracle.compare import column_errors, mode_field_errors
 from oracle.p2 import MeshTriLite, P2Basis
@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 N_EFF_TOL = 5e-5      # north_star
 FIELD_TOL = 1e-6      # north_star
+SPMV_TOL = 1e-13      # sparse products, of the largest entry of |M| |x|
 
 
 class Problem:
@@ -55,39 +56,12 @@ def medium(c1_geometry, gpu_device, built_library):
     return Problem(c1_geometry, generate_mesh(c1_geometry, 1.0, 0), gpu_device)
 
 
-def _abs_assembled(P, name_terms):
-    """Sum of |element entries| per CSR slot: the magnitude rounding errors are measured against."""
-    ed = P.basis.element_dofs
-    rows = np.broadcast_to(ed.T[:, :, None], (ed.shape[1], 6, 6)).ravel()
-    cols = np.broadcast_to(ed.T[:, None, :], (ed.shape[1], 6, 6)).ravel()
-    # per-element scale = largest entry of that element's matrices: inside a sliver element an entry
-    # can be a cancelling sum of quadrature terms as large as the element's largest entry
-    mag = sum(np.abs(t) for t in name_terms)
-    mag = np.broadcast_to(mag.max(axis=(1, 2), keepdims=True), mag.shape)
-    return sp.coo_matrix((mag.ravel(), (rows, cols)), shape=(P.N, P.N)).tocsr()
-
-
 @pytest.mark.parametrize("prob", ["small", "medium"])
 def test_assembled_blocks_match_oracle(prob, request):
+    """Slot by slot, |diff| <= 1e-13 * (sum over contributing elements of the element's largest entry): assembly_checks.py."""
     P = request.getfixturevalue(prob)
-    N, em, k0sq = P.N, P.em, P.g.k0 ** 2
-    rowptr, colind = P.sym.array("rowptr"), P.sym.array("colind")
-    refs = {
-        "Axx": (P.A[:N, :N], [em["kxx"], em["div_xx"], k0sq * em["mass"]]),
-        "Axy": (P.A[:N, N:], [em["kxy"], em["div_xy"]]),
-        "Ayx": (P.A[N:, :N], [em["kyx"], em["div_xy"]]),
-        "Ayy": (P.A[N:, N:], [em["kyy"], em["div_yy"], k0sq * em["mass"]]),
-        "Minv": (P.Minv, [em["mass_eps_inv"]]), "Dxx": (P.Dxx, [em["div_xx"]]),
-        "Dxy": (P.Dxy, [em["div_xy"]]), "Dyy": (P.Dyy, [em["div_yy"]]),
-    }
-    for name, (R, terms) in refs.items():
-        G = sp.csr_matrix((P.ctx.block_values(name), colind, rowptr), shape=(N, N))
-        mag = _abs_assembled(P, terms)
-        D = abs(G - R)
-        D.eliminate_zeros()
-        # |diff| <= 1e-13 * (sum over contributing elements of the element's largest entry), slot by slot
-        viol = D - 1e-13 * mag
-        assert viol.max() <= 0.0, (name, D.max(), mag.max())
+    refs = vectorial_refs(P.A, P.Minv, P.Dxx, P.Dxy, P.Dyy, P.em, P.g.k0 ** 2, P.N)
+    check_blocks(P.ctx, P.sym, P.basis, refs)
 
 
 def test_reference_surface_assemble_hfield_system(small, gpu_device):
@@ -113,7 +87,7 @@ def test_spmv_matches_restricted_pencil(medium):
     for which, M in (("A", P.A_int), ("B", P.B_int)):
         y = P.ctx.spmv(which, xd).cpu().numpy()
         ref = M @ x
-        assert np.abs(y[P.idx] - ref).max() <= 1e-13 * (abs(M) @ np.abs(x)).max()
+        assert np.abs(y[P.idx] - ref).max() <= SPMV_TOL * (abs(M) @ np.abs(x)).max()
         assert np.abs(np.delete(y, P.idx)).max() == 0.0            # Dirichlet rows masked
 
 

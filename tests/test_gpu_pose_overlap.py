@@ -22,6 +22,9 @@ POSES = (IDENTITY, COVERING, HALF_OUT)
 QUARTER = (0.05, 0.1, 0.0, 1.0, 0.9)                     # an exact quarter turn
 
 
+POSED_TOL = 1e-12       # posed overlaps against the emulation, of the largest reference entry
+
+
 def discs_in_b():
     """Core discs inside mesh B ([-0.5, 0.5]^2) (no PML: only the real permittivity is read)."""
     g = MCFGeometry(7, 8.0, 1.5, 1.535, 1.0, wavelength_um=1.55, use_complex_pml=False)
@@ -86,7 +89,7 @@ def test_posed_overlap_matches_emulation(pair, kind, wname):
             ref = pair.ref[kind, wname, ip][:ka, KMAX - kb:]
             err = rel(O[ip], ref)
             print(kind, wname, ka, kb, ip, f"{err:.2e}")
-            assert err <= 1e-12, (kind, wname, ka, kb, ip, err)
+            assert err <= POSED_TOL, (kind, wname, ka, kb, ip, err)
 
 
 @pytest.mark.parametrize("wname", ["none", "discs"])

@@ -12,6 +12,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 import front_emulation as fe
+from front_checks import check_tree_invariants
 from oracle import hfield
 from oracle.p2 import MeshTriLite, P2Basis
 from pl_fem_vectoriel_amd import _native
@@ -106,40 +107,7 @@ def test_numbering_and_pattern_match_oracle(built_library, c1_geometry, which):
 def test_front_tree_invariants(built_library, c1_geometry):
     mesh = generate_mesh(c1_geometry, 0.5, 0)
     sym = _native.Symbolic(mesh.p, mesh.t, leaf_elems=24)
-    T = fe.FrontTree(sym)
-    owner = sym.array("owner")
-    bmask = sym.array("bmask").astype(bool)
-    assert (owner[bmask] == -1).all() and (owner[~bmask] >= 0).all()
-    seen = np.zeros(sym.N, dtype=int)
-    for f in range(T.nf):
-        fn = T.nodes(f)
-        own = fn[:T.fs[f]]
-        own = own[own >= 0]
-        assert (owner[own] == f).all()
-        seen[own] += 1
-        bnd = fn[T.fs[f]:]
-        bnd = bnd[bnd >= 0]
-        # boundary nodes are owned by proper ancestors
-        for v in bnd[:: max(1, len(bnd) // 8)]:
-            a = owner[v]
-            g = f
-            while g > a:
-                g = (g - 1) // 2
-            assert g == a and a != f
-        assert T.fs[f] % 8 == 0 and T.fb[f] % 8 == 0
-    assert (seen[~bmask] == 1).all() and (seen[bmask] == 0).all()
-    assert T.fb[0] == 0                                            # the root has no boundary
-    # every element sits in exactly one leaf, with all its non-Dirichlet nodes present in that front
-    epos = T.epos
-    edof = sym.array("edof").reshape(6, -1)
-    leaf = sym.array("leaf_of_elem")
-    for e in np.random.default_rng(1).integers(0, sym.ne, 300):
-        fn = T.nodes(T.leaf0 + leaf[e])
-        for a in range(6):
-            if bmask[edof[a, e]]:
-                assert epos[a, e] == -1
-            else:
-                assert fn[epos[a, e]] == edof[a, e]
+    check_tree_invariants(sym)          # (front_checks.py: every front, boundary node and element)
 
 
 @pytest.mark.parametrize("refinement,leaf", [(0.35, 12), (0.5, 24)])
