@@ -230,56 +230,36 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_locator_destroy.restype = None
     lib.plfem_locator_last_error.argtypes = [ctypes.c_void_p]
     lib.plfem_locator_last_error.restype = ctypes.c_char_p
-    lib.plfem_stage_modes.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                      ctypes.c_void_p]
-    lib.plfem_sample_fields.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.plfem_overlap_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_field_overlap.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] * 2 +
-                                        [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
-                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p])
-    lib.plfem_overlap_posed_work_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                   ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_field_overlap_posed.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] * 2 +
-                                              [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
-                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p])
-    lib.plfem_gram_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_mode_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                     ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-    lib.plfem_core_gram_work_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_core_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                     ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                     ctypes.c_void_p]
-    lib.plfem_moment_gram_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_moment_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                       ctypes.c_void_p]
-    lib.plfem_set_index_profile.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]
-    lib.plfem_set_index_map.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_double] * 4
+    # the field entry points: the mode calls begin (locator, ncomp, k, modes, indexed), the overlaps with that per mesh, and
+    # every call that takes a work buffer ends (work, work_bytes, out); every sizer ends with the int64 it fills
+    vp, i32, i64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+    head, tail, size = [vp, i32, i32, vp, i32], [vp, i64, vp], [ctypes.POINTER(i64)]
+    pair = [vp, vp, i32, i32] * 2 + [i32, vp, i32, f64, f64]       # A, B, ncomp, cores, ncore, eps_core, eps_clad
+    lib.plfem_stage_modes.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.plfem_sample_fields.argtypes = head + [vp, i32, vp, vp, vp]
+    lib.plfem_overlap_work_bytes.argtypes = [i32, i32] + size
+    lib.plfem_field_overlap.argtypes = pair + tail
+    lib.plfem_overlap_posed_work_bytes.argtypes = [vp, i32, i32, i32] + size
+    lib.plfem_field_overlap_posed.argtypes = pair + [i32, vp] + tail
+    lib.plfem_gram_work_bytes.argtypes = [i32, i32] + size
+    lib.plfem_mode_grams.argtypes = head + [vp, i32] + tail
+    lib.plfem_core_gram_work_bytes.argtypes = [vp, i32, i32, i32] + size
+    lib.plfem_core_grams.argtypes = head + [vp, i32] + tail + [vp]
+    lib.plfem_moment_gram_work_bytes.argtypes = [i32, i32] + size
+    lib.plfem_moment_grams.argtypes = head + [vp, i32, vp] + tail
+    lib.plfem_set_index_profile.argtypes = [vp, vp, i32, f64]
+    lib.plfem_set_index_map.argtypes = [vp, vp, i32, i32] + [f64] * 4
     lib.plfem_locator_set_index_map.argtypes = lib.plfem_set_index_map.argtypes
-    lib.plfem_profile_gram_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_profile_grams.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int64,
-                                        ctypes.c_void_p]
-    lib.plfem_quartic_work_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_mode_quartic.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
-                                       ctypes.c_int64, ctypes.c_void_p]
-    lib.plfem_project_work_bytes.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_mode_project.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                       ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_int64, ctypes.c_void_p]
-    lib.plfem_project_sampled_work_bytes.argtypes = [ctypes.c_int32] * 3 + [ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_mode_project_sampled.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                               ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                               ctypes.c_void_p]
-    lib.plfem_indicator_work_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
-    lib.plfem_mode_indicators.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                          ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32,
-                                          ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double,
-                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    lib.plfem_profile_gram_work_bytes.argtypes = [i32, i32] + size
+    lib.plfem_profile_grams.argtypes = head + [vp, i32, f64] + tail
+    lib.plfem_quartic_work_bytes.argtypes = [i32, i32] + size
+    lib.plfem_mode_quartic.argtypes = head + [vp, i32, f64, f64] + tail
+    lib.plfem_project_work_bytes.argtypes = [i32] * 4 + size
+    lib.plfem_mode_project.argtypes = head + [i32, vp, i32, vp] + tail
+    lib.plfem_project_sampled_work_bytes.argtypes = [i32] * 3 + size
+    lib.plfem_mode_project_sampled.argtypes = head + [i32, i32, f64, f64, f64, f64, i32, vp] + tail
+    lib.plfem_indicator_work_bytes.argtypes = [vp, i32, i32] + size
+    lib.plfem_mode_indicators.argtypes = head + [vp, f64, f64, vp, i32, f64, f64, vp, i32, f64] + tail
     lib.plfem_mesh_refine_marked_count.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_int32]

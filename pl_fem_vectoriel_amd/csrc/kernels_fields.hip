@@ -1618,12 +1618,117 @@ extern "C" int plfem_locator_set_index_map(plfem_locator* L, const double* eps_h
 
 extern "C" const char* plfem_locator_last_error(const plfem_locator* loc) { return loc ? loc->err.c_str() : "null locator"; }
 
-extern "C" int plfem_stage_modes(plfem_locator* L, int32_t ncomp, int32_t k, int32_t nrows, const double* src_dev, double* dst_dev) try {
-  if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k < 0 || nrows < 0 || ((!src_dev || !dst_dev) && k > 0 && nrows > 0)) {
-    L->err = "plfem_stage_modes: bad arguments";
+// ---- the field entry points ---------------------------------------------------------------------------------------
+// Every one has the same shape ("The shape of a field entry point"): null locator; the call's own argument
+// checks, each one expression `return call.reject(...)`, in a fixed order; FieldCall::enter (interior DOFs, work buffer,
+// device); the launches, each followed by check_launch; result_to_host.
+namespace {
+int overlap_chunks(int k) { return (k + OC - 1) / OC; }
+
+// ncomp 1 or 2 and 1 <= k <= kmax: what the mode calls and their sizers accept
+bool modes_ok(int ncomp, int k, int kmax = INT32_MAX) { return ncomp >= 1 && ncomp <= 2 && k >= 1 && k <= kmax; }
+
+// a core count: at most MAX_CORES, and negative ("no weight") only in the calls that have an unweighted form
+bool ncore_ok(int ncore, bool unweighted_ok) { return ncore <= MAX_CORES && (ncore >= 0 || unweighted_ok); }
+
+// the cores as the kernels' by-value table, zero past ncore
+CoreTable pack_cores(const double* cores_host, int ncore) {
+  CoreTable ct;
+  std::memset(&ct, 0, sizeof(ct));
+  if (ncore > 0) std::memcpy(ct.c, cores_host, sizeof(double) * 3 * ncore);
+  return ct;
+}
+
+// A field call on its way from its arguments to its launches: the locator that takes the error text and whose stream
+// runs the call, the entry point's name, and what enter() makes of `indexed` and the work buffer
+struct FieldCall {
+  plfem_locator* L;
+  const char* fn;
+  plfem_locator* Lb = nullptr;               // the second mesh of an overlap (pair())
+  int64_t nrows = 0, nrows_b = 0;            // rows of the staged modes
+  LocArgs loc{}, loc_b{};
+  double *O = nullptr, *partial = nullptr;   // the work buffer: the result at its start, the partial sums behind it
+
+  int reject(const std::string& what) const {
+    L->err = std::string(fn) + ": " + what;
     return PLFEM_EINVAL;
   }
+  int pair(plfem_locator* other) {
+    if (!other || L->device != other->device) return reject("the two locators must be on one device");
+    Lb = other;
+    return PLFEM_OK;
+  }
+  // interior-indexed modes need interior DOFs; the rows and the kernels' locator arguments of each mesh
+  int modes(int indexed, int indexed_b = 0) {
+    if ((indexed && L->nsolve == 0) || (Lb && indexed_b && Lb->nsolve == 0)) return reject("the analysis has no interior DOFs");
+    nrows = indexed ? L->nsolve : L->N;
+    loc = loc_args(L, indexed != 0);
+    if (Lb) {
+      nrows_b = indexed_b ? Lb->nsolve : Lb->N;
+      loc_b = loc_args(Lb, indexed_b != 0);
+    }
+    return PLFEM_OK;
+  }
+  // the caller's work buffer: at least `need` bytes (what `sizer` returns), 256-byte aligned, partial sums from
+  // `off_partial`; then the device
+  int work(const char* sizer, void* work_dev, int64_t work_bytes, size_t need, size_t off_partial) {
+    if (work_bytes < (int64_t)need) return reject(std::string("work buffer smaller than ") + sizer);
+    if ((uintptr_t)work_dev & 255) return reject("work buffer must be 256-byte aligned");
+    HIP_TRY(L, hipSetDevice(L->device));
+    O = (double*)work_dev;
+    partial = (double*)((char*)work_dev + off_partial);
+    return PLFEM_OK;
+  }
+  // what follows a call's own checks
+  int enter(int indexed, const char* sizer, void* work_dev, int64_t work_bytes, size_t need, size_t off_partial,
+            int indexed_b = 0) {
+    TRY(modes(indexed, indexed_b));
+    return work(sizer, work_dev, work_bytes, need, off_partial);
+  }
+};
+
+// f(map) with the locator's sampled map when it carries one, f() otherwise: a kernel template <..., typename... Map> is
+// launched as its EpsMap or its plain instance by one line, `kernel<..., decltype(map)...>` with `map...` as last argument
+template <typename F>
+void with_map(const plfem_locator* L, F&& f) {
+  if (L->map.set()) f(eps_map(L->map));
+  else f();
+}
+
+// how a call ends: the first `n` doubles of the work buffer to `out_host`, the stream synchronised
+int result_to_host(plfem_locator* L, const double* O, size_t n, double* out_host) {
+  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * n, hipMemcpyDeviceToHost, L->stream));
+  HIP_TRY(L, hipStreamSynchronize(L->stream));
+  return PLFEM_OK;
+}
+
+// k_overlap_reduce over `grid` (chunk pairs, output matrices, entry slices), then O [grid.y][ka][kb] to the host
+int reduce_to_host(plfem_locator* L, dim3 grid, int ka, int kb, int nblk, int nchunk_b, const double* partial, double* O,
+                   double* out_host) {
+  hipLaunchKernelGGL(k_overlap_reduce, grid, dim3(256), 0, L->stream, ka, kb, nblk, nchunk_b, partial, O);
+  TRY(check_launch(L, "k_overlap_reduce"));
+  return result_to_host(L, O, (size_t)grid.y * ka * kb, out_host);
+}
+
+// at most `slices` element slices, one per element of a small mesh, at least 1
+int element_slices(int slices, int ne) { return std::max(1, std::min(slices, ne)); }
+
+// A field call's work buffer: the result (`result` doubles), then, 256-byte aligned, `partial` doubles of partial sums
+struct WorkLayout { size_t off_partial, total; };   // bytes
+WorkLayout work_layout(size_t result, size_t partial) {
+  const size_t off = align256(result * sizeof(double));
+  return {off, off + partial * sizeof(double)};
+}
+WorkLayout overlap_layout(int ka, int kb) {
+  return work_layout((size_t)ka * kb, (size_t)overlap_chunks(ka) * overlap_chunks(kb) * OVL_BLOCKS * OC * OC);
+}
+}  // namespace
+
+extern "C" int plfem_stage_modes(plfem_locator* L, int32_t ncomp, int32_t k, int32_t nrows, const double* src_dev, double* dst_dev) try {
+  if (!L) return PLFEM_EINVAL;
+  const FieldCall call{L, "plfem_stage_modes"};
+  if (ncomp < 1 || ncomp > 2 || k < 0 || nrows < 0 || ((!src_dev || !dst_dev) && k > 0 && nrows > 0))
+    return call.reject("bad arguments");
   if (k == 0 || nrows == 0) return PLFEM_OK;
   HIP_TRY(L, hipSetDevice(L->device));
   dim3 grid((nrows + 31) / 32, (k + 31) / 32, ncomp);
@@ -1635,63 +1740,16 @@ extern "C" int plfem_sample_fields(plfem_locator* L, int32_t ncomp, int32_t k, c
                                    const double* beta_dev, int32_t npts, const double* points_dev, double* out_dev,
                                    int32_t* elem_dev) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k < 0 || npts < 0) {
-    L->err = "plfem_sample_fields: ncomp must be 1 or 2, k and npts >= 0";
-    return PLFEM_EINVAL;
-  }
+  FieldCall call{L, "plfem_sample_fields"};
+  if (ncomp < 1 || ncomp > 2 || k < 0 || npts < 0) return call.reject("ncomp must be 1 or 2, k and npts >= 0");
   if (npts == 0) return PLFEM_OK;
-  if (!points_dev || !elem_dev || (k > 0 && (!modes_dev || !out_dev))) {
-    L->err = "plfem_sample_fields: null device array";
-    return PLFEM_EINVAL;
-  }
-  if (indexed && L->S->nsolve == 0) { L->err = "plfem_sample_fields: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  if (!points_dev || !elem_dev || (k > 0 && (!modes_dev || !out_dev))) return call.reject("null device array");
+  TRY(call.modes(indexed));
   HIP_TRY(L, hipSetDevice(L->device));
-  const int64_t nrows = indexed ? L->nsolve : L->N;
-  hipLaunchKernelGGL(k_sample_fields, dim3((npts + 255) / 256), dim3(256), 0, L->stream, loc_args(L, indexed != 0),
-                     (int)ncomp, (int)k, nrows, modes_dev, ncomp == 2 ? beta_dev : nullptr, (int)npts, points_dev, out_dev, elem_dev);
+  hipLaunchKernelGGL(k_sample_fields, dim3((npts + 255) / 256), dim3(256), 0, L->stream, call.loc, (int)ncomp, (int)k, call.nrows,
+                     modes_dev, ncomp == 2 ? beta_dev : nullptr, (int)npts, points_dev, out_dev, elem_dev);
   return check_launch(L, "k_sample_fields");
 } catch (...) { return host_failure(L); }
-
-namespace {
-int overlap_chunks(int k) { return (k + OC - 1) / OC; }
-
-// the cores as the kernels' by-value table, zero past ncore
-CoreTable pack_cores(const double* cores_host, int ncore) {
-  CoreTable ct;
-  std::memset(&ct, 0, sizeof(ct));
-  if (ncore > 0) std::memcpy(ct.c, cores_host, sizeof(double) * 3 * ncore);
-  return ct;
-}
-
-// the caller's work buffer: at least `need` bytes (what `sizer` returns), 256-byte aligned
-int check_work(plfem_locator* L, const char* fn, const char* sizer, const void* work_dev, int64_t work_bytes, int64_t need) {
-  if (work_bytes < need) { L->err = std::string(fn) + ": work buffer smaller than " + sizer; return PLFEM_EINVAL; }
-  if ((uintptr_t)work_dev & 255) { L->err = std::string(fn) + ": work buffer must be 256-byte aligned"; return PLFEM_EINVAL; }
-  return PLFEM_OK;
-}
-
-// k_overlap_reduce over `grid` (chunk pairs, output matrices, entry slices), then O [grid.y][ka][kb] to the host
-int reduce_to_host(plfem_locator* L, dim3 grid, int ka, int kb, int nblk, int nchunk_b, const double* partial, double* O,
-                   double* out_host) {
-  hipLaunchKernelGGL(k_overlap_reduce, grid, dim3(256), 0, L->stream, ka, kb, nblk, nchunk_b, partial, O);
-  TRY(check_launch(L, "k_overlap_reduce"));
-  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * grid.y * ka * kb, hipMemcpyDeviceToHost, L->stream));
-  HIP_TRY(L, hipStreamSynchronize(L->stream));
-  return PLFEM_OK;
-}
-}  // namespace
-
-namespace {
-// A field call's work buffer: the result (`result` doubles), then, 256-byte aligned, `partial` doubles of partial sums
-struct WorkLayout { size_t off_partial, total; };   // bytes
-WorkLayout work_layout(size_t result, size_t partial) {
-  const size_t off = align256(result * sizeof(double));
-  return {off, off + partial * sizeof(double)};
-}
-WorkLayout overlap_layout(int ka, int kb) {
-  return work_layout((size_t)ka * kb, (size_t)overlap_chunks(ka) * overlap_chunks(kb) * OVL_BLOCKS * OC * OC);
-}
-}  // namespace
 
 extern "C" int plfem_overlap_work_bytes(int32_t ka, int32_t kb, int64_t* bytes) {
   if (!bytes || ka < 0 || kb < 0) return PLFEM_EINVAL;
@@ -1704,28 +1762,22 @@ extern "C" int plfem_field_overlap(plfem_locator* La, const double* modes_a_dev,
                                    const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
                                    void* work_dev, int64_t work_bytes, double* out_host) try {
   if (!La) return PLFEM_EINVAL;
-  if (!Lb || La->device != Lb->device) { La->err = "plfem_field_overlap: the two locators must be on one device"; return PLFEM_EINVAL; }
-  if (ncomp < 1 || ncomp > 2 || ka < 0 || kb < 0) { La->err = "plfem_field_overlap: bad ncomp / ka / kb"; return PLFEM_EINVAL; }
+  FieldCall call{La, "plfem_field_overlap"};
+  TRY(call.pair(Lb));
+  if (ncomp < 1 || ncomp > 2 || ka < 0 || kb < 0) return call.reject("bad ncomp / ka / kb");
   if (ka == 0 || kb == 0) return PLFEM_OK;
-  if (!modes_a_dev || !modes_b_dev || !work_dev || !out_host) { La->err = "plfem_field_overlap: null array"; return PLFEM_EINVAL; }
-  if (ncore > MAX_CORES || (ncore > 0 && !cores_host)) { La->err = "plfem_field_overlap: at most 64 cores"; return PLFEM_EINVAL; }
-  if ((indexed_a && La->nsolve == 0) || (indexed_b && Lb->nsolve == 0)) {
-    La->err = "plfem_field_overlap: the analysis has no interior DOFs";
-    return PLFEM_EINVAL;
-  }
+  if (!modes_a_dev || !modes_b_dev || !work_dev || !out_host) return call.reject("null array");
+  if (!ncore_ok(ncore, true) || (ncore > 0 && !cores_host)) return call.reject("at most 64 cores");
   const WorkLayout lay = overlap_layout(ka, kb);
-  TRY(check_work(La, "plfem_field_overlap", "plfem_overlap_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
-  HIP_TRY(La, hipSetDevice(La->device));
+  TRY(call.enter(indexed_a, "plfem_overlap_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial, indexed_b));
   const int nca = overlap_chunks(ka), ncb = overlap_chunks(kb);
   const int64_t ntiles = ((int64_t)6 * Lb->ne + OT - 1) / OT;
   const int nblk = (int)std::min<int64_t>(OVL_BLOCKS, ntiles);
-  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
-  hipLaunchKernelGGL(k_field_overlap, dim3(nblk, nca * ncb), dim3(256), 0, La->stream, loc_args(La, indexed_a != 0),
-                     loc_args(Lb, indexed_b != 0), (int)ncomp, (int)ka, (int64_t)(indexed_a ? La->nsolve : La->N), modes_a_dev,
-                     (int)kb, (int64_t)(indexed_b ? Lb->nsolve : Lb->N), modes_b_dev, pack_cores(cores_host, ncore),
-                     ncore < 0 ? -1 : (int)ncore, 1.0 / eps_core, 1.0 / eps_clad, ncb, partial);
+  hipLaunchKernelGGL(k_field_overlap, dim3(nblk, nca * ncb), dim3(256), 0, La->stream, call.loc, call.loc_b, (int)ncomp, (int)ka,
+                     call.nrows, modes_a_dev, (int)kb, call.nrows_b, modes_b_dev, pack_cores(cores_host, ncore),
+                     ncore < 0 ? -1 : (int)ncore, 1.0 / eps_core, 1.0 / eps_clad, ncb, call.partial);
   TRY(check_launch(La, "k_field_overlap"));
-  return reduce_to_host(La, dim3(nca * ncb), (int)ka, (int)kb, nblk, ncb, partial, O, out_host);
+  return reduce_to_host(La, dim3(nca * ncb), (int)ka, (int)kb, nblk, ncb, call.partial, call.O, out_host);
 } catch (...) { return host_failure(La); }
 
 namespace {
@@ -1782,28 +1834,18 @@ extern "C" int plfem_field_overlap_posed(plfem_locator* La, const double* modes_
                                          int32_t nposes, const double* poses_host, void* work_dev, int64_t work_bytes,
                                          double* out_host) try {
   if (!La) return PLFEM_EINVAL;
-  if (!Lb || La->device != Lb->device) { La->err = "plfem_field_overlap_posed: the two locators must be on one device"; return PLFEM_EINVAL; }
-  if (ncomp < 1 || ncomp > 2) { La->err = "plfem_field_overlap_posed: ncomp must be 1 or 2"; return PLFEM_EINVAL; }
-  if (const char* bad = posed_sizes(ka, kb, nposes)) { La->err = std::string("plfem_field_overlap_posed: ") + bad; return PLFEM_EINVAL; }
-  if (!modes_a_dev || !modes_b_dev || !poses_host || !work_dev || !out_host) {
-    La->err = "plfem_field_overlap_posed: null array";
-    return PLFEM_EINVAL;
-  }
-  if (ncore > MAX_CORES || (ncore > 0 && !cores_host)) { La->err = "plfem_field_overlap_posed: at most 64 cores"; return PLFEM_EINVAL; }
-  if ((indexed_a && La->nsolve == 0) || (indexed_b && Lb->nsolve == 0)) {
-    La->err = "plfem_field_overlap_posed: the analysis has no interior DOFs";
-    return PLFEM_EINVAL;
-  }
-  if (!poses_ok(poses_host, nposes)) {
-    La->err = "plfem_field_overlap_posed: every pose (tx, ty, c, s, m) must be finite with m > 0 and |c^2 + s^2 - 1| <= 1e-12";
-    return PLFEM_EINVAL;
-  }
+  FieldCall call{La, "plfem_field_overlap_posed"};
+  TRY(call.pair(Lb));
+  if (ncomp < 1 || ncomp > 2) return call.reject("ncomp must be 1 or 2");
+  if (const char* bad = posed_sizes(ka, kb, nposes)) return call.reject(bad);
+  if (!modes_a_dev || !modes_b_dev || !poses_host || !work_dev || !out_host) return call.reject("null array");
+  if (!ncore_ok(ncore, true) || (ncore > 0 && !cores_host)) return call.reject("at most 64 cores");
+  TRY(call.modes(indexed_a, indexed_b));
+  if (!poses_ok(poses_host, nposes))
+    return call.reject("every pose (tx, ty, c, s, m) must be finite with m > 0 and |c^2 + s^2 - 1| <= 1e-12");
   const PosedPlan plan = posed_plan(Lb->ne, ka, kb, nposes);
-  TRY(check_work(La, "plfem_field_overlap_posed", "plfem_overlap_posed_work_bytes", work_dev, work_bytes, (int64_t)plan.total));
-  HIP_TRY(La, hipSetDevice(La->device));
-  char* base = (char*)work_dev;
-  double *O = (double*)base, *partial = (double*)(base + plan.off_partial), *poses = (double*)(base + plan.off_poses);
-  const LocArgs la = loc_args(La, indexed_a != 0), lb = loc_args(Lb, indexed_b != 0);
+  TRY(call.work("plfem_overlap_posed_work_bytes", work_dev, work_bytes, plan.total, plan.off_partial));
+  double* poses = (double*)((char*)work_dev + plan.off_poses);
   const CoreTable ct = pack_cores(cores_host, ncore);
   const int npair = plan.nca * plan.ncb;
   // the batches follow each other on one stream: a batch's pose rows, partials and results are read before the next
@@ -1812,76 +1854,67 @@ extern "C" int plfem_field_overlap_posed(plfem_locator* La, const double* modes_
     const int nb = std::min(plan.batch, nposes - p0);
     HIP_TRY(La, hipMemcpyAsync(poses, poses_host + (size_t)POSE_DOUBLES * p0, sizeof(double) * POSE_DOUBLES * nb,
                                hipMemcpyHostToDevice, La->stream));
-    hipLaunchKernelGGL(k_field_overlap_posed, dim3(plan.slices, npair, nb), dim3(256), 0, La->stream, la, lb, (int)ncomp, (int)ka,
-                       (int64_t)(indexed_a ? La->nsolve : La->N), modes_a_dev, (int)kb, (int64_t)(indexed_b ? Lb->nsolve : Lb->N),
-                       modes_b_dev, ct, ncore < 0 ? -1 : (int)ncore, 1.0 / eps_core, 1.0 / eps_clad, plan.ncb, poses, partial);
+    hipLaunchKernelGGL(k_field_overlap_posed, dim3(plan.slices, npair, nb), dim3(256), 0, La->stream, call.loc, call.loc_b,
+                       (int)ncomp, (int)ka, call.nrows, modes_a_dev, (int)kb, call.nrows_b, modes_b_dev, ct,
+                       ncore < 0 ? -1 : (int)ncore, 1.0 / eps_core, 1.0 / eps_clad, plan.ncb, poses, call.partial);
     TRY(check_launch(La, "k_field_overlap_posed"));
     hipLaunchKernelGGL(k_overlap_reduce, dim3(npair, nb, OC * OC / 256), dim3(256), 0, La->stream, (int)ka, (int)kb, plan.slices,
-                       plan.ncb, partial, O);
+                       plan.ncb, call.partial, call.O);
     TRY(check_launch(La, "k_overlap_reduce"));
-    HIP_TRY(La, hipMemcpyAsync(out_host + (size_t)p0 * ka * kb, O, sizeof(double) * nb * ka * kb, hipMemcpyDeviceToHost, La->stream));
+    HIP_TRY(La, hipMemcpyAsync(out_host + (size_t)p0 * ka * kb, call.O, sizeof(double) * nb * ka * kb, hipMemcpyDeviceToHost,
+                               La->stream));
   }
   HIP_TRY(La, hipStreamSynchronize(La->stream));
   return PLFEM_OK;
 } catch (...) { return host_failure(La); }
 
 namespace {
+// The Gram calls on the whole mesh (plfem_mode_grams, plfem_profile_grams, plfem_moment_grams) share one grid and one work
+// buffer: `nout` matrices [k][k], then per matrix and chunk pair GRAM_BLOCKS partial blocks
 int gram_outputs(int ncomp) { return ncomp == 2 ? 5 : 3; }
-WorkLayout gram_layout(int ncomp, int k) {
-  const size_t nout = gram_outputs(ncomp), nc = overlap_chunks(k);
-  return work_layout(nout * k * k, nout * nc * nc * GRAM_BLOCKS * OC * OC);
-}
-// plfem_profile_grams: the same grid, 4 or 3 outputs
 int profile_gram_outputs(int ncomp) { return ncomp == 2 ? 4 : 3; }
-WorkLayout profile_gram_layout(int ncomp, int k) {
-  const size_t nout = profile_gram_outputs(ncomp), nc = overlap_chunks(k);
-  return work_layout(nout * k * k, nout * nc * nc * GRAM_BLOCKS * OC * OC);
-}
-// plfem_moment_grams: the same grid, 7 or 11 outputs
 int moment_gram_outputs(int ncomp) { return ncomp == 2 ? 11 : 7; }
-WorkLayout moment_gram_layout(int ncomp, int k) {
-  const size_t nout = moment_gram_outputs(ncomp), nc = overlap_chunks(k);
-  return work_layout(nout * k * k, nout * nc * nc * GRAM_BLOCKS * OC * OC);
+WorkLayout gram_layout(int nout, int k) {
+  const size_t no = nout, nc = overlap_chunks(k);
+  return work_layout(no * k * k, no * nc * nc * GRAM_BLOCKS * OC * OC);
+}
+// blocks per chunk pair: a function of the mesh alone, so the bits of an entry do not change with the number of modes
+int gram_blocks(int ne) { return (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ((int64_t)6 * ne + GT - 1) / GT)); }
+// the partial blocks (`nblk` per chunk pair) summed into `nmat` matrices [k][k], and those to the host
+int grams_to_host(const FieldCall& call, int nmat, int k, int nblk, double* out_host) {
+  const int nc = overlap_chunks(k);
+  return reduce_to_host(call.L, dim3(nc * nc, nmat, OC * OC / 256), k, k, nblk, nc, call.partial, call.O, out_host);
 }
 }  // namespace
 
 extern "C" int plfem_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
-  if (!bytes || ncomp < 1 || ncomp > 2 || k <= 0) return PLFEM_EINVAL;
-  *bytes = (int64_t)gram_layout(ncomp, k).total;
+  if (!bytes || !modes_ok(ncomp, k)) return PLFEM_EINVAL;
+  *bytes = (int64_t)gram_layout(gram_outputs(ncomp), k).total;
   return PLFEM_OK;
 }
 
 extern "C" int plfem_mode_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
                                 const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k <= 0) { L->err = "plfem_mode_grams: ncomp must be 1 or 2 and k > 0"; return PLFEM_EINVAL; }
-  if (ncore < 0 || ncore > MAX_CORES) { L->err = "plfem_mode_grams: ncore must be in [0, 64]"; return PLFEM_EINVAL; }
-  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host)) {
-    L->err = "plfem_mode_grams: null array";
-    return PLFEM_EINVAL;
-  }
-  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
-  const WorkLayout lay = gram_layout(ncomp, k);
-  TRY(check_work(L, "plfem_mode_grams", "plfem_gram_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
-  HIP_TRY(L, hipSetDevice(L->device));
+  FieldCall call{L, "plfem_mode_grams"};
+  if (!modes_ok(ncomp, k)) return call.reject("ncomp must be 1 or 2 and k > 0");
+  if (!ncore_ok(ncore, false)) return call.reject("ncore must be in [0, 64]");
+  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host)) return call.reject("null array");
+  const WorkLayout lay = gram_layout(gram_outputs(ncomp), k);
+  TRY(call.enter(indexed, "plfem_gram_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial));
   const CoreTable ct = pack_cores(cores_host, ncore);
-  const int nout = gram_outputs(ncomp), nc = overlap_chunks(k);
-  const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
-  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ntiles));
-  const int64_t nrows = indexed ? L->nsolve : L->N;
-  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
-  const dim3 grid(nblk, nc * nc);
+  const int nc = overlap_chunks(k), nblk = gram_blocks(L->ne);
   with_constant<2, 1>(ncomp, [&](auto nco) {
-    hipLaunchKernelGGL(k_mode_grams<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows,
-                       modes_dev, ct, (int)ncore, nc, partial);
+    hipLaunchKernelGGL(k_mode_grams<decltype(nco)::value>, dim3(nblk, nc * nc), dim3(256), 0, L->stream, call.loc, (int)k,
+                       call.nrows, modes_dev, ct, (int)ncore, nc, call.partial);
   });
   TRY(check_launch(L, "k_mode_grams"));
-  return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
+  return grams_to_host(call, gram_outputs(ncomp), k, nblk, out_host);
 } catch (...) { return host_failure(L); }
 
 extern "C" int plfem_profile_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
-  if (!bytes || ncomp < 1 || ncomp > 2 || k <= 0) return PLFEM_EINVAL;
-  *bytes = (int64_t)profile_gram_layout(ncomp, k).total;
+  if (!bytes || !modes_ok(ncomp, k)) return PLFEM_EINVAL;
+  *bytes = (int64_t)gram_layout(profile_gram_outputs(ncomp), k).total;
   return PLFEM_OK;
 }
 
@@ -1889,35 +1922,24 @@ extern "C" int plfem_profile_grams(plfem_locator* L, int32_t ncomp, int32_t k, c
                                    const double* layers_host, int32_t nlayer, double eps_bg, void* work_dev, int64_t work_bytes,
                                    double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k <= 0) { L->err = "plfem_profile_grams: ncomp must be 1 or 2 and k > 0"; return PLFEM_EINVAL; }
-  if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) {
-    L->err = std::string("plfem_profile_grams: ") + bad;
-    return PLFEM_EINVAL;
-  }
-  if (!modes_dev || !work_dev || !out_host) { L->err = "plfem_profile_grams: null array"; return PLFEM_EINVAL; }
-  if (indexed && L->nsolve == 0) { L->err = "plfem_profile_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
-  const WorkLayout lay = profile_gram_layout(ncomp, k);
-  TRY(check_work(L, "plfem_profile_grams", "plfem_profile_gram_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
-  HIP_TRY(L, hipSetDevice(L->device));
+  FieldCall call{L, "plfem_profile_grams"};
+  if (!modes_ok(ncomp, k)) return call.reject("ncomp must be 1 or 2 and k > 0");
+  if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) return call.reject(bad);
+  if (!modes_dev || !work_dev || !out_host) return call.reject("null array");
+  const WorkLayout lay = gram_layout(profile_gram_outputs(ncomp), k);
+  TRY(call.enter(indexed, "plfem_profile_gram_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial));
   // (every call of a locator that reads the table ends with a stream synchronisation: nothing in flight reads the old one)
   if (nlayer > 0)
     HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
-  const int nout = profile_gram_outputs(ncomp), nc = overlap_chunks(k);
-  const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
-  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ntiles));   // (no function of k)
-  const int64_t nrows = indexed ? L->nsolve : L->N;
-  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
-  const dim3 grid(nblk, nc * nc);
+  const int nc = overlap_chunks(k), nblk = gram_blocks(L->ne);
   with_constant<2, 1>(ncomp, [&](auto nco) {
-    if (L->map.set())
-      hipLaunchKernelGGL((k_profile_grams<decltype(nco)::value, EpsMap>), grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0),
-                         (int)k, nrows, modes_dev, L->d_layers, (int)nlayer, eps_bg, nc, partial, eps_map(L->map));
-    else
-      hipLaunchKernelGGL(k_profile_grams<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k,
-                         nrows, modes_dev, L->d_layers, (int)nlayer, eps_bg, nc, partial);
+    with_map(L, [&](auto... map) {
+      hipLaunchKernelGGL((k_profile_grams<decltype(nco)::value, decltype(map)...>), dim3(nblk, nc * nc), dim3(256), 0, L->stream,
+                         call.loc, (int)k, call.nrows, modes_dev, L->d_layers, (int)nlayer, eps_bg, nc, call.partial, map...);
+    });
   });
   TRY(check_launch(L, "k_profile_grams"));
-  return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
+  return grams_to_host(call, profile_gram_outputs(ncomp), k, nblk, out_host);
 } catch (...) { return host_failure(L); }
 
 namespace {
@@ -1933,7 +1955,7 @@ IndicatorLayout indicator_layout(int ne, int k) {
 }  // namespace
 
 extern "C" int plfem_indicator_work_bytes(const plfem_locator* L, int32_t ncomp, int32_t k, int64_t* bytes) {
-  if (!L || !bytes || ncomp < 1 || ncomp > 2 || k <= 0) return PLFEM_EINVAL;
+  if (!L || !bytes || !modes_ok(ncomp, k)) return PLFEM_EINVAL;
   *bytes = (int64_t)indicator_layout(L->ne, k).total;
   return PLFEM_OK;
 }
@@ -1943,32 +1965,23 @@ extern "C" int plfem_mode_indicators(plfem_locator* L, int32_t ncomp, int32_t k,
                                      int32_t ncore, double eps_core, double eps_clad, const double* layers_host,
                                      int32_t nlayer, double eps_bg, void* work_dev, int64_t work_bytes, double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k <= 0) { L->err = "plfem_mode_indicators: ncomp must be 1 or 2 and k > 0"; return PLFEM_EINVAL; }
-  if (!modes_dev || !lambda_host || !work_dev || !out_host) { L->err = "plfem_mode_indicators: null array"; return PLFEM_EINVAL; }
-  if (!std::isfinite(k0) || !std::isfinite(alpha_p)) { L->err = "plfem_mode_indicators: k0 and alpha_p must be finite"; return PLFEM_EINVAL; }
+  FieldCall call{L, "plfem_mode_indicators"};
+  if (!modes_ok(ncomp, k)) return call.reject("ncomp must be 1 or 2 and k > 0");
+  if (!modes_dev || !lambda_host || !work_dev || !out_host) return call.reject("null array");
+  if (!std::isfinite(k0) || !std::isfinite(alpha_p)) return call.reject("k0 and alpha_p must be finite");
   for (int m = 0; m < k; ++m)
-    if (!std::isfinite(lambda_host[m])) { L->err = "plfem_mode_indicators: every eigenvalue must be finite"; return PLFEM_EINVAL; }
-  if (nlayer != 0 || L->map.set()) {              // the profile path: layers, a map (plfem_locator_set_index_map) or both
-    if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) {
-      L->err = std::string("plfem_mode_indicators: ") + bad;
-      return PLFEM_EINVAL;
-    }
+    if (!std::isfinite(lambda_host[m])) return call.reject("every eigenvalue must be finite");
+  const bool profile = nlayer != 0 || L->map.set();   // the profile path: layers, a map (plfem_locator_set_index_map) or both
+  if (profile) {
+    if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) return call.reject(bad);
   } else {
-    if (ncore < 0 || ncore > MAX_CORES || (ncore > 0 && !cores_host)) {
-      L->err = "plfem_mode_indicators: ncore must be in [0, 64], with a core table";
-      return PLFEM_EINVAL;
-    }
-    if (!std::isfinite(eps_core) || !std::isfinite(eps_clad) || !(eps_core > 0.0) || !(eps_clad > 0.0)) {
-      L->err = "plfem_mode_indicators: eps_core and eps_clad must be finite and positive";
-      return PLFEM_EINVAL;
-    }
+    if (!ncore_ok(ncore, false) || (ncore > 0 && !cores_host)) return call.reject("ncore must be in [0, 64], with a core table");
+    if (!std::isfinite(eps_core) || !std::isfinite(eps_clad) || !(eps_core > 0.0) || !(eps_clad > 0.0))
+      return call.reject("eps_core and eps_clad must be finite and positive");
   }
-  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_indicators: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
   const IndicatorLayout lay = indicator_layout(L->ne, k);
-  TRY(check_work(L, "plfem_mode_indicators", "plfem_indicator_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
+  TRY(call.enter(indexed, "plfem_indicator_work_bytes", work_dev, work_bytes, lay.total, 0));
   ensure_elem_nbr(*L->S);
-  HIP_TRY(L, hipSetDevice(L->device));
-  double* O = (double*)work_dev;
   int32_t* d_nbr = (int32_t*)((char*)work_dev + lay.off_nbr);
   double* d_lam = (double*)((char*)work_dev + lay.off_lam);
   // (the call ends with a stream synchronisation: the host arrays outlive the copies, and nothing in flight reads the
@@ -1977,24 +1990,17 @@ extern "C" int plfem_mode_indicators(plfem_locator* L, int32_t ncomp, int32_t k,
   HIP_TRY(L, hipMemcpyAsync(d_lam, lambda_host, sizeof(double) * k, hipMemcpyHostToDevice, L->stream));
   if (nlayer > 0)
     HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
-  const bool profile = nlayer > 0 || L->map.set();
-  const CoreTable ct = pack_cores(cores_host, profile ? 0 : ncore);
-  const int64_t nrows = indexed ? L->nsolve : L->N;
-  const dim3 grid((L->ne + IND_E - 1) / IND_E);
+  const int kcore = profile ? 0 : (int)ncore;          // the profile path reads no cores
+  const CoreTable ct = pack_cores(cores_host, kcore);
   with_constant<2, 1>(ncomp, [&](auto nco) {
-    if (L->map.set())
-      hipLaunchKernelGGL((k_mode_indicators<decltype(nco)::value, EpsMap>), grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0),
-                         (int)k, nrows, modes_dev, d_nbr, d_lam, k0 * k0, alpha_p, ct, 0, eps_core, eps_clad, L->d_layers,
-                         (int)nlayer, eps_bg, O, eps_map(L->map));
-    else
-      hipLaunchKernelGGL(k_mode_indicators<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k,
-                         nrows, modes_dev, d_nbr, d_lam, k0 * k0, alpha_p, ct, profile ? 0 : (int)ncore, eps_core, eps_clad,
-                         L->d_layers, (int)nlayer, eps_bg, O);
+    with_map(L, [&](auto... map) {
+      hipLaunchKernelGGL((k_mode_indicators<decltype(nco)::value, decltype(map)...>), dim3((L->ne + IND_E - 1) / IND_E), dim3(256), 0,
+                         L->stream, call.loc, (int)k, call.nrows, modes_dev, d_nbr, d_lam, k0 * k0, alpha_p, ct, kcore, eps_core,
+                         eps_clad, L->d_layers, (int)nlayer, eps_bg, call.O, map...);
+    });
   });
   TRY(check_launch(L, "k_mode_indicators"));
-  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * (size_t)k * L->ne, hipMemcpyDeviceToHost, L->stream));
-  HIP_TRY(L, hipStreamSynchronize(L->stream));
-  return PLFEM_OK;
+  return result_to_host(L, call.O, (size_t)k * L->ne, out_host);
 } catch (...) { return host_failure(L); }
 
 namespace {
@@ -2039,24 +2045,18 @@ extern "C" int plfem_core_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
                                 const double* cores_host, int32_t ncore, void* work_dev, int64_t work_bytes, double* out_host,
                                 int64_t* count_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (const char* bad = core_gram_args(ncomp, k, ncore)) { L->err = std::string("plfem_core_grams: ") + bad; return PLFEM_EINVAL; }
-  if (!modes_dev || !cores_host || !work_dev || !out_host || !count_host) {
-    L->err = "plfem_core_grams: null array";
-    return PLFEM_EINVAL;
-  }
-  if (indexed && L->nsolve == 0) { L->err = "plfem_core_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  FieldCall call{L, "plfem_core_grams"};
+  if (const char* bad = core_gram_args(ncomp, k, ncore)) return call.reject(bad);
+  if (!modes_dev || !cores_host || !work_dev || !out_host || !count_host) return call.reject("null array");
   const CoreGramLayout lay = core_gram_layout(L->ne, ncomp, k, ncore);
-  TRY(check_work(L, "plfem_core_grams", "plfem_core_gram_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
-  HIP_TRY(L, hipSetDevice(L->device));
+  TRY(call.enter(indexed, "plfem_core_gram_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial));
   const CoreTable ct = pack_cores(cores_host, ncore);
-  const int nout = core_gram_outputs(ncomp), nc = overlap_chunks(k);
-  const int64_t nq = (int64_t)6 * L->ne, nrows = indexed ? L->nsolve : L->N;
+  const int nc = overlap_chunks(k);
+  const int64_t nq = (int64_t)6 * L->ne;
   char* base = (char*)work_dev;
-  double *O = (double*)base, *partial = (double*)(base + lay.off_partial);
   int32_t *owner = (int32_t*)(base + lay.off_owner), *list = (int32_t*)(base + lay.off_list), *meta = (int32_t*)(base + lay.off_meta);
-  const LocArgs la = loc_args(L, indexed != 0);
   if (nq > 0) {
-    hipLaunchKernelGGL(k_core_owner, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, L->stream, la, ct, (int)ncore, owner);
+    hipLaunchKernelGGL(k_core_owner, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, L->stream, call.loc, ct, (int)ncore, owner);
     TRY(check_launch(L, "k_core_owner"));
   }
   hipLaunchKernelGGL(k_core_count, dim3(ncore), dim3(256), 0, L->stream, nq, owner, meta);
@@ -2064,20 +2064,20 @@ extern "C" int plfem_core_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
   hipLaunchKernelGGL(k_core_fill, dim3(ncore), dim3(256), 0, L->stream, nq, owner, meta, list);
   TRY(check_launch(L, "k_core_fill"));
   with_constant<2, 1>(ncomp, [&](auto nco) {
-    hipLaunchKernelGGL(k_core_grams<decltype(nco)::value>, dim3(lay.slices, nc * nc, ncore), dim3(256), 0, L->stream, la, (int)k,
-                       nrows, modes_dev, meta, list, nc, partial);
+    hipLaunchKernelGGL(k_core_grams<decltype(nco)::value>, dim3(lay.slices, nc * nc, ncore), dim3(256), 0, L->stream, call.loc,
+                       (int)k, call.nrows, modes_dev, meta, list, nc, call.partial);
   });
   TRY(check_launch(L, "k_core_grams"));
   int32_t counts[MAX_CORES];
   HIP_TRY(L, hipMemcpyAsync(counts, meta, sizeof(int32_t) * ncore, hipMemcpyDeviceToHost, L->stream));
-  TRY(reduce_to_host(L, dim3(nc * nc, ncore * nout, OC * OC / 256), (int)k, (int)k, lay.slices, nc, partial, O, out_host));
+  TRY(grams_to_host(call, ncore * core_gram_outputs(ncomp), k, lay.slices, out_host));
   for (int c = 0; c < ncore; ++c) count_host[c] = counts[c];   // (the stream is synchronised)
   return PLFEM_OK;
 } catch (...) { return host_failure(L); }
 
 extern "C" int plfem_moment_gram_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
-  if (!bytes || ncomp < 1 || ncomp > 2 || k < 1) return PLFEM_EINVAL;
-  *bytes = (int64_t)moment_gram_layout(ncomp, k).total;
+  if (!bytes || !modes_ok(ncomp, k)) return PLFEM_EINVAL;
+  *bytes = (int64_t)gram_layout(moment_gram_outputs(ncomp), k).total;
   return PLFEM_OK;
 }
 
@@ -2085,40 +2085,28 @@ extern "C" int plfem_moment_grams(plfem_locator* L, int32_t ncomp, int32_t k, co
                                   const double* cores_host, int32_t ncore, const double* origin_host, void* work_dev,
                                   int64_t work_bytes, double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k < 1) { L->err = "plfem_moment_grams: ncomp must be 1 or 2 and k >= 1"; return PLFEM_EINVAL; }
-  if (ncore < 0 || ncore > MAX_CORES) { L->err = "plfem_moment_grams: ncore must be in [0, 64]"; return PLFEM_EINVAL; }
-  if (!modes_dev || !work_dev || !out_host || !origin_host || (ncore > 0 && !cores_host)) {
-    L->err = "plfem_moment_grams: null array";
-    return PLFEM_EINVAL;
-  }
-  if (!std::isfinite(origin_host[0]) || !std::isfinite(origin_host[1])) {
-    L->err = "plfem_moment_grams: the origin must be finite";
-    return PLFEM_EINVAL;
-  }
-  if (indexed && L->nsolve == 0) { L->err = "plfem_moment_grams: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
-  const WorkLayout lay = moment_gram_layout(ncomp, k);
-  TRY(check_work(L, "plfem_moment_grams", "plfem_moment_gram_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
-  HIP_TRY(L, hipSetDevice(L->device));
+  FieldCall call{L, "plfem_moment_grams"};
+  if (!modes_ok(ncomp, k)) return call.reject("ncomp must be 1 or 2 and k >= 1");
+  if (!ncore_ok(ncore, false)) return call.reject("ncore must be in [0, 64]");
+  if (!modes_dev || !work_dev || !out_host || !origin_host || (ncore > 0 && !cores_host)) return call.reject("null array");
+  if (!std::isfinite(origin_host[0]) || !std::isfinite(origin_host[1])) return call.reject("the origin must be finite");
+  const WorkLayout lay = gram_layout(moment_gram_outputs(ncomp), k);
+  TRY(call.enter(indexed, "plfem_moment_gram_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial));
   const CoreTable ct = pack_cores(cores_host, ncore);
-  const int nout = moment_gram_outputs(ncomp), nc = overlap_chunks(k);
-  const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
-  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(GRAM_BLOCKS, ntiles));   // (no function of k)
-  const int64_t nrows = indexed ? L->nsolve : L->N;
-  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
+  const int nc = overlap_chunks(k), nblk = gram_blocks(L->ne);
   const dim3 grid(nblk, nc * nc);
-  const LocArgs la = loc_args(L, indexed != 0);
   const double ox = origin_host[0], oy = origin_host[1];
   if (ncomp == 2) {                           // a second instance for the four outputs made of K
-    hipLaunchKernelGGL((k_moment_grams<2, true>), grid, dim3(256), 0, L->stream, la, (int)k, nrows, modes_dev, ct,
-                       (int)ncore, ox, oy, nc, partial);
+    hipLaunchKernelGGL((k_moment_grams<2, true>), grid, dim3(256), 0, L->stream, call.loc, (int)k, call.nrows, modes_dev, ct,
+                       (int)ncore, ox, oy, nc, call.partial);
     TRY(check_launch(L, "k_moment_grams"));
   }
   with_constant<2, 1>(ncomp, [&](auto nco) {
-    hipLaunchKernelGGL((k_moment_grams<decltype(nco)::value, false>), grid, dim3(256), 0, L->stream, la, (int)k, nrows, modes_dev,
-                       ct, (int)ncore, ox, oy, nc, partial);
+    hipLaunchKernelGGL((k_moment_grams<decltype(nco)::value, false>), grid, dim3(256), 0, L->stream, call.loc, (int)k, call.nrows,
+                       modes_dev, ct, (int)ncore, ox, oy, nc, call.partial);
   });
   TRY(check_launch(L, "k_moment_grams"));
-  return reduce_to_host(L, dim3(nc * nc, nout, OC * OC / 256), (int)k, (int)k, nblk, nc, partial, O, out_host);
+  return grams_to_host(call, moment_gram_outputs(ncomp), k, nblk, out_host);
 } catch (...) { return host_failure(L); }
 
 namespace {
@@ -2135,7 +2123,7 @@ WorkLayout quartic_layout(int k) {
 }  // namespace
 
 extern "C" int plfem_quartic_work_bytes(int32_t ncomp, int32_t k, int64_t* bytes) {
-  if (!bytes || ncomp < 1 || ncomp > 2 || k < 1 || k > QKMAX) return PLFEM_EINVAL;
+  if (!bytes || !modes_ok(ncomp, k, QKMAX)) return PLFEM_EINVAL;
   *bytes = (int64_t)quartic_layout(k).total;
   return PLFEM_OK;
 }
@@ -2144,36 +2132,23 @@ extern "C" int plfem_mode_quartic(plfem_locator* L, int32_t ncomp, int32_t k, co
                                   const double* cores_host, int32_t ncore, double w_core, double w_clad, void* work_dev,
                                   int64_t work_bytes, double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (ncomp < 1 || ncomp > 2 || k < 1 || k > QKMAX) {
-    L->err = "plfem_mode_quartic: ncomp must be 1 or 2 and 1 <= k <= 64";
-    return PLFEM_EINVAL;
-  }
-  if (ncore > MAX_CORES) { L->err = "plfem_mode_quartic: at most 64 cores"; return PLFEM_EINVAL; }
-  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host)) {
-    L->err = "plfem_mode_quartic: null array";
-    return PLFEM_EINVAL;
-  }
-  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_quartic: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  FieldCall call{L, "plfem_mode_quartic"};
+  if (!modes_ok(ncomp, k, QKMAX)) return call.reject("ncomp must be 1 or 2 and 1 <= k <= 64");
+  if (!ncore_ok(ncore, true)) return call.reject("at most 64 cores");
+  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host)) return call.reject("null array");
   const WorkLayout lay = quartic_layout(k);
-  TRY(check_work(L, "plfem_mode_quartic", "plfem_quartic_work_bytes", work_dev, work_bytes, (int64_t)lay.total));
-  HIP_TRY(L, hipSetDevice(L->device));
+  TRY(call.enter(indexed, "plfem_quartic_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial));
   const CoreTable ct = pack_cores(cores_host, ncore);
   const int np = quartic_pairs(k), nt = quartic_tiles(k), ntp = quartic_tile_pairs(k);
-  const int nblk = std::max(1, std::min(quartic_slices(k), L->ne));
-  const int64_t nrows = indexed ? L->nsolve : L->N;
-  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + lay.off_partial);
-  const dim3 grid(nblk, ntp);
-  const int nc = ncore < 0 ? -1 : (int)ncore;
+  const int nblk = element_slices(quartic_slices(k), L->ne);
   with_constant<2, 1>(ncomp, [&](auto nco) {
-    hipLaunchKernelGGL(k_mode_quartic<decltype(nco)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)k, nrows,
-                       modes_dev, ct, nc, w_core, w_clad, np, nt, partial);
+    hipLaunchKernelGGL(k_mode_quartic<decltype(nco)::value>, dim3(nblk, ntp), dim3(256), 0, L->stream, call.loc, (int)k, call.nrows,
+                       modes_dev, ct, ncore < 0 ? -1 : (int)ncore, w_core, w_clad, np, nt, call.partial);
   });
   TRY(check_launch(L, "k_mode_quartic"));
-  hipLaunchKernelGGL(k_quartic_reduce, dim3(ntp, 1, QP * QP / 256), dim3(256), 0, L->stream, np, nt, nblk, partial, O);
+  hipLaunchKernelGGL(k_quartic_reduce, dim3(ntp, 1, QP * QP / 256), dim3(256), 0, L->stream, np, nt, nblk, call.partial, call.O);
   TRY(check_launch(L, "k_quartic_reduce"));
-  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * np * np, hipMemcpyDeviceToHost, L->stream));
-  HIP_TRY(L, hipStreamSynchronize(L->stream));
-  return PLFEM_OK;
+  return result_to_host(L, call.O, (size_t)np * np, out_host);
 } catch (...) { return host_failure(L); }
 
 namespace {
@@ -2201,7 +2176,7 @@ ProjectPlan project_plan(int ncomp, int k, int la, int lb) {
   return p;
 }
 bool project_sizes_ok(int ncomp, int k, int la, int lb) {
-  return ncomp >= 1 && ncomp <= 2 && k >= 1 && k <= PJ_KMAX && la >= 1 && la <= PJ_LMAX && lb >= 1 && lb <= PJ_LMAX;
+  return modes_ok(ncomp, k, PJ_KMAX) && la >= 1 && la <= PJ_LMAX && lb >= 1 && lb <= PJ_LMAX;
 }
 // every (c, s, kappa) finite and s >= 0
 bool factors_ok(const double* fac, int n) {
@@ -2223,42 +2198,27 @@ extern "C" int plfem_mode_project(plfem_locator* L, int32_t ncomp, int32_t k, co
                                   int32_t la, const double* xfac_host, int32_t lb, const double* yfac_host, void* work_dev,
                                   int64_t work_bytes, double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (!project_sizes_ok(ncomp, k, la, lb)) {
-    L->err = "plfem_mode_project: ncomp must be 1 or 2, 1 <= k <= 64 and 1 <= la, lb <= 4096";
-    return PLFEM_EINVAL;
-  }
-  if (!modes_dev || !xfac_host || !yfac_host || !work_dev || !out_host) {
-    L->err = "plfem_mode_project: null array";
-    return PLFEM_EINVAL;
-  }
-  if (!factors_ok(xfac_host, la) || !factors_ok(yfac_host, lb)) {
-    L->err = "plfem_mode_project: every factor (c, s, kappa) must be finite with s >= 0";
-    return PLFEM_EINVAL;
-  }
-  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_project: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+  FieldCall call{L, "plfem_mode_project"};
+  if (!project_sizes_ok(ncomp, k, la, lb)) return call.reject("ncomp must be 1 or 2, 1 <= k <= 64 and 1 <= la, lb <= 4096");
+  if (!modes_dev || !xfac_host || !yfac_host || !work_dev || !out_host) return call.reject("null array");
+  if (!factors_ok(xfac_host, la) || !factors_ok(yfac_host, lb))
+    return call.reject("every factor (c, s, kappa) must be finite with s >= 0");
   const ProjectPlan plan = project_plan(ncomp, k, la, lb);
-  TRY(check_work(L, "plfem_mode_project", "plfem_project_work_bytes", work_dev, work_bytes, (int64_t)plan.total));
-  HIP_TRY(L, hipSetDevice(L->device));
-  char* base = (char*)work_dev;
-  double *O = (double*)base, *partial = (double*)(base + plan.off_partial);
-  double *xfac = (double*)(base + plan.off_xfac), *yfac = (double*)(base + plan.off_yfac);
+  TRY(call.enter(indexed, "plfem_project_work_bytes", work_dev, work_bytes, plan.total, plan.off_partial));
+  double *xfac = (double*)((char*)work_dev + plan.off_xfac), *yfac = (double*)((char*)work_dev + plan.off_yfac);
   HIP_TRY(L, hipMemcpyAsync(xfac, xfac_host, sizeof(double) * 3 * la, hipMemcpyHostToDevice, L->stream));
   HIP_TRY(L, hipMemcpyAsync(yfac, yfac_host, sizeof(double) * 3 * lb, hipMemcpyHostToDevice, L->stream));
-  const int nblk = std::max(1, std::min(plan.slices, L->ne));
-  const int64_t nrows = indexed ? L->nsolve : L->N;
-  const dim3 grid((unsigned)plan.tiles, nblk);
+  const int nblk = element_slices(plan.slices, L->ne);
   with_constant<2, 4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32>(plan.maxt, [&](auto mt) {
-    hipLaunchKernelGGL(k_mode_project<decltype(mt)::value>, grid, dim3(256), 0, L->stream, loc_args(L, indexed != 0), (int)ncomp,
-                       (int)k, nrows, modes_dev, (int)la, xfac, (int)lb, yfac, plan.ntx, partial);
+    hipLaunchKernelGGL(k_mode_project<decltype(mt)::value>, dim3((unsigned)plan.tiles, nblk), dim3(256), 0, L->stream, call.loc,
+                       (int)ncomp, (int)k, call.nrows, modes_dev, (int)la, xfac, (int)lb, yfac, plan.ntx, call.partial);
   });
   TRY(check_launch(L, "k_mode_project"));
   const int64_t entries = (int64_t)plan.nf * lb * la;
   hipLaunchKernelGGL(k_project_reduce, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, L->stream, plan.nf, (int)la, (int)lb,
-                     plan.ntx, nblk, partial, O);
+                     plan.ntx, nblk, call.partial, call.O);
   TRY(check_launch(L, "k_project_reduce"));
-  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * 2 * entries, hipMemcpyDeviceToHost, L->stream));
-  HIP_TRY(L, hipStreamSynchronize(L->stream));
-  return PLFEM_OK;
+  return result_to_host(L, call.O, (size_t)2 * entries, out_host);
 } catch (...) { return host_failure(L); }
 
 namespace {
@@ -2281,9 +2241,7 @@ SampledPlan sampled_plan(int ncomp, int k, int nfr) {
   p.total = o;
   return p;
 }
-bool sampled_sizes_ok(int ncomp, int k, int nfr) {
-  return ncomp >= 1 && ncomp <= 2 && k >= 1 && k <= PJ_KMAX && nfr >= 1 && nfr <= PS_FRAMES;
-}
+bool sampled_sizes_ok(int ncomp, int k, int nfr) { return modes_ok(ncomp, k, PJ_KMAX) && nfr >= 1 && nfr <= PS_FRAMES; }
 }  // namespace
 
 extern "C" int plfem_project_sampled_work_bytes(int32_t ncomp, int32_t k, int32_t nf, int64_t* bytes) {
@@ -2296,41 +2254,30 @@ extern "C" int plfem_mode_project_sampled(plfem_locator* L, int32_t ncomp, int32
                                           int32_t nx, int32_t ny, double x0, double y0, double dx, double dy, int32_t nf,
                                           const double* frames_dev, void* work_dev, int64_t work_bytes, double* out_host) try {
   if (!L) return PLFEM_EINVAL;
-  if (!sampled_sizes_ok(ncomp, k, nf) || nx < 2 || nx > PS_NMAX || ny < 2 || ny > PS_NMAX) {
-    L->err = "plfem_mode_project_sampled: ncomp must be 1 or 2, 1 <= k <= 64, 2 <= nx, ny <= 8192 and 1 <= nf <= 4096";
-    return PLFEM_EINVAL;
-  }
+  FieldCall call{L, "plfem_mode_project_sampled"};
+  if (!sampled_sizes_ok(ncomp, k, nf) || nx < 2 || nx > PS_NMAX || ny < 2 || ny > PS_NMAX)
+    return call.reject("ncomp must be 1 or 2, 1 <= k <= 64, 2 <= nx, ny <= 8192 and 1 <= nf <= 4096");
   const SampledGrid grid{x0, y0, 1.0 / dx, 1.0 / dy, nx, ny};
   if (!(dx > 0.0) || !(dy > 0.0) || !std::isfinite(dx) || !std::isfinite(dy) || !std::isfinite(x0) || !std::isfinite(y0) ||
-      !std::isfinite(grid.inv_dx) || !std::isfinite(grid.inv_dy)) {
-    L->err = "plfem_mode_project_sampled: x0, y0, dx, dy, 1 / dx and 1 / dy must be finite with dx, dy > 0";
-    return PLFEM_EINVAL;
-  }
-  if (!modes_dev || !frames_dev || !work_dev || !out_host) {
-    L->err = "plfem_mode_project_sampled: null array";
-    return PLFEM_EINVAL;
-  }
-  if (indexed && L->nsolve == 0) { L->err = "plfem_mode_project_sampled: the analysis has no interior DOFs"; return PLFEM_EINVAL; }
+      !std::isfinite(grid.inv_dx) || !std::isfinite(grid.inv_dy))
+    return call.reject("x0, y0, dx, dy, 1 / dx and 1 / dy must be finite with dx, dy > 0");
+  if (!modes_dev || !frames_dev || !work_dev || !out_host) return call.reject("null array");
   const SampledPlan plan = sampled_plan(ncomp, k, nf);
-  TRY(check_work(L, "plfem_mode_project_sampled", "plfem_project_sampled_work_bytes", work_dev, work_bytes, (int64_t)plan.total));
-  HIP_TRY(L, hipSetDevice(L->device));
-  double *O = (double*)work_dev, *partial = (double*)((char*)work_dev + plan.off_partial);
-  const int nblk = std::max(1, std::min(PS_SLICES, L->ne));           // the mesh alone decides: a frame's bits do not depend on nf
-  const int64_t nrows = indexed ? L->nsolve : L->N;
+  TRY(call.enter(indexed, "plfem_project_sampled_work_bytes", work_dev, work_bytes, plan.total, plan.off_partial));
+  const int nblk = element_slices(PS_SLICES, L->ne);                  // the mesh alone decides: a frame's bits do not depend on nf
   for (int t0 = 0; t0 < plan.tiles; t0 += PS_GROUP) {                 // (stream order keeps a group's partial tiles until its reduce)
     const int nt = std::min(PS_GROUP, plan.tiles - t0);
     with_constant<1, 2, 3, 4, 6, 8>(plan.nft, [&](auto nft) {
-      hipLaunchKernelGGL(k_mode_project_sampled<decltype(nft)::value>, dim3(nt, nblk), dim3(256), 0, L->stream,
-                         loc_args(L, indexed != 0), (int)ncomp, (int)k, nrows, modes_dev, grid, (int)nf, t0, frames_dev, partial);
+      hipLaunchKernelGGL(k_mode_project_sampled<decltype(nft)::value>, dim3(nt, nblk), dim3(256), 0, L->stream, call.loc, (int)ncomp,
+                         (int)k, call.nrows, modes_dev, grid, (int)nf, t0, frames_dev, call.partial);
     });
     TRY(check_launch(L, "k_mode_project_sampled"));
     const int c0 = t0 * PS_COLS, c1 = std::min(2 * (int)nf, (t0 + nt) * PS_COLS);
     const int64_t entries = (int64_t)plan.nf * (c1 - c0);
     hipLaunchKernelGGL(k_project_sampled_reduce, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, L->stream, plan.nf, (int)nf,
-                       c0, c1, nblk, partial, O);
+                       c0, c1, nblk, call.partial, call.O);
     TRY(check_launch(L, "k_project_sampled_reduce"));
   }
-  HIP_TRY(L, hipMemcpyAsync(out_host, O, sizeof(double) * 2 * plan.nf * nf, hipMemcpyDeviceToHost, L->stream));
-  HIP_TRY(L, hipStreamSynchronize(L->stream));
-  return PLFEM_OK;
+  return result_to_host(L, call.O, (size_t)2 * plan.nf * nf, out_host);
 } catch (...) { return host_failure(L); }
+

@@ -33,6 +33,7 @@ several elements contain it the smallest element id wins; a point inside none ge
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -48,6 +49,7 @@ PROFILE_GRAM_NAMES = {"vectorial": ("M", "M_w", "K_w", "D"), "scalar": ("M", "M_
 MOMENT_GRAM_NAMES = {"vectorial": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "K_core_X", "K_core_Y", "K_clad_X",
                                    "K_clad_Y", "M_XX", "M_XY", "M_YY"),
                      "scalar": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "M_XX", "M_XY", "M_YY")}
+POSE_MAX_CHUNK_PAIRS = 256         # POSE_MAX_PAIRS of csrc/kernels_fields.hip: pairs of 32-mode chunks per posed call
 PROJECT_TILE = (8, 8)              # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
 PROJECT_MAX_FACTORS = 4096         # PJ_LMAX
 PROJECT_SAMPLED_TILE = 32          # PS_F: frames per workgroup tile of the sampled projection
@@ -236,11 +238,53 @@ class ModeFields:
                                                     ctypes.c_void_p(dst.data_ptr())), "plfem_stage_modes")
         return dst, src
 
+    def _checked(self, modes):
+        """:meth:`_check_records` and the number of modes: ``(kind, vals, beta, k)``; nothing touches the device."""
+        kind, vals, beta = self._check_records(modes)
+        return kind, vals, beta, 0 if kind is None else vals.shape[1]
+
+    def _staged(self, vals):
+        """The modes on the device, the locator created if this is its first use."""
+        self._ensure_locator()
+        return self._stage(vals)[0]
+
+    def _work_bytes(self, sizer: str, *sizes: Dict, loc=None) -> int:
+        """What ``sizer`` asks for, the largest over the ``sizes`` (each the sizer's arguments by name, in order, ``loc``
+        in front of them if it takes a locator); ``ValueError`` when it rejects them."""
+        need, nbytes = ctypes.c_int64(0), 0
+        for sz in sizes:
+            if getattr(self._lib, sizer)(*(() if loc is None else (loc,)), *sz.values(), ctypes.byref(need)) != _native.PLFEM_OK:
+                raise ValueError(f"{sizer} rejected " + ", ".join(f"{nm} = {v}" for nm, v in sz.items()))
+            nbytes = max(nbytes, int(need.value))
+        return nbytes
+
+    def _work_buffer(self, sizer: str, nbytes: int, work=None):
+        """``(buffer, aligned pointer)`` of a work buffer of ``nbytes``: fresh scratch, or the caller's ``work`` (a uint8
+        device tensor of at least ``nbytes + 256`` bytes)."""
+        if work is None:
+            work = _native.device_scratch(nbytes + 256, self.tdev)
+        elif work.numel() < nbytes + 256:
+            raise ValueError(f"work buffer smaller than {sizer} + 256")
+        return work, (work.data_ptr() + 255) & ~255
+
+    def _work_call(self, sizer: str, sizes: Dict, fn: str, args, outs, work=None, loc=None) -> None:
+        """One entry point that takes a work buffer: ``fn(*args, work, work_bytes, *outs)`` with the buffer sized by
+        ``sizer(**sizes)``; ``outs`` are the host arrays it fills."""
+        nbytes = self._work_bytes(sizer, sizes, loc=loc)
+        work, aligned = self._work_buffer(sizer, nbytes, work)
+        self._check(getattr(self._lib, fn)(*args, aligned, nbytes, *(_native._ptr(o) for o in outs)), fn)
+
+    def _mode_call(self, sizer: str, sizes: Dict, fn: str, kind, staged, args, outs, work=None, loc=None) -> None:
+        """:meth:`_work_call` of an entry point whose arguments begin ``(locator, ncomp, k, modes, indexed)``."""
+        ncomp, _, k = staged.shape
+        self._work_call(sizer, sizes, fn, (self._loc, ncomp, k, staged.data_ptr(), 1 if kind == "vectorial" else 0, *args), outs,
+                        work=work, loc=loc)
+
     def sample(self, modes: Sequence[Dict], points, hz: bool = True) -> Dict[str, np.ndarray]:
         """Values of the modes at ``points`` (2, npts): ``{"Hx", "Hy"[, "Hz_im"]}`` (vectorial records; ``Hz_im`` =
         -(dHx/dx + dHy/dy) / beta when ``hz``) or ``{"u"}`` (scalar records), each (k, npts); ``"element"`` (npts,)
         int32, the element each point was found in or -1 (value 0)."""
-        kind, vals, beta = self._check_records(modes)
+        kind, vals, beta, k = self._checked(modes)
         pts = np.asarray(points, dtype=np.float64)
         if pts.ndim != 2 or pts.shape[0] != 2:
             raise ValueError("points must be an array of shape (2, npts)")
@@ -248,7 +292,6 @@ class ModeFields:
             raise ValueError("Hz_im needs a finite, non-zero 'beta' in every vectorial record (or hz=False)")
         import torch
         npts = pts.shape[1]
-        k = 0 if kind is None else vals.shape[1]
         ncomp = 0 if kind is None else vals.shape[0]
         names = {"vectorial": ["Hx", "Hy"] + (["Hz_im"] if hz else []), "scalar": ["u"], None: []}[kind]
         nout = len(names)
@@ -259,8 +302,7 @@ class ModeFields:
         self._ensure_locator()
         staged = beta_d = None
         if k:
-            staged, _src = self._stage(vals)
-            del _src
+            staged = self._staged(vals)
             if kind == "vectorial" and hz:
                 beta_d = torch.from_numpy(beta).to(self.tdev)
         chunk = int(max(1024, min(npts, self.CHUNK_BYTES // (8 * max(1, nout * k) + 20), 1 << 30)))
@@ -308,14 +350,11 @@ class ModeFields:
         alpha_p D - k0^2 (M_core + M_clad)`` and ``V^T B V = sum_r M_r / eps_r`` on the interior DOFs), scalar records
         ``M_core``, ``M_clad``, ``S`` (``V^T A V = S - k0^2 sum_r eps_r M_r``, ``V^T B V = M_core + M_clad``)."""
         reject_profile(geometry, "ModeFields.grams")
-        kind, vals, _ = self._check_records(modes)
+        kind, vals, _, k = self._checked(modes)
         cores = self._cores(geometry)
-        k = 0 if kind is None else vals.shape[1]
         if k == 0:
             return {nm: np.zeros((0, 0)) for nm in GRAM_NAMES.get(kind, ())}
-        self._ensure_locator()
-        staged, _src = self._stage(vals)
-        return self._grams_staged(kind, staged, cores)
+        return self._grams_staged(kind, self._staged(vals), cores)
 
     @staticmethod
     def _cores(geometry) -> np.ndarray:
@@ -331,16 +370,9 @@ class ModeFields:
         """``plfem_mode_grams`` on modes already staged (ncomp, n, k) on the device."""
         names = GRAM_NAMES[kind]
         ncomp, _, k = staged.shape
-        need = ctypes.c_int64(0)
-        if self._lib.plfem_gram_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
-            raise ValueError(f"plfem_gram_work_bytes rejected ncomp = {ncomp}, k = {k}")
-        work = _native.device_scratch(int(need.value) + 256, self.tdev)
-        aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((len(names), k, k), dtype=np.float64)
-        self._check(self._lib.plfem_mode_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
-                                               1 if kind == "vectorial" else 0, cores.ctypes.data_as(ctypes.c_void_p),
-                                               cores.shape[0], ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
-                                               out.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_grams")
+        self._mode_call("plfem_gram_work_bytes", {"ncomp": ncomp, "k": k}, "plfem_mode_grams", kind, staged,
+                        (_native._ptr(cores), cores.shape[0]), (out,))
         return {nm: out[i] for i, nm in enumerate(names)}
 
     def profile_grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
@@ -353,13 +385,10 @@ class ModeFields:
         if profile is None:
             raise ValueError("profile_grams needs a geometry that carries an index profile (ProfiledGeometry); "
                              "for core discs on a cladding use grams")
-        kind, vals, _ = self._check_records(modes)
-        k = 0 if kind is None else vals.shape[1]
+        kind, vals, _, k = self._checked(modes)
         if k == 0:
             return {nm: np.zeros((0, 0)) for nm in PROFILE_GRAM_NAMES.get(kind, ())}
-        self._ensure_locator()
-        staged, _src = self._stage(vals)
-        return self._profile_grams_staged(kind, staged, profile.table(), profile.eps_background, index_map=profile.index_map)
+        return self._profile_grams_staged(kind, self._staged(vals), profile.table(), profile.eps_background, index_map=profile.index_map)
 
     def _set_index_map(self, index_map) -> None:
         """``plfem_locator_set_index_map``: the map of the profile of the call in flight, or None: clear.  Every profile
@@ -375,20 +404,9 @@ class ModeFields:
         names = PROFILE_GRAM_NAMES[kind]
         ncomp, _, k = staged.shape
         table = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, 8))
-        need = ctypes.c_int64(0)
-        if self._lib.plfem_profile_gram_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
-            raise ValueError(f"plfem_profile_gram_work_bytes rejected ncomp = {ncomp}, k = {k}")
-        if work is None:
-            work = _native.device_scratch(int(need.value) + 256, self.tdev)
-        elif work.numel() < int(need.value) + 256:
-            raise ValueError("work buffer smaller than plfem_profile_gram_work_bytes + 256")
-        aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((len(names), k, k), dtype=np.float64)
-        self._check(self._lib.plfem_profile_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
-                                                  1 if kind == "vectorial" else 0, table.ctypes.data_as(ctypes.c_void_p),
-                                                  table.shape[0], float(eps_bg), ctypes.c_void_p(aligned),
-                                                  ctypes.c_int64(int(need.value)), out.ctypes.data_as(ctypes.c_void_p)),
-                    "plfem_profile_grams")
+        self._mode_call("plfem_profile_gram_work_bytes", {"ncomp": ncomp, "k": k}, "plfem_profile_grams", kind, staged,
+                        (_native._ptr(table), table.shape[0], float(eps_bg)), (out,), work=work)
         return {nm: out[i] for i, nm in enumerate(names)}
 
     def indicators(self, modes: Sequence[Dict], geometry, alpha_p: float = 1.0) -> Dict[str, np.ndarray]:
@@ -398,7 +416,7 @@ class ModeFields:
         for scalar ones), ``k0`` and the material map from ``geometry`` (its index profile if it carries one, otherwise
         its core discs at ``n_core`` on ``n_clad``), ``alpha_p`` the divergence penalty of the vectorial solve -- and
         ``total[m] = eta2[m].sum()``.  :mod:`.adapt` marks and refines with them."""
-        kind, vals, beta = self._check_records(modes)
+        kind, vals, beta, k = self._checked(modes)
         try:
             alpha_p = float(alpha_p)
             k0 = float(geometry.k0)
@@ -415,15 +433,12 @@ class ModeFields:
         else:
             cores = np.zeros((0, 3))
             table, eps, index_map = profile.table(), (1.0, 1.0, float(profile.eps_background)), profile.index_map
-        k = 0 if kind is None else vals.shape[1]
         if k == 0:
             return {"eta2": np.zeros((0, self.ne)), "total": np.zeros(0)}
         if not np.all(np.isfinite(beta)):
             raise ValueError("every mode record needs a finite 'beta': the indicator is that of the eigenpair")
         lam = np.ascontiguousarray(beta * beta if kind == "vectorial" else -(beta * beta))
-        self._ensure_locator()
-        staged, _src = self._stage(vals)
-        eta2 = self._indicators_staged(kind, staged, lam, k0, alpha_p, cores, eps, table, index_map=index_map)
+        eta2 = self._indicators_staged(kind, self._staged(vals), lam, k0, alpha_p, cores, eps, table, index_map=index_map)
         return {"eta2": eta2, "total": eta2.sum(axis=1)}
 
     def _indicators_staged(self, kind, staged, lam, k0, alpha_p, cores, eps, table, work=None, index_map=None) -> np.ndarray:
@@ -435,21 +450,10 @@ class ModeFields:
         table = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, 8))
         cores = np.ascontiguousarray(np.asarray(cores, dtype=np.float64).reshape(-1, 3))
         lam = np.ascontiguousarray(lam, dtype=np.float64)
-        need = ctypes.c_int64(0)
-        if self._lib.plfem_indicator_work_bytes(self._loc, ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
-            raise ValueError(f"plfem_indicator_work_bytes rejected ncomp = {ncomp}, k = {k}")
-        if work is None:
-            work = _native.device_scratch(int(need.value) + 256, self.tdev)
-        elif work.numel() < int(need.value) + 256:
-            raise ValueError("work buffer smaller than plfem_indicator_work_bytes + 256")
-        aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((k, self.ne), dtype=np.float64)
-        self._check(self._lib.plfem_mode_indicators(
-            self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()), 1 if kind == "vectorial" else 0,
-            lam.ctypes.data_as(ctypes.c_void_p), float(k0), float(alpha_p), cores.ctypes.data_as(ctypes.c_void_p),
-            cores.shape[0], float(eps[0]), float(eps[1]), table.ctypes.data_as(ctypes.c_void_p), table.shape[0], float(eps[2]),
-            ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)), out.ctypes.data_as(ctypes.c_void_p)),
-            "plfem_mode_indicators")
+        self._mode_call("plfem_indicator_work_bytes", {"ncomp": ncomp, "k": k}, "plfem_mode_indicators", kind, staged,
+                        (_native._ptr(lam), float(k0), float(alpha_p), _native._ptr(cores), cores.shape[0], float(eps[0]),
+                         float(eps[1]), _native._ptr(table), table.shape[0], float(eps[2])), (out,), work=work, loc=self._loc)
         return out
 
     def core_grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
@@ -461,37 +465,26 @@ class ModeFields:
         With core c at eps_c instead of eps_core the pencils of :meth:`grams` become ``sum_c K_c / eps_c + ...``: these
         are the exact projections of a pencil with unequal core indices on the span of the modes."""
         reject_profile(geometry, "ModeFields.core_grams")
-        kind, vals, _ = self._check_records(modes)
+        kind, vals, _, k = self._checked(modes)
         cores = self._cores(geometry)
         ncore = cores.shape[0]
         if ncore < 1:
             raise ValueError("geometry has no cores")
-        k = 0 if kind is None else vals.shape[1]
         if k == 0:
             res = {nm: np.zeros((ncore, 0, 0)) for nm in CORE_GRAM_NAMES.get(kind, ())}
             res["points"] = np.zeros(ncore, dtype=np.int64)
             return res
-        self._ensure_locator()
-        staged, _src = self._stage(vals)
-        return self._core_grams_staged(kind, staged, cores)
+        return self._core_grams_staged(kind, self._staged(vals), cores)
 
     def _core_grams_staged(self, kind, staged, cores) -> Dict[str, np.ndarray]:
         """``plfem_core_grams`` on modes already staged (ncomp, n, k) on the device."""
         names = CORE_GRAM_NAMES[kind]
         ncomp, _, k = staged.shape
         ncore = cores.shape[0]
-        need = ctypes.c_int64(0)
-        if self._lib.plfem_core_gram_work_bytes(self._loc, ncomp, k, ncore, ctypes.byref(need)) != _native.PLFEM_OK:
-            raise ValueError(f"plfem_core_gram_work_bytes rejected ncomp = {ncomp}, k = {k}, ncore = {ncore}")
-        work = _native.device_scratch(int(need.value) + 256, self.tdev)
-        aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((ncore, len(names), k, k), dtype=np.float64)
         points = np.empty(ncore, dtype=np.int64)
-        self._check(self._lib.plfem_core_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
-                                               1 if kind == "vectorial" else 0, cores.ctypes.data_as(ctypes.c_void_p), ncore,
-                                               ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
-                                               out.ctypes.data_as(ctypes.c_void_p), points.ctypes.data_as(ctypes.c_void_p)),
-                    "plfem_core_grams")
+        self._mode_call("plfem_core_gram_work_bytes", {"ncomp": ncomp, "k": k, "ncore": ncore}, "plfem_core_grams", kind, staged,
+                        (_native._ptr(cores), ncore), (out, points), loc=self._loc)
         res = {nm: np.ascontiguousarray(out[:, i]) for i, nm in enumerate(names)}
         res["points"] = points
         return res
@@ -514,31 +507,20 @@ class ModeFields:
         ``K_clad_X``, ``K_clad_Y`` (the form of ``K_r``), and the second moments ``M_XX``, ``M_XY``, ``M_YY`` over both
         regions.  A bend enters both pencils linearly in the curvature through exactly these (:mod:`.bend`)."""
         reject_profile(geometry, "ModeFields.moment_grams")
-        kind, vals, _ = self._check_records(modes)
+        kind, vals, _, k = self._checked(modes)
         cores = self._cores(geometry)
         o = self._origin(origin)
-        k = 0 if kind is None else vals.shape[1]
         if k == 0:
             return {nm: np.zeros((0, 0)) for nm in MOMENT_GRAM_NAMES.get(kind, ())}
-        self._ensure_locator()
-        staged, _src = self._stage(vals)
-        return self._moment_grams_staged(kind, staged, cores, o)
+        return self._moment_grams_staged(kind, self._staged(vals), cores, o)
 
     def _moment_grams_staged(self, kind, staged, cores, origin) -> Dict[str, np.ndarray]:
         """``plfem_moment_grams`` on modes already staged (ncomp, n, k) on the device."""
         names = MOMENT_GRAM_NAMES[kind]
         ncomp, _, k = staged.shape
-        need = ctypes.c_int64(0)
-        if self._lib.plfem_moment_gram_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
-            raise ValueError(f"plfem_moment_gram_work_bytes rejected ncomp = {ncomp}, k = {k}")
-        work = _native.device_scratch(int(need.value) + 256, self.tdev)
-        aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((len(names), k, k), dtype=np.float64)
-        self._check(self._lib.plfem_moment_grams(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
-                                                 1 if kind == "vectorial" else 0, cores.ctypes.data_as(ctypes.c_void_p),
-                                                 cores.shape[0], origin.ctypes.data_as(ctypes.c_void_p),
-                                                 ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
-                                                 out.ctypes.data_as(ctypes.c_void_p)), "plfem_moment_grams")
+        self._mode_call("plfem_moment_gram_work_bytes", {"ncomp": ncomp, "k": k}, "plfem_moment_grams", kind, staged,
+                        (_native._ptr(cores), cores.shape[0], _native._ptr(origin)), (out,))
         return {nm: out[i] for i, nm in enumerate(names)}
 
     def quartic(self, modes: Sequence[Dict], geometry=None, weights=(1.0, 1.0)) -> np.ndarray:
@@ -548,10 +530,9 @@ class ModeFields:
         transverse dot product for vectorial records.  ``geometry=None``: wt = 1; otherwise wt = ``weights[0]`` in the
         closed core discs of the assembly's core test and ``weights[1]`` outside.  At most 64 modes."""
         reject_profile(geometry, "ModeFields.quartic with a geometry")
-        kind, vals, _ = self._check_records(modes)
+        kind, vals, _, k = self._checked(modes)
         if kind is None:
             return np.zeros((0, 0))
-        k = vals.shape[1]
         if k > 64:
             raise ValueError(f"at most 64 modes per quartic overlap, got {k}")
         try:
@@ -569,21 +550,10 @@ class ModeFields:
             ncore = cores.shape[0]
             if ncore > 64:
                 raise ValueError("at most 64 cores")
-        self._ensure_locator()
-        import torch
-        ncomp = vals.shape[0]
-        need = ctypes.c_int64(0)
-        if self._lib.plfem_quartic_work_bytes(ncomp, k, ctypes.byref(need)) != _native.PLFEM_OK:
-            raise ValueError(f"plfem_quartic_work_bytes rejected ncomp = {ncomp}, k = {k}")
-        staged, _src = self._stage(vals)
-        work = _native.device_scratch(int(need.value) + 256, self.tdev)
-        aligned = (work.data_ptr() + 255) & ~255
         npair = k * (k + 1) // 2
         out = np.empty((npair, npair), dtype=np.float64)
-        self._check(self._lib.plfem_mode_quartic(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
-                                                 1 if kind == "vectorial" else 0, cores.ctypes.data_as(ctypes.c_void_p),
-                                                 ncore, wc, wl, ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
-                                                 out.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_quartic")
+        self._mode_call("plfem_quartic_work_bytes", {"ncomp": vals.shape[0], "k": k}, "plfem_mode_quartic", kind,
+                        self._staged(vals), (_native._ptr(cores), ncore, wc, wl), (out,))
         return out
 
     def project(self, modes: Sequence[Dict], x_factors, y_factors) -> np.ndarray:
@@ -595,34 +565,28 @@ class ModeFields:
         projected on its own; ncomp = 1 for scalar records.  At most 64 modes and 4096 factors per axis; the y-factors
         are split into chunks so that one call's device result stays under ``CHUNK_BYTES``.  An empty mode list gives
         an empty array."""
-        kind, vals, _ = self._check_records(modes)
+        kind, vals, _, k = self._checked(modes)
         xf, yf = _factors(x_factors, "x_factors"), _factors(y_factors, "y_factors")
         la, lb = xf.shape[0], yf.shape[0]
         if kind is None:
             return np.zeros((0, 0, lb, la), dtype=np.complex128)
-        ncomp, k = vals.shape[0], vals.shape[1]
+        ncomp = vals.shape[0]
         if k > 64:
             raise ValueError(f"at most 64 modes per projection, got {k}")
         self._ensure_locator()
-        import torch
         chunk = int(max(1, min(lb, self.CHUNK_BYTES // (16 * ncomp * k * la))))
-        nbytes = 0
-        for n in {chunk, lb % chunk or chunk}:                  # the full chunks and a shorter last one
-            need = ctypes.c_int64(0)
-            if self._lib.plfem_project_work_bytes(ncomp, k, la, n, ctypes.byref(need)) != _native.PLFEM_OK:
-                raise ValueError(f"plfem_project_work_bytes rejected ncomp = {ncomp}, k = {k}, la = {la}, lb = {n}")
-            nbytes = max(nbytes, int(need.value))
-        staged, _src = self._stage(vals)
-        work = _native.device_scratch(nbytes + 256, self.tdev)
-        aligned = (work.data_ptr() + 255) & ~255
+        # one buffer for the full chunks and a shorter last one
+        nbytes = self._work_bytes("plfem_project_work_bytes",
+                                  *({"ncomp": ncomp, "k": k, "la": la, "lb": n} for n in {chunk, lb % chunk or chunk}))
+        staged = self._staged(vals)
+        work, aligned = self._work_buffer("plfem_project_work_bytes", nbytes)
+        indexed = 1 if kind == "vectorial" else 0
         out = np.empty((ncomp, k, lb, la), dtype=np.complex128)
         for s in range(0, lb, chunk):
             yc = np.ascontiguousarray(yf[s:s + chunk])
             part = np.empty((ncomp, k, yc.shape[0], la), dtype=np.complex128)
-            self._check(self._lib.plfem_mode_project(self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()),
-                                                     1 if kind == "vectorial" else 0, la, xf.ctypes.data_as(ctypes.c_void_p),
-                                                     yc.shape[0], yc.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(aligned),
-                                                     ctypes.c_int64(nbytes), part.ctypes.data_as(ctypes.c_void_p)),
+            self._check(self._lib.plfem_mode_project(self._loc, ncomp, k, staged.data_ptr(), indexed, la, _native._ptr(xf),
+                                                     yc.shape[0], _native._ptr(yc), aligned, nbytes, _native._ptr(part)),
                         "plfem_mode_project")
             out[:, :, s:s + chunk] = part
         return out
@@ -638,7 +602,7 @@ class ModeFields:
         device in chunks of at most ``CHUNK_BYTES`` and 4096 frames, and the bits of a frame's result do not depend on
         the chunking.  A NaN pixel gives NaN for its frame only.  At most 64 modes; an empty mode list gives an empty
         array, ``nf = 0`` gives (ncomp, k, 0).  Argument errors raise ``ValueError`` before any device call."""
-        kind, vals, _ = self._check_records(modes)
+        kind, vals, _, k = self._checked(modes)
         xa, dx = _grid_axis(x, "x")
         ya, dy = _grid_axis(y, "y")
         nx, ny = xa.size, ya.size
@@ -646,7 +610,7 @@ class ModeFields:
         nf = fr.shape[0]
         if kind is None:
             return np.zeros((0, 0, nf), dtype=np.complex128)
-        ncomp, k = vals.shape[0], vals.shape[1]
+        ncomp = vals.shape[0]
         if k > 64:
             raise ValueError(f"at most 64 modes per projection, got {k}")
         out = np.empty((ncomp, k, nf), dtype=np.complex128)
@@ -655,13 +619,11 @@ class ModeFields:
         self._ensure_locator()
         import torch
         chunk = int(max(1, min(nf, PROJECT_SAMPLED_MAX_FRAMES, self.CHUNK_BYTES // (16 * ny * nx))))
-        need = ctypes.c_int64(0)
-        if self._lib.plfem_project_sampled_work_bytes(ncomp, k, chunk, ctypes.byref(need)) != _native.PLFEM_OK:
-            raise ValueError(f"plfem_project_sampled_work_bytes rejected ncomp = {ncomp}, k = {k}, nf = {chunk}")
-        nbytes = int(need.value)                                  # (a shorter last chunk needs no more)
-        staged, _src = self._stage(vals)
-        work = _native.device_scratch(nbytes + 256, self.tdev)
-        aligned = (work.data_ptr() + 255) & ~255
+        # (a shorter last chunk needs no more)
+        nbytes = self._work_bytes("plfem_project_sampled_work_bytes", {"ncomp": ncomp, "k": k, "nf": chunk})
+        staged = self._staged(vals)
+        work, aligned = self._work_buffer("plfem_project_sampled_work_bytes", nbytes)
+        indexed = 1 if kind == "vectorial" else 0
         with torch.cuda.stream(self.stream):
             for s in range(0, nf, chunk):
                 src = torch.from_numpy(np.ascontiguousarray(fr[s:s + chunk])).to(self.tdev)       # (n, ny, nx) complex
@@ -670,9 +632,8 @@ class ModeFields:
                 del src
                 part = np.empty((ncomp, k, n), dtype=np.complex128)
                 self._check(self._lib.plfem_mode_project_sampled(
-                    self._loc, ncomp, k, ctypes.c_void_p(staged.data_ptr()), 1 if kind == "vectorial" else 0, nx, ny,
-                    float(xa[0]), float(ya[0]), dx, dy, n, ctypes.c_void_p(dev.data_ptr()), ctypes.c_void_p(aligned),
-                    ctypes.c_int64(nbytes), part.ctypes.data_as(ctypes.c_void_p)), "plfem_mode_project_sampled")
+                    self._loc, ncomp, k, staged.data_ptr(), indexed, nx, ny, float(xa[0]), float(ya[0]), dx, dy, n,
+                    dev.data_ptr(), aligned, nbytes, _native._ptr(part)), "plfem_mode_project_sampled")
                 out[:, :, s:s + chunk] = part
         return out
 
@@ -693,6 +654,51 @@ def _as_fields(m, device) -> ModeFields:
     return m if isinstance(m, ModeFields) else ModeFields(m, device=device)
 
 
+def _overlap_pair(what: str, modes_a, mesh_a, modes_b, mesh_b, weight, device, posed: bool = False, poses=None,
+                  normalize: bool = False):
+    """The arguments of :func:`mode_overlap` / :func:`mode_overlap_poses` (``what``), checked in one order: the records'
+    kinds, the pose table of a ``posed`` call (returned as ``P``), the weight, ``fa`` / ``fb`` (one :class:`ModeFields` when both meshes are
+    the same), the records against each mesh (``va``, ``vb``, ``ka``, ``kb``).  With modes on both sides (``ready``) also
+    the chunk pairs of a posed call, ``indexed``, ``weight`` = (core table or None, ncore, eps_core, eps_clad) as the
+    entry points take it, both locators and that they share a device.  Only the locators touch the device."""
+    ka_kind, va, _ = _records(modes_a)
+    kb_kind, vb, _ = _records(modes_b)
+    if ka_kind is not None and kb_kind is not None and ka_kind != kb_kind:
+        raise ValueError("vectorial and scalar mode records cannot be mixed")
+    P = _poses(poses) if posed else None
+    if weight is not None and not all(hasattr(weight, a) for a in ("positions", "core_radii", "n_core", "n_clad")):
+        raise ValueError("weight must be None or a geometry (positions, core_radii, n_core, n_clad)")
+    reject_profile(weight, f"{what} with a weight")
+    if posed and normalize and weight is not None:
+        raise ValueError("normalize=True is defined for weight=None only")
+    fa = _as_fields(mesh_a, device)
+    fb = fa if (mesh_b is mesh_a or (not isinstance(mesh_b, ModeFields) and not isinstance(mesh_a, ModeFields)
+                                     and mesh_key(mesh_b) == mesh_key(mesh_a))) else _as_fields(mesh_b, device)
+    _, va, _ = fa._check_records(modes_a)
+    _, vb, _ = fb._check_records(modes_b)
+    pr = SimpleNamespace(fa=fa, va=va, fb=fb, vb=vb, P=P, ka=0 if va is None else va.shape[1],
+                         kb=0 if vb is None else vb.shape[1])
+    pr.ready = pr.ka > 0 and pr.kb > 0
+    if not pr.ready:
+        return pr
+    if posed and ((pr.ka + 31) // 32) * ((pr.kb + 31) // 32) > POSE_MAX_CHUNK_PAIRS:
+        raise ValueError(f"at most {POSE_MAX_CHUNK_PAIRS} pairs of 32-mode chunks per posed overlap, got ka = {pr.ka}, "
+                         f"kb = {pr.kb}")
+    pr.indexed = 1 if ka_kind == "vectorial" else 0
+    if weight is None:
+        pr.weight = (None, -1, 1.0, 1.0)
+    else:
+        cores = _core_table(weight)
+        if cores.shape[0] > 64:
+            raise ValueError("at most 64 cores")
+        pr.weight = (_native._ptr(cores), cores.shape[0], float(weight.n_core) ** 2, float(weight.n_clad) ** 2)
+    fa._ensure_locator()
+    fb._ensure_locator()
+    if fa.device != fb.device:
+        raise ValueError("both meshes must be evaluated on one device")
+    return pr
+
+
 def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_b, weight=None, normalize: bool = False,
                  device: Optional[int] = None) -> np.ndarray:
     """``O[i, j] = sum over the elements of mesh_b and its six-point rule |det J| w_q wt(x_q) u_a,i(x_q) . u_b,j(x_q)``
@@ -700,52 +706,19 @@ def mode_overlap(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_
     the closed-disc core test of the assembly: on one mesh O = V^T M_(1/eps) V, the B of the eigenproblem).
     ``normalize=True``: the power coupling |O_ij|^2 / (O^aa_ii O^bb_jj), each self-overlap on its own mesh.  ``mesh_a`` /
     ``mesh_b`` may be :class:`ModeFields` (their analyses and locators are reused)."""
-    ka_kind, va, _ = _records(modes_a)
-    kb_kind, vb, _ = _records(modes_b)
-    if ka_kind is not None and kb_kind is not None and ka_kind != kb_kind:
-        raise ValueError("vectorial and scalar mode records cannot be mixed")
-    if weight is not None and not all(hasattr(weight, a) for a in ("positions", "core_radii", "n_core", "n_clad")):
-        raise ValueError("weight must be None or a geometry (positions, core_radii, n_core, n_clad)")
-    reject_profile(weight, "mode_overlap with a weight")
-    fa = _as_fields(mesh_a, device)
-    fb = fa if (mesh_b is mesh_a or (not isinstance(mesh_b, ModeFields) and not isinstance(mesh_a, ModeFields)
-                                     and mesh_key(mesh_b) == mesh_key(mesh_a))) else _as_fields(mesh_b, device)
-    _, va, _ = fa._check_records(modes_a)
-    _, vb, _ = fb._check_records(modes_b)
-    ka = 0 if va is None else va.shape[1]
-    kb = 0 if vb is None else vb.shape[1]
-    if ka == 0 or kb == 0:
-        return np.zeros((ka, kb), dtype=np.float64)
-    indexed = 1 if ka_kind == "vectorial" else 0
-    if weight is None:
-        cores, ncore, ec, el = None, -1, 1.0, 1.0
-    else:
-        cores = _core_table(weight)
-        ncore, ec, el = cores.shape[0], float(weight.n_core) ** 2, float(weight.n_clad) ** 2
-        if ncore > 64:
-            raise ValueError("at most 64 cores")
-    fa._ensure_locator()
-    fb._ensure_locator()
-    if fa.device != fb.device:
-        raise ValueError("both meshes must be evaluated on one device")
+    pr = _overlap_pair("mode_overlap", modes_a, mesh_a, modes_b, mesh_b, weight, device)
+    if not pr.ready:
+        return np.zeros((pr.ka, pr.kb), dtype=np.float64)
+    fa, va, fb, vb = pr.fa, pr.va, pr.fb, pr.vb
 
     def overlap(f1, v1, f2, v2):
-        import torch
-        lib = f1._lib
-        s1, _ = f1._stage(v1)
-        s2, _ = f2._stage(v2)
+        s1, s2 = f1._stage(v1)[0], f2._stage(v2)[0]
         k1, k2 = v1.shape[1], v2.shape[1]
-        need = ctypes.c_int64(0)
-        lib.plfem_overlap_work_bytes(k1, k2, ctypes.byref(need))
-        work = _native.device_scratch(int(need.value) + 256, f1.tdev)
-        aligned = (work.data_ptr() + 255) & ~255
         out = np.empty((k1, k2), dtype=np.float64)
         f2.stream.synchronize()                 # (B's staging ran on B's stream; the overlap runs on A's)
-        f1._check(lib.plfem_field_overlap(f1._loc, ctypes.c_void_p(s1.data_ptr()), k1, indexed,
-                                          f2._loc, ctypes.c_void_p(s2.data_ptr()), k2, indexed, v1.shape[0],
-                                          cores.ctypes.data_as(ctypes.c_void_p) if cores is not None else None, ncore,
-                                          ec, el, ctypes.c_void_p(aligned), ctypes.c_int64(int(need.value)),
-                                          out.ctypes.data_as(ctypes.c_void_p)), "plfem_field_overlap")
+        f1._work_call("plfem_overlap_work_bytes", {"ka": k1, "kb": k2}, "plfem_field_overlap",
+                      (f1._loc, s1.data_ptr(), k1, pr.indexed, f2._loc, s2.data_ptr(), k2, pr.indexed, v1.shape[0], *pr.weight),
+                      (out,))
         return out
 
     O = overlap(fa, va, fb, vb)
@@ -786,9 +759,6 @@ def _poses(poses) -> np.ndarray:
     return p
 
 
-POSE_MAX_CHUNK_PAIRS = 256         # POSE_MAX_PAIRS of csrc/kernels_fields.hip: pairs of 32-mode chunks per posed call
-
-
 def mode_overlap_poses(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict], mesh_b, poses, weight=None,
                        normalize: bool = False, device: Optional[int] = None) -> np.ndarray:
     """:func:`mode_overlap` under T poses of mesh A relative to mesh B in one call (``plfem_field_overlap_posed``), (T, ka,
@@ -802,56 +772,19 @@ def mode_overlap_poses(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict],
     There is no amplitude factor for m: the self-overlap of the posed A is ``m^2`` times A's own.  ``normalize=True``
     (``weight=None`` only) gives the power coupling ``|O_ij|^2 / (m^2 O^aa_ii O^bb_jj)``.  Argument errors raise
     ``ValueError`` before anything touches the device."""
-    ka_kind, va, _ = _records(modes_a)
-    kb_kind, vb, _ = _records(modes_b)
-    if ka_kind is not None and kb_kind is not None and ka_kind != kb_kind:
-        raise ValueError("vectorial and scalar mode records cannot be mixed")
-    P = _poses(poses)
-    if weight is not None and not all(hasattr(weight, a) for a in ("positions", "core_radii", "n_core", "n_clad")):
-        raise ValueError("weight must be None or a geometry (positions, core_radii, n_core, n_clad)")
-    reject_profile(weight, "mode_overlap_poses with a weight")
-    if normalize and weight is not None:
-        raise ValueError("normalize=True is defined for weight=None only")
-    fa = _as_fields(mesh_a, device)
-    fb = fa if (mesh_b is mesh_a or (not isinstance(mesh_b, ModeFields) and not isinstance(mesh_a, ModeFields)
-                                     and mesh_key(mesh_b) == mesh_key(mesh_a))) else _as_fields(mesh_b, device)
-    _, va, _ = fa._check_records(modes_a)
-    _, vb, _ = fb._check_records(modes_b)
-    ka = 0 if va is None else va.shape[1]
-    kb = 0 if vb is None else vb.shape[1]
+    pr = _overlap_pair("mode_overlap_poses", modes_a, mesh_a, modes_b, mesh_b, weight, device, posed=True, poses=poses,
+                       normalize=normalize)
+    P, ka, kb = pr.P, pr.ka, pr.kb
     T = P.shape[0]
-    if ka == 0 or kb == 0:
+    if not pr.ready:
         return np.zeros((T, ka, kb), dtype=np.float64)
-    if ((ka + 31) // 32) * ((kb + 31) // 32) > POSE_MAX_CHUNK_PAIRS:
-        raise ValueError(f"at most {POSE_MAX_CHUNK_PAIRS} pairs of 32-mode chunks per posed overlap, got ka = {ka}, kb = {kb}")
-    indexed = 1 if ka_kind == "vectorial" else 0
-    if weight is None:
-        cores, ncore, ec, el = None, -1, 1.0, 1.0
-    else:
-        cores = _core_table(weight)
-        ncore, ec, el = cores.shape[0], float(weight.n_core) ** 2, float(weight.n_clad) ** 2
-        if ncore > 64:
-            raise ValueError("at most 64 cores")
-    fa._ensure_locator()
-    fb._ensure_locator()
-    if fa.device != fb.device:
-        raise ValueError("both meshes must be evaluated on one device")
-    lib = fa._lib
-    sa, _ = fa._stage(va)
-    sb, _ = fb._stage(vb)
-    need = ctypes.c_int64(0)
-    if lib.plfem_overlap_posed_work_bytes(fb._loc, ka, kb, T, ctypes.byref(need)) != _native.PLFEM_OK:
-        raise ValueError(f"plfem_overlap_posed_work_bytes rejected ka = {ka}, kb = {kb}, nposes = {T}")
-    work = _native.device_scratch(int(need.value) + 256, fa.tdev)
-    aligned = (work.data_ptr() + 255) & ~255
+    fa, fb = pr.fa, pr.fb
+    sa, sb = fa._stage(pr.va)[0], fb._stage(pr.vb)[0]
     out = np.empty((T, ka, kb), dtype=np.float64)
     fb.stream.synchronize()                     # (B's staging ran on B's stream; the overlap runs on A's)
-    fa._check(lib.plfem_field_overlap_posed(fa._loc, ctypes.c_void_p(sa.data_ptr()), ka, indexed,
-                                            fb._loc, ctypes.c_void_p(sb.data_ptr()), kb, indexed, va.shape[0],
-                                            cores.ctypes.data_as(ctypes.c_void_p) if cores is not None else None, ncore,
-                                            ec, el, T, P.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(aligned),
-                                            ctypes.c_int64(int(need.value)), out.ctypes.data_as(ctypes.c_void_p)),
-              "plfem_field_overlap_posed")
+    fa._work_call("plfem_overlap_posed_work_bytes", {"ka": ka, "kb": kb, "nposes": T}, "plfem_field_overlap_posed",
+                  (fa._loc, sa.data_ptr(), ka, pr.indexed, fb._loc, sb.data_ptr(), kb, pr.indexed, pr.va.shape[0], *pr.weight, T,
+                   _native._ptr(P)), (out,), loc=fb._loc)
     if not normalize:
         return out
     daa = np.diag(mode_overlap(modes_a, fa, modes_a, fa)).copy()
