@@ -647,6 +647,56 @@ int plfem_mode_indicators(plfem_locator* loc, int32_t ncomp, int32_t k, const do
                           const double* layers_host, int32_t nlayer, double eps_bg,
                           void* work_dev, int64_t work_bytes, double* out_host /* [k][ne] */);
 
+/* Electric field, axial Poynting flux and power Grams of k staged vectorial modes (ncomp = 2 only).  Convention of
+ * plfem_sample_fields: fields vary as exp(j (w t - beta z)), H = (hx, hy, j hz_im).  From curl H = j w eps0 eps E, with
+ * e = E / Z0 (e has the units of H; Z0 = 376.730313668 ohm) and w = 1 / eps(x):
+ *   gx = -(hx,xx + hy,xy),  gy = -(hx,xy + hy,yy)        (-grad of div_t H: constant per element for P2)
+ *   Ex = w (beta hy + gy / beta) / k0,  Ey = -w (beta hx + gx / beta) / k0,  Ez_im = -w (dx hy - dy hx) / k0  (Ez = j Ez_im),
+ *   Sz = (Ex hy - Ey hx) / 2,
+ * hence for two modes m, n of one mesh
+ *   P[m][n] = 1/2 int (Ex_m hy_n - Ey_m hx_n) dA = (beta_m M_w[m][n] + G_w[m][n] / beta_m) / (2 k0),
+ *   M_w[m][n] = int w (hx_m hx_n + hy_m hy_n)  (symmetric: the M_w of plfem_profile_grams),
+ *   G_w[m][n] = int w (gx_m hx_n + gy_m hy_n)  (not symmetric),
+ * so the device sums are free of beta and k0.  These are the formulas for any staged P2 field with a given beta, eigenpair
+ * or not; the transverse E rests on element-wise second derivatives of a P2 field and converges at first order in h.
+ * Material: use_profile != 0: the index profile (layers_host, nlayer in [0, 64], eps_bg as for plfem_set_index_profile) over
+ * the locator's sampled map if one is set (plfem_locator_set_index_map); eps_core and eps_clad are not read.
+ * use_profile == 0: eps_core in the closed discs of cores_host (ncore in [0, 64], the core test of plfem_assemble_hfield)
+ * and eps_clad outside; a map set on the locator is then an argument error.  Either way a point is decided by the helpers
+ * the assembly uses.  modes_dev: staged by plfem_stage_modes ([2][nrows][k]); indexed as in plfem_sample_fields (a boundary
+ * DOF of an indexed record contributes 0).
+ *
+ * plfem_flux_grams: out_host[0..3][k][k] = M_w_core, M_w_rest, G_w_core, G_w_rest, every sum over the mesh's own six-point
+ * rule with |det J| w_q, split by the closed discs of cores_host whatever the material (ncore = 0: everything is "rest").
+ * Grid, tiling and second stage of plfem_mode_grams: the same bits on every run, for a subset or a permutation of the
+ * modes, and whatever the work buffer held before.  Synchronises the locator's stream.
+ * work_dev: device scratch of plfem_flux_gram_work_bytes(k) bytes, 256-byte aligned: the layout of plfem_profile_grams
+ * with nout = 4: nout k^2 doubles, rounded up to 256 bytes, plus nout ceil(k / 32)^2 x 768 partial blocks of 8 KiB.
+ *
+ * plfem_sample_efields: one lane per point (points_dev [2][npts], located as in plfem_sample_fields: same containment and
+ * tie rule), eps taken at the point itself; out_dev[0..3][k][npts] = Ex, Ey, Ez_im, Sz; eps_dev[npts] (or NULL) the
+ * permittivity used; elem_dev[npts] the element, -1 for a point in no element, whose outputs and eps are 0.  beta_dev [k]
+ * is device memory and is not validated: the kernel writes what the arithmetic gives (beta = 0: inf / NaN).  Runs on the
+ * locator's stream and synchronises it.  npts = 0 returns PLFEM_OK without a launch.
+ *
+ * Argument errors return PLFEM_EINVAL with the locator's last error set, before any launch, checked in this order:
+ * ncomp != 2 or k < 1 (plfem_sample_efields: or npts < 0); ncore outside [0, 64]; a null array (eps_dev may be NULL);
+ * use_profile != 0: a table plfem_set_index_profile rejects, eps_bg included; use_profile == 0: eps_core or eps_clad not
+ * finite and positive, then a map set on the locator; plfem_sample_efields: k0 not finite and positive; an indexed record
+ * on an analysis without interior DOFs; plfem_flux_grams: work_bytes too small, then a misaligned buffer.
+ * plfem_flux_gram_work_bytes rejects k < 1 and a null bytes (left alone). */
+int plfem_flux_gram_work_bytes(int32_t k, int64_t* bytes);
+int plfem_flux_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                     const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                     const double* layers_host, int32_t nlayer, double eps_bg, int32_t use_profile,
+                     void* work_dev, int64_t work_bytes, double* out_host /* [4][k][k] */);
+int plfem_sample_efields(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                         const double* beta_dev /* [k] */, double k0,
+                         const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                         const double* layers_host, int32_t nlayer, double eps_bg, int32_t use_profile,
+                         int32_t npts, const double* points_dev, double* out_dev /* [4][k][npts] */,
+                         double* eps_dev /* [npts] or NULL */, int32_t* elem_dev);
+
 #ifdef PLFEM_TEST_HOOKS
 /* ---------------------------------------------------------------------------------------------
  * TEST HOOKS -- NOT exported by libplfem_hip.so.  They live in the add-on libplfem_testhooks.so (csrc/api_debug.hip,

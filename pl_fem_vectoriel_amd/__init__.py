@@ -10,9 +10,11 @@ from .bend import bend_propagate, bend_quantities_from_grams, bend_response  # n
 from .profile import IndexProfile, ProfiledGeometry  # noqa: F401
 from .adapt import adaptive_solve, mark_elements, mode_error_indicators, refine_marked  # noqa: F401
 from .splice import splice_map, splice_quantities_from_overlaps, taper_from_interfaces, taper_transfer  # noqa: F401
+from .power import Z0_OHM, mode_power, power_quantities_from_grams  # noqa: F401
 
 __all__ = ["MCFGeometry", "PhotonicLanternGeometry", "mcf_positions", "TriMesh", "generate_mesh", "ModeFields", "mode_overlap",
            "mode_dispersion", "mode_nonlinearity", "far_field", "encircled_na", "gaussian_coupling", "field_coupling", "core_decomposition",
            "core_quantities_from_grams", "bend_response", "bend_quantities_from_grams", "bend_propagate", "IndexProfile",
            "ProfiledGeometry", "mode_overlap_poses", "pose_table", "splice_map", "splice_quantities_from_overlaps",
-           "taper_from_interfaces", "taper_transfer", "mode_error_indicators", "mark_elements", "refine_marked", "adaptive_solve"]
+           "taper_from_interfaces", "taper_transfer", "mode_error_indicators", "mark_elements", "refine_marked", "adaptive_solve",
+           "mode_power", "power_quantities_from_grams", "Z0_OHM"]

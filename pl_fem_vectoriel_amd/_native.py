@@ -46,6 +46,7 @@ EXPORTS = (
     "plfem_project_sampled_work_bytes", "plfem_mode_project_sampled",
     "plfem_indicator_work_bytes", "plfem_mode_indicators", "plfem_mesh_refine_marked_count", "plfem_mesh_refine_marked",
     "plfem_set_index_map", "plfem_locator_set_index_map",
+    "plfem_flux_gram_work_bytes", "plfem_flux_grams", "plfem_sample_efields",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -260,6 +261,10 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_mode_project_sampled.argtypes = head + [i32, i32, f64, f64, f64, f64, i32, vp] + tail
     lib.plfem_indicator_work_bytes.argtypes = [vp, i32, i32] + size
     lib.plfem_mode_indicators.argtypes = head + [vp, f64, f64, vp, i32, f64, f64, vp, i32, f64] + tail
+    material = [vp, i32, f64, f64, vp, i32, f64, i32]     # cores, ncore, eps_core, eps_clad, layers, nlayer, eps_bg, use_profile
+    lib.plfem_flux_gram_work_bytes.argtypes = [i32] + size
+    lib.plfem_flux_grams.argtypes = head + material + tail
+    lib.plfem_sample_efields.argtypes = head + [vp, f64] + material + [i32, vp, vp, vp, vp]
     lib.plfem_mesh_refine_marked_count.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_int32]

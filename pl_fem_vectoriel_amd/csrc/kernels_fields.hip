@@ -10,7 +10,8 @@
 // k_core_count + k_core_fill, k_core_grams + k_overlap_reduce), and the region Grams weighted by the coordinates of the
 // quadrature point (k_moment_grams + k_overlap_reduce), and the Grams under the permittivity of an index profile
 // (k_profile_grams + k_overlap_reduce), and the per-element a-posteriori error indicators of a mode set: element residual
-// plus flux jumps across the edges (k_mode_indicators).
+// plus flux jumps across the edges (k_mode_indicators), and the electric field and axial Poynting flux of vectorial modes
+// at points (k_sample_efields) with the Grams their cross powers are built from (k_flux_grams + k_overlap_reduce).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
@@ -20,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "device.h"
 #include "p2_element.h"
@@ -54,6 +56,25 @@ struct LocArgs {
 struct CoreTable {
   double c[MAX_CORES * 3];
 };
+
+// The material of the electric-field kernels (k_sample_efields, k_flux_grams), one of three instances: PROFILE false: eps_core
+// in the closed discs of `cores` and eps_clad outside; PROFILE true: the index profile (layers, nlayer, eps_bg), plain or
+// over a sampled map (Map... = one EpsMap).  The discs are also the region split of k_flux_grams, whatever the instance.
+struct Material {
+  CoreTable cores;
+  int ncore;
+  double eps_core, eps_clad;
+  const double* layers;
+  int nlayer;
+  double eps_bg;
+};
+
+// permittivity at a point, by the helpers the assembly uses; in_core: in_any_core of the point (read by the disc instance only)
+template <bool PROFILE, typename... Map>
+__device__ __forceinline__ double material_eps(const Material& mat, double X, double Y, bool in_core, Map... map) {
+  if constexpr (PROFILE) return profile_eps(X, Y, mat.layers, mat.nlayer, mat.eps_bg, map...);
+  else return in_core ? mat.eps_core : mat.eps_clad;
+}
 
 EpsMap eps_map(const IndexMap& m) { return {m.d}; }
 
@@ -118,6 +139,15 @@ __device__ __forceinline__ int dev_row(const LocArgs& L, int e, int a) {
   return L.map ? L.map[d] : d;
 }
 
+// offsets of the six DOFs of element e into one component of the staged modes ([nrows][k]), -1 = contributes nothing
+__device__ __forceinline__ void dev_row_offsets(const LocArgs& L, int e, int k, int64_t row[6]) {
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const int r = dev_row(L, e, a);
+    row[a] = r < 0 ? -1 : (int64_t)r * k;
+  }
+}
+
 // One lane per point.  Modes staged DOF-major ([comp][nrows][k]): the six gathers of a point are six contiguous runs of k
 // doubles, read one mode per iteration; the output is [comp][k][npts], so a wave's stores of one mode are coalesced.
 __global__ __launch_bounds__(256) void k_sample_fields(LocArgs L, int ncomp, int k, int64_t nrows, const double* __restrict__ V,
@@ -139,11 +169,7 @@ __global__ __launch_bounds__(256) void k_sample_fields(LocArgs L, int ncomp, int
   p2_phi(xi, eta, phi);
   p2_grad(inv, xi, eta, gx, gy);
   int64_t row[6];
-#pragma unroll
-  for (int a = 0; a < 6; ++a) {
-    const int r = dev_row(L, e, a);
-    row[a] = r < 0 ? -1 : (int64_t)r * k;
-  }
+  dev_row_offsets(L, e, k, row);
   const double* V1 = V + nrows * k;
   for (int m = 0; m < k; ++m) {
     double u0 = 0.0, u1 = 0.0, dv = 0.0;
@@ -163,6 +189,65 @@ __global__ __launch_bounds__(256) void k_sample_fields(LocArgs L, int ncomp, int
       out[plane + (int64_t)m * npts + p] = u1;
       if (beta) out[2 * plane + (int64_t)m * npts + p] = -dv / beta[m];
     }
+  }
+}
+
+// Electric field and axial Poynting flux of vectorial modes at points (plfem_sample_efields).  One lane per point, located
+// as in k_sample_fields (dev_locate: the same scan and tie rule).  Fields vary as exp(j (w t - beta z)), H = (hx, hy,
+// j hz_im); from curl H = j w eps0 eps E with e = E / Z0 and w = 1 / eps at the point itself,
+//   gx = -(hx,xx + hy,xy),  gy = -(hx,xy + hy,yy)     (constant over the element)
+//   Ex = w (beta hy + gy / beta) / k0,  Ey = -w (beta hx + gx / beta) / k0,  Ez_im = -w (dx hy - dy hx) / k0,
+//   Sz = (Ex hy - Ey hx) / 2,
+// evaluated per mode in this order.  Output [4][k][npts] = Ex, Ey, Ez_im, Sz, a wave's stores of one mode coalesced;
+// eps_out[npts] (optional) the permittivity used.  A point in no element: element -1, every output and eps 0.
+template <bool PROFILE, typename... Map>
+__global__ __launch_bounds__(256) void k_sample_efields(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
+                                                        const double* __restrict__ beta, double k0, Material mat, int npts,
+                                                        const double* __restrict__ pts, double* __restrict__ out,
+                                                        double* __restrict__ eps_out, int32_t* __restrict__ elem, Map... map) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npts) return;
+  const double X = pts[p], Y = pts[(int64_t)npts + p];
+  double xi = 0, eta = 0, inv[4] = {0, 0, 0, 0};
+  const int e = dev_locate(L, X, Y, xi, eta, inv);
+  elem[p] = e;
+  const int64_t plane = (int64_t)k * npts;
+  if (e < 0) {
+    for (int c = 0; c < 4; ++c)
+      for (int m = 0; m < k; ++m) out[c * plane + (int64_t)m * npts + p] = 0.0;
+    if (eps_out) eps_out[p] = 0.0;
+    return;
+  }
+  const double eps = material_eps<PROFILE>(mat, X, Y, PROFILE ? false : in_any_core(X, Y, mat.cores.c, mat.ncore), map...);
+  if (eps_out) eps_out[p] = eps;
+  const double w = 1.0 / eps;
+  double phi[6], gx[6], gy[6], hxx[6], hxy[6], hyy[6];
+  p2_phi(xi, eta, phi);
+  p2_grad(inv, xi, eta, gx, gy);
+  p2_basis_hess(inv, hxx, hxy, hyy);
+  int64_t row[6];
+  dev_row_offsets(L, e, k, row);
+  const double* V1 = V + nrows * k;
+  for (int m = 0; m < k; ++m) {
+    double hx = 0.0, hy = 0.0, dxhy = 0.0, dyhx = 0.0, sx = 0.0, sy = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      if (row[a] < 0) continue;
+      const double vx = V[row[a] + m], vy = V1[row[a] + m];
+      hx += phi[a] * vx;
+      hy += phi[a] * vy;
+      dxhy += gx[a] * vy;
+      dyhx += gy[a] * vx;
+      sx += hxx[a] * vx + hxy[a] * vy;
+      sy += hxy[a] * vx + hyy[a] * vy;
+    }
+    const double b = beta[m];
+    const double ex = w * (b * hy - sy / b) / k0;       // gy = -sy
+    const double ey = -w * (b * hx - sx / b) / k0;      // gx = -sx
+    out[(int64_t)m * npts + p] = ex;
+    out[plane + (int64_t)m * npts + p] = ey;
+    out[2 * plane + (int64_t)m * npts + p] = -w * (dxhy - dyhx) / k0;
+    out[3 * plane + (int64_t)m * npts + p] = (ex * hy - ey * hx) / 2;
   }
 }
 
@@ -428,7 +513,7 @@ constexpr int GRAM_BLOCKS = 768;
 // What k_mode_grams and k_core_grams share.  gram_stage_point: lane `lane` of a tile stages quadrature point g (element
 // g / 6, point g % 6 of the six-point rule) -- det J, J^-1, the physical basis gradients, the weight |det J| w_q, the
 // staged rows -- or, when not `live`, a point that contributes nothing (rows -1, weight 0).  at_point(X, Y) is called for
-// a live point with the physical point as the assembly forms it.
+// a live point with the physical point as the assembly forms it; an at_point(X, Y, inv) also gets the point's J^-1.
 template <typename AtPoint>
 __device__ __forceinline__ void gram_stage_point(const LocArgs& L, int64_t g, bool live, int lane, double (&s_gx)[6][GT],
                                                  double (&s_gy)[6][GT], int (&s_r)[6][GT], double (&s_w)[GT], int (&s_q)[GT],
@@ -444,7 +529,8 @@ __device__ __forceinline__ void gram_stage_point(const LocArgs& L, int64_t g, bo
     double det = M.det(), inv[4], X, Y, gx[6], gy[6];
     M.inverse(det, inv);
     M.point(xi, eta, X, Y);
-    at_point(X, Y);
+    if constexpr (std::is_invocable_v<AtPoint, double, double, const double(&)[4]>) at_point(X, Y, inv);
+    else at_point(X, Y);
     w = fabs(det) * c_qw[q];
     p2_grad(inv, xi, eta, gx, gy);
     for (int a = 0; a < 6; ++a) {
@@ -756,6 +842,117 @@ __global__ __launch_bounds__(256) void k_profile_grams(LocArgs L, int k, int64_t
         GRAM_ACC(0, 0, 0, 1.0)
         GRAM_ACC(1, 0, 0, w)
         GRAM_ACC(2, 1, 1, 1.0) GRAM_ACC(2, 2, 2, 1.0)
+      }
+    }
+    __syncthreads();
+  }
+  const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) {
+    double* out = partial + (((int64_t)o * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+    for (int r = 0; r < 2; ++r)
+      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
+  }
+}
+
+// Power Grams of vectorial modes (plfem_flux_grams): with e = E / Z0 from curl H = j w eps0 eps E, the cross power of
+// modes m, n is P[m][n] = 1/2 int (Ex_m Hy_n - Ey_m Hx_n) = (beta_m M_w[m][n] + G_w[m][n] / beta_m) / (2 k0) with
+//   M_w[m][n] = int w (hx_m hx_n + hy_m hy_n),   G_w[m][n] = int w (gx_m hx_n + gy_m hy_n),   w = 1 / eps,
+//   gx = -(hx,xx + hy,xy),  gy = -(hx,xy + hy,yy)   (-grad of the transverse divergence: constant per element for P2),
+// so the device sums are free of beta and k0.  Grid, tiling and staging as in k_profile_grams; the staging lane also puts
+// the physical Hessians of the six basis functions (p2_basis_hess: 18 values per point) and the point's region -- the
+// closed discs of `mat.cores`, whatever the material instance -- into LDS.  Features per (point, mode): hx, hy, gx, gy for
+// the row chunk; hx, hy times |det J| w_q for the column chunk (G_w is not symmetric: its rows carry g).  w enters as
+// GRAM_ACC's factor as in k_profile_grams.  Outputs: M_w_core, M_w_rest, G_w_core, G_w_rest.  A padding point has rows
+// -1, Hessians 0 and weight 0; a boundary DOF of an indexed record is skipped: both contribute 0.
+template <bool PROFILE, typename... Map>
+__global__ __launch_bounds__(256) void k_flux_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V, Material mat,
+                                                    int nchunk, double* __restrict__ partial, Map... map) {
+  constexpr int NOUT = 4;
+  __shared__ double s_fr[4][GT][OC];          // row chunk: hx, hy, gx, gy
+  __shared__ double s_fc[2][GT][OC];          // column chunk: hx, hy, times the weight
+  __shared__ double s_gx[6][GT], s_gy[6][GT]; // (staged by gram_stage_point; the features here need no gradients)
+  __shared__ double s_h[3][6][GT];            // xx, xy, yy of the six basis functions
+  __shared__ int s_r[6][GT];
+  __shared__ double s_w[GT], s_wt[GT];        // |det J| w_q, and 1 / eps of the point
+  __shared__ int s_q[GT], s_core[GT];
+  const int tid = threadIdx.x;
+  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
+  const int i0 = ci * OC, j0 = cj * OC;
+  const int64_t nq = (int64_t)6 * L.ne;
+  const int64_t ntiles = (nq + GT - 1) / GT;
+  const int ti = tid >> 4, tj = tid & 15;
+  const double* V1 = V + nrows * k;
+  double acc[NOUT][2][2];
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < GT) {
+      const int64_t g = tile * GT + tid;
+      double wt = 1.0;
+      int core = 0;
+      for (int a = 0; a < 6; ++a) s_h[0][a][tid] = s_h[1][a][tid] = s_h[2][a][tid] = 0.0;
+      gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q, [&](double X, double Y, const double(&inv)[4]) {
+        double hxx[6], hxy[6], hyy[6];
+        p2_basis_hess(inv, hxx, hxy, hyy);
+        for (int a = 0; a < 6; ++a) { s_h[0][a][tid] = hxx[a]; s_h[1][a][tid] = hxy[a]; s_h[2][a][tid] = hyy[a]; }
+        const bool in = in_any_core(X, Y, mat.cores.c, mat.ncore);
+        core = in ? 1 : 0;
+        wt = 1.0 / material_eps<PROFILE>(mat, X, Y, in, map...);
+      });
+      s_wt[tid] = wt;
+      s_core[tid] = core;
+    }
+    __syncthreads();
+    // the features: GT OC (point, mode) pairs per side, the side the same for all lanes of a pass
+    for (int idx = tid; idx < 2 * GT * OC; idx += 256) {
+      const int i = idx % OC, t = (idx / OC) % GT, side = idx / (OC * GT);
+      const int m = (side ? j0 : i0) + i;
+      double hx = 0.0, hy = 0.0, sx = 0.0, sy = 0.0;
+      if (m < k) {
+        double phi[6];
+        p2_phi(c_qx[s_q[t]], c_qy[s_q[t]], phi);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          const int r = s_r[a][t];
+          if (r < 0) continue;
+          const double vx = V[(int64_t)r * k + m], vy = V1[(int64_t)r * k + m];
+          hx += phi[a] * vx;
+          hy += phi[a] * vy;
+          if (!side) {
+            const double hxy = s_h[1][a][t];
+            sx += s_h[0][a][t] * vx + hxy * vy;
+            sy += hxy * vx + s_h[2][a][t] * vy;
+          }
+        }
+      }
+      if (side) {
+        const double w = s_w[t];
+        s_fc[0][t][i] = hx * w;
+        s_fc[1][t][i] = hy * w;
+      } else {
+        s_fr[0][t][i] = hx;
+        s_fr[1][t][i] = hy;
+        s_fr[2][t][i] = -sx;
+        s_fr[3][t][i] = -sy;
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < GT; ++t) {
+      double2 a[4], b[2];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) a[c] = *reinterpret_cast<const double2*>(&s_fr[c][t][2 * ti]);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) b[c] = *reinterpret_cast<const double2*>(&s_fc[c][t][2 * tj]);
+      const double w = s_wt[t];                 // the same for every lane, as is the region
+      // row features 0 hx, 1 hy, 2 gx, 3 gy; column features 0 hx, 1 hy
+      if (s_core[t]) {
+        GRAM_ACC(0, 0, 0, w) GRAM_ACC(0, 1, 1, w)
+        GRAM_ACC(2, 2, 0, w) GRAM_ACC(2, 3, 1, w)
+      } else {
+        GRAM_ACC(1, 0, 0, w) GRAM_ACC(1, 1, 1, w)
+        GRAM_ACC(3, 2, 0, w) GRAM_ACC(3, 3, 1, w)
       }
     }
     __syncthreads();
@@ -1940,6 +2137,96 @@ extern "C" int plfem_profile_grams(plfem_locator* L, int32_t ncomp, int32_t k, c
   });
   TRY(check_launch(L, "k_profile_grams"));
   return grams_to_host(call, profile_gram_outputs(ncomp), k, nblk, out_host);
+} catch (...) { return host_failure(L); }
+
+namespace {
+constexpr int FLUX_GRAM_OUTPUTS = 4;   // M_w_core, M_w_rest, G_w_core, G_w_rest
+
+// The material arguments of the electric-field calls (plfem_flux_grams, plfem_sample_efields): nullptr if they are
+// acceptable, otherwise what is wrong with them.  use_profile: the layer table as plfem_set_index_profile takes it, over
+// the locator's map if one is set; otherwise eps_core / eps_clad, and a map on the locator is an error, not ignored.
+const char* material_error(const plfem_locator* L, double eps_core, double eps_clad, const double* layers_host, int nlayer,
+                           double eps_bg, int use_profile) {
+  if (use_profile) return profile_table_error(layers_host, nlayer, eps_bg);
+  if (!std::isfinite(eps_core) || !std::isfinite(eps_clad) || !(eps_core > 0.0) || !(eps_clad > 0.0))
+    return "eps_core and eps_clad must be finite and positive";
+  if (L->map.set()) return "the locator carries a sampled index map: use_profile must be set (or the map cleared)";
+  return nullptr;
+}
+
+// the kernels' Material; the layer table of a profile goes to the locator's device buffer on its stream (the call ends with
+// a stream synchronisation: the host table outlives the copy and nothing in flight reads the table of an earlier call)
+int stage_material(plfem_locator* L, const double* cores_host, int ncore, double eps_core, double eps_clad,
+                   const double* layers_host, int nlayer, double eps_bg, int use_profile, Material& mat) {
+  if (use_profile && nlayer > 0)
+    HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
+  mat = Material{pack_cores(cores_host, ncore), ncore, eps_core, eps_clad, L->d_layers, use_profile ? nlayer : 0, eps_bg};
+  return PLFEM_OK;
+}
+
+// f(profile, map...) for the three material instances: discs (std::false_type), profile, profile over the locator's map
+template <typename F>
+void with_material(const plfem_locator* L, int use_profile, F&& f) {
+  if (use_profile) with_map(L, [&](auto... map) { f(std::true_type{}, map...); });
+  else f(std::false_type{});
+}
+}  // namespace
+
+extern "C" int plfem_flux_gram_work_bytes(int32_t k, int64_t* bytes) {
+  if (!bytes || k < 1) return PLFEM_EINVAL;
+  *bytes = (int64_t)gram_layout(FLUX_GRAM_OUTPUTS, k).total;
+  return PLFEM_OK;
+}
+
+extern "C" int plfem_flux_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                                const double* layers_host, int32_t nlayer, double eps_bg, int32_t use_profile, void* work_dev,
+                                int64_t work_bytes, double* out_host) try {
+  if (!L) return PLFEM_EINVAL;
+  FieldCall call{L, "plfem_flux_grams"};
+  if (ncomp != 2 || k < 1) return call.reject("ncomp must be 2 (vectorial records) and k > 0");
+  if (!ncore_ok(ncore, false)) return call.reject("ncore must be in [0, 64]");
+  if (!modes_dev || !work_dev || !out_host || (ncore > 0 && !cores_host)) return call.reject("null array");
+  if (const char* bad = material_error(L, eps_core, eps_clad, layers_host, nlayer, eps_bg, use_profile)) return call.reject(bad);
+  const WorkLayout lay = gram_layout(FLUX_GRAM_OUTPUTS, k);
+  TRY(call.enter(indexed, "plfem_flux_gram_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial));
+  Material mat;
+  TRY(stage_material(L, cores_host, ncore, eps_core, eps_clad, layers_host, nlayer, eps_bg, use_profile, mat));
+  const int nc = overlap_chunks(k), nblk = gram_blocks(L->ne);
+  with_material(L, use_profile, [&](auto profile, auto... map) {
+    hipLaunchKernelGGL((k_flux_grams<decltype(profile)::value, decltype(map)...>), dim3(nblk, nc * nc), dim3(256), 0, L->stream,
+                       call.loc, (int)k, call.nrows, modes_dev, mat, nc, call.partial, map...);
+  });
+  TRY(check_launch(L, "k_flux_grams"));
+  return grams_to_host(call, FLUX_GRAM_OUTPUTS, k, nblk, out_host);
+} catch (...) { return host_failure(L); }
+
+extern "C" int plfem_sample_efields(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                    const double* beta_dev, double k0, const double* cores_host, int32_t ncore, double eps_core,
+                                    double eps_clad, const double* layers_host, int32_t nlayer, double eps_bg,
+                                    int32_t use_profile, int32_t npts, const double* points_dev, double* out_dev,
+                                    double* eps_dev, int32_t* elem_dev) try {
+  if (!L) return PLFEM_EINVAL;
+  FieldCall call{L, "plfem_sample_efields"};
+  if (ncomp != 2 || k < 1 || npts < 0) return call.reject("ncomp must be 2 (vectorial records), k > 0 and npts >= 0");
+  if (!ncore_ok(ncore, false)) return call.reject("ncore must be in [0, 64]");
+  if (npts == 0) return PLFEM_OK;
+  if (!modes_dev || !beta_dev || !points_dev || !out_dev || !elem_dev || (ncore > 0 && !cores_host))
+    return call.reject("null array");
+  if (const char* bad = material_error(L, eps_core, eps_clad, layers_host, nlayer, eps_bg, use_profile)) return call.reject(bad);
+  if (!std::isfinite(k0) || !(k0 > 0.0)) return call.reject("k0 must be finite and positive");
+  TRY(call.modes(indexed));
+  HIP_TRY(L, hipSetDevice(L->device));
+  Material mat;
+  TRY(stage_material(L, cores_host, ncore, eps_core, eps_clad, layers_host, nlayer, eps_bg, use_profile, mat));
+  with_material(L, use_profile, [&](auto profile, auto... map) {
+    hipLaunchKernelGGL((k_sample_efields<decltype(profile)::value, decltype(map)...>), dim3((npts + 255) / 256), dim3(256), 0,
+                       L->stream, call.loc, (int)k, call.nrows, modes_dev, beta_dev, k0, mat, (int)npts, points_dev, out_dev,
+                       eps_dev, elem_dev, map...);
+  });
+  TRY(check_launch(L, "k_sample_efields"));
+  HIP_TRY(L, hipStreamSynchronize(L->stream));
+  return PLFEM_OK;
 } catch (...) { return host_failure(L); }
 
 namespace {

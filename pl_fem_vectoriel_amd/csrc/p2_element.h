@@ -1,7 +1,7 @@
 // The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
 // integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
 // k_field_overlap, k_mode_grams, k_profile_grams, k_mode_quartic, k_mode_project, k_mode_project_sampled, k_core_owner,
-// k_mode_indicators).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// k_mode_indicators, k_flux_grams, k_sample_efields).  One definition, so that a quadrature point lands in the same region, and det J rounds
 // the same way, in the assembly and in every kernel that must reproduce it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -90,6 +90,21 @@ __device__ __forceinline__ void p2_hess(const double inv[4], const double u[6], 
   uxx = inv[0] * inv[0] * h00 + 2.0 * (inv[0] * inv[2]) * h01 + inv[2] * inv[2] * h11;
   uxy = inv[0] * inv[1] * h00 + (inv[0] * inv[3] + inv[2] * inv[1]) * h01 + inv[2] * inv[3] * h11;
   uyy = inv[1] * inv[1] * h00 + 2.0 * (inv[1] * inv[3]) * h01 + inv[3] * inv[3] * h11;
+}
+
+// physical second derivatives of the six basis functions themselves (constant over the element): the J^-1 products of
+// p2_hess applied to the reference Hessians listed there, for the kernels that contract them with many DOF vectors
+// (k_flux_grams, k_sample_efields)
+__device__ __forceinline__ void p2_basis_hess(const double inv[4], double hxx[6], double hxy[6], double hyy[6]) {
+  const double h00[6] = {4.0, 4.0, 0.0, -8.0, 0.0, 0.0};
+  const double h11[6] = {4.0, 0.0, 4.0, 0.0, 0.0, -8.0};
+  const double h01[6] = {4.0, 0.0, 0.0, -4.0, 4.0, -4.0};
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    hxx[i] = inv[0] * inv[0] * h00[i] + 2.0 * (inv[0] * inv[2]) * h01[i] + inv[2] * inv[2] * h11[i];
+    hxy[i] = inv[0] * inv[1] * h00[i] + (inv[0] * inv[3] + inv[2] * inv[1]) * h01[i] + inv[2] * inv[3] * h11[i];
+    hyy[i] = inv[1] * inv[1] * h00[i] + 2.0 * (inv[1] * inv[3]) * h01[i] + inv[3] * inv[3] * h11[i];
+  }
 }
 
 // Affine map of element e: vertices = rows 0-2 of vrow ([3+][ne], sorted), coordinates x[v], y[v].  The type of ne is

@@ -18,6 +18,9 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
   (``plfem_moment_grams``): what :mod:`.bend` builds bend-induced index shifts, mode mixing and beam widths from;
 * :meth:`ModeFields.indicators` -- per-element a-posteriori error indicators of the modes, element residual plus flux
   jumps (``plfem_mode_indicators``): what :mod:`.adapt` marks and refines a mesh with;
+* :meth:`ModeFields.sample_e`, :meth:`ModeFields.flux_grams` -- the electric field and axial Poynting flux of vectorial
+  modes at points (``plfem_sample_efields``) and the Grams their cross powers are built from (``plfem_flux_grams``): what
+  :mod:`.power` builds modal power, power confinement and power orthogonality from;
 * :meth:`ModeFields.quartic` -- the packed overlap of products of four modes on a 16-point degree-8 rule
   (``plfem_mode_quartic``): what :mod:`.nonlinear` builds the nonlinear coupling tensor, A_eff and gamma from;
 * :meth:`ModeFields.project` -- the projection of the modes on plane waves and Gaussian beams, fields that separate in
@@ -46,6 +49,7 @@ LOC_TOL = 1e-10                    # PLFEM_LOC_TOL of include/plfem.h
 GRAM_NAMES = {"vectorial": ("M_core", "M_clad", "K_core", "K_clad", "D"), "scalar": ("M_core", "M_clad", "S")}
 CORE_GRAM_NAMES = {"vectorial": ("Mx", "My", "K"), "scalar": ("M",)}
 PROFILE_GRAM_NAMES = {"vectorial": ("M", "M_w", "K_w", "D"), "scalar": ("M", "M_w", "S")}
+FLUX_GRAM_NAMES = ("M_w_core", "M_w_rest", "G_w_core", "G_w_rest")      # vectorial records only
 MOMENT_GRAM_NAMES = {"vectorial": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "K_core_X", "K_core_Y", "K_clad_X",
                                    "K_clad_Y", "M_XX", "M_XY", "M_YY"),
                      "scalar": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "M_XX", "M_XY", "M_YY")}
@@ -327,6 +331,16 @@ class ModeFields:
     def sample_grid(self, modes: Sequence[Dict], nx: int, ny: int, extent=None, hz: bool = True) -> Dict[str, np.ndarray]:
         """:meth:`sample` on the regular nx x ny grid over ``extent`` = (xmin, xmax, ymin, ymax) (default: the mesh's
         bounding box): every component (k, ny, nx), ``"element"`` (ny, nx), and the axes ``"x"`` (nx,), ``"y"`` (ny,)."""
+        x, y, pts = self._grid_points(nx, ny, extent)
+        res = self.sample(modes, pts, hz=hz)
+        ny, nx = y.size, x.size
+        out = {nm: (v.reshape(ny, nx) if nm == "element" else v.reshape(v.shape[0], ny, nx)) for nm, v in res.items()}
+        out["x"], out["y"] = x, y
+        return out
+
+    def _grid_points(self, nx: int, ny: int, extent) -> tuple:
+        """The axes ``x`` (nx,), ``y`` (ny,) of the regular grid over ``extent`` (default: the mesh's bounding box) and its
+        points (2, ny nx), x fastest."""
         nx, ny = int(nx), int(ny)
         if nx < 1 or ny < 1:
             raise ValueError("nx and ny must be >= 1")
@@ -338,10 +352,7 @@ class ModeFields:
         pts = np.empty((2, ny * nx), dtype=np.float64)
         pts[0] = np.tile(x, ny)
         pts[1] = np.repeat(y, nx)
-        res = self.sample(modes, pts, hz=hz)
-        out = {nm: (v.reshape(ny, nx) if nm == "element" else v.reshape(v.shape[0], ny, nx)) for nm, v in res.items()}
-        out["x"], out["y"] = x, y
-        return out
+        return x, y, pts
 
     def grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
         """Same-mesh Grams of the modes under the element forms of the assembly, split by material region
@@ -454,6 +465,129 @@ class ModeFields:
         self._mode_call("plfem_indicator_work_bytes", {"ncomp": ncomp, "k": k}, "plfem_mode_indicators", kind, staged,
                         (_native._ptr(lam), float(k0), float(alpha_p), _native._ptr(cores), cores.shape[0], float(eps[0]),
                          float(eps[1]), _native._ptr(table), table.shape[0], float(eps[2])), (out,), work=work, loc=self._loc)
+        return out
+
+    # -- electric field and power --------------------------------------------------------------------------------
+    def _material(self, geometry) -> SimpleNamespace:
+        """The material arguments of the electric-field calls from ``geometry``: its index profile if it carries one
+        (``use_profile = 1``), else its core discs at ``n_core`` on ``n_clad``.  ``cores`` (n, 3) are the region discs of
+        :meth:`flux_grams` either way: the (base) geometry's ``positions`` / ``core_radii``, empty without them."""
+        profile = index_profile_of(geometry)
+        has_cores = all(hasattr(geometry, a) for a in ("positions", "core_radii"))
+        if profile is None:
+            if not (has_cores and all(hasattr(geometry, a) for a in ("n_core", "n_clad"))):
+                raise ValueError("geometry must carry an index profile, or have positions, core_radii, n_core and n_clad")
+            eps = (float(geometry.n_core) ** 2, float(geometry.n_clad) ** 2)
+            if not all(np.isfinite(e) and e > 0 for e in eps):
+                raise ValueError("n_core and n_clad must be finite and non-zero")
+            return SimpleNamespace(cores=self._cores(geometry), eps_core=eps[0], eps_clad=eps[1], table=np.zeros((0, 8)),
+                                   eps_bg=1.0, use_profile=0, index_map=None)
+        cores = self._cores(geometry) if has_cores else np.zeros((0, 3))
+        return SimpleNamespace(cores=cores, eps_core=1.0, eps_clad=1.0, table=profile.table(),
+                               eps_bg=float(profile.eps_background), use_profile=1, index_map=profile.index_map)
+
+    @staticmethod
+    def _material_args(mat) -> tuple:
+        """``mat`` as the entry points take it; the arrays stay alive in ``mat``."""
+        mat.cores = np.ascontiguousarray(np.asarray(mat.cores, dtype=np.float64).reshape(-1, 3))
+        mat.table = np.ascontiguousarray(np.asarray(mat.table, dtype=np.float64).reshape(-1, 8))
+        return (_native._ptr(mat.cores), mat.cores.shape[0], float(mat.eps_core), float(mat.eps_clad), _native._ptr(mat.table),
+                mat.table.shape[0], float(mat.eps_bg), int(mat.use_profile))
+
+    def _checked_vectorial(self, modes, what: str):
+        """:meth:`_checked` for the calls that need vectorial records with a usable ``beta``."""
+        kind, vals, beta, k = self._checked(modes)
+        if kind == "scalar":
+            raise ValueError(f"{what}: the electric field needs vectorial records")
+        if k and not np.all(np.isfinite(beta) & (beta != 0)):
+            raise ValueError(f"{what} needs a finite, non-zero 'beta' in every vectorial record")
+        return vals, beta, k
+
+    def flux_grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
+        """Power Grams of vectorial modes (``plfem_flux_grams``), each (k, k): ``M_w_core``, ``M_w_rest``, ``G_w_core``,
+        ``G_w_rest`` with ``M_w[m, n] = int w (hx_m hx_n + hy_m hy_n)``, ``G_w[m, n] = int w (gx_m hx_n + gy_m hy_n)``,
+        ``w = 1 / eps`` and ``g = -grad (dx hx + dy hy)`` (element-wise second derivatives), over the mesh's own six-point
+        rule, split by the closed core discs of ``geometry`` (of its base for a ``ProfiledGeometry``; none: everything is
+        "rest").  The material is the geometry's index profile if it carries one, else its discs at ``n_core`` on
+        ``n_clad``.  With ``e = E / Z0`` the cross power is ``P[m, n] = 1/2 int (Ex_m Hy_n - Ey_m Hx_n) = (beta_m M_w[m, n] +
+        G_w[m, n] / beta_m) / (2 k0)``: :func:`.power.power_quantities_from_grams`."""
+        mat = self._material(geometry)
+        vals, _, k = self._checked_vectorial(modes, "ModeFields.flux_grams")
+        if k == 0:
+            return {nm: np.zeros((0, 0)) for nm in FLUX_GRAM_NAMES}
+        return self._flux_grams_staged(self._staged(vals), mat)
+
+    def _flux_grams_staged(self, staged, mat, work=None) -> Dict[str, np.ndarray]:
+        """``plfem_flux_grams`` on modes already staged (2, n, k) on the device; ``mat``: what :meth:`_material` returns;
+        ``work``: a uint8 device tensor to use as the work buffer instead of a fresh one."""
+        self._set_index_map(mat.index_map)
+        k = staged.shape[2]
+        out = np.empty((len(FLUX_GRAM_NAMES), k, k), dtype=np.float64)
+        self._mode_call("plfem_flux_gram_work_bytes", {"k": k}, "plfem_flux_grams", "vectorial", staged,
+                        self._material_args(mat), (out,), work=work)
+        return {nm: out[i] for i, nm in enumerate(FLUX_GRAM_NAMES)}
+
+    def sample_e(self, modes: Sequence[Dict], points, geometry) -> Dict[str, np.ndarray]:
+        """Electric field and axial Poynting flux of vectorial modes at ``points`` (2, npts) (``plfem_sample_efields``):
+        ``{"Ex", "Ey", "Ez_im", "Sz"}`` each (k, npts), ``"eps"`` (npts,) the permittivity used and ``"element"`` (npts,)
+        int32 (-1 and zeros for a point in no element).  Convention of :meth:`sample`: fields vary as exp(j (w t - beta
+        z)), ``H = (Hx, Hy, j Hz_im)``, ``E = (Ex, Ey, j Ez_im)`` in units of ``Z0`` (``e = E / Z0``), from ``curl H = j w
+        eps0 eps E`` with ``k0`` and the material of ``geometry`` (its index profile if it carries one, else its discs at
+        ``n_core`` on ``n_clad``) and ``beta`` of each record; ``Sz = (Ex Hy - Ey Hx) / 2``.  The transverse E rests on
+        element-wise second derivatives of the P2 field: first order in h."""
+        mat = self._material(geometry)
+        try:
+            k0 = float(geometry.k0)
+        except (AttributeError, TypeError, ValueError):
+            raise ValueError("geometry must have k0") from None
+        if not (np.isfinite(k0) and k0 > 0):
+            raise ValueError("k0 must be finite and positive")
+        vals, beta, k = self._checked_vectorial(modes, "ModeFields.sample_e")
+        pts = np.asarray(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[0] != 2:
+            raise ValueError("points must be an array of shape (2, npts)")
+        npts = pts.shape[1]
+        names = ("Ex", "Ey", "Ez_im", "Sz")
+        res = {nm: np.empty((k, npts), dtype=np.float64) for nm in names}
+        res["eps"] = np.empty(npts, dtype=np.float64)
+        res["element"] = np.empty(npts, dtype=np.int32)
+        if k == 0 or npts == 0:
+            if k == 0:                               # nothing to evaluate: the device is not touched
+                res["eps"][:] = 0.0
+                res["element"][:] = -1
+            return res
+        import torch
+        staged = self._staged(vals)
+        self._set_index_map(mat.index_map)
+        margs = self._material_args(mat)
+        chunk = int(max(1024, min(npts, self.CHUNK_BYTES // (8 * 4 * k + 28), 1 << 30)))
+        with torch.cuda.stream(self.stream):
+            beta_d = torch.from_numpy(np.ascontiguousarray(beta)).to(self.tdev)
+            for s in range(0, npts, chunk):
+                e = min(npts, s + chunk)
+                n = e - s
+                pd = torch.from_numpy(np.ascontiguousarray(pts[:, s:e])).to(self.tdev)
+                od = _native.device_output((4, k, n), torch.float64, self.tdev)
+                epd = _native.device_output((n,), torch.float64, self.tdev)
+                ed = _native.device_output((n,), torch.int32, self.tdev)
+                self._check(self._lib.plfem_sample_efields(
+                    self._loc, 2, k, staged.data_ptr(), 1, beta_d.data_ptr(), k0, *margs, n, pd.data_ptr(), od.data_ptr(),
+                    epd.data_ptr(), ed.data_ptr()), "plfem_sample_efields")
+                oh = od.cpu().numpy()
+                for c, nm in enumerate(names):
+                    res[nm][:, s:e] = oh[c]
+                res["eps"][s:e] = epd.cpu().numpy()
+                res["element"][s:e] = ed.cpu().numpy()
+        return res
+
+    def sample_grid_e(self, modes: Sequence[Dict], nx: int, ny: int, geometry, extent=None) -> Dict[str, np.ndarray]:
+        """:meth:`sample_e` on the regular nx x ny grid of :meth:`sample_grid`: every component (k, ny, nx), ``"eps"`` and
+        ``"element"`` (ny, nx), and the axes ``"x"`` (nx,), ``"y"`` (ny,)."""
+        x, y, pts = self._grid_points(nx, ny, extent)
+        res = self.sample_e(modes, pts, geometry)
+        ny, nx = y.size, x.size
+        out = {nm: (v.reshape(ny, nx) if v.ndim == 1 else v.reshape(v.shape[0], ny, nx)) for nm, v in res.items()}
+        out["x"], out["y"] = x, y
         return out
 
     def core_grams(self, modes: Sequence[Dict], geometry) -> Dict[str, np.ndarray]:
@@ -792,6 +926,6 @@ def mode_overlap_poses(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict],
     return out * out / (P[:, 4, None, None] ** 2 * daa[None, :, None] * dbb[None, None, :])
 
 
-__all__ = ["ModeFields", "mode_overlap", "mode_overlap_poses", "pose_table", "POSE_MAX_CHUNK_PAIRS", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES", "PROFILE_GRAM_NAMES",
+__all__ = ["ModeFields", "mode_overlap", "mode_overlap_poses", "pose_table", "POSE_MAX_CHUNK_PAIRS", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES", "PROFILE_GRAM_NAMES", "FLUX_GRAM_NAMES",
            "PROJECT_TILE", "PROJECT_MAX_FACTORS", "PROJECT_SAMPLED_TILE", "PROJECT_SAMPLED_MAX_FRAMES",
            "PROJECT_SAMPLED_MAX_PIXELS"]

@@ -2,12 +2,16 @@
 mode_overlap C1 -> C1 refined (the C1 modes sampled at the DOF locations of mesh.refined(): ~1.1 M quadrature points of
 the finer mesh, 22 x 22); locator build times at C1 and L = 2; the projection on a 1 x 1 Gaussian beam and on 64 x 64 and
 256 x 256 plane-wave grids up to k0 (``ModeFields.project``); optionally the NumPy emulation of the same calls (the
-projection up to ``--emulation-grid`` factors per axis: the 256 x 256 grid would take the host hours).
+projection up to ``--emulation-grid`` factors per axis: the 256 x 256 grid would take the host hours); the power leg:
+``ModeFields.flux_grams`` with the discs, with the seven cores written as seven layers and with those layers over a sampled
+map, next to ``ModeFields.profile_grams`` on the same two profiles (the yardstick), and ``ModeFields.sample_grid_e`` next to
+``ModeFields.sample_grid`` on the same grid.
 
-    python scripts/time_fields.py [--grid 1024] [--reps 3] [--project-only] [--emulation] [--out FILE]
+    python scripts/time_fields.py [--grid 1024] [--reps 3] [--project-only | --power-only] [--emulation] [--out FILE]
 
 Run it under ``rocprofv3 --kernel-trace --stats`` for the kernel times (k_sample_fields, k_field_overlap,
-k_overlap_reduce, k_stage_modes, k_mode_project, k_project_reduce; the projection leg dispatches k_mode_project ``--reps``
+k_overlap_reduce, k_stage_modes, k_mode_project, k_project_reduce, k_flux_grams, k_profile_grams, k_sample_efields; the
+power leg dispatches each kernel instance ``--reps`` times, in the order discs, layers, map; the projection leg dispatches k_mode_project ``--reps``
 times per grid, in the order of ``--project-grids``); the wall times printed here include the host-device copies."""
 from __future__ import annotations
 
@@ -31,6 +35,7 @@ def main():
     ap.add_argument("--modes", type=int, default=22)
     ap.add_argument("--emulation", action="store_true", help="also time the NumPy emulation (minutes)")
     ap.add_argument("--project-only", action="store_true", help="run the projection leg alone")
+    ap.add_argument("--power-only", action="store_true", help="run the power leg alone")
     ap.add_argument("--project-grids", default="1,64,256", help="factors per axis of the projection leg (1: one Gaussian beam)")
     ap.add_argument("--emulation-grid", type=int, default=64, help="largest projection grid the emulation is timed on")
     ap.add_argument("--out", default=None)
@@ -50,7 +55,7 @@ def main():
     res = {"k": len(modes), "ne_c1": int(mesh.t.shape[1]), "ne_l2": int(fine.t.shape[1])}
 
     # locator build (host) on fresh analyses
-    for name, m in () if args.project_only else (("c1", mesh), ("l2", fine)):
+    for name, m in () if args.project_only or args.power_only else (("c1", mesh), ("l2", fine)):
         sym = _native.Symbolic(m.p, m.t)
         t0 = time.perf_counter()
         st = sym.array("loc_stats")
@@ -71,9 +76,13 @@ def main():
             best = dt if best is None else min(best, dt)
         return out, best
 
+    if args.power_only:
+        power_leg(args, geom, mf, modes, timed, res)
+        return finish(args, res)
     project_leg(args, geom, mesh, mf, modes, timed, res)
     if args.project_only:
         return finish(args, res)
+    power_leg(args, geom, mf, modes, timed, res)
     img, dt = timed(lambda: mf.sample_grid(modes, args.grid, args.grid))
     out_bytes = 3 * len(modes) * args.grid * args.grid * 8
     res["sample_grid"] = {"nx": args.grid, "wall_ms": dt * 1e3, "output_bytes": out_bytes,
@@ -133,6 +142,38 @@ def project_leg(args, geom, mesh, mf, modes, timed, res):
             entry["emulation_s"] = time.perf_counter() - t0
             entry["emulation_excess"] = float((np.abs(P - ref) / em.tolerance(vals, True, xf, yf)).max())
         res["project"][f"{n}x{n}"] = entry
+
+
+def power_leg(args, geom, mf, modes, timed, res):
+    """``ModeFields.flux_grams`` under the three material instances next to ``ModeFields.profile_grams``, and
+    ``ModeFields.sample_grid_e`` next to ``ModeFields.sample_grid``: wall times (staging and copies included)."""
+    from pl_fem_vectoriel_amd import IndexProfile, ProfiledGeometry, power_quantities_from_grams
+
+    def layers(prof):
+        for (cx, cy), r in zip(np.atleast_2d(geom.positions), np.asarray(geom.core_radii).reshape(-1)):
+            prof.disc((cx, cy), r, geom.n_core)
+        return ProfiledGeometry(geom, prof, n_core=geom.n_core, n_clad=geom.n_clad)
+
+    x0, x1, y0, y1 = mf.bbox
+    x, y = np.linspace(x0, x1, 257), np.linspace(y0, y1, 257)
+    geoms = {"discs": geom, "layers": layers(IndexProfile(geom.n_clad)),
+             "map": layers(IndexProfile(geom.n_clad).sampled(x, y, np.full((257, 257), float(geom.n_clad))))}
+    res["power"] = {"layers": len(geoms["layers"].index_profile)}
+    for name, g in geoms.items():
+        G, dt = timed(lambda: mf.flux_grams(modes, g))
+        q = power_quantities_from_grams(G, np.array([m["beta"] for m in modes]), float(geom.k0))
+        entry = {"flux_grams_wall_ms": dt * 1e3, "orthogonality_max": float(q["orthogonality"].max()),
+                 "core_fraction_min": float(q["core_fraction"].min()), "core_fraction_max": float(q["core_fraction"].max())}
+        if name != "discs":
+            _, dt = timed(lambda: mf.profile_grams(modes, g))
+            entry["profile_grams_wall_ms"] = dt * 1e3
+        res["power"][name] = entry
+    _, dt = timed(lambda: mf.sample_grid(modes, args.grid, args.grid))
+    res["power"]["sample_grid_wall_ms"] = dt * 1e3
+    img, dt = timed(lambda: mf.sample_grid_e(modes, args.grid, args.grid, geom))
+    res["power"]["sample_grid_e_wall_ms"] = dt * 1e3
+    res["power"]["output_bytes"] = 4 * len(modes) * args.grid * args.grid * 8
+    res["power"]["finite"] = bool(all(np.all(np.isfinite(img[nm])) for nm in ("Ex", "Ey", "Ez_im", "Sz")))
 
 
 def finish(args, res):
