@@ -696,6 +696,56 @@ int plfem_sample_efields(plfem_locator* loc, int32_t ncomp, int32_t k, const dou
                          const double* layers_host, int32_t nlayer, double eps_bg, int32_t use_profile,
                          int32_t npts, const double* points_dev, double* out_dev /* [4][k][npts] */,
                          double* eps_dev /* [npts] or NULL */, int32_t* elem_dev);
+/* Posed flux overlap: the cross flux int (E_a x H_b + E_b x H_a) . z of two vectorial mode sets on two meshes under nposes
+ * poses of mesh A relative to mesh B, as four matrices per pose that are free of beta, k0 and m.  Vectorial records only
+ * (both mode sets staged [2][nrows][k]).  The pose contract of plfem_field_overlap_posed applies unchanged: a pose row is
+ * (tx, ty, c, s, m), B's quadrature point (X, Y) is looked up in A at
+ *   xa = (fl(c dx) + fl(s dy)) / m,  ya = (fl(c dy) - fl(s dx)) / m,  dx = X - tx, dy = Y - ty
+ * (the identity pose gives (X, Y) bit for bit; the location decisions are those of plfem_sample_fields).  With
+ *   hA' = R hA(xa, ya),  gA' = R gA,  g = (-(hx,xx + hy,xy), -(hx,xy + hy,yy)) from the physical Hessians of the element
+ *   (as plfem_flux_grams forms it; no factor of m: the host owns every m, beta and k0),
+ *   hB, gB: B's own at its quadrature point,  wA = 1 / eps_A at (xa, ya) in A's frame,  wB = 1 / eps_B at (X, Y),
+ * out_host[p][0..3][ka][kb] = MA, GA, MB, GB, every sum over the elements of B and B's six-point rule with |det J| w_q:
+ *   MA[i][j] = sum wA (hA'_i . hB_j)      GA[i][j] = sum wA (gA'_i . hB_j)
+ *   MB[i][j] = sum wB (hA'_i . hB_j)      GB[i][j] = sum wB (hA'_i . gB_j).
+ * A point that lands in no element of A contributes 0 to all four; a boundary DOF of an indexed record contributes 0.
+ * With X_ab = (beta_a MA + GA / beta_a) / k0_a = int (E_a' x H_b) . z and X_ba = (beta_b MB + GB / beta_b) / k0_b =
+ * int (E_b x H_a') . z (beta_a along the rows, beta_b along the columns; k0_b = k0_a / m: the magnified field has every
+ * wavenumber divided by m and g by m^2, so its E is A's own E turned and its power m^2 P_a) the power-normalised
+ * transfer is (X_ab + X_ba)[i][j] / (4 m sqrt(|P_a,i| |P_b,j|)).
+ * Material of each side, a flat argument set as in plfem_flux_grams: use_profile == 0: eps_core in the closed discs of
+ * cores (ncore in [0, 64]) and eps_clad outside; use_profile != 0: the layer profile (layers, nlayer, eps_bg).  Either way
+ * a point is decided by the helpers the assembly uses.  Each side's layer table travels through its own locator's device
+ * buffer; with one locator on both sides and a profile on both, the two tables must be the same.  Sampled index maps are
+ * out of scope of this call: a map set on either locator is an argument error, whatever use_profile says.
+ * One workgroup per (slice of B's 32-point tiles, pair of 32-mode chunks, pose) writes its four partial blocks to their own
+ * slots, slices = min(128, tiles of B) whatever nposes, ka and kb are, and the fixed-order second stage of
+ * plfem_field_overlap sums them: no atomics, and the bits of out_host[p] depend on pose p, the modes, the materials and the
+ * two meshes only -- not on the other poses, on nposes, on the batch boundary, on what the work buffer held, on the run, or
+ * on a permutation of the modes of either side.  The poses are worked off in batches of
+ *   batch = max(1, min(nposes, 4096, (512 MiB - 768) / (8 (4 ka kb + 4096 pairs slices + 5)))) poses,
+ * pairs = ceil(ka / 32) ceil(kb / 32) <= 64 -- a quarter of plfem_field_overlap_posed's limit, so that one pose of the
+ * largest call (256 MiB of partial blocks) still fits -- and work_dev holds one batch: its results [batch][4][ka][kb], its
+ * partial blocks [batch][4][pairs][slices][1024] and its pose rows, each part 256-byte aligned, so
+ * plfem_flux_overlap_posed_work_bytes(loc_b, ka, kb, nposes) never exceeds 512 MiB.  Runs on loc_a's stream and
+ * synchronises it once, at the end; both locators on one device.
+ * Argument errors return PLFEM_EINVAL with loc_a's last error set, before any launch, checked in this order: loc_b null
+ * or on another device; ka or kb < 1, nposes < 1, more than 64 chunk pairs; ncore of a side outside [0, 64]; a null
+ * array (cores only with ncore > 0); side A's material, then side B's, each by the rules of plfem_flux_grams (a profile's
+ * table, or the discs' two permittivities) followed by a map set on that side's locator; one locator on both sides with
+ * two different layer tables; an indexed record on an analysis without interior DOFs; a non-finite pose entry, m <= 0 or
+ * |c^2 + s^2 - 1| > 1e-12; work_bytes too small, then a misaligned buffer.  A null loc_a returns PLFEM_EINVAL alone.
+ * plfem_flux_overlap_posed_work_bytes rejects a null loc_b or bytes (left alone), ka, kb or nposes < 1 and more than 64
+ * chunk pairs. */
+int plfem_flux_overlap_posed_work_bytes(const plfem_locator* loc_b, int32_t ka, int32_t kb, int32_t nposes, int64_t* bytes);
+int plfem_flux_overlap_posed(plfem_locator* loc_a, const double* modes_a_dev, int32_t ka, int32_t indexed_a,
+                             const double* cores_a_host, int32_t ncore_a, double eps_core_a, double eps_clad_a,
+                             const double* layers_a_host, int32_t nlayer_a, double eps_bg_a, int32_t use_profile_a,
+                             plfem_locator* loc_b, const double* modes_b_dev, int32_t kb, int32_t indexed_b,
+                             const double* cores_b_host, int32_t ncore_b, double eps_core_b, double eps_clad_b,
+                             const double* layers_b_host, int32_t nlayer_b, double eps_bg_b, int32_t use_profile_b,
+                             int32_t nposes, const double* poses_host /* [nposes][5] = tx, ty, c, s, m */,
+                             void* work_dev, int64_t work_bytes, double* out_host /* [nposes][4][ka][kb] */);
 
 #ifdef PLFEM_TEST_HOOKS
 /* ---------------------------------------------------------------------------------------------

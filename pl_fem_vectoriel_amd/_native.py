@@ -47,6 +47,7 @@ EXPORTS = (
     "plfem_indicator_work_bytes", "plfem_mode_indicators", "plfem_mesh_refine_marked_count", "plfem_mesh_refine_marked",
     "plfem_set_index_map", "plfem_locator_set_index_map",
     "plfem_flux_gram_work_bytes", "plfem_flux_grams", "plfem_sample_efields",
+    "plfem_flux_overlap_posed_work_bytes", "plfem_flux_overlap_posed",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -265,6 +266,8 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_flux_gram_work_bytes.argtypes = [i32] + size
     lib.plfem_flux_grams.argtypes = head + material + tail
     lib.plfem_sample_efields.argtypes = head + [vp, f64] + material + [i32, vp, vp, vp, vp]
+    lib.plfem_flux_overlap_posed_work_bytes.argtypes = [vp, i32, i32, i32] + size
+    lib.plfem_flux_overlap_posed.argtypes = ([vp, vp, i32, i32] + material) * 2 + [i32, vp] + tail
     lib.plfem_mesh_refine_marked_count.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_int32]

@@ -11,7 +11,8 @@
 // quadrature point (k_moment_grams + k_overlap_reduce), and the Grams under the permittivity of an index profile
 // (k_profile_grams + k_overlap_reduce), and the per-element a-posteriori error indicators of a mode set: element residual
 // plus flux jumps across the edges (k_mode_indicators), and the electric field and axial Poynting flux of vectorial modes
-// at points (k_sample_efields) with the Grams their cross powers are built from (k_flux_grams + k_overlap_reduce).
+// at points (k_sample_efields) with the Grams their cross powers are built from (k_flux_grams + k_overlap_reduce), and the
+// E x H cross flux of two vectorial mode sets on two meshes under a table of poses (k_flux_overlap_posed + k_overlap_reduce).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
@@ -966,6 +967,177 @@ __global__ __launch_bounds__(256) void k_flux_grams(LocArgs L, int k, int64_t nr
   }
 }
 #undef GRAM_ACC
+
+// Posed flux overlap (plfem_flux_overlap_posed): the cross flux int (E_a x H_b + E_b x H_a) . z of two vectorial mode sets
+// on two meshes under a pose, as the four sums the host needs, free of beta, k0 and m.  Pose, location and the turn of A's
+// value are those of k_field_overlap_posed, operation for operation (xa, ya through mul_rn and an IEEE division; the
+// identity pose gives (X, Y) bit for bit).  With hA' = R hA(xa, ya), gA' = R gA (g = -(hx,xx + hy,xy), -(hx,xy + hy,yy)
+// from the physical Hessians of A's element, p2_basis_hess, as in k_flux_grams; no factor of m), hB and gB B's own at its
+// quadrature point, wA = 1 / eps_A at (xa, ya) in A's frame and wB = 1 / eps_B at (X, Y):
+//   MA[i][j] = sum wA (hA'_i . hB_j)    GA[i][j] = sum wA (gA'_i . hB_j)
+//   MB[i][j] = sum wB (hA'_i . hB_j)    GB[i][j] = sum wB (hA'_i . gB_j)
+// over B's elements and six-point rule with |det J| w_q.  Each side's material is discs or a layer profile (material_eps:
+// in_any_core / profile_eps, the helpers of the assembly): four instances.  Sampled index maps are out of scope here: the
+// entry point refuses a locator that carries one.  A point in no element of A has both weights 0 and contributes 0 to all
+// four; a boundary DOF of an indexed record is skipped.
+// Grid = (slice of B's tiles, chunk pair, pose of the batch) as in k_field_overlap_posed, gridDim.x a function of B's
+// element count alone.  Tiles of FT = 32 points: the features -- hA', gA', hB, gB, two components each, for 32 modes per
+// side -- are 64 KiB of LDS, 78 KiB with the staging, so two workgroups share a CU.  Per point pair a lane forms
+// hA' . hB, gA' . hB and hA' . gB of its 2 x 2 block once, each as one product and one fused multiply-add in a written
+// order, and adds them with the two weights (the same for every lane) to its four accumulator blocks: an entry's bits
+// depend neither on its place in the block nor on the chunk.  Partials [pose][output][chunk pair][slice][OC * OC], every
+// slot written: what k_overlap_reduce sums with blockIdx.y = 4 pose + output.  Outputs in the order MA, GA, MB, GB.
+constexpr int FT = 32;                  // quadrature points per tile
+constexpr int FLUX_POSED_OUTPUTS = 4;   // MA, GA, MB, GB
+
+// one entry (r, s) of the lane's block: p, q pick the row / column mode of the double2 features
+#define FLUX_POSED_ACC(r, s, p, q)                                          \
+      {                                                                     \
+        const double d = fma(a[0].p, b[0].q, a[1].p * b[1].q);              \
+        const double ga = fma(a[2].p, b[0].q, a[3].p * b[1].q);             \
+        const double gb = fma(a[0].p, b[2].q, a[1].p * b[3].q);             \
+        acc[0][r][s] = fma(wa, d, acc[0][r][s]);                            \
+        acc[1][r][s] = fma(wa, ga, acc[1][r][s]);                           \
+        acc[2][r][s] = fma(wb, d, acc[2][r][s]);                            \
+        acc[3][r][s] = fma(wb, gb, acc[3][r][s]);                           \
+      }
+
+template <bool PROFILE_A, bool PROFILE_B>
+__global__ __launch_bounds__(256) void k_flux_overlap_posed(LocArgs A, LocArgs B, int ka, int64_t nrows_a,
+                                                            const double* __restrict__ Va, Material mat_a, int kb,
+                                                            int64_t nrows_b, const double* __restrict__ Vb, Material mat_b,
+                                                            int nchunk_b, const double* __restrict__ poses,
+                                                            double* __restrict__ partial) {
+  __shared__ double s_fa[4][FT][OC];          // A's chunk: hA'x, hA'y, gA'x, gA'y
+  __shared__ double s_fb[4][FT][OC];          // B's chunk: hBx, hBy, gBx, gBy
+  __shared__ double s_phi[6][FT];             // A's basis at the located point
+  __shared__ double s_ha[3][6][FT];           // xx, xy, yy of the six basis functions of A's element
+  __shared__ double s_hb[3][6][FT];           // and of B's
+  __shared__ int s_ra[6][FT], s_rb[6][FT];
+  __shared__ double s_wa[FT], s_wb[FT];       // |det J| w_q / eps_A and / eps_B
+  __shared__ int s_q[FT];
+  const int tid = threadIdx.x;
+  const int ca = blockIdx.y / nchunk_b, cb = blockIdx.y % nchunk_b;
+  const int ia0 = ca * OC, jb0 = cb * OC;
+  const double* pose = poses + (int64_t)blockIdx.z * POSE_DOUBLES;     // the same for every lane
+  const double tx = pose[0], ty = pose[1], pc = pose[2], ps = pose[3], pm = pose[4];
+  const int64_t nq = (int64_t)6 * B.ne;
+  const int64_t ntiles = (nq + FT - 1) / FT;
+  const int ti = tid >> 4, tj = tid & 15;
+  const double* Va1 = Va + nrows_a * ka;
+  const double* Vb1 = Vb + nrows_b * kb;
+  double acc[FLUX_POSED_OUTPUTS][2][2];
+#pragma unroll
+  for (int o = 0; o < FLUX_POSED_OUTPUTS; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
+  const double* pbx = B.pxy;
+  const double* pby = B.pxy + B.nv;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < FT) {
+      const int64_t g = tile * FT + tid;
+      double wa = 0.0, wb = 0.0;
+      int q = 0;
+      for (int a = 0; a < 6; ++a) {
+        s_ra[a][tid] = -1; s_rb[a][tid] = -1; s_phi[a][tid] = 0.0;
+        s_ha[0][a][tid] = s_ha[1][a][tid] = s_ha[2][a][tid] = 0.0;
+        s_hb[0][a][tid] = s_hb[1][a][tid] = s_hb[2][a][tid] = 0.0;
+      }
+      if (g < nq) {
+        const int e = (int)(g / 6);
+        q = (int)(g % 6);
+        const P2Map M(B.edof, B.ne, pbx, pby, e);
+        double X, Y;
+        M.point(c_qx[q], c_qy[q], X, Y);
+        const double detb = M.det();
+        const double dx = X - tx, dy = Y - ty;
+        const double xa = (mul_rn(pc, dx) + mul_rn(ps, dy)) / pm;
+        const double ya = (mul_rn(pc, dy) - mul_rn(ps, dx)) / pm;
+        double axi, aeta, inva[4];
+        const int ea = dev_locate(A, xa, ya, axi, aeta, inva);
+        if (ea >= 0) {
+          const double w = fabs(detb) * c_qw[q];
+          const double eps_a = material_eps<PROFILE_A>(mat_a, xa, ya, PROFILE_A ? false : in_any_core(xa, ya, mat_a.cores.c, mat_a.ncore));
+          const double eps_b = material_eps<PROFILE_B>(mat_b, X, Y, PROFILE_B ? false : in_any_core(X, Y, mat_b.cores.c, mat_b.ncore));
+          wa = w * (1.0 / eps_a);
+          wb = w * (1.0 / eps_b);
+          double phi[6], hxx[6], hxy[6], hyy[6], invb[4];
+          p2_phi(axi, aeta, phi);
+          p2_basis_hess(inva, hxx, hxy, hyy);
+          for (int a = 0; a < 6; ++a) {
+            s_phi[a][tid] = phi[a];
+            s_ha[0][a][tid] = hxx[a]; s_ha[1][a][tid] = hxy[a]; s_ha[2][a][tid] = hyy[a];
+            s_ra[a][tid] = dev_row(A, ea, a);
+            s_rb[a][tid] = dev_row(B, e, a);
+          }
+          M.inverse(detb, invb);
+          p2_basis_hess(invb, hxx, hxy, hyy);
+          for (int a = 0; a < 6; ++a) { s_hb[0][a][tid] = hxx[a]; s_hb[1][a][tid] = hxy[a]; s_hb[2][a][tid] = hyy[a]; }
+        }
+      }
+      s_wa[tid] = wa;
+      s_wb[tid] = wb;
+      s_q[tid] = q;
+    }
+    __syncthreads();
+    // the features of every (point, mode): a lane holds both components, so that it can turn A's h and g
+    for (int idx = tid; idx < FT * OC; idx += 256) {
+      const int i = idx % OC, t = idx / OC;
+      const int q = s_q[t];
+      const bool la = ia0 + i < ka, lb = jb0 + i < kb;
+      double hax = 0.0, hay = 0.0, sax = 0.0, say = 0.0, hbx = 0.0, hby = 0.0, sbx = 0.0, sby = 0.0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const int ra = s_ra[a][t], rb = s_rb[a][t];
+        if (la && ra >= 0) {
+          const double vx = Va[(int64_t)ra * ka + ia0 + i], vy = Va1[(int64_t)ra * ka + ia0 + i];
+          const double ph = s_phi[a][t], hxy = s_ha[1][a][t];
+          hax += ph * vx;
+          hay += ph * vy;
+          sax += s_ha[0][a][t] * vx + hxy * vy;
+          say += hxy * vx + s_ha[2][a][t] * vy;
+        }
+        if (lb && rb >= 0) {
+          const double vx = Vb[(int64_t)rb * kb + jb0 + i], vy = Vb1[(int64_t)rb * kb + jb0 + i];
+          const double ph = p2_phi(a, c_qx[q], c_qy[q]), hxy = s_hb[1][a][t];   // B's basis at its own quadrature point q
+          hbx += ph * vx;
+          hby += ph * vy;
+          sbx += s_hb[0][a][t] * vx + hxy * vy;
+          sby += hxy * vx + s_hb[2][a][t] * vy;
+        }
+      }
+      const double gax = -sax, gay = -say;
+      s_fa[0][t][i] = mul_rn(pc, hax) - mul_rn(ps, hay);
+      s_fa[1][t][i] = mul_rn(ps, hax) + mul_rn(pc, hay);
+      s_fa[2][t][i] = mul_rn(pc, gax) - mul_rn(ps, gay);
+      s_fa[3][t][i] = mul_rn(ps, gax) + mul_rn(pc, gay);
+      s_fb[0][t][i] = hbx;
+      s_fb[1][t][i] = hby;
+      s_fb[2][t][i] = -sbx;
+      s_fb[3][t][i] = -sby;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < FT; ++t) {
+      double2 a[4], b[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        a[c] = *reinterpret_cast<const double2*>(&s_fa[c][t][2 * ti]);
+        b[c] = *reinterpret_cast<const double2*>(&s_fb[c][t][2 * tj]);
+      }
+      const double wa = s_wa[t], wb = s_wb[t];  // the same for every lane
+      FLUX_POSED_ACC(0, 0, x, x) FLUX_POSED_ACC(0, 1, x, y)
+      FLUX_POSED_ACC(1, 0, y, x) FLUX_POSED_ACC(1, 1, y, y)
+    }
+    __syncthreads();
+  }
+  const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+  for (int o = 0; o < FLUX_POSED_OUTPUTS; ++o) {
+    double* out = partial + ((((int64_t)blockIdx.z * FLUX_POSED_OUTPUTS + o) * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+    for (int r = 0; r < 2; ++r)
+      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
+  }
+}
+#undef FLUX_POSED_ACC
 
 // Coordinate-weighted Grams (plfem_moment_grams): the M_r (and K_r) of k_mode_grams weighted by the point's X = x - ox,
 // Y = y - oy, and the unweighted M by X^2, XY, Y^2.  Grid, tiling, staging and features as in k_mode_grams; the staging
@@ -1987,24 +2159,27 @@ struct PosedPlan {
   int nca, ncb, slices, batch;
   size_t off_partial, off_poses, total;   // bytes
 };
-PosedPlan posed_plan(int ne_b, int ka, int kb, int nposes) {
+// (`tile` points per tile of B and `nout` matrices per pose: OT and 1 for plfem_field_overlap_posed, FT and 4 for
+// plfem_flux_overlap_posed, whose results are [batch][nout][ka][kb] and partials [batch][nout][chunk pair][slice][OC * OC])
+PosedPlan posed_plan(int ne_b, int ka, int kb, int nposes, int tile = OT, int nout = 1) {
   PosedPlan p;
   p.nca = overlap_chunks(ka);
   p.ncb = overlap_chunks(kb);
-  const int64_t ntiles = ((int64_t)6 * ne_b + OT - 1) / OT;
+  const int64_t ntiles = ((int64_t)6 * ne_b + tile - 1) / tile;
   p.slices = (int)std::max<int64_t>(1, std::min<int64_t>(POSE_SLICES, ntiles));
-  const int64_t per_pose = (int64_t)sizeof(double) * ((int64_t)ka * kb + (int64_t)p.nca * p.ncb * p.slices * OC * OC + POSE_DOUBLES);
+  const int64_t per_pose = (int64_t)sizeof(double) * ((int64_t)nout * ka * kb + (int64_t)nout * p.nca * p.ncb * p.slices * OC * OC + POSE_DOUBLES);
   p.batch = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(nposes, POSE_BATCH), (POSE_SCRATCH - 768) / per_pose));
-  size_t o = align256(sizeof(double) * p.batch * ka * kb);
-  p.off_partial = o; o += align256(sizeof(double) * p.batch * p.nca * p.ncb * p.slices * OC * OC);
+  size_t o = align256(sizeof(double) * p.batch * nout * ka * kb);
+  p.off_partial = o; o += align256(sizeof(double) * p.batch * nout * p.nca * p.ncb * p.slices * OC * OC);
   p.off_poses = o;   o += align256(sizeof(double) * p.batch * POSE_DOUBLES);
   p.total = o;
   return p;
 }
-const char* posed_sizes(int ka, int kb, int nposes) {
+const char* posed_sizes(int ka, int kb, int nposes, int max_pairs = POSE_MAX_PAIRS) {
   if (ka < 1 || kb < 1) return "ka and kb must be >= 1";
   if (nposes < 1) return "nposes must be >= 1";
-  if ((int64_t)overlap_chunks(ka) * overlap_chunks(kb) > POSE_MAX_PAIRS) return "at most 256 pairs of 32-mode chunks";
+  if ((int64_t)overlap_chunks(ka) * overlap_chunks(kb) > max_pairs)
+    return max_pairs == POSE_MAX_PAIRS ? "at most 256 pairs of 32-mode chunks" : "at most 64 pairs of 32-mode chunks";
   return nullptr;
 }
 // every entry finite, m > 0, |c^2 + s^2 - 1| <= 1e-12
@@ -2155,12 +2330,16 @@ const char* material_error(const plfem_locator* L, double eps_core, double eps_c
 }
 
 // the kernels' Material; the layer table of a profile goes to the locator's device buffer on its stream (the call ends with
-// a stream synchronisation: the host table outlives the copy and nothing in flight reads the table of an earlier call)
+// a stream synchronisation: the host table outlives the copy and nothing in flight reads the table of an earlier call).
+// `owner`: the locator whose buffer carries the table when it is not L's own -- the second mesh of
+// plfem_flux_overlap_posed; the copy still runs on L's stream, which runs the call
 int stage_material(plfem_locator* L, const double* cores_host, int ncore, double eps_core, double eps_clad,
-                   const double* layers_host, int nlayer, double eps_bg, int use_profile, Material& mat) {
+                   const double* layers_host, int nlayer, double eps_bg, int use_profile, Material& mat,
+                   plfem_locator* owner = nullptr) {
+  double* d_layers = owner ? owner->d_layers : L->d_layers;
   if (use_profile && nlayer > 0)
-    HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
-  mat = Material{pack_cores(cores_host, ncore), ncore, eps_core, eps_clad, L->d_layers, use_profile ? nlayer : 0, eps_bg};
+    HIP_TRY(L, hipMemcpyAsync(d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
+  mat = Material{pack_cores(cores_host, ncore), ncore, eps_core, eps_clad, d_layers, use_profile ? nlayer : 0, eps_bg};
   return PLFEM_OK;
 }
 
@@ -2228,6 +2407,91 @@ extern "C" int plfem_sample_efields(plfem_locator* L, int32_t ncomp, int32_t k, 
   HIP_TRY(L, hipStreamSynchronize(L->stream));
   return PLFEM_OK;
 } catch (...) { return host_failure(L); }
+
+namespace {
+// Most chunk pairs of a posed flux call.  Four outputs make a pose's partials four times those of plfem_field_overlap_posed:
+// with 128 slices, 64 pairs are 256 MiB of them, so one pose of the largest call fits POSE_SCRATCH (256 pairs would not)
+constexpr int FLUX_POSE_MAX_PAIRS = 64;
+
+// one side's material of plfem_flux_overlap_posed: the rules of material_error, and no sampled map on its locator
+const char* flux_side_error(const plfem_locator* L, double eps_core, double eps_clad, const double* layers_host, int nlayer,
+                            double eps_bg, int use_profile) {
+  if (const char* bad = material_error(L, eps_core, eps_clad, layers_host, nlayer, eps_bg, use_profile)) return bad;
+  if (L->map.set()) return "the locator carries a sampled index map: maps are out of scope of this call (clear the map)";
+  return nullptr;
+}
+
+// f(std::true_type / std::false_type) by a run-time flag
+template <typename F>
+void with_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+}  // namespace
+
+extern "C" int plfem_flux_overlap_posed_work_bytes(const plfem_locator* Lb, int32_t ka, int32_t kb, int32_t nposes, int64_t* bytes) try {
+  if (!Lb || !bytes || posed_sizes(ka, kb, nposes, FLUX_POSE_MAX_PAIRS)) return PLFEM_EINVAL;
+  *bytes = (int64_t)posed_plan(Lb->ne, ka, kb, nposes, FT, FLUX_POSED_OUTPUTS).total;
+  return PLFEM_OK;
+} catch (...) { return host_failure(nullptr, 0); }
+
+extern "C" int plfem_flux_overlap_posed(plfem_locator* La, const double* modes_a_dev, int32_t ka, int32_t indexed_a,
+                                        const double* cores_a_host, int32_t ncore_a, double eps_core_a, double eps_clad_a,
+                                        const double* layers_a_host, int32_t nlayer_a, double eps_bg_a, int32_t use_profile_a,
+                                        plfem_locator* Lb, const double* modes_b_dev, int32_t kb, int32_t indexed_b,
+                                        const double* cores_b_host, int32_t ncore_b, double eps_core_b, double eps_clad_b,
+                                        const double* layers_b_host, int32_t nlayer_b, double eps_bg_b, int32_t use_profile_b,
+                                        int32_t nposes, const double* poses_host, void* work_dev, int64_t work_bytes,
+                                        double* out_host) try {
+  if (!La) return PLFEM_EINVAL;
+  FieldCall call{La, "plfem_flux_overlap_posed"};
+  TRY(call.pair(Lb));
+  if (const char* bad = posed_sizes(ka, kb, nposes, FLUX_POSE_MAX_PAIRS)) return call.reject(bad);
+  if (!ncore_ok(ncore_a, false) || !ncore_ok(ncore_b, false)) return call.reject("ncore of each side must be in [0, 64]");
+  if (!modes_a_dev || !modes_b_dev || !poses_host || !work_dev || !out_host || (ncore_a > 0 && !cores_a_host) ||
+      (ncore_b > 0 && !cores_b_host))
+    return call.reject("null array");
+  if (const char* bad = flux_side_error(La, eps_core_a, eps_clad_a, layers_a_host, nlayer_a, eps_bg_a, use_profile_a))
+    return call.reject(std::string("side A: ") + bad);
+  if (const char* bad = flux_side_error(Lb, eps_core_b, eps_clad_b, layers_b_host, nlayer_b, eps_bg_b, use_profile_b))
+    return call.reject(std::string("side B: ") + bad);
+  // each side's layer table travels through its own locator's buffer: one locator on both sides has one table
+  if (La == Lb && use_profile_a && use_profile_b &&
+      (nlayer_a != nlayer_b ||
+       (nlayer_a > 0 && std::memcmp(layers_a_host, layers_b_host, sizeof(double) * LAYER_DOUBLES * nlayer_a) != 0)))
+    return call.reject("one locator on both sides carries one layer table: the two profiles must have the same layers");
+  TRY(call.modes(indexed_a, indexed_b));
+  if (!poses_ok(poses_host, nposes))
+    return call.reject("every pose (tx, ty, c, s, m) must be finite with m > 0 and |c^2 + s^2 - 1| <= 1e-12");
+  const PosedPlan plan = posed_plan(Lb->ne, ka, kb, nposes, FT, FLUX_POSED_OUTPUTS);
+  TRY(call.work("plfem_flux_overlap_posed_work_bytes", work_dev, work_bytes, plan.total, plan.off_partial));
+  double* poses = (double*)((char*)work_dev + plan.off_poses);
+  Material mat_a, mat_b;
+  TRY(stage_material(La, cores_a_host, ncore_a, eps_core_a, eps_clad_a, layers_a_host, nlayer_a, eps_bg_a, use_profile_a, mat_a));
+  TRY(stage_material(La, cores_b_host, ncore_b, eps_core_b, eps_clad_b, layers_b_host, nlayer_b, eps_bg_b, use_profile_b, mat_b, Lb));
+  const int npair = plan.nca * plan.ncb;
+  const size_t per_pose = (size_t)FLUX_POSED_OUTPUTS * ka * kb;
+  // the batches follow each other on one stream, as in plfem_field_overlap_posed
+  for (int p0 = 0; p0 < nposes; p0 += plan.batch) {
+    const int nb = std::min(plan.batch, nposes - p0);
+    HIP_TRY(La, hipMemcpyAsync(poses, poses_host + (size_t)POSE_DOUBLES * p0, sizeof(double) * POSE_DOUBLES * nb,
+                               hipMemcpyHostToDevice, La->stream));
+    with_flag(use_profile_a != 0, [&](auto pa) {
+      with_flag(use_profile_b != 0, [&](auto pb) {
+        hipLaunchKernelGGL((k_flux_overlap_posed<decltype(pa)::value, decltype(pb)::value>), dim3(plan.slices, npair, nb),
+                           dim3(256), 0, La->stream, call.loc, call.loc_b, (int)ka, call.nrows, modes_a_dev, mat_a, (int)kb,
+                           call.nrows_b, modes_b_dev, mat_b, plan.ncb, poses, call.partial);
+      });
+    });
+    TRY(check_launch(La, "k_flux_overlap_posed"));
+    hipLaunchKernelGGL(k_overlap_reduce, dim3(npair, nb * FLUX_POSED_OUTPUTS, OC * OC / 256), dim3(256), 0, La->stream, (int)ka,
+                       (int)kb, plan.slices, plan.ncb, call.partial, call.O);
+    TRY(check_launch(La, "k_overlap_reduce"));
+    HIP_TRY(La, hipMemcpyAsync(out_host + per_pose * p0, call.O, sizeof(double) * per_pose * nb, hipMemcpyDeviceToHost, La->stream));
+  }
+  HIP_TRY(La, hipStreamSynchronize(La->stream));
+  return PLFEM_OK;
+} catch (...) { return host_failure(La); }
 
 namespace {
 // plfem_mode_indicators: the result [k][ne], then the element-neighbour table [3][ne] int32, then the k eigenvalues

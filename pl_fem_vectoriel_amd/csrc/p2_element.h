@@ -1,7 +1,7 @@
 // The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
 // integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
 // k_field_overlap, k_mode_grams, k_profile_grams, k_mode_quartic, k_mode_project, k_mode_project_sampled, k_core_owner,
-// k_mode_indicators, k_flux_grams, k_sample_efields).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// k_mode_indicators, k_flux_grams, k_sample_efields, k_flux_overlap_posed).  One definition, so that a quadrature point lands in the same region, and det J rounds
 // the same way, in the assembly and in every kernel that must reproduce it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -94,7 +94,7 @@ __device__ __forceinline__ void p2_hess(const double inv[4], const double u[6], 
 
 // physical second derivatives of the six basis functions themselves (constant over the element): the J^-1 products of
 // p2_hess applied to the reference Hessians listed there, for the kernels that contract them with many DOF vectors
-// (k_flux_grams, k_sample_efields)
+// (k_flux_grams, k_sample_efields, k_flux_overlap_posed)
 __device__ __forceinline__ void p2_basis_hess(const double inv[4], double hxx[6], double hxy[6], double hyy[6]) {
   const double h00[6] = {4.0, 4.0, 0.0, -8.0, 0.0, 0.0};
   const double h11[6] = {4.0, 0.0, 4.0, 0.0, 0.0, -8.0};

@@ -21,6 +21,9 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
 * :meth:`ModeFields.sample_e`, :meth:`ModeFields.flux_grams` -- the electric field and axial Poynting flux of vectorial
   modes at points (``plfem_sample_efields``) and the Grams their cross powers are built from (``plfem_flux_grams``): what
   :mod:`.power` builds modal power, power confinement and power orthogonality from;
+* :func:`flux_overlap_poses` -- the four beta-free sums of the E x H cross flux of two vectorial mode sets on two meshes
+  under a table of poses (``plfem_flux_overlap_posed``): what :mod:`.splice` builds power-normalised splice maps and
+  vectorial taper steps from;
 * :meth:`ModeFields.quartic` -- the packed overlap of products of four modes on a 16-point degree-8 rule
   (``plfem_mode_quartic``): what :mod:`.nonlinear` builds the nonlinear coupling tensor, A_eff and gamma from;
 * :meth:`ModeFields.project` -- the projection of the modes on plane waves and Gaussian beams, fields that separate in
@@ -53,7 +56,9 @@ FLUX_GRAM_NAMES = ("M_w_core", "M_w_rest", "G_w_core", "G_w_rest")      # vector
 MOMENT_GRAM_NAMES = {"vectorial": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "K_core_X", "K_core_Y", "K_clad_X",
                                    "K_clad_Y", "M_XX", "M_XY", "M_YY"),
                      "scalar": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "M_XX", "M_XY", "M_YY")}
+FLUX_OVERLAP_NAMES = ("MA", "GA", "MB", "GB")                           # plfem_flux_overlap_posed, per pose
 POSE_MAX_CHUNK_PAIRS = 256         # POSE_MAX_PAIRS of csrc/kernels_fields.hip: pairs of 32-mode chunks per posed call
+FLUX_POSE_MAX_CHUNK_PAIRS = 64     # FLUX_POSE_MAX_PAIRS: the same per posed flux call
 PROJECT_TILE = (8, 8)              # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
 PROJECT_MAX_FACTORS = 4096         # PJ_LMAX
 PROJECT_SAMPLED_TILE = 32          # PS_F: frames per workgroup tile of the sampled projection
@@ -926,6 +931,58 @@ def mode_overlap_poses(modes_a: Sequence[Dict], mesh_a, modes_b: Sequence[Dict],
     return out * out / (P[:, 4, None, None] ** 2 * daa[None, :, None] * dbb[None, None, :])
 
 
-__all__ = ["ModeFields", "mode_overlap", "mode_overlap_poses", "pose_table", "POSE_MAX_CHUNK_PAIRS", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES", "PROFILE_GRAM_NAMES", "FLUX_GRAM_NAMES",
+def flux_overlap_poses(modes_a: Sequence[Dict], mesh_a, geometry_a, modes_b: Sequence[Dict], mesh_b, geometry_b, poses,
+                       device: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """The four raw matrices of the posed cross flux of two vectorial mode sets (``plfem_flux_overlap_posed``), each (T,
+    ka, kb), under the pose table of :func:`mode_overlap_poses`: with ``hA' = R hA``, ``gA' = R gA`` at B's quadrature
+    point taken into A's frame (``g = -grad (dx hx + dy hy)``, element-wise second derivatives as in
+    :meth:`ModeFields.flux_grams`), B's own ``hB``, ``gB``, ``wA = 1 / eps`` of ``geometry_a`` at the point in A's frame and
+    ``wB = 1 / eps`` of ``geometry_b`` at B's point,
+
+    ``MA = sum wA hA'_i . hB_j``, ``GA = sum wA gA'_i . hB_j``, ``MB = sum wB hA'_i . hB_j``, ``GB = sum wB hA'_i . gB_j``
+
+    over mesh B's six-point rule.  They are free of beta, k0 and the magnification:
+    :func:`.splice.flux_transfer_from_grams` makes the power-normalised transfer from them.  Each geometry is marshalled as
+    for :meth:`ModeFields.flux_grams` (its index profile if it carries one, else its discs at ``n_core`` on ``n_clad``); a
+    profile with a sampled map is not supported.  Record checks and :class:`ModeFields` reuse as in
+    :func:`mode_overlap_poses`; at most 64 pairs of 32-mode chunks.  A scalar record, a sampled map and every other
+    argument error raise ``ValueError`` before any device call."""
+    ka_kind, va, _ = _records(modes_a)
+    kb_kind, vb, _ = _records(modes_b)
+    if "scalar" in (ka_kind, kb_kind):
+        raise ValueError("flux_overlap_poses: the electric field needs vectorial records")
+    P = _poses(poses)
+    fa = _as_fields(mesh_a, device)
+    fb = fa if (mesh_b is mesh_a or (not isinstance(mesh_b, ModeFields) and not isinstance(mesh_a, ModeFields)
+                                     and mesh_key(mesh_b) == mesh_key(mesh_a))) else _as_fields(mesh_b, device)
+    mat_a, mat_b = fa._material(geometry_a), fb._material(geometry_b)
+    if mat_a.index_map is not None or mat_b.index_map is not None:
+        raise ValueError("flux_overlap_poses: an index profile with a sampled map is not supported")
+    _, va, _ = fa._check_records(modes_a)
+    _, vb, _ = fb._check_records(modes_b)
+    ka, kb = (0 if v is None else v.shape[1] for v in (va, vb))
+    T = P.shape[0]
+    if ka == 0 or kb == 0:
+        return {nm: np.zeros((T, ka, kb), dtype=np.float64) for nm in FLUX_OVERLAP_NAMES}
+    if ((ka + 31) // 32) * ((kb + 31) // 32) > FLUX_POSE_MAX_CHUNK_PAIRS:
+        raise ValueError(f"at most {FLUX_POSE_MAX_CHUNK_PAIRS} pairs of 32-mode chunks per posed flux overlap, got ka = {ka}, "
+                         f"kb = {kb}")
+    fa._ensure_locator()
+    fb._ensure_locator()
+    if fa.device != fb.device:
+        raise ValueError("both meshes must be evaluated on one device")
+    sa, sb = fa._stage(va)[0], fb._stage(vb)[0]
+    fa._set_index_map(None)                      # a cached locator carries no map into this call
+    fb._set_index_map(None)
+    out = np.empty((T, len(FLUX_OVERLAP_NAMES), ka, kb), dtype=np.float64)
+    fb.stream.synchronize()                     # (B's staging ran on B's stream; the overlap runs on A's)
+    fa._work_call("plfem_flux_overlap_posed_work_bytes", {"ka": ka, "kb": kb, "nposes": T}, "plfem_flux_overlap_posed",
+                  (fa._loc, sa.data_ptr(), ka, 1, *fa._material_args(mat_a), fb._loc, sb.data_ptr(), kb, 1,
+                   *fb._material_args(mat_b), T, _native._ptr(P)), (out,), loc=fb._loc)
+    return {nm: np.ascontiguousarray(out[:, i]) for i, nm in enumerate(FLUX_OVERLAP_NAMES)}
+
+
+__all__ = ["ModeFields", "mode_overlap", "mode_overlap_poses", "pose_table", "flux_overlap_poses", "FLUX_OVERLAP_NAMES",
+           "FLUX_POSE_MAX_CHUNK_PAIRS", "POSE_MAX_CHUNK_PAIRS", "LOC_TOL", "GRAM_NAMES", "CORE_GRAM_NAMES", "MOMENT_GRAM_NAMES", "PROFILE_GRAM_NAMES", "FLUX_GRAM_NAMES",
            "PROJECT_TILE", "PROJECT_MAX_FACTORS", "PROJECT_SAMPLED_TILE", "PROJECT_SAMPLED_MAX_FRAMES",
            "PROJECT_SAMPLED_MAX_PIXELS"]

@@ -12,6 +12,12 @@ mesh A relative to mesh B in one GPU call; the rest is host math on ka x kb matr
 
 This is plain overlap projection: what is not captured by set B is lost, reflections and the admittance factor ``2
 sqrt(beta_a beta_b) / (beta_a + beta_b)`` of a step are neglected.  Lengths are in um.
+
+For vectorial records the H.H overlap above is not the power inner product: the physically
+meaningful transfer is the cross flux ``int (E_a x H_b + E_b x H_a) . z`` over the modal powers.
+:func:`.fields.flux_overlap_poses` returns its four beta-free sums per pose, :func:`flux_transfer_from_grams` is the host
+math on them (with each set Loewdin-orthonormalised under its cross powers when those are given as a matrix), :func:`splice_power_map` and :func:`taper_transfer_vectorial` are the counterparts of :func:`splice_map` and
+:func:`taper_transfer`.  Reflections and the backward modes stay neglected there too.
 """
 from __future__ import annotations
 
@@ -19,7 +25,8 @@ from typing import Dict, Sequence
 
 import numpy as np
 
-from .fields import ModeFields, _records, mode_overlap, mode_overlap_poses, pose_table
+from .fields import ModeFields, _records, flux_overlap_poses, mode_overlap, mode_overlap_poses, pose_table
+from .power import power_quantities_from_grams
 
 
 def _inv_sqrt(G, name: str) -> np.ndarray:
@@ -217,4 +224,230 @@ def taper_transfer(modes_list, mesh, scales, lengths, k0: float, device=None) ->
     return res
 
 
-__all__ = ["splice_quantities_from_overlaps", "splice_map", "taper_from_interfaces", "taper_transfer"]
+def _vector(v, n: int, name: str) -> np.ndarray:
+    try:
+        a = np.asarray(v, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be {n} numbers") from None
+    if a.size != n or not np.all(np.isfinite(a)):
+        raise ValueError(f"{name} must be {n} finite numbers")
+    return a
+
+
+def _power(p, n: int, name: str) -> np.ndarray:
+    """The powers of a set of n modes: a finite vector (n,), or a finite symmetric matrix (n, n) of cross powers."""
+    try:
+        a = np.asarray(p, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be {n} numbers or an ({n}, {n}) matrix") from None
+    if a.ndim == 2 and a.shape == (n, n) and (n > 1 or np.ndim(p) == 2):
+        if not np.all(np.isfinite(a)) or np.abs(a - a.T).max() > 1e-12 * np.abs(a).max():
+            raise ValueError(f"{name} as a matrix must be finite and symmetric (cross_sym of mode_power)")
+        return a
+    return _vector(a, n, name)
+
+
+def _inv_sqrt_abs(p: np.ndarray) -> np.ndarray:
+    """``1 / sqrt(|p|)`` entry by entry, 0 where p is 0."""
+    live = p != 0
+    return np.where(live, 1.0 / np.sqrt(np.abs(np.where(live, p, 1.0))), 0.0)
+
+
+def flux_transfer_from_grams(MA, GA, MB, GB, beta_a, k0_a, beta_b, k0_b, power_a, power_b, scale=1.0) -> Dict[str, np.ndarray]:
+    """The host math of :func:`splice_power_map`: a pure function of the four posed flux sums ``MA``, ``GA``, ``MB``, ``GB``
+    of :func:`.fields.flux_overlap_poses`, each (T, ka, kb) (or one (ka, kb) matrix), the propagation constants and vacuum
+    wavenumbers each set was solved with, the modal powers ``power_a`` (ka,), ``power_b`` (kb,) of each set on its own mesh
+    (``power`` of :func:`.power.mode_power`), and the magnification ``scale`` = m of each pose (a number or (T,))::
+
+        X_ab = (beta_a[:, None] MA + GA / beta_a[:, None]) / k0_a         int (E_a' x H_b) . z
+        X_ba = (beta_b[None, :] MB + GB / beta_b[None, :]) / k0_b         int (E_b x H_a') . z
+        T[j, i] = (X_ab + X_ba)[i, j] / (4 m sqrt(|P_a,i| |P_b,j|))
+
+    A field magnified by m has every wavenumber divided by m and ``g`` divided by m^2, so its E is A's own E turned and its
+    power is ``m^2 P_a``; the two sets meet at one optical frequency, so ``k0_a / m`` must equal ``k0_b`` to 1e-9 relative
+    (``ValueError`` otherwise).  A mode of zero power gives a zero row or column, as in
+    :func:`.power.power_quantities_from_grams`.
+
+    With power vectors the modes of a set are taken as they are: ``transfer`` is the matrix of normalised cross fluxes, and
+    it is the transfer between the two sets only as far as the modes of each are power-orthogonal.  Either power may
+    instead be the set's symmetrised cross-power matrix, (ka, ka) or (kb, kb) (``cross_sym`` of :func:`.power.mode_power`),
+    whose diagonal is the power vector: the set is then Loewdin-orthonormalised under it, as
+    :func:`splice_quantities_from_overlaps` orthonormalises under the self-Gram::
+
+        T = P_b^(-1/2) (X_ab + X_ba)^T P_a^(-1/2) / (4 m)
+
+    which takes amplitudes on the power-orthonormalised set A to amplitudes on the power-orthonormalised set B; a set
+    onto itself at the identity pose gives the identity whatever its cross powers are, and a diagonal matrix gives the
+    vector formula.  ``ValueError`` unless such a matrix is symmetric positive definite (a set with a backward or a
+    powerless mode has no such basis).
+
+    Returns ``transfer`` (T, kb, ka); ``power`` = ``|transfer|^2``; ``singular_values`` (T, min(ka, kb)), descending;
+    ``IL_dB`` and ``MDL_dB`` (T,) as in :func:`splice_quantities_from_overlaps`.  Single (ka, kb) matrices give the same
+    without the leading axis."""
+    try:
+        G = [np.asarray(g, dtype=np.float64) for g in (MA, GA, MB, GB)]
+    except (TypeError, ValueError):
+        raise ValueError("MA, GA, MB and GB must be real arrays") from None
+    single = G[0].ndim == 2
+    if single:
+        G = [g[None] if g.ndim == 2 else g for g in G]
+    if G[0].ndim != 3 or G[0].shape[1] < 1 or G[0].shape[2] < 1 or any(g.shape != G[0].shape for g in G):
+        raise ValueError("MA, GA, MB and GB must have one shape, (T, ka, kb) or (ka, kb)")
+    if not all(np.all(np.isfinite(g)) for g in G):
+        raise ValueError("MA, GA, MB and GB must be finite")
+    nT, ka, kb = G[0].shape
+    ba, bb = _vector(beta_a, ka, "beta_a"), _vector(beta_b, kb, "beta_b")
+    if np.any(ba == 0) or np.any(bb == 0):
+        raise ValueError("every beta must be finite and non-zero")
+    pa, pb = _power(power_a, ka, "power_a"), _power(power_b, kb, "power_b")
+    k0a, k0b = _number(k0_a, "k0_a", positive=True), _number(k0_b, "k0_b", positive=True)
+    try:
+        m = np.broadcast_to(np.asarray(scale, dtype=np.float64), (nT,))
+    except (TypeError, ValueError):
+        raise ValueError("scale must be a positive number or one per pose") from None
+    if not np.all(np.isfinite(m) & (m > 0)):
+        raise ValueError("scale must be finite and > 0")
+    if np.any(np.abs(k0a / m - k0b) > 1e-9 * k0b):
+        raise ValueError("k0_a / scale must equal k0_b to 1e-9 relative: a set magnified by m stands at the wavenumber k0_a / m, "
+                         f"got k0_a = {k0a}, k0_b = {k0b}, scale = {m.tolist() if nT > 1 else float(m[0])}")
+    X_ab = (ba[None, :, None] * G[0] + G[1] / ba[None, :, None]) / k0a
+    X_ba = (bb[None, None, :] * G[2] + G[3] / bb[None, None, :]) / k0b
+    if pa.ndim == 1 and pb.ndim == 1:
+        na, nb = _inv_sqrt_abs(pa), _inv_sqrt_abs(pb)
+        T = ((X_ab + X_ba) * na[None, :, None] * nb[None, None, :] / (4.0 * m[:, None, None])).transpose(0, 2, 1)
+    else:
+        Na = np.diag(_inv_sqrt_abs(pa)) if pa.ndim == 1 else _inv_sqrt(pa, "power_a")
+        Nb = np.diag(_inv_sqrt_abs(pb)) if pb.ndim == 1 else _inv_sqrt(pb, "power_b")
+        T = (Nb @ (X_ab + X_ba).transpose(0, 2, 1) @ Na) / (4.0 * m[:, None, None])
+    sv = np.linalg.svd(T, compute_uv=False)
+    il, mdl = _db_of_singular_values(sv)
+    res = {"transfer": T, "singular_values": sv, "IL_dB": il, "MDL_dB": mdl, "power": T * T}
+    return {nm: v[0] for nm, v in res.items()} if single else res
+
+
+def _k0_of(geometry, name: str) -> float:
+    try:
+        return _number(geometry.k0, f"{name}.k0", positive=True)
+    except AttributeError:
+        raise ValueError(f"{name} must have k0") from None
+
+
+def _betas_of(modes, what: str) -> np.ndarray:
+    try:
+        b = np.array([float(m["beta"]) for m in modes], dtype=np.float64)
+    except (KeyError, TypeError, ValueError):
+        raise ValueError(f"every record of {what} needs a numeric 'beta'") from None
+    if not np.all(np.isfinite(b) & (b != 0)):
+        raise ValueError(f"every record of {what} needs a finite, non-zero 'beta'")
+    return b
+
+
+def _vectorial(modes, what: str) -> list:
+    try:
+        modes = list(modes)
+    except TypeError:
+        raise ValueError(f"{what} must be a list of mode records") from None
+    kind, _, _ = _records(modes)
+    if kind is None:
+        raise ValueError(f"{what} has no mode records")
+    if kind != "vectorial":
+        raise ValueError(f"{what}: the power-normalised transfer needs vectorial records (scalar ones: splice_map, taper_transfer)")
+    return modes
+
+
+def splice_power_map(modes_a: Sequence[Dict], mesh_a, geometry_a, modes_b: Sequence[Dict], mesh_b, geometry_b, dx, dy,
+                     angle: float = 0.0, scale: float = 1.0, orthonormalize: bool = True, device=None) -> Dict[str, np.ndarray]:
+    """Power-normalised splice of the vectorial mode set A (on ``mesh_a``, solved with ``geometry_a``) to set B on the grid
+    of lateral offsets ``dx`` (nx,) x ``dy`` (ny,) (um), A turned by ``angle`` (rad) and magnified by ``scale``: one
+    :func:`.fields.flux_overlap_poses` call for all ny nx poses plus the power quantities of each side
+    (:func:`.power.mode_power`: one ``flux_grams`` call each), then :func:`flux_transfer_from_grams` (see there for every
+    returned quantity and for ``geometry_a.k0 / scale == geometry_b.k0``), each with the leading axes (ny, nx); also
+    ``grams`` (the four raw sums, each (ny, nx, ka, kb)), ``power_a``, ``power_b``, ``cross_a``, ``cross_b`` (the symmetrised
+    cross powers), ``dx``, ``dy``.
+
+    ``orthonormalize=True``: each set is Loewdin-orthonormalised under its symmetrised cross powers, as :func:`splice_map`
+    orthonormalises under the self-overlap, so that the solver's records need not be power-orthogonal (they are not, to a
+    few per cent on coarse meshes) and a set spliced onto itself at zero offset gives the identity; ``ValueError`` when a
+    set's cross-power matrix is not positive definite.  ``orthonormalize=False``: the modes as they are, each divided by
+    the root of its own power.
+
+    Each geometry gives its side's material (its index profile if it carries one, without a sampled map, else its
+    discs) and k0.  An offset that takes A off B's mesh gives exact zeros.  Reflections are neglected.  Argument errors
+    raise ``ValueError`` before anything touches the device."""
+    x, y = _axis(dx, "dx"), _axis(dy, "dy")
+    ang, m = _number(angle, "angle"), _number(scale, "scale", positive=True)
+    modes_a, modes_b = _vectorial(modes_a, "modes_a"), _vectorial(modes_b, "modes_b")
+    ba, bb = _betas_of(modes_a, "modes_a"), _betas_of(modes_b, "modes_b")
+    k0a, k0b = _k0_of(geometry_a, "geometry_a"), _k0_of(geometry_b, "geometry_b")
+    if abs(k0a / m - k0b) > 1e-9 * k0b:
+        raise ValueError(f"geometry_a.k0 / scale must equal geometry_b.k0 to 1e-9 relative, got {k0a}, {k0b} and scale = {m}")
+    fa = mesh_a if isinstance(mesh_a, ModeFields) else ModeFields(mesh_a, device=device)
+    fb = fa if mesh_b is mesh_a else (mesh_b if isinstance(mesh_b, ModeFields) else ModeFields(mesh_b, device=device))
+    poses = pose_table(x[None, :], y[:, None], ang, m)     # row iy nx + ix
+    G = flux_overlap_poses(modes_a, fa, geometry_a, modes_b, fb, geometry_b, poses)
+    qa = power_quantities_from_grams(fa.flux_grams(modes_a, geometry_a), ba, k0a)
+    qb = qa if (fb is fa and modes_b is modes_a and geometry_b is geometry_a) else \
+        power_quantities_from_grams(fb.flux_grams(modes_b, geometry_b), bb, k0b)
+    pa, pb = (qa["cross_sym"], qb["cross_sym"]) if orthonormalize else (qa["power"], qb["power"])
+    res = flux_transfer_from_grams(G["MA"], G["GA"], G["MB"], G["GB"], ba, k0a, bb, k0b, pa, pb, m)
+    res = {nm: v.reshape((y.size, x.size) + v.shape[1:]) for nm, v in res.items()}
+    res.update(grams={nm: v.reshape((y.size, x.size) + v.shape[1:]) for nm, v in G.items()}, power_a=qa["power"],
+               power_b=qb["power"], cross_a=qa["cross_sym"], cross_b=qb["cross_sym"], dx=x, dy=y)
+    return res
+
+
+def taper_transfer_vectorial(modes_list, mesh, geometry, scales, lengths, k0: float, device=None) -> Dict:
+    """:func:`taper_transfer` for vectorial records, with power-normalised interfaces.
+
+    Section i is the cross-section of ``mesh`` and ``geometry`` magnified by ``scales[i]``, of length ``lengths[i]`` (um), at
+    the vacuum wavenumber ``k0`` (1 / um).  The scaling equivalence of :func:`taper_transfer` holds for the vectorial pencil
+    too (its curl and divergence forms K and D are scale invariant in 2-D, both mass forms scale by s^2): ``modes_list[i]``
+    are the records solved on ``mesh`` itself at the wavenumber ``k0 scales[i]`` (the geometry's wavelength divided by
+    ``scales[i]``), whose ``beta`` is ``scales[i]`` times the section's own.  Interface i is one posed flux overlap of
+    ``modes_list[i]`` (set A, magnification ``scales[i] / scales[i+1]``, no shift, no rotation) on ``modes_list[i+1]`` (set B)
+    through :func:`flux_transfer_from_grams`, with the modal powers of each section from its own flux Grams; the mode
+    counts may differ.  The product is :func:`taper_from_interfaces` with ``betas[i] = beta / scales[i]``; also
+    ``interfaces``, ``betas``, ``interface_IL_dB`` and ``powers``.
+
+    Reflections at the steps and the backward modes are neglected, what a step scatters out of the next section's set is
+    lost, and the modes of a section are not assumed power-orthogonal.  ``geometry`` gives the material only (its index
+    profile without a sampled map, else its discs).  ``ValueError`` for scalar records and malformed arguments, before
+    anything touches the device."""
+    try:
+        sections = [list(m) for m in modes_list]
+        s = np.asarray(scales, dtype=np.float64).reshape(-1)
+        L = np.asarray(lengths, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("modes_list must be a list of record lists, scales and lengths 1-D arrays of numbers") from None
+    n = len(sections)
+    if n < 1 or s.size != n or L.size != n:
+        raise ValueError("modes_list, scales and lengths must have one entry per section")
+    if not np.all(np.isfinite(s) & (s > 0)) or not np.all(np.isfinite(L) & (L >= 0)):
+        raise ValueError("scales must be finite and > 0, lengths finite and >= 0")
+    k0 = _number(k0, "k0", positive=True)
+    sections = [_vectorial(modes, f"section {i}") for i, modes in enumerate(sections)]
+    rec_betas = [_betas_of(modes, f"section {i}") for i, modes in enumerate(sections)]
+    mf = mesh if isinstance(mesh, ModeFields) else ModeFields(mesh, device=device)
+    mat = mf._material(geometry)                             # the material, before the device
+    if mat.index_map is not None:
+        raise ValueError("taper_transfer_vectorial: an index profile with a sampled map is not supported")
+    for modes in sections:
+        mf._check_records(modes)                             # lengths, before the device
+    powers = [power_quantities_from_grams(mf.flux_grams(modes, geometry), b, k0 * si)["power"]
+              for modes, b, si in zip(sections, rec_betas, s)]
+    Ts, ils = [], []
+    for i in range(n - 1):
+        m = s[i] / s[i + 1]
+        G = flux_overlap_poses(sections[i], mf, geometry, sections[i + 1], mf, geometry, pose_table(scale=m))
+        q = flux_transfer_from_grams(G["MA"][0], G["GA"][0], G["MB"][0], G["GB"][0], rec_betas[i], k0 * s[i], rec_betas[i + 1],
+                                     k0 * s[i + 1], powers[i], powers[i + 1], m)
+        Ts.append(q["transfer"])
+        ils.append(float(q["IL_dB"]))
+    betas = [b / si for b, si in zip(rec_betas, s)]
+    res = taper_from_interfaces(Ts, betas, L)
+    res.update(interfaces=Ts, betas=betas, interface_IL_dB=np.array(ils), powers=powers)
+    return res
+
+
+__all__ = ["splice_quantities_from_overlaps", "splice_map", "taper_from_interfaces", "taper_transfer", "flux_transfer_from_grams",
+           "splice_power_map", "taper_transfer_vectorial"]
