@@ -529,6 +529,50 @@ int plfem_moment_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const doubl
                        const double* cores_host, int32_t ncore, const double origin_host[2], void* work_dev,
                        int64_t work_bytes, double* out_host);
 
+/* Tangent Grams of a profile solve: the M_w (and K_w) of plfem_profile_grams under a batch of point weights ("columns")
+ * in place of w.  Modes, indexed, layers_host, nlayer, eps_bg and the locator's sampled map as for plfem_profile_grams.
+ * Both pencils are linear in the VALUES of the profile at fixed shapes (eps_bg, eps_a and eps_b of every layer, every
+ * pixel of the map), so a first-order change of those values -- a tangent -- is a profile with the same layers and the
+ * same grid: tangents_host[t] = (d_eps_bg, then (d_eps_a, d_eps_b) of every layer), and optionally a map of d eps on the
+ * locator's map grid, tangent_maps_host[tangent_map_host[t]] (tangent_map_host may be null when nmap = 0; nmap > 0 needs
+ * a map on the locator).  At a quadrature point, as the assembly forms it, d eps_t is d_eps_a + (d_eps_b - d_eps_a) t^g in
+ * the topmost layer that holds the point (d_eps_a for a constant layer: g = 0; membership, t and g of the profile);
+ * otherwise, inside the closed extent of the locator's map, the bilinear interpolant of the tangent's map -- or
+ * tangents[t][0] if it has none --; otherwise tangents[t][0].  With w = 1 / eps (ncomp = 2) or w = eps (ncomp = 1) formed
+ * as plfem_profile_grams forms it, column t < ntan has the point weight dw_t = -(d eps_t w) w (ncomp = 2) or d eps_t
+ * (ncomp = 1); with moments != 0 two more columns follow, w X and w Y, X = x - origin_host[0], Y = y - origin_host[1]
+ * (origin_host is always read).  Every sum over the six-point rule with |det J| w_q and the column's weight c:
+ *   ncomp = 2: out_host[col][0..1][k][k] = M_col, K_col with M_col[m][n] = sum c (hx_m hx_n + hy_m hy_n) and K_col the
+ *     form of K_r of plfem_mode_grams under c: d(V^T B V) = M_col and d(V^T A V) = K_col along tangent col; a bend of
+ *     curvature kappa along X moves the pencil by -2 kappa (K_wX, M_wX);
+ *   ncomp = 1: out_host[col][0][k][k] = M_col: d(V^T A V) = -k0^2 M_col, and -2 kappa k0^2 M_wX for a bend.
+ * The unweighted moments (centroids, widths) carry no material: plfem_moment_grams with ncore = 0 has them.
+ * Columns go in groups of 4.  Per group: a pre-pass with one lane per quadrature point walks the layer table once, forms
+ * w and writes the group's four weights of the point; a Gram kernel with the grid and tiling of plfem_mode_grams forms
+ * the unweighted products m = u . u' and kk (the form of K_r) of a point once and adds them, times each column's
+ * weight, to that column's partial blocks; the fixed-order second stage of plfem_field_overlap sums them.  The same bits
+ * on every run, for a subset or a permutation of the modes, whatever the work buffer held before, and for a column
+ * whatever other columns share the call and however they fall into groups.  Synchronises the locator's stream.
+ * work_dev: device scratch of plfem_profile_tangent_gram_work_bytes(loc, ncomp, k, ntan, nmap, moments) bytes, 256-byte
+ * aligned, every part rounded up to 256 bytes: the result, ncol nout k^2 doubles (ncol = ntan + 2 for moments, nout = 2 or
+ * 1); the partials of one group, 4 nout ceil(k / 32)^2 x 768 blocks of 8 KiB (48 MiB for ncomp = 2 up to k = 32, 432 MiB at
+ * k = 70); 4 x 6 ne point weights; ntan x 129 doubles of tangent rows; ntan int32; nmap nx ny doubles of tangent maps (the
+ * locator's grid), the last three at least one entry each.  So bytes <= 8 (ncol nout k^2 + 4 nout ceil(k / 32)^2 786432 +
+ * 24 ne + 129 max(ntan, 1) + max(nmap nx ny, 1)) + 4 max(ntan, 1) + 6 x 256.
+ * Argument errors (ncomp not 1 or 2, k < 1, ntan outside [0, 256], ntan + 2 moments < 1, nmap outside [0, min(ntan, 8)],
+ * nmap > 0 without a map on the locator, a table plfem_set_index_profile rejects, a null pointer, a map index outside
+ * [-1, nmap), a tangent entry or an origin that is not finite, work_bytes too small) return PLFEM_EINVAL with the
+ * locator's last error set. */
+int plfem_profile_tangent_gram_work_bytes(const plfem_locator* loc, int32_t ncomp, int32_t k, int32_t ntan, int32_t nmap,
+                                          int32_t moments, int64_t* bytes);
+int plfem_profile_tangent_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                const double* layers_host, int32_t nlayer, double eps_bg,
+                                const double* tangents_host /* [ntan][1 + 2 nlayer] */, int32_t ntan,
+                                const double* tangent_maps_host /* [nmap][ny][nx] or NULL */, int32_t nmap,
+                                const int32_t* tangent_map_host /* [ntan]: index into the maps, or -1 */,
+                                int32_t moments, const double origin_host[2],
+                                void* work_dev, int64_t work_bytes, double* out_host);
+
 /* Quartic mode-overlap tensor of k staged modes over the locator's mesh (the input of multimode nonlinear propagation:
  * f_ijkl, A_eff, gamma), on the 16-point degree-8 rule (products of four P2 fields are of degree 8).  Pairs i <= j are
  * numbered p(i,j) = i k - i (i - 1) / 2 + (j - i), np = k (k + 1) / 2.

@@ -7,7 +7,9 @@ from .nonlinear import mode_nonlinearity  # noqa: F401
 from .launch import encircled_na, far_field, field_coupling, gaussian_coupling  # noqa: F401
 from .cores import core_decomposition, core_quantities_from_grams  # noqa: F401
 from .bend import bend_propagate, bend_quantities_from_grams, bend_response  # noqa: F401
-from .profile import IndexProfile, ProfiledGeometry  # noqa: F401
+from .profile import IndexProfile, ProfileTangent, ProfiledGeometry  # noqa: F401
+from .profile_response import (profile_bend_from_grams, profile_bend_response, profile_dispersion,  # noqa: F401
+                               profile_dispersion_from_grams, profile_sensitivity, profile_sensitivity_from_grams)
 from .adapt import adaptive_solve, mark_elements, mode_error_indicators, refine_marked  # noqa: F401
 from .splice import (flux_transfer_from_grams, splice_map, splice_power_map, splice_quantities_from_overlaps,  # noqa: F401
                      taper_from_interfaces, taper_transfer, taper_transfer_vectorial)
@@ -19,4 +21,5 @@ __all__ = ["MCFGeometry", "PhotonicLanternGeometry", "mcf_positions", "TriMesh",
            "ProfiledGeometry", "mode_overlap_poses", "pose_table", "splice_map", "splice_quantities_from_overlaps",
            "taper_from_interfaces", "taper_transfer", "mode_error_indicators", "mark_elements", "refine_marked", "adaptive_solve",
            "mode_power", "power_quantities_from_grams", "Z0_OHM", "flux_overlap_poses", "flux_transfer_from_grams",
-           "splice_power_map", "taper_transfer_vectorial"]
+           "splice_power_map", "taper_transfer_vectorial", "ProfileTangent", "profile_dispersion", "profile_dispersion_from_grams",
+           "profile_sensitivity", "profile_sensitivity_from_grams", "profile_bend_response", "profile_bend_from_grams"]

@@ -48,6 +48,7 @@ EXPORTS = (
     "plfem_set_index_map", "plfem_locator_set_index_map",
     "plfem_flux_gram_work_bytes", "plfem_flux_grams", "plfem_sample_efields",
     "plfem_flux_overlap_posed_work_bytes", "plfem_flux_overlap_posed",
+    "plfem_profile_tangent_gram_work_bytes", "plfem_profile_tangent_grams",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -254,6 +255,8 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_locator_set_index_map.argtypes = lib.plfem_set_index_map.argtypes
     lib.plfem_profile_gram_work_bytes.argtypes = [i32, i32] + size
     lib.plfem_profile_grams.argtypes = head + [vp, i32, f64] + tail
+    lib.plfem_profile_tangent_gram_work_bytes.argtypes = [vp, i32, i32, i32, i32, i32] + size
+    lib.plfem_profile_tangent_grams.argtypes = head + [vp, i32, f64, vp, i32, vp, i32, vp, i32, vp] + tail
     lib.plfem_quartic_work_bytes.argtypes = [i32, i32] + size
     lib.plfem_mode_quartic.argtypes = head + [vp, i32, f64, f64] + tail
     lib.plfem_project_work_bytes.argtypes = [i32] * 4 + size

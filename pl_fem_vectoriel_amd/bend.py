@@ -116,10 +116,19 @@ def bend_quantities_from_grams(kind: str, moment_grams: Dict[str, np.ndarray], g
         B1 = np.zeros_like(A1)
         mu, sgn = -beta ** 2, -1.0
 
+    return _bend_from_pencil(kind, A, B, A1, B1, mu, sgn, beta, k0, M, P["M_core_X"] + P["M_clad_X"], P["M_core_Y"] + P["M_clad_Y"],
+                             P["M_XX"], P["M_XY"], P["M_YY"], kappa, ang, angle, cluster_rtol)
+
+
+def _bend_from_pencil(kind, A, B, A1, B1, mu, sgn, beta, k0, M, MX, MY, MXX, MXY, MYY, kappa, ang, angle, cluster_rtol) -> Dict:
+    """What :func:`bend_quantities_from_grams` makes of the projected pencil ``(A, B)`` of the records, its curvature
+    derivatives ``A1``, ``B1`` (2, k, k) and the unweighted Grams ``M``, ``MX`` .. ``MYY`` of the beam moments; ``kappa``,
+    ``ang`` from :func:`_curvature_and_angle` (shared with :mod:`.profile_response`)."""
+    k = beta.size
     dm = np.diag(M)
-    cx = np.diag(P["M_core_X"] + P["M_clad_X"]) / dm
-    cy = np.diag(P["M_core_Y"] + P["M_clad_Y"]) / dm
-    sxx, sxy, syy = np.diag(P["M_XX"]) / dm - cx * cx, np.diag(P["M_XY"]) / dm - cx * cy, np.diag(P["M_YY"]) / dm - cy * cy
+    cx = np.diag(MX) / dm
+    cy = np.diag(MY) / dm
+    sxx, sxy, syy = np.diag(MXX) / dm - cx * cx, np.diag(MXY) / dm - cx * cy, np.diag(MYY) / dm - cy * cy
     second = np.stack([np.stack([sxx, sxy], -1), np.stack([sxy, syy], -1)], -2)
     res = {"centroid": np.stack([cx, cy], -1), "second_moment": second,
            "width_d4sigma": 4.0 * np.sqrt(np.maximum(np.linalg.eigvalsh(second)[:, ::-1], 0.0))}

@@ -1241,6 +1241,175 @@ __global__ __launch_bounds__(256) void k_moment_grams(LocArgs L, int k, int64_t 
 }
 #undef MOM_ACC
 
+// Tangent Grams of a profile solve (plfem_profile_tangent_grams): the M_w (and K_w) of k_profile_grams under a batch of
+// point weights ("columns") in place of w -- the first-order change dw of w along a tangent of the profile's values, or
+// w X, w Y for a bend -- in two kernels per group of NW columns.
+//
+// The pre-pass, k_profile_point_weights: one lane per quadrature point of the six-point rule, element-major; the point
+// formed as the assembly forms it (P2Map::point).  The lane walks the layer table once (profile_top_layer: the topmost
+// layer and t^g), finds the cell and the bilinear weights of the map (sampled_cell) where there is one and no layer
+// holds the point, forms eps with the bits of profile_eps and w = 1 / eps (NCOMP = 2) or eps (NCOMP = 1) as
+// k_profile_grams does, and then writes one weight per column c0 .. c0 + NW - 1 of the group to wbuf[column][point]:
+//   a tangent t (row[1 + 2 nlayer] = d_eps_bg, then (d_a, d_b) per layer; tmap_of[t] its map among tmaps, or -1):
+//     d_eps = layer_value(d_a, d_b) of the topmost layer, or the bilinear interpolant of its map in the cell, or row[0];
+//     the weight is -(d_eps w) w (NCOMP = 2), d_eps (NCOMP = 1), every product rounded on its own;
+//   with `moments`, columns ntan and ntan + 1: w X and w Y, X = x - ox, Y = y - oy;
+//   a column past the call's last: 0.
+// A column's weight depends on the point and the column alone, not on the group it is in.  The rows are gathered at
+// the lane's own layer; the walk is over indices every lane shares (uniform loads).
+template <int NCOMP, int NW, typename... Map>
+__global__ __launch_bounds__(256) void k_profile_point_weights(LocArgs L, const double* __restrict__ layers, int nlayer,
+                                                               double eps_bg, const double* __restrict__ tangents,
+                                                               const int32_t* __restrict__ tmap_of,
+                                                               const double* __restrict__ tmaps, int ntan, int c0, int moments,
+                                                               double ox, double oy, double* __restrict__ wbuf, Map... map) {
+  const int64_t nq = (int64_t)6 * L.ne;
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= nq) return;
+  const int e = (int)(g / 6), q = (int)(g % 6);
+  const P2Map M(L.edof, L.ne, L.pxy, L.pxy + L.nv, e);
+  double X, Y, tg;
+  M.point(c_qx[q], c_qy[q], X, Y);
+  const int top = profile_top_layer(X, Y, layers, nlayer, tg);
+  const double gl = top >= 0 ? layers[LAYER_DOUBLES * top + 6] : 0.0;
+  [[maybe_unused]] bool in_map = false;
+  [[maybe_unused]] int i0 = 0, j0 = 0, nx = 0, ny = 0;
+  [[maybe_unused]] double a = 0.0, b = 0.0;
+  double eps = eps_bg;
+  if constexpr (sizeof...(Map) == 1) {
+    const EpsMap& em = (map, ...);
+    const SampledGrid G = em.grid();
+    nx = G.nx;
+    ny = G.ny;
+    in_map = sampled_cell(G, X, Y, i0, j0, a, b);
+    if (in_map && top < 0) eps = map_bilinear(em.eps(), nx, i0, j0, a, b);
+  }
+  if (top >= 0) eps = layer_value(layers[LAYER_DOUBLES * top + 4], layers[LAYER_DOUBLES * top + 5], gl, tg);
+  const double w = NCOMP == 2 ? 1.0 / eps : eps;
+  const int nrow = 1 + 2 * nlayer;
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    const int c = c0 + j;
+    double v = 0.0;
+    if (c < ntan) {
+      const double* row = tangents + (int64_t)c * nrow;
+      double d = row[0];
+      if (top >= 0) {
+        d = layer_value(row[1 + 2 * top], row[2 + 2 * top], gl, tg);
+      } else if constexpr (sizeof...(Map) == 1) {
+        const int mi = tmap_of[c];
+        if (in_map && mi >= 0) d = map_bilinear(tmaps + (int64_t)mi * nx * ny, nx, i0, j0, a, b);
+      }
+      v = NCOMP == 2 ? -mul_rn(mul_rn(d, w), w) : d;
+    } else if (moments && c < ntan + 2) {
+      v = mul_rn(w, c == ntan ? X - ox : Y - oy);
+    }
+    wbuf[(int64_t)j * nq + g] = v;
+  }
+}
+
+// The Gram kernel, k_weighted_grams: grid, tiling, staging and features of k_mode_grams; the weights of the tile's
+// points come from the pre-pass (NW x GT loads by lanes of the second wave, beside the staging lanes of the first; 0 for
+// a padding point).  Per point every lane forms the unweighted 2 x 2 products of its block once, as k_moment_grams
+// does -- m = u u' (hx hx' + hy hy') and, NCOMP = 2, kk = the form of K_r -- and adds them, times the column's weight,
+// to the column's outputs: M_col (and K_col).  Every product and sum is an explicit multiply or fused multiply-add in one
+// written order, the same for the four entries of the block and for every column, so an entry's bits depend neither on
+// its place in the block nor on the column's place in the group.  Partials [column of the group][output][chunk pair]
+// [workgroup][OC * OC], every slot written.
+#define WG_ACC(c, o, p)                                                                             \
+      acc[c][o][0][0] = fma(wt, p[0][0], acc[c][o][0][0]); acc[c][o][0][1] = fma(wt, p[0][1], acc[c][o][0][1]); \
+      acc[c][o][1][0] = fma(wt, p[1][0], acc[c][o][1][0]); acc[c][o][1][1] = fma(wt, p[1][1], acc[c][o][1][1]);
+
+template <int NCOMP, int NW>
+__global__ __launch_bounds__(256) void k_weighted_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
+                                                        const double* __restrict__ wbuf, int nchunk,
+                                                        double* __restrict__ partial) {
+  static_assert(NW * GT <= 192, "the weights are loaded by lanes GT .. of one pass");
+  constexpr int NF = 3 * NCOMP;
+  constexpr int NOUT = NCOMP == 2 ? 2 : 1;
+  __shared__ double s_f[2][NF][GT][OC];
+  __shared__ double s_gx[6][GT], s_gy[6][GT];
+  __shared__ int s_r[6][GT];
+  __shared__ double s_w[GT], s_wt[NW][GT];    // |det J| w_q, and the columns' weights of the point
+  __shared__ int s_q[GT];
+  const int tid = threadIdx.x;
+  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
+  const int i0 = ci * OC, j0 = cj * OC;
+  const int64_t nq = (int64_t)6 * L.ne;
+  const int64_t ntiles = (nq + GT - 1) / GT;
+  const int ti = tid >> 4, tj = tid & 15;
+  double acc[NW][NOUT][2][2];
+#pragma unroll
+  for (int c = 0; c < NW; ++c)
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) acc[c][o][0][0] = acc[c][o][0][1] = acc[c][o][1][0] = acc[c][o][1][1] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < GT) {
+      const int64_t g = tile * GT + tid;
+      gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q, [](double, double) {});
+    } else if (tid >= 64 && tid < 64 + NW * GT) {
+      const int c = (tid - 64) / GT, t = (tid - 64) % GT;
+      const int64_t g = tile * GT + t;
+      s_wt[c][t] = g < nq ? wbuf[(int64_t)c * nq + g] : 0.0;
+    }
+    __syncthreads();
+    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < GT; ++t) {
+      double p[2][2];
+      {
+        double2 a[NCOMP], b[NCOMP];
+#pragma unroll
+        for (int c = 0; c < NCOMP; ++c) {
+          a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
+          b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
+        }
+        p[0][0] = a[0].x * b[0].x; p[0][1] = a[0].x * b[0].y; p[1][0] = a[0].y * b[0].x; p[1][1] = a[0].y * b[0].y;
+        if constexpr (NCOMP == 2) {
+          p[0][0] = fma(a[1].x, b[1].x, p[0][0]); p[0][1] = fma(a[1].x, b[1].y, p[0][1]);
+          p[1][0] = fma(a[1].y, b[1].x, p[1][0]); p[1][1] = fma(a[1].y, b[1].y, p[1][1]);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NW; ++c) {
+        const double wt = s_wt[c][t];           // the same for every lane
+        WG_ACC(c, 0, p)
+      }
+      if constexpr (NCOMP == 2) {
+        // dy hx dy hx' + dx hy dx hy' - dx hx dy hy' - dy hy dx hx'  (features 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy)
+        double2 a[NF], b[NF];
+#pragma unroll
+        for (int c = 2; c < NF; ++c) {
+          a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
+          b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
+        }
+#define WG_K(r_, s_, ar, bs)                                                                        \
+        p[r_][s_] = a[3].ar * b[3].bs; p[r_][s_] = fma(a[4].ar, b[4].bs, p[r_][s_]);                  \
+        p[r_][s_] = fma(-a[2].ar, b[5].bs, p[r_][s_]); p[r_][s_] = fma(-a[5].ar, b[2].bs, p[r_][s_]);
+        WG_K(0, 0, x, x) WG_K(0, 1, x, y) WG_K(1, 0, y, x) WG_K(1, 1, y, y)
+#undef WG_K
+#pragma unroll
+        for (int c = 0; c < NW; ++c) {
+          const double wt = s_wt[c][t];
+          WG_ACC(c, NOUT - 1, p)
+        }
+      }
+    }
+    __syncthreads();
+  }
+  const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+  for (int c = 0; c < NW; ++c)
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) {
+      double* out = partial + ((((int64_t)c * NOUT + o) * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+      for (int r = 0; r < 2; ++r)
+        for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[c][o][r][s];
+    }
+}
+#undef WG_ACC
+
 // Quartic mode-overlap tensor (plfem_mode_quartic): Q[p(i,j)][p(l,m)] = sum over the points of the 16-point degree-8 rule
 // of |det J| w_q wt(x) (u_i . u_j)(u_l . u_m), i.e. Q = R^T diag(w) R with R[point][pair] = u_i . u_j.  R never reaches
 // HBM: one workgroup owns one 64 x 64 tile of Q on or above the diagonal (blockIdx.y, upper-triangle order) and walks
@@ -2658,6 +2827,112 @@ extern "C" int plfem_moment_grams(plfem_locator* L, int32_t ncomp, int32_t k, co
   });
   TRY(check_launch(L, "k_moment_grams"));
   return grams_to_host(call, moment_gram_outputs(ncomp), k, nblk, out_host);
+} catch (...) { return host_failure(L); }
+
+namespace {
+constexpr int TAN_NW = 4;        // columns per group: one launch of k_profile_point_weights and of k_weighted_grams
+constexpr int TAN_MAX = 256;     // most tangents per call
+constexpr int TAN_MAPS = 8;      // most tangent maps per call
+int tangent_gram_outputs(int ncomp) { return ncomp == 2 ? 2 : 1; }
+// Work buffer of plfem_profile_tangent_grams: the result [column][nout][k][k]; the partials of ONE column group
+// [TAN_NW][nout][chunk pair][GRAM_BLOCKS][OC * OC]; the point weights of one group [TAN_NW][6 ne]; the tangent rows
+// [ntan][1 + 2 MAX_LAYERS] (room for the largest table: the sizer does not know nlayer), their map indices [ntan] and
+// the tangent maps [nmap][ny][nx] on the locator's map grid; every part 256-byte aligned.
+struct TangentGramLayout { size_t off_partial, off_weights, off_rows, off_mapidx, off_maps, total; };
+TangentGramLayout tangent_gram_layout(const plfem_locator* L, int ncomp, int k, int ntan, int nmap, int moments) {
+  const size_t nout = tangent_gram_outputs(ncomp), nc = overlap_chunks(k), ncol = (size_t)ntan + (moments ? 2 : 0);
+  const size_t nq = std::max<size_t>(1, (size_t)6 * L->ne), npix = (size_t)L->map.nx * L->map.ny;
+  TangentGramLayout l;
+  size_t o = align256(ncol * nout * k * k * sizeof(double));
+  l.off_partial = o; o += align256((size_t)TAN_NW * nout * nc * nc * GRAM_BLOCKS * OC * OC * sizeof(double));
+  l.off_weights = o; o += align256((size_t)TAN_NW * nq * sizeof(double));
+  l.off_rows = o;    o += align256(std::max<size_t>(1, ntan) * (1 + 2 * MAX_LAYERS) * sizeof(double));
+  l.off_mapidx = o;  o += align256(std::max<size_t>(1, ntan) * sizeof(int32_t));
+  l.off_maps = o;    o += align256(std::max<size_t>(1, (size_t)nmap * npix) * sizeof(double));
+  l.total = o;
+  return l;
+}
+const char* tangent_gram_args(const plfem_locator* L, int ncomp, int k, int ntan, int nmap, int moments) {
+  if (!modes_ok(ncomp, k)) return "ncomp must be 1 or 2 and k >= 1";
+  if (ntan < 0 || ntan > TAN_MAX || ntan + (moments ? 2 : 0) < 1)
+    return "ntan must be in [0, 256], with at least one column (ntan + 2 moments >= 1)";
+  if (nmap < 0 || nmap > std::min(ntan, TAN_MAPS)) return "nmap must be in [0, min(ntan, 8)]";
+  if (nmap > 0 && !L->map.set()) return "tangent maps need a map on the locator (plfem_locator_set_index_map)";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int plfem_profile_tangent_gram_work_bytes(const plfem_locator* L, int32_t ncomp, int32_t k, int32_t ntan,
+                                                     int32_t nmap, int32_t moments, int64_t* bytes) try {
+  if (!L || !bytes || tangent_gram_args(L, ncomp, k, ntan, nmap, moments)) return PLFEM_EINVAL;
+  *bytes = (int64_t)tangent_gram_layout(L, ncomp, k, ntan, nmap, moments).total;
+  return PLFEM_OK;
+} catch (...) { return host_failure(nullptr, 0); }
+
+extern "C" int plfem_profile_tangent_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                           const double* layers_host, int32_t nlayer, double eps_bg,
+                                           const double* tangents_host, int32_t ntan, const double* tangent_maps_host,
+                                           int32_t nmap, const int32_t* tangent_map_host, int32_t moments,
+                                           const double* origin_host, void* work_dev, int64_t work_bytes,
+                                           double* out_host) try {
+  if (!L) return PLFEM_EINVAL;
+  FieldCall call{L, "plfem_profile_tangent_grams"};
+  if (const char* bad = tangent_gram_args(L, ncomp, k, ntan, nmap, moments)) return call.reject(bad);
+  if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) return call.reject(bad);
+  if (!modes_dev || !work_dev || !out_host || !origin_host || (ntan > 0 && !tangents_host) ||
+      (nmap > 0 && (!tangent_maps_host || !tangent_map_host)))
+    return call.reject("null array");
+  const int nrow = 1 + 2 * nlayer;
+  const size_t npix = (size_t)L->map.nx * L->map.ny;
+  for (int t = 0; t < ntan && nmap > 0; ++t)
+    if (tangent_map_host[t] < -1 || tangent_map_host[t] >= nmap) return call.reject("every tangent map index must be in [-1, nmap)");
+  for (size_t i = 0, n = (size_t)ntan * nrow; i < n; ++i)
+    if (!std::isfinite(tangents_host[i])) return call.reject("every tangent entry must be finite");
+  for (size_t i = 0, n = (size_t)nmap * npix; i < n; ++i)
+    if (!std::isfinite(tangent_maps_host[i])) return call.reject("every tangent entry must be finite");
+  if (!std::isfinite(origin_host[0]) || !std::isfinite(origin_host[1])) return call.reject("the origin must be finite");
+  const TangentGramLayout lay = tangent_gram_layout(L, ncomp, k, ntan, nmap, moments);
+  TRY(call.enter(indexed, "plfem_profile_tangent_gram_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial));
+  char* base = (char*)work_dev;
+  double *wbuf = (double*)(base + lay.off_weights), *d_rows = (double*)(base + lay.off_rows), *d_maps = (double*)(base + lay.off_maps);
+  int32_t* d_mapidx = (int32_t*)(base + lay.off_mapidx);
+  // (every call of a locator that reads the table ends with a stream synchronisation: nothing in flight reads the old one)
+  if (nlayer > 0)
+    HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
+  if (ntan > 0)
+    HIP_TRY(L, hipMemcpyAsync(d_rows, tangents_host, sizeof(double) * ntan * nrow, hipMemcpyHostToDevice, L->stream));
+  if (nmap > 0) {
+    HIP_TRY(L, hipMemcpyAsync(d_mapidx, tangent_map_host, sizeof(int32_t) * ntan, hipMemcpyHostToDevice, L->stream));
+    HIP_TRY(L, hipMemcpyAsync(d_maps, tangent_maps_host, sizeof(double) * nmap * npix, hipMemcpyHostToDevice, L->stream));
+  } else if (ntan > 0) {
+    HIP_TRY(L, hipMemsetAsync(d_mapidx, 0xff, sizeof(int32_t) * ntan, L->stream));   // -1: no tangent has a map
+  }
+  const int nc = overlap_chunks(k), nblk = gram_blocks(L->ne), nout = tangent_gram_outputs(ncomp);
+  const int ncol = ntan + (moments ? 2 : 0);
+  const int64_t nq = (int64_t)6 * L->ne;
+  const double ox = origin_host[0], oy = origin_host[1];
+  for (int c0 = 0; c0 < ncol; c0 += TAN_NW) {
+    const int nhere = std::min(TAN_NW, ncol - c0);
+    if (nq > 0) {
+      with_constant<2, 1>(ncomp, [&](auto nco) {
+        with_map(L, [&](auto... map) {
+          hipLaunchKernelGGL((k_profile_point_weights<decltype(nco)::value, TAN_NW, decltype(map)...>),
+                             dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, L->stream, call.loc, L->d_layers, (int)nlayer,
+                             eps_bg, d_rows, d_mapidx, d_maps, (int)ntan, c0, (int)(moments != 0), ox, oy, wbuf, map...);
+        });
+      });
+      TRY(check_launch(L, "k_profile_point_weights"));
+    }
+    with_constant<2, 1>(ncomp, [&](auto nco) {
+      hipLaunchKernelGGL((k_weighted_grams<decltype(nco)::value, TAN_NW>), dim3(nblk, nc * nc), dim3(256), 0, L->stream,
+                         call.loc, (int)k, call.nrows, modes_dev, wbuf, nc, call.partial);
+    });
+    TRY(check_launch(L, "k_weighted_grams"));
+    hipLaunchKernelGGL(k_overlap_reduce, dim3(nc * nc, nhere * nout, OC * OC / 256), dim3(256), 0, L->stream, (int)k, (int)k, nblk,
+                       nc, call.partial, call.O + (size_t)c0 * nout * k * k);
+    TRY(check_launch(L, "k_overlap_reduce"));
+  }
+  return result_to_host(L, call.O, (size_t)ncol * nout * k * k, out_host);
 } catch (...) { return host_failure(L); }
 
 namespace {

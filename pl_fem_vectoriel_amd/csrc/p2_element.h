@@ -1,7 +1,7 @@
 // The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
 // integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
 // k_field_overlap, k_mode_grams, k_profile_grams, k_mode_quartic, k_mode_project, k_mode_project_sampled, k_core_owner,
-// k_mode_indicators, k_flux_grams, k_sample_efields, k_flux_overlap_posed).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// k_mode_indicators, k_flux_grams, k_sample_efields, k_flux_overlap_posed, k_profile_point_weights, k_weighted_grams).  One definition, so that a quadrature point lands in the same region, and det J rounds
 // the same way, in the assembly and in every kernel that must reproduce it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -234,6 +234,48 @@ __device__ __forceinline__ double profile_eps(double X, double Y, const double* 
     eps_bg = mul_rn(lo, b1) + mul_rn(hi, b);
   }
   return profile_eps(X, Y, layers, nlayer, eps_bg);
+}
+
+// Where a point lies in the layer table, in one walk (k_profile_point_weights): the topmost layer that holds it -- the
+// membership test of profile_eps, operation for operation -- or -1, and tg = t^g of that layer when it is graded (0
+// otherwise), t as profile_eps forms it.  profile_eps evaluates every graded layer it meets; the last one it meets is this
+// one, so layer_value(eps_a, eps_b, tg) of the returned layer has the bits of profile_eps.
+__device__ __forceinline__ int profile_top_layer(double X, double Y, const double* __restrict__ layers, int nlayer, double& tg) {
+  int top = -1;
+  double d2_top = 0.0;
+  for (int l = 0; l < nlayer; ++l) {
+    const double* p = layers + LAYER_DOUBLES * l;
+    const double dx = X - p[0], dy = Y - p[1], r_in = p[2], r_out = p[3];
+    const double d2 = mul_rn(dx, dx) + mul_rn(dy, dy);
+    if (mul_rn(r_in, r_in) <= d2 && d2 <= mul_rn(r_out, r_out)) {
+      top = l;
+      d2_top = d2;
+    }
+  }
+  tg = 0.0;
+  if (top >= 0) {
+    const double* p = layers + LAYER_DOUBLES * top;
+    const double r_in = p[2], r_out = p[3], g = p[6];
+    if (g > 0.0) tg = pow(fmin(fmax((sqrt(d2_top) - r_in) / (r_out - r_in), 0.0), 1.0), g);
+  }
+  return top;
+}
+
+// value of a layer at a point with tg = t^g: v_a for a constant layer (g = 0), v_a + (v_b - v_a) t^g for a graded one,
+// the product rounded on its own -- for the permittivities of the table this is profile_eps, for a tangent's (d_a, d_b)
+// the first-order change of it
+__device__ __forceinline__ double layer_value(double v_a, double v_b, double g, double tg) {
+  return g > 0.0 ? v_a + mul_rn(v_b - v_a, tg) : v_a;
+}
+
+// the bilinear interpolant of a map E[ny][nx] in the cell (i0, j0) with the weights (a, b) of sampled_cell: the order and
+// the roundings of profile_eps over a map
+__device__ __forceinline__ double map_bilinear(const double* __restrict__ E, int nx, int i0, int j0, double a, double b) {
+  const double* p = E + ((int64_t)j0 * nx + i0);
+  const double e00 = p[0], e01 = p[1], e10 = p[nx], e11 = p[nx + 1];
+  const double a1 = 1.0 - a, b1 = 1.0 - b;
+  const double lo = mul_rn(a1, e00) + mul_rn(a, e01), hi = mul_rn(a1, e10) + mul_rn(a, e11);
+  return mul_rn(lo, b1) + mul_rn(hi, b);
 }
 
 }  // namespace

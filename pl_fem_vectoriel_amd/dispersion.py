@@ -79,6 +79,12 @@ def dispersion_from_grams(kind: str, grams: Dict[str, np.ndarray], beta, k0: flo
         Ad = -2.0 * k0 * (ec * Mc + el * Ml) - k0 * k0 * (dc * Mc + dl * Ml)
         Bd = np.zeros_like(B)
         mu, sgn = -beta ** 2, -1.0
+    return _dispersion_from_pencil(A, B, Ad, Bd, mu, sgn, beta, cluster_rtol)
+
+
+def _dispersion_from_pencil(A, B, Ad, Bd, mu, sgn, beta, cluster_rtol) -> Dict:
+    """What :func:`dispersion_from_grams` makes of the projected pencil ``(A, B)`` of the records, its k0-derivative
+    ``(Ad, Bd)`` and ``mu`` = ``sgn beta^2`` (shared with :mod:`.profile_response`)."""
     k = beta.size
     s = 1.0 / np.sqrt(np.diag(B))                          # B-normalisation of every record
     A, B, Ad, Bd = (s[:, None] * X * s[None, :] for X in (A, B, Ad, Bd))

@@ -45,7 +45,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native
-from .profile import index_profile_of, reject_profile
+from .profile import ProfileTangent, index_profile_of, reject_profile
 from .solver_fem import _core_table, mesh_key
 
 LOC_TOL = 1e-10                    # PLFEM_LOC_TOL of include/plfem.h
@@ -59,7 +59,9 @@ MOMENT_GRAM_NAMES = {"vectorial": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y
 FLUX_OVERLAP_NAMES = ("MA", "GA", "MB", "GB")                           # plfem_flux_overlap_posed, per pose
 POSE_MAX_CHUNK_PAIRS = 256         # POSE_MAX_PAIRS of csrc/kernels_fields.hip: pairs of 32-mode chunks per posed call
 FLUX_POSE_MAX_CHUNK_PAIRS = 64     # FLUX_POSE_MAX_PAIRS: the same per posed flux call
-PROJECT_TILE = (8, 8)              # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
+TANGENT_MAX = 256                  # TAN_MAX of csrc/kernels_fields.hip: tangents per call of plfem_profile_tangent_grams
+TANGENT_MAPS = 8                   # TAN_MAPS: tangent maps per call
+PROJECT_TILE = (8, 8)             # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
 PROJECT_MAX_FACTORS = 4096         # PJ_LMAX
 PROJECT_SAMPLED_TILE = 32          # PS_F: frames per workgroup tile of the sampled projection
 PROJECT_SAMPLED_MAX_FRAMES = 4096  # PS_FRAMES: frames per call of plfem_mode_project_sampled
@@ -424,6 +426,96 @@ class ModeFields:
         self._mode_call("plfem_profile_gram_work_bytes", {"ncomp": ncomp, "k": k}, "plfem_profile_grams", kind, staged,
                         (_native._ptr(table), table.shape[0], float(eps_bg)), (out,), work=work)
         return {nm: out[i] for i, nm in enumerate(names)}
+
+    def profile_tangent_grams(self, modes: Sequence[Dict], geometry, tangents=(), moments: bool = False,
+                              origin=(0.0, 0.0)) -> Dict[str, np.ndarray]:
+        """Grams of the modes of a profile solve under first-order changes of the profile's values
+        (``plfem_profile_tangent_grams``).  ``tangents``: :class:`.profile.ProfileTangent` objects of the profile that
+        ``geometry`` carries.  With ``w`` the weight of :meth:`profile_grams` and ``dw_t`` its change along tangent t --
+        ``-d eps_t / eps^2`` for vectorial records, ``d eps_t`` for scalar ones -- ``M_d`` (ntan, k, k) is ``M_w`` under
+        ``dw_t`` and, for vectorial records, ``K_d`` is ``K_w`` under it: the derivatives of ``V^T B V`` and ``V^T A V``
+        (vectorial) or, times ``-k0^2``, of ``V^T A V`` (scalar) along the tangent.  ``moments``: also ``M_wX``, ``M_wY``
+        (k, k) and, for vectorial records, ``K_wX``, ``K_wY``: ``M_w`` and ``K_w`` under ``w X``, ``w Y`` with ``X = x -
+        origin[0]``, ``Y = y - origin[1]`` -- what a bend moves the pencils by (:mod:`.profile_response`)."""
+        profile = index_profile_of(geometry)
+        if profile is None:
+            raise ValueError("profile_tangent_grams needs a geometry that carries an index profile (ProfiledGeometry)")
+        tangents = self._tangents(profile, tangents)
+        o = self._origin(origin)
+        kind, vals, _, k = self._checked(modes)
+        if not tangents and not moments:
+            raise ValueError("nothing to compute: no tangents and moments = False")
+        if k == 0:
+            return self._tangent_result(kind, np.zeros((len(tangents) + (2 if moments else 0), 2, 0, 0)), len(tangents), bool(moments))
+        return self._profile_tangent_grams_staged(kind, self._staged(vals), profile, tangents, bool(moments), o)
+
+    @staticmethod
+    def _tangents(profile, tangents) -> list:
+        """``tangents`` as a list of tangents of ``profile``, at most 256; ``ValueError`` otherwise."""
+        if isinstance(tangents, ProfileTangent):
+            tangents = [tangents]
+        try:
+            tangents = list(tangents)
+        except TypeError:
+            raise ValueError("tangents must be a sequence of ProfileTangent objects") from None
+        if not all(isinstance(t, ProfileTangent) for t in tangents):
+            raise ValueError("tangents must be a sequence of ProfileTangent objects")
+        if len(tangents) > TANGENT_MAX:
+            raise ValueError(f"at most {TANGENT_MAX} tangents per call")
+        return [t.check(profile) for t in tangents]
+
+    @staticmethod
+    def _tangent_result(kind, out, ntan: int, moments: bool) -> Dict[str, np.ndarray]:
+        """``out`` (ncol, nout, k, k) of ``plfem_profile_tangent_grams`` under the names of :meth:`profile_tangent_grams`."""
+        names = {"vectorial": ("M", "K"), "scalar": ("M",), None: ()}[kind]
+        res = {nm + "_d": np.ascontiguousarray(out[:ntan, i]) for i, nm in enumerate(names)}
+        if moments:
+            for i, nm in enumerate(names):
+                res[nm + "_wX"], res[nm + "_wY"] = out[ntan, i].copy(), out[ntan + 1, i].copy()
+        return res
+
+    def _profile_tangent_grams_staged(self, kind, staged, profile, tangents, moments, origin, work=None) -> Dict[str, np.ndarray]:
+        """``plfem_profile_tangent_grams`` on modes already staged (ncomp, n, k) on the device, in calls of at most
+        ``TANGENT_MAPS`` tangent maps each (the moment columns ride on the first); ``work`` as for
+        :meth:`_profile_grams_staged`."""
+        self._set_index_map(profile.index_map)
+        ncomp, _, k = staged.shape
+        nout = 2 if ncomp == 2 else 1
+        table = profile.table()
+        ntan = len(tangents)
+        out = np.empty((ntan + (2 if moments else 0), nout, k, k), dtype=np.float64)
+        calls, cur, nmaps = [], [], 0                         # lists of tangent indices, each with at most TANGENT_MAPS maps
+        for i, t in enumerate(tangents):
+            if t.d_map is not None and nmaps == TANGENT_MAPS:
+                calls.append(cur)
+                cur, nmaps = [], 0
+            cur.append(i)
+            nmaps += t.d_map is not None
+        if cur or not calls:
+            calls.append(cur)
+        for ci, idx in enumerate(calls):
+            mom = bool(moments and ci == 0)
+            if not idx and not mom:
+                continue
+            rows = np.ascontiguousarray(np.stack([tangents[i].row() for i in idx])) if idx else np.zeros((0, 1 + 2 * len(profile)))
+            maps = [tangents[i].d_map for i in idx if tangents[i].d_map is not None]
+            which, n = np.full(len(idx), -1, dtype=np.int32), 0
+            for j, i in enumerate(idx):
+                if tangents[i].d_map is not None:
+                    which[j], n = n, n + 1
+            maps_a = np.ascontiguousarray(np.stack(maps)) if maps else None
+            part = np.empty((len(idx) + (2 if mom else 0), nout, k, k), dtype=np.float64)
+            self._mode_call("plfem_profile_tangent_gram_work_bytes",
+                            {"ncomp": ncomp, "k": k, "ntan": len(idx), "nmap": len(maps), "moments": int(mom)},
+                            "plfem_profile_tangent_grams", kind, staged,
+                            (_native._ptr(table), table.shape[0], float(profile.eps_background),
+                             _native._ptr(rows) if idx else None, len(idx), None if maps_a is None else _native._ptr(maps_a),
+                             len(maps), _native._ptr(which) if maps else None, int(mom), _native._ptr(origin)), (part,),
+                            work=work, loc=self._loc)
+            out[idx] = part[:len(idx)]
+            if mom:
+                out[ntan:] = part[len(idx):]
+        return self._tangent_result(kind, out, ntan, moments)
 
     def indicators(self, modes: Sequence[Dict], geometry, alpha_p: float = 1.0) -> Dict[str, np.ndarray]:
         """A-posteriori error indicators of the modes on this mesh (``plfem_mode_indicators``): ``{"eta2": (k, ne),

@@ -26,6 +26,12 @@ outside it the constant background; the layers are painted over both.  With ``in
 * ``lo = (1 - a) E[j0, i0] + a E[j0, i0 + 1]``, ``hi`` the same in row ``j0 + 1``, ``eps = lo (1 - b) + hi b``, every
   product rounded on its own (``plfem_set_index_map``).
 
+``epsilon`` is linear in the VALUES of a profile at fixed shapes -- the background, ``eps_a`` and ``eps_b`` of every layer,
+every pixel of the map.  A :class:`ProfileTangent` (``tangent_eps``, ``tangent_index``, ``unit_tangents``) is a first-order
+change of them, evaluated with the same membership, ``t``, ``g`` and bilinear weights; group index, index sensitivities and
+bend response of a profile solve are Grams of the modes under such tangents (:mod:`.profile_response`,
+:meth:`.fields.ModeFields.profile_tangent_grams`).
+
 A section that is not made of circles is resolved by refinement on the error indicators (:func:`.adapt.adaptive_solve`),
 not by the mesh recipe.
 """
@@ -173,6 +179,75 @@ class IndexProfile:
                 eps[inside] = eps_a
         return eps
 
+    # -- tangents: first-order changes of the values at fixed shapes ---------------------------------------------
+    def tangent_eps(self, d_background=0.0, d_layers=0.0, d_map=None) -> "ProfileTangent":
+        """The tangent with raw ``d eps``: ``d_background`` a number, ``d_layers`` a number, ``(nlayer,)`` or ``(nlayer,
+        2)`` = (d_eps_a, d_eps_b) per layer (a constant layer has one value: both must agree), ``d_map`` None or
+        ``(ny, nx)`` on the profile's own pixel grid (only if the profile has a map)."""
+        return ProfileTangent(self, d_background, d_layers, d_map)
+
+    def tangent_index(self, dn_background=0.0, dn_layers=0.0, dn_map=None) -> "ProfileTangent":
+        """The tangent of an index change, ``d eps = 2 n dn``: centre and edge of a graded layer separately, the map by
+        ``2 sqrt(E) dn_map`` (a scalar ``dn_map`` is broadcast).  Shapes as for :meth:`tangent_eps`."""
+        n_layers = np.sqrt(self.table()[:, 4:6])
+        d_layers = 2.0 * n_layers * _layer_pairs(dn_layers, len(self), "dn_layers")
+        d_map = None
+        if dn_map is not None:
+            if self._map is None:
+                raise ValueError("dn_map needs a profile with a map")
+            E = self._map[0]
+            try:
+                dn = np.broadcast_to(np.asarray(dn_map, dtype=np.float64), E.shape)
+            except (TypeError, ValueError):
+                raise ValueError(f"dn_map must be a number or have shape (ny, nx) = {E.shape}") from None
+            d_map = 2.0 * np.sqrt(E) * dn
+        return ProfileTangent(self, 2.0 * self.n_background * _number(dn_background, "dn_background"), d_layers, d_map)
+
+    def unit_tangents(self) -> list:
+        """``nlayer + 1`` tangents: ``dn = 1`` on the background (with the map, when there is one), then on each layer in
+        turn (a graded layer: a uniform offset of centre and edge)."""
+        out = [self.tangent_index(dn_background=1.0, dn_map=None if self._map is None else 1.0)]
+        for l in range(len(self)):
+            dn = np.zeros(len(self))
+            dn[l] = 1.0
+            out.append(self.tangent_index(dn_layers=dn))
+        return out
+
+    def _placement(self, x, y):
+        """Where the points lie: ``(top, tg, inside, cell)`` -- the index of the topmost layer that holds each point or
+        -1, ``t ** g`` there (1 where the layer is constant or there is none), whether the point is inside the closed extent
+        of the map, and ``(i0, j0, a, b)`` of the inside points (None without a map): the membership, ``t`` and the cell
+        of :meth:`epsilon`."""
+        x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
+        top = np.full(x.shape, -1, dtype=np.int64)
+        tg = np.ones(x.shape, dtype=np.float64)
+        for l, (cx, cy, r_in, r_out, _, _, g, _) in enumerate(self._layers):
+            dx, dy = x - cx, y - cy
+            d2 = dx * dx + dy * dy
+            inside = (r_in * r_in <= d2) & (d2 <= r_out * r_out)
+            top[inside] = l
+            if g > 0:
+                t = np.minimum(np.maximum((np.sqrt(d2[inside]) - r_in) / (r_out - r_in), 0.0), 1.0)
+                tg[inside] = np.power(t, g)
+            else:
+                tg[inside] = 1.0
+        if self._map is None:
+            return top, tg, np.zeros(x.shape, dtype=bool), None
+        inside, cell = self._map_cells(x, y)
+        return top, tg, inside, cell
+
+    def _map_cells(self, x, y):
+        """``inside`` (the points in the closed extent of the map) and ``(i0, j0, a, b)`` of those points."""
+        E, x0, y0, dx, dy = self._map
+        ny, nx = E.shape
+        with np.errstate(invalid="ignore"):
+            tx, ty = (x - x0) * (1.0 / dx), (y - y0) * (1.0 / dy)
+            inside = (tx >= 0.0) & (tx <= nx - 1) & (ty >= 0.0) & (ty <= ny - 1)       # (False for a NaN)
+        tx, ty = tx[inside], ty[inside]
+        i0 = np.minimum(np.floor(tx).astype(np.int64), nx - 2)
+        j0 = np.minimum(np.floor(ty).astype(np.int64), ny - 2)
+        return inside, (i0, j0, tx - i0, ty - j0)
+
     def _paint_map(self, eps, x, y):
         """The bilinear interpolant of the map into ``eps`` at the points inside its closed extent."""
         E, x0, y0, dx, dy = self._map
@@ -188,6 +263,106 @@ class IndexProfile:
         lo = a1 * E[j0, i0] + a * E[j0, i0 + 1]
         hi = a1 * E[j0 + 1, i0] + a * E[j0 + 1, i0 + 1]
         eps[inside] = lo * b1 + hi * b
+
+
+def _layer_pairs(v, nlayer: int, name: str) -> np.ndarray:
+    """``v`` -- a number, ``(nlayer,)`` or ``(nlayer, 2)`` -- as a finite ``(nlayer, 2)`` float64 array."""
+    try:
+        a = np.asarray(v, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number, ({nlayer},) or ({nlayer}, 2) finite numbers") from None
+    if a.ndim == 0:
+        a = np.full((nlayer, 2), float(a))
+    elif a.shape == (nlayer,):
+        a = np.repeat(a[:, None], 2, axis=1)
+    elif a.shape != (nlayer, 2):
+        raise ValueError(f"{name} must be a number, ({nlayer},) or ({nlayer}, 2) finite numbers, not shape {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name} must be finite")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+class ProfileTangent:
+    """A first-order change of the permittivity VALUES of one :class:`IndexProfile` at fixed shapes: ``d_eps_background``,
+    ``d_layers`` (nlayer, 2) = (d_eps_a, d_eps_b) per layer and, for a profile with a map, optionally ``d_map`` (ny, nx)
+    on the profile's own pixel grid.  ``IndexProfile.epsilon`` is linear in exactly these values, so the tangent is
+    itself a profile with the same layers and the same grid: :meth:`epsilon` is the change of ``profile.epsilon`` per
+    unit step along it.  Made by ``IndexProfile.tangent_eps`` / ``tangent_index`` / ``unit_tangents``; bound to the profile
+    that made it (``ValueError`` with another one).  A tangent without a map over a profile with one changes the
+    interpolated background by ``d_eps_background`` inside the extent too."""
+
+    def __init__(self, profile: IndexProfile, d_background=0.0, d_layers=0.0, d_map=None):
+        if not isinstance(profile, IndexProfile):
+            raise ValueError("profile must be an IndexProfile")
+        self.profile = profile
+        self._table_bytes = profile.table().tobytes()
+        self._map_ref = profile.index_map
+        self.d_eps_background = _number(d_background, "d_background")
+        self.d_layers = _layer_pairs(d_layers, len(profile), "d_layers")
+        for l, row in enumerate(profile.table()):
+            if row[6] == 0 and self.d_layers[l, 0] != self.d_layers[l, 1]:
+                raise ValueError(f"layer {l} is constant: its two tangent values must agree")
+        self.d_map = None
+        if d_map is not None:
+            if profile.index_map is None:
+                raise ValueError("d_map needs a profile with a map")
+            shape = profile.index_map[0].shape
+            try:
+                m = np.array(d_map, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"d_map must have shape (ny, nx) = {shape}") from None
+            if m.shape != shape:
+                raise ValueError(f"d_map must have shape (ny, nx) = {shape}, not {m.shape}")
+            if not np.all(np.isfinite(m)):
+                raise ValueError("d_map must be finite")
+            self.d_map = np.ascontiguousarray(m)
+            self.d_map.setflags(write=False)
+        self.d_layers.setflags(write=False)
+
+    def check(self, profile: IndexProfile) -> "ProfileTangent":
+        """``self`` if the tangent belongs to ``profile`` -- the same object, or the same table and map -- else
+        ``ValueError``; also when the profile has gained a layer or another map since the tangent was made."""
+        if not isinstance(profile, IndexProfile):
+            raise ValueError("the tangent belongs to another index profile")
+        m, mine = profile.index_map, self._map_ref
+        same_map = (m is None and mine is None) or (m is not None and mine is not None and m[1:] == mine[1:] and
+                                                    (m[0] is mine[0] or np.array_equal(m[0], mine[0])))
+        if not (profile.table().tobytes() == self._table_bytes and same_map and
+                profile.eps_background == self.profile.eps_background):
+            raise ValueError("the tangent belongs to another index profile")
+        return self
+
+    def row(self) -> np.ndarray:
+        """``(1 + 2 nlayer,)`` float64: ``d_eps_background``, then (d_eps_a, d_eps_b) per layer, as the C ABI takes it."""
+        return np.concatenate([[self.d_eps_background], self.d_layers.reshape(-1)]).astype(np.float64)
+
+    def scaled(self, factor: float) -> "ProfileTangent":
+        """The tangent times ``factor``."""
+        f = _number(factor, "factor")
+        return ProfileTangent(self.profile, f * self.d_eps_background, f * self.d_layers,
+                              None if self.d_map is None else f * self.d_map)
+
+    def epsilon(self, x, y) -> np.ndarray:
+        """``d eps`` at the points (float64, the shape of ``x``): ``d_a + (d_b - d_a) t ** g`` in the topmost layer that
+        holds the point; otherwise the bilinear interpolant of ``d_map`` inside the extent of the map (or
+        ``d_eps_background`` when the tangent has no map), and ``d_eps_background`` outside it -- membership, overwrite
+        order, ``t``, ``g`` and bilinear weights of ``IndexProfile.epsilon``."""
+        prof = self.check(self.profile).profile
+        x = np.asarray(x, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        top, tg, inside, cell = prof._placement(x, y)
+        d = np.full(top.shape, self.d_eps_background, dtype=np.float64)
+        if self.d_map is not None:
+            i0, j0, a, b = cell
+            a1, b1 = 1.0 - a, 1.0 - b
+            E = self.d_map
+            lo = a1 * E[j0, i0] + a * E[j0, i0 + 1]
+            hi = a1 * E[j0 + 1, i0] + a * E[j0 + 1, i0 + 1]
+            d[inside] = lo * b1 + hi * b
+        lay = top >= 0
+        da, db = self.d_layers[top[lay], 0], self.d_layers[top[lay], 1]
+        d[lay] = da + (db - da) * tg[lay]
+        return d
 
 
 _PROFILED_CLASSES = {}
@@ -271,7 +446,8 @@ def reject_profile(geometry, what: str) -> None:
     and would compute with the wrong material map."""
     if geometry is not None and getattr(geometry, "index_profile", None) is not None:
         raise ValueError(f"{what} assumes two material regions (core discs on a cladding) and the geometry carries an index "
-                         "profile: use ModeFields.profile_grams, the Grams of a profile solve")
+                         "profile: use ModeFields.profile_grams, the Grams of a profile solve, and profile_dispersion, "
+                         "profile_sensitivity, profile_bend_response of profile_response")
 
 
-__all__ = ["IndexProfile", "ProfiledGeometry", "index_profile_of", "reject_profile", "MAX_LAYERS"]
+__all__ = ["IndexProfile", "ProfileTangent", "ProfiledGeometry", "index_profile_of", "reject_profile", "MAX_LAYERS"]

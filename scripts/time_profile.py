@@ -1,11 +1,15 @@
 """Timing aid of the index-profile path at C1: the assembly with a profile of ``--layers`` layers beside the step
 assembly, and ``ModeFields.profile_grams`` beside ``ModeFields.grams`` for 22 vectorial and scalar modes.
 
-    python scripts/time_profile.py [--layers 7] [--map NX NY] [--modes 22] [--reps 10] [--out FILE]
+    python scripts/time_profile.py [--layers 7] [--map NX NY] [--modes 22] [--reps 10] [--tangents N] [--out FILE]
 
 ``--map NX NY`` puts a sampled index map of NX x NY pixels over the bounding box of the mesh under the layers
 (``IndexProfile.sampled``): the profile kernels are then their map instances (k_element_matrices<true, EpsMap>,
 k_profile_grams<.., EpsMap>).
+
+``--tangents N`` also times ``ModeFields.profile_tangent_grams`` with N tangents (the profile's unit tangents, repeated or
+cut to N) and, on the same modes, ``profile_dispersion`` and ``profile_sensitivity`` with those tangents: the kernels are
+k_profile_point_weights and k_weighted_grams, one launch of each per group of four columns.
 
 Run it under ``rocprofv3 --kernel-trace --stats``, in a run of its own and once per ``--layers`` / ``--map`` (the profile
 assemblies without a map are the one instance k_element_matrices<true>), for the kernel times of k_element_matrices and
@@ -56,6 +60,7 @@ def main():
     ap.add_argument("--map", type=int, nargs=2, metavar=("NX", "NY"), default=None)
     ap.add_argument("--modes", type=int, default=22)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--tangents", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -99,6 +104,15 @@ def main():
     for kind, modes in (("vectorial", vec), ("scalar", scal)):
         res[kind] = {"k": len(modes), "grams_wall_ms": timed(lambda: mf.grams(modes, geom)),
                      "profile_grams_wall_ms": timed(lambda: mf.profile_grams(modes, pg))}
+        if args.tangents > 0:
+            from pl_fem_vectoriel_amd import profile_dispersion, profile_sensitivity
+            unit = prof.unit_tangents()
+            tans = [unit[i % len(unit)] for i in range(args.tangents)]
+            slope = prof.tangent_index(-0.012, -0.012, -0.012 if args.map else None)
+            res[kind].update(tangents=len(tans),
+                             tangent_grams_wall_ms=timed(lambda: mf.profile_tangent_grams(modes, pg, tans)),
+                             profile_dispersion_wall_ms=timed(lambda: profile_dispersion(modes, mf, pg, dn_dlambda=slope)),
+                             profile_sensitivity_wall_ms=timed(lambda: profile_sensitivity(modes, mf, pg, tangents=tans)))
     mf.close()
     line = json.dumps(res)
     print(line)
