@@ -505,6 +505,48 @@ int plfem_core_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double*
                      double* out_host   /* [ncore][NOUT][k][k], NOUT = 3 (Mx, My, K) or 1 (M) */,
                      int64_t* count_host /* [ncore] quadrature points owned */);
 
+/* Velocity Grams: the first-order change of the projected forms when the mesh moves with a velocity field and carries
+ * its material along (the volume form of the shape derivative).  velocities_host [nvel][nv][2]: per
+ * velocity a P1 field V on the mesh vertices, nvel in [1, 256].  Under x -> x + t V, every quadrature point keeping the
+ * material it has, an element with the constant gradient G_ab = dV_a / dx_b, tr = G_xx + G_yy, changes
+ *   grad f by -G^T grad f  ((G^T grad f)_b = sum_c G_cb d_c f)   and   |det J| w_q by tr |det J| w_q,
+ * so with gt(f) = -G^T grad f + (tr / 2) grad f every gradient form changes by P + P^T, P[m][n] the form with gt on mode m
+ * and the plain gradient on mode n, and every mass form by sum tr |det J| w_q c u_m . u_n.  For straight-sided P2 that is
+ * the exact t-derivative of the discrete forms.  Modes staged and indexed as for plfem_mode_grams; the material
+ * arguments are those of plfem_flux_grams (discs, a layer profile, or a profile over the locator's map), read at the
+ * points of the unmoved mesh.  out_host[v][0..NOUT-1][k][k]:
+ *   ncomp = 2: dK_w, dD, dM, dM_w -- K_w the form of K_r of plfem_mode_grams under w = 1 / eps, D, M = u . u', M_w under w --
+ *     so that d(V^T A V) = dK_w + alpha_p dD - k0^2 dM and d(V^T B V) = dM_w;
+ *   ncomp = 1: dS, dM, dM_w with w = eps, so that d(V^T A V) = dS - k0^2 dM_w and d(V^T B V) = dM.
+ * count_host[v]: the elements with G != 0 (any of the four entries non-zero); the others contribute nothing, however large
+ * V is there, and a velocity with none (zero, or a translation of everything) gives exact zeros and count 0.
+ * Passes, per group of g velocities: G and the flag of every (velocity, element); per-velocity ascending element lists
+ * (counts, exclusive offsets, a stable fill: no atomic decides a position); the Gram kernel over (slice of a list, 32-mode
+ * chunk pair, velocity), which accumulates the asymmetric halves; the fixed-order second stage of plfem_field_overlap; and
+ * X + X^T formed once per entry pair, so every matrix is bitwise symmetric.  The bits of out_host[v] depend on velocity v,
+ * the modes, the material and the mesh only: not on the other velocities or v's place among them, on a subset or
+ * permutation of the modes, on what the work buffer held, or on the run.  Synchronises the locator's stream.
+ * work_dev: device scratch of plfem_velocity_gram_work_bytes(loc, ncomp, k, nvel) bytes, 256-byte aligned.  The bound, with
+ * P = ceil(k / 32)^2 chunk pairs, nout = 4 or 3 and slices = min(128, ceil(6 ne / 16)) (at least 1; the same for every k
+ * and nvel): a velocity takes nout P slices partial blocks of 8 KiB (4 MiB per chunk pair for ncomp = 2), and a group is
+ * g = min(16, nvel, 256 MiB / that) velocities, at least 1 (16 up to k = 64, 7 at k = 70): at most 256 MiB of partial
+ * blocks.  With the results, nvel nout k^2 doubles (38.3 MiB at nvel = 256, k = 70), and per group the velocities, flags and
+ * lists of the mesh, g (16 nv + 8 ne) bytes, plus 128 bytes of counts, the scratch stays below 512 MiB for k <= 70 and any
+ * nvel on meshes of up to about 800 000 elements.
+ * Argument errors return PLFEM_EINVAL with the locator's last error set, before any launch, checked in this order: ncomp
+ * not 1 or 2 or k < 1; nvel outside [1, 256]; ncore outside [0, 64]; a null array (cores only with ncore > 0); a non-finite
+ * velocity entry; the material errors of plfem_flux_grams in its order; an indexed record on an analysis without interior
+ * DOFs; work_bytes too small, then a misaligned buffer.  A null loc returns PLFEM_EINVAL alone.
+ * plfem_velocity_gram_work_bytes rejects a null loc or bytes (left alone) and ncomp, k or nvel out of range. */
+int plfem_velocity_gram_work_bytes(const plfem_locator* loc, int32_t ncomp, int32_t k, int32_t nvel, int64_t* bytes);
+int plfem_velocity_grams(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                         const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                         const double* layers_host, int32_t nlayer, double eps_bg, int32_t use_profile,
+                         const double* velocities_host /* [nvel][nv][2] */, int32_t nvel,
+                         void* work_dev, int64_t work_bytes,
+                         double* out_host    /* [nvel][NOUT][k][k], NOUT = 4 (dK_w, dD, dM, dM_w) or 3 (dS, dM, dM_w) */,
+                         int64_t* count_host /* [nvel] elements with a non-zero velocity gradient */);
+
 /* Coordinate-weighted ("moment") Grams: the region Grams of plfem_mode_grams weighted by the coordinates of the
  * quadrature point, X = x - origin_host[0], Y = y - origin_host[1], (x, y) the physical point exactly as the assembly
  * forms it; modes, indexed, cores and regions as for plfem_mode_grams (ncore in [0, 64]); every sum is over the six-point

@@ -14,6 +14,7 @@ from .adapt import adaptive_solve, mark_elements, mode_error_indicators, refine_
 from .splice import (flux_transfer_from_grams, splice_map, splice_power_map, splice_quantities_from_overlaps,  # noqa: F401
                      taper_from_interfaces, taper_transfer, taper_transfer_vectorial)
 from .power import Z0_OHM, mode_power, power_quantities_from_grams  # noqa: F401
+from .shape import core_velocities, disorder_statistics, shape_response, shape_response_from_grams  # noqa: F401
 
 __all__ = ["MCFGeometry", "PhotonicLanternGeometry", "mcf_positions", "TriMesh", "generate_mesh", "ModeFields", "mode_overlap",
            "mode_dispersion", "mode_nonlinearity", "far_field", "encircled_na", "gaussian_coupling", "field_coupling", "core_decomposition",
@@ -22,4 +23,5 @@ __all__ = ["MCFGeometry", "PhotonicLanternGeometry", "mcf_positions", "TriMesh",
            "taper_from_interfaces", "taper_transfer", "mode_error_indicators", "mark_elements", "refine_marked", "adaptive_solve",
            "mode_power", "power_quantities_from_grams", "Z0_OHM", "flux_overlap_poses", "flux_transfer_from_grams",
            "splice_power_map", "taper_transfer_vectorial", "ProfileTangent", "profile_dispersion", "profile_dispersion_from_grams",
-           "profile_sensitivity", "profile_sensitivity_from_grams", "profile_bend_response", "profile_bend_from_grams"]
+           "profile_sensitivity", "profile_sensitivity_from_grams", "profile_bend_response", "profile_bend_from_grams",
+           "core_velocities", "shape_response", "shape_response_from_grams", "disorder_statistics"]

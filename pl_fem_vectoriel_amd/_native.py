@@ -49,6 +49,7 @@ EXPORTS = (
     "plfem_flux_gram_work_bytes", "plfem_flux_grams", "plfem_sample_efields",
     "plfem_flux_overlap_posed_work_bytes", "plfem_flux_overlap_posed",
     "plfem_profile_tangent_gram_work_bytes", "plfem_profile_tangent_grams",
+    "plfem_velocity_gram_work_bytes", "plfem_velocity_grams",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -271,6 +272,8 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_sample_efields.argtypes = head + [vp, f64] + material + [i32, vp, vp, vp, vp]
     lib.plfem_flux_overlap_posed_work_bytes.argtypes = [vp, i32, i32, i32] + size
     lib.plfem_flux_overlap_posed.argtypes = ([vp, vp, i32, i32] + material) * 2 + [i32, vp] + tail
+    lib.plfem_velocity_gram_work_bytes.argtypes = [vp, i32, i32, i32] + size
+    lib.plfem_velocity_grams.argtypes = head + material + [vp, i32] + tail + [vp]
     lib.plfem_mesh_refine_marked_count.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_int32]

@@ -12,7 +12,9 @@
 // (k_profile_grams + k_overlap_reduce), and the per-element a-posteriori error indicators of a mode set: element residual
 // plus flux jumps across the edges (k_mode_indicators), and the electric field and axial Poynting flux of vectorial modes
 // at points (k_sample_efields) with the Grams their cross powers are built from (k_flux_grams + k_overlap_reduce), and the
-// E x H cross flux of two vectorial mode sets on two meshes under a table of poses (k_flux_overlap_posed + k_overlap_reduce).
+// E x H cross flux of two vectorial mode sets on two meshes under a table of poses (k_flux_overlap_posed + k_overlap_reduce),
+// and the first-order change of the Grams when the mesh moves with a vertex velocity field and carries its material along
+// (k_velocity_flag, k_velocity_count + k_velocity_fill, k_velocity_grams + k_overlap_reduce + k_velocity_symmetrise).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
@@ -964,6 +966,194 @@ __global__ __launch_bounds__(256) void k_flux_grams(LocArgs L, int k, int64_t nr
     double* out = partial + (((int64_t)o * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
     for (int r = 0; r < 2; ++r)
       for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
+  }
+}
+
+// Velocity Grams (plfem_velocity_grams): the first-order change of the forms of k_profile_grams when the mesh moves by
+// x -> x + t V with the material convected with the points (the volume form of the shape derivative).  V is P1 on the
+// vertices ([nv][2] per velocity), so on an element it has a constant gradient G[2 a + b] = dV_a / dx_b, and with
+// tr = G_xx + G_yy and gt(f) = -G^T grad f + (tr / 2) grad f every gradient form changes by P + P^T, P the form with gt on
+// the row mode and the plain gradient on the column mode; a mass form changes by sum tr |det J| w_q c u_m . u_n, which
+// is Q + Q^T with (tr / 2) u on the row mode.  An element with G = 0 contributes nothing: the walk is over the elements
+// with G != 0 only, in four passes as in plfem_core_grams.
+constexpr int VG_GROUP = 16;     // most velocities per group: one launch of each pass
+constexpr int VG_SLICES = 128;   // most slices (partial blocks) per velocity and chunk pair
+
+// G of element e from the three vertex velocities and the element map: G = [v1 - v0, v2 - v0] adj(J) / det J, every
+// product rounded on its own as in P2Map::det, then one division.  Equal vertex velocities give exact zeros, and V = x
+// gives the identity exactly on every element, a sliver included: its numerators are det J and 0 bit for bit.
+__device__ __forceinline__ void velocity_grad(const LocArgs& L, const double* __restrict__ vel, int e, const P2Map& M, double det,
+                                              double G[4]) {
+  const int v0 = L.edof[e], v1 = L.edof[L.ne + e], v2 = L.edof[2 * L.ne + e];
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    const double d1 = vel[2 * v1 + a] - vel[2 * v0 + a], d2 = vel[2 * v2 + a] - vel[2 * v0 + a];
+    G[2 * a] = (mul_rn(d1, M.j11) - mul_rn(d2, M.j10)) / det;
+    G[2 * a + 1] = (mul_rn(d2, M.j00) - mul_rn(d1, M.j01)) / det;
+  }
+}
+
+// Pass 1, k_velocity_flag: one lane per (element, velocity = blockIdx.y); flag = any entry of G non-zero.
+__global__ __launch_bounds__(256) void k_velocity_flag(LocArgs L, const double* __restrict__ vel, int32_t* __restrict__ flag) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= L.ne) return;
+  const P2Map M(L.edof, L.ne, L.pxy, L.pxy + L.nv, e);
+  double G[4];
+  velocity_grad(L, vel + (int64_t)blockIdx.y * 2 * L.nv, e, M, M.det(), G);
+  flag[(int64_t)blockIdx.y * L.ne + e] = (G[0] != 0.0 || G[1] != 0.0 || G[2] != 0.0 || G[3] != 0.0) ? 1 : 0;
+}
+
+// Pass 2, compaction, the scheme of k_core_count / k_core_fill: one workgroup per velocity counts its flagged elements,
+// then, with the exclusive offsets summed from the counts, fills its ascending list by rank -- ballot and popcount inside
+// a wave, the four wave totals in wave order, a running base across the 256-element steps: no atomic decides a position.
+// meta = counts [VG_GROUP], then offsets [VG_GROUP].
+__global__ __launch_bounds__(256) void k_velocity_count(int ne, const int32_t* __restrict__ flag, int32_t* __restrict__ meta) {
+  __shared__ int s_n[256];
+  const int tid = threadIdx.x, v = blockIdx.x;
+  const int32_t* mine = flag + (int64_t)v * ne;
+  int n = 0;
+  for (int e = tid; e < ne; e += 256) n += mine[e] ? 1 : 0;
+  s_n[tid] = n;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) s_n[tid] += s_n[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) meta[v] = s_n[0];
+}
+
+__global__ __launch_bounds__(256) void k_velocity_fill(int ne, const int32_t* __restrict__ flag, int32_t* __restrict__ meta,
+                                                       int32_t* __restrict__ list) {
+  __shared__ int s_wave[4];
+  const int tid = threadIdx.x, v = blockIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t* mine = flag + (int64_t)v * ne;
+  int64_t base = 0;
+  for (int j = 0; j < v; ++j) base += meta[j];
+  if (tid == 0) meta[VG_GROUP + v] = (int32_t)base;
+  for (int e0 = 0; e0 < ne; e0 += 256) {
+    const int e = e0 + tid;
+    const bool in = e < ne && mine[e] != 0;
+    const unsigned long long votes = __ballot(in);
+    if (lane == 0) s_wave[wave] = __popcll(votes);
+    __syncthreads();
+    int before = __popcll(votes & ((1ull << lane) - 1ull)), total = 0;
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) before += s_wave[w];
+      total += s_wave[w];
+    }
+    if (in) list[base + before] = e;
+    base += total;
+    __syncthreads();
+  }
+}
+
+// Pass 3, k_velocity_grams: grid = (slice, chunk pair, velocity of the group).  The workgroup walks tiles of GT points of
+// its velocity's element list (six points per listed element, element-major; tiles blockIdx.x, blockIdx.x + gridDim.x,
+// ...), staging and features as in k_profile_grams; the staging lane also forms G of its element (velocity_grad) and the
+// point's material weight -- ncomp = 2: 1 / eps, ncomp = 1: eps, by material_eps as in k_flux_grams.  The lane that wrote a
+// row-chunk feature then turns it into the transformed one: value -> (tr / 2) value, gradient -> gt.  Outputs, each the
+// asymmetric half X of X + X^T (k_velocity_symmetrise): (ncomp = 2) K under w with the signs of k_mode_grams, D, M, M under
+// w; (ncomp = 1) S, M, M under w.  Partials [velocity][output][chunk pair][slice][OC * OC], every slot written.
+template <int NCOMP, bool PROFILE, typename... Map>
+__global__ __launch_bounds__(256) void k_velocity_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V, Material mat,
+                                                        const double* __restrict__ vel, const int32_t* __restrict__ meta,
+                                                        const int32_t* __restrict__ list, int nchunk,
+                                                        double* __restrict__ partial, Map... map) {
+  constexpr int NF = 3 * NCOMP;
+  constexpr int NOUT = NCOMP == 2 ? 4 : 3;
+  __shared__ double s_f[2][NF][GT][OC];
+  __shared__ double s_gx[6][GT], s_gy[6][GT];
+  __shared__ int s_r[6][GT];
+  __shared__ double s_w[GT], s_wt[GT], s_G[4][GT];
+  __shared__ int s_q[GT];
+  const int tid = threadIdx.x, v = blockIdx.z;
+  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
+  const int i0 = ci * OC, j0 = cj * OC;
+  const int64_t npts = (int64_t)6 * meta[v];
+  const int32_t* mine = list + meta[VG_GROUP + v];
+  const double* myvel = vel + (int64_t)v * 2 * L.nv;
+  const int64_t ntiles = (npts + GT - 1) / GT;
+  const int ti = tid >> 4, tj = tid & 15;
+  double acc[NOUT][2][2];
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    if (tid < GT) {
+      const int64_t p = tile * GT + tid;
+      const bool live = p < npts;
+      const int e = live ? mine[p / 6] : 0;
+      double wt = 1.0, G[4] = {0.0, 0.0, 0.0, 0.0};
+      gram_stage_point(L, (int64_t)6 * e + p % 6, live, tid, s_gx, s_gy, s_r, s_w, s_q,
+                       [&](double X, double Y) {
+        bool in = false;
+        if constexpr (!PROFILE) in = in_any_core(X, Y, mat.cores.c, mat.ncore);
+        const double eps = material_eps<PROFILE>(mat, X, Y, in, map...);
+        wt = NCOMP == 2 ? 1.0 / eps : eps;
+        const P2Map M(L.edof, L.ne, L.pxy, L.pxy + L.nv, e);
+        velocity_grad(L, myvel, e, M, M.det(), G);
+      });
+      s_wt[tid] = wt;
+      for (int c = 0; c < 4; ++c) s_G[c][tid] = G[c];
+    }
+    __syncthreads();
+    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
+    // the row chunk (side 0 of gram_features: the same idx -> (mode, point) map, so every lane reads what it wrote)
+    for (int idx = tid; idx < GT * OC; idx += 256) {
+      const int i = idx % OC, t = idx / OC;
+      const double gxx = s_G[0][t], gxy = s_G[1][t], gyx = s_G[2][t], gyy = s_G[3][t];
+      const double h = 0.5 * (gxx + gyy);
+#pragma unroll
+      for (int c = 0; c < NCOMP; ++c) {
+        const double fx = s_f[0][NCOMP + 2 * c][t][i], fy = s_f[0][NCOMP + 2 * c + 1][t][i];
+        s_f[0][c][t][i] *= h;
+        s_f[0][NCOMP + 2 * c][t][i] = h * fx - (gxx * fx + gyx * fy);
+        s_f[0][NCOMP + 2 * c + 1][t][i] = h * fy - (gxy * fx + gyy * fy);
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < GT; ++t) {
+      double2 a[NF], b[NF];
+#pragma unroll
+      for (int c = 0; c < NF; ++c) {
+        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
+        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
+      }
+      const double w = s_wt[t];                 // the same for every lane
+      if constexpr (NCOMP == 2) {
+        // features 0 hx, 1 hy, 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy (row chunk: transformed)
+        GRAM_ACC(0, 3, 3, w) GRAM_ACC(0, 4, 4, w) GRAM_ACC(0, 2, 5, -w) GRAM_ACC(0, 5, 2, -w)
+        GRAM_ACC(1, 2, 2, 1.0) GRAM_ACC(1, 5, 5, 1.0) GRAM_ACC(1, 3, 4, 1.0) GRAM_ACC(1, 4, 3, 1.0)
+        GRAM_ACC(2, 0, 0, 1.0) GRAM_ACC(2, 1, 1, 1.0)
+        GRAM_ACC(3, 0, 0, w) GRAM_ACC(3, 1, 1, w)
+      } else {
+        // features 0 u, 1 dx u, 2 dy u (row chunk: transformed)
+        GRAM_ACC(0, 1, 1, 1.0) GRAM_ACC(0, 2, 2, 1.0)
+        GRAM_ACC(1, 0, 0, 1.0)
+        GRAM_ACC(2, 0, 0, w)
+      }
+    }
+    __syncthreads();
+  }
+  const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) {
+    double* out = partial + ((((int64_t)v * NOUT + o) * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+    for (int r = 0; r < 2; ++r)
+      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
+  }
+}
+
+// Pass 4, after k_overlap_reduce: O[m] <- O[m] + O[m]^T in place, blockIdx.y = matrix.  One lane per pair i <= j reads both
+// entries, adds them once and writes the one sum to both places: the matrices are bitwise symmetric.
+__global__ __launch_bounds__(256) void k_velocity_symmetrise(int k, double* __restrict__ O) {
+  O += (int64_t)blockIdx.y * k * k;
+  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < k * k; idx += 256 * gridDim.x) {
+    const int i = idx / k, j = idx % k;
+    if (i > j) continue;
+    const double s = O[(int64_t)i * k + j] + O[(int64_t)j * k + i];
+    O[(int64_t)i * k + j] = s;
+    O[(int64_t)j * k + i] = s;
   }
 }
 #undef GRAM_ACC
@@ -2792,6 +2982,106 @@ extern "C" int plfem_core_grams(plfem_locator* L, int32_t ncomp, int32_t k, cons
   HIP_TRY(L, hipMemcpyAsync(counts, meta, sizeof(int32_t) * ncore, hipMemcpyDeviceToHost, L->stream));
   TRY(grams_to_host(call, ncore * core_gram_outputs(ncomp), k, lay.slices, out_host));
   for (int c = 0; c < ncore; ++c) count_host[c] = counts[c];   // (the stream is synchronised)
+  return PLFEM_OK;
+} catch (...) { return host_failure(L); }
+
+namespace {
+constexpr int VG_MAX = 256;      // most velocities per call
+constexpr size_t VG_PARTIAL_BYTES = (size_t)256 << 20;   // most partial blocks of one group
+int velocity_gram_outputs(int ncomp) { return ncomp == 2 ? 4 : 3; }
+// Work buffer of plfem_velocity_grams: the result [nvel][nout][k][k]; then for ONE group of `group` velocities -- at most
+// VG_GROUP, and no more than VG_PARTIAL_BYTES of partial blocks hold (7 at k = 70) -- the partials
+// [group][nout][chunk pair][slice][OC * OC], the vertex velocities [group][nv][2], the element flags [group][ne], the
+// element lists (group x ne int32), counts and offsets; every part 256-byte aligned.  Slices: no more than the mesh has
+// tiles, at least 1, a function of the mesh alone -- the tiles a slice sums, and so the bits of an entry, must change
+// neither with the number of modes nor with the velocities of the call.
+struct VelocityGramLayout { int slices, group; size_t off_partial, off_vel, off_flag, off_list, off_meta, total; };
+VelocityGramLayout velocity_gram_layout(const plfem_locator* L, int ncomp, int k, int nvel) {
+  const size_t nout = velocity_gram_outputs(ncomp), nc = overlap_chunks(k);
+  const size_t ne = std::max(1, L->ne), nv = std::max(1, L->nv);
+  const int64_t ntiles = ((int64_t)6 * L->ne + GT - 1) / GT;
+  VelocityGramLayout l;
+  l.slices = (int)std::max<int64_t>(1, std::min<int64_t>(VG_SLICES, ntiles));
+  const size_t per_vel = nout * nc * nc * l.slices * OC * OC * sizeof(double);
+  l.group = (int)std::max<size_t>(1, std::min<size_t>({(size_t)VG_GROUP, (size_t)nvel, VG_PARTIAL_BYTES / per_vel}));
+  const size_t g = l.group;
+  size_t o = align256((size_t)nvel * nout * k * k * sizeof(double));
+  l.off_partial = o; o += align256(g * per_vel);
+  l.off_vel = o;     o += align256(g * nv * 2 * sizeof(double));
+  l.off_flag = o;    o += align256(g * ne * sizeof(int32_t));
+  l.off_list = o;    o += align256(g * ne * sizeof(int32_t));
+  l.off_meta = o;    o += align256((size_t)2 * VG_GROUP * sizeof(int32_t));
+  l.total = o;
+  return l;
+}
+const char* velocity_gram_args(int ncomp, int k, int nvel) {
+  if (!modes_ok(ncomp, k)) return "ncomp must be 1 or 2 and k >= 1";
+  if (nvel < 1 || nvel > VG_MAX) return "nvel must be in [1, 256]";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int plfem_velocity_gram_work_bytes(const plfem_locator* L, int32_t ncomp, int32_t k, int32_t nvel, int64_t* bytes) try {
+  if (!L || !bytes || velocity_gram_args(ncomp, k, nvel)) return PLFEM_EINVAL;
+  *bytes = (int64_t)velocity_gram_layout(L, ncomp, k, nvel).total;
+  return PLFEM_OK;
+} catch (...) { return host_failure(nullptr, 0); }
+
+extern "C" int plfem_velocity_grams(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                    const double* cores_host, int32_t ncore, double eps_core, double eps_clad,
+                                    const double* layers_host, int32_t nlayer, double eps_bg, int32_t use_profile,
+                                    const double* velocities_host, int32_t nvel, void* work_dev, int64_t work_bytes,
+                                    double* out_host, int64_t* count_host) try {
+  if (!L) return PLFEM_EINVAL;
+  FieldCall call{L, "plfem_velocity_grams"};
+  if (const char* bad = velocity_gram_args(ncomp, k, nvel)) return call.reject(bad);
+  if (!ncore_ok(ncore, false)) return call.reject("ncore must be in [0, 64]");
+  if (!modes_dev || !velocities_host || !work_dev || !out_host || !count_host || (ncore > 0 && !cores_host))
+    return call.reject("null array");
+  const size_t per_vel = (size_t)2 * L->nv;
+  for (size_t i = 0, n = (size_t)nvel * per_vel; i < n; ++i)
+    if (!std::isfinite(velocities_host[i])) return call.reject("every velocity entry must be finite");
+  if (const char* bad = material_error(L, eps_core, eps_clad, layers_host, nlayer, eps_bg, use_profile)) return call.reject(bad);
+  const VelocityGramLayout lay = velocity_gram_layout(L, ncomp, k, nvel);
+  TRY(call.enter(indexed, "plfem_velocity_gram_work_bytes", work_dev, work_bytes, lay.total, lay.off_partial));
+  Material mat;
+  TRY(stage_material(L, cores_host, ncore, eps_core, eps_clad, layers_host, nlayer, eps_bg, use_profile, mat));
+  char* base = (char*)work_dev;
+  double* d_vel = (double*)(base + lay.off_vel);
+  int32_t *flag = (int32_t*)(base + lay.off_flag), *list = (int32_t*)(base + lay.off_list), *meta = (int32_t*)(base + lay.off_meta);
+  const int nc = overlap_chunks(k), nout = velocity_gram_outputs(ncomp);
+  int32_t counts[VG_MAX];
+  for (int v0 = 0; v0 < nvel; v0 += lay.group) {
+    const int nhere = std::min(lay.group, nvel - v0);
+    double* O = call.O + (size_t)v0 * nout * k * k;
+    if (per_vel > 0)
+      HIP_TRY(L, hipMemcpyAsync(d_vel, velocities_host + (size_t)v0 * per_vel, sizeof(double) * nhere * per_vel,
+                                hipMemcpyHostToDevice, L->stream));
+    if (L->ne > 0) {
+      hipLaunchKernelGGL(k_velocity_flag, dim3((unsigned)((L->ne + 255) / 256), nhere), dim3(256), 0, L->stream, call.loc, d_vel, flag);
+      TRY(check_launch(L, "k_velocity_flag"));
+    }
+    hipLaunchKernelGGL(k_velocity_count, dim3(nhere), dim3(256), 0, L->stream, L->ne, flag, meta);
+    TRY(check_launch(L, "k_velocity_count"));
+    hipLaunchKernelGGL(k_velocity_fill, dim3(nhere), dim3(256), 0, L->stream, L->ne, flag, meta, list);
+    TRY(check_launch(L, "k_velocity_fill"));
+    with_constant<2, 1>(ncomp, [&](auto nco) {
+      with_material(L, use_profile, [&](auto profile, auto... map) {
+        hipLaunchKernelGGL((k_velocity_grams<decltype(nco)::value, decltype(profile)::value, decltype(map)...>),
+                           dim3(lay.slices, nc * nc, nhere), dim3(256), 0, L->stream, call.loc, (int)k, call.nrows, modes_dev, mat,
+                           d_vel, meta, list, nc, call.partial, map...);
+      });
+    });
+    TRY(check_launch(L, "k_velocity_grams"));
+    hipLaunchKernelGGL(k_overlap_reduce, dim3(nc * nc, nhere * nout, OC * OC / 256), dim3(256), 0, L->stream, (int)k, (int)k,
+                       lay.slices, nc, call.partial, O);
+    TRY(check_launch(L, "k_overlap_reduce"));
+    hipLaunchKernelGGL(k_velocity_symmetrise, dim3((k * k + 255) / 256, nhere * nout), dim3(256), 0, L->stream, (int)k, O);
+    TRY(check_launch(L, "k_velocity_symmetrise"));
+    HIP_TRY(L, hipMemcpyAsync(counts + v0, meta, sizeof(int32_t) * nhere, hipMemcpyDeviceToHost, L->stream));
+  }
+  TRY(result_to_host(L, call.O, (size_t)nvel * nout * k * k, out_host));
+  for (int v = 0; v < nvel; ++v) count_host[v] = counts[v];   // (the stream is synchronised)
   return PLFEM_OK;
 } catch (...) { return host_failure(L); }
 

@@ -21,6 +21,9 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
 * :meth:`ModeFields.sample_e`, :meth:`ModeFields.flux_grams` -- the electric field and axial Poynting flux of vectorial
   modes at points (``plfem_sample_efields``) and the Grams their cross powers are built from (``plfem_flux_grams``): what
   :mod:`.power` builds modal power, power confinement and power orthogonality from;
+* :meth:`ModeFields.velocity_grams` -- the first-order change of the projected forms when the mesh moves with a vertex
+  velocity field and carries its material along (``plfem_velocity_grams``): what :mod:`.shape` builds the sensitivities
+  of n_eff to core position, radius and ellipticity from;
 * :func:`flux_overlap_poses` -- the four beta-free sums of the E x H cross flux of two vectorial mode sets on two meshes
   under a table of poses (``plfem_flux_overlap_posed``): what :mod:`.splice` builds power-normalised splice maps and
   vectorial taper steps from;
@@ -56,6 +59,8 @@ FLUX_GRAM_NAMES = ("M_w_core", "M_w_rest", "G_w_core", "G_w_rest")      # vector
 MOMENT_GRAM_NAMES = {"vectorial": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "K_core_X", "K_core_Y", "K_clad_X",
                                    "K_clad_Y", "M_XX", "M_XY", "M_YY"),
                      "scalar": ("M_core_X", "M_core_Y", "M_clad_X", "M_clad_Y", "M_XX", "M_XY", "M_YY")}
+VELOCITY_GRAM_NAMES = {"vectorial": ("dK_w", "dD", "dM", "dM_w"), "scalar": ("dS", "dM", "dM_w")}
+VELOCITY_MAX = 256                 # VG_MAX of csrc/kernels_fields.hip: velocities per call of plfem_velocity_grams
 FLUX_OVERLAP_NAMES = ("MA", "GA", "MB", "GB")                           # plfem_flux_overlap_posed, per pose
 POSE_MAX_CHUNK_PAIRS = 256         # POSE_MAX_PAIRS of csrc/kernels_fields.hip: pairs of 32-mode chunks per posed call
 FLUX_POSE_MAX_CHUNK_PAIRS = 64     # FLUX_POSE_MAX_PAIRS: the same per posed flux call
@@ -182,6 +187,7 @@ class ModeFields:
                 sym = ent["sym"]
         self.sym = sym if sym is not None else _native.Symbolic(p, t)
         self.N, self.nsolve, self.ne = self.sym.N, self.sym.nsolve, self.sym.ne
+        self.nv = int(p.shape[1])
         self.bbox = (float(p[0].min()), float(p[0].max()), float(p[1].min()), float(p[1].max()))
         self._loc = None
         self._mem = None
@@ -718,6 +724,48 @@ class ModeFields:
                         (_native._ptr(cores), ncore), (out, points), loc=self._loc)
         res = {nm: np.ascontiguousarray(out[:, i]) for i, nm in enumerate(names)}
         res["points"] = points
+        return res
+
+    def velocity_grams(self, modes: Sequence[Dict], geometry, velocities) -> Dict[str, np.ndarray]:
+        """First-order change of the projected forms under mesh velocities (``plfem_velocity_grams``).  ``velocities``
+        (nvel, nv, 2) or (nv, 2): per velocity a P1 field V on the mesh vertices, at most 256.  Under ``x -> x + t V``, every
+        quadrature point keeping the material ``geometry`` gives it on the unmoved mesh (its index profile if it carries
+        one, else its discs at ``n_core`` on ``n_clad``), the forms of :meth:`profile_grams` change at first order by the
+        returned arrays, each (nvel, k, k) and bitwise symmetric: vectorial records ``dK_w``, ``dD``, ``dM``, ``dM_w``
+        (``w = 1 / eps``; ``d(V^T A V) = dK_w + alpha_p dD - k0^2 dM``, ``d(V^T B V) = dM_w``), scalar records ``dS``,
+        ``dM``, ``dM_w`` (``w = eps``; ``d(V^T A V) = dS - k0^2 dM_w``, ``d(V^T B V) = dM``); and ``count`` (nvel,) int64,
+        the elements on which the velocity has a non-zero gradient -- the only ones that contribute."""
+        mat = self._material(geometry)
+        kind, vals, _, k = self._checked(modes)
+        vel = np.asarray(velocities, dtype=np.float64)
+        if vel.ndim == 2:
+            vel = vel[None]
+        if vel.ndim != 3 or vel.shape[1:] != (self.nv, 2):
+            raise ValueError(f"velocities must have shape (nvel, {self.nv}, 2) or ({self.nv}, 2)")
+        nvel = vel.shape[0]
+        if not 1 <= nvel <= VELOCITY_MAX:
+            raise ValueError(f"between 1 and {VELOCITY_MAX} velocities per call")
+        if not np.all(np.isfinite(vel)):
+            raise ValueError("every velocity entry must be finite")
+        if k == 0:
+            res = {nm: np.zeros((nvel, 0, 0)) for nm in VELOCITY_GRAM_NAMES.get(kind, ())}
+            res["count"] = np.zeros(nvel, dtype=np.int64)
+            return res
+        return self._velocity_grams_staged(kind, self._staged(vals), mat, np.ascontiguousarray(vel))
+
+    def _velocity_grams_staged(self, kind, staged, mat, vel, work=None) -> Dict[str, np.ndarray]:
+        """``plfem_velocity_grams`` on modes already staged (ncomp, n, k) on the device; ``mat``: what :meth:`_material`
+        returns; ``vel`` (nvel, nv, 2) contiguous float64; ``work``: a uint8 device tensor to use as the work buffer."""
+        self._set_index_map(mat.index_map)
+        names = VELOCITY_GRAM_NAMES[kind]
+        ncomp, _, k = staged.shape
+        nvel = vel.shape[0]
+        out = np.empty((nvel, len(names), k, k), dtype=np.float64)
+        count = np.empty(nvel, dtype=np.int64)
+        self._mode_call("plfem_velocity_gram_work_bytes", {"ncomp": ncomp, "k": k, "nvel": nvel}, "plfem_velocity_grams", kind,
+                        staged, (*self._material_args(mat), _native._ptr(vel), nvel), (out, count), work=work, loc=self._loc)
+        res = {nm: np.ascontiguousarray(out[:, i]) for i, nm in enumerate(names)}
+        res["count"] = count
         return res
 
     @staticmethod

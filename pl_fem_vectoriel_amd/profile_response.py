@@ -15,7 +15,8 @@ Material dispersion (a tangent of ``dn / d lambda0``), the index of a layer (the
 bends are the same Hellmann-Feynman computation with different tangents; everything here is k x k host math on the
 Grams.  Nothing is assembled, factorised or solved again.
 
-Shapes (radii, centres) are not values: the discrete permittivity is a staircase in them.  The
+Shapes (radii, centres) are not values: on a fixed mesh the discrete permittivity is a staircase in them (DESIGN.md
+section 20); their derivatives come from moving the mesh with the core, :mod:`.shape`.  The
 vectorial numbers describe the reference's pencil as it is ("What the vectorial numbers mean").
 """
 from __future__ import annotations
@@ -120,6 +121,13 @@ def profile_sensitivity_from_grams(kind: str, grams: Dict[str, np.ndarray], tang
             raise ValueError(f"direction must be {ntan} finite numbers, one per tangent") from None
         if dirs.size != ntan or not np.all(np.isfinite(dirs)):
             raise ValueError(f"direction must be {ntan} finite numbers, one per tangent")
+    return _sensitivity_from_pencil(A, B, dA, dB, mu, sgn, beta, k0, dirs, cluster_rtol)
+
+
+def _sensitivity_from_pencil(A, B, dA, dB, mu, sgn, beta, k0: float, dirs, cluster_rtol: float) -> Dict:
+    """What :func:`profile_sensitivity_from_grams` returns, from the projected pencil ``(A, B)`` and its derivatives ``dA``,
+    ``dB`` (n, k, k) along n parameters; ``dirs`` (n,) or None (shared with :mod:`.shape`)."""
+    k, ntan = beta.size, dA.shape[0]
     s = 1.0 / np.sqrt(np.diag(B))                          # B-normalisation of every record
     A, B = (s[:, None] * X * s[None, :] for X in (A, B))
     dA, dB = (s[None, :, None] * X * s[None, None, :] for X in (dA, dB))
