@@ -615,6 +615,46 @@ int plfem_profile_tangent_grams(plfem_locator* loc, int32_t ncomp, int32_t k, co
                                 int32_t moments, const double origin_host[2],
                                 void* work_dev, int64_t work_bytes, double* out_host);
 
+/* Pixel densities of a sampled map: the derivative of the diagonal of M_w (and K_w) of plfem_profile_grams in the value
+ * of EVERY pixel of the locator's map E[ny][nx] (plfem_locator_set_index_map), in one pass over the quadrature points
+ * whatever the number of pixels -- the adjoint of the bilinear interpolant of the profile.  Modes, indexed, layers_host,
+ * nlayer and eps_bg as for plfem_profile_grams; the staged fields v_r are the modes or any combination of them formed
+ * before staging.  At a point of the six-point rule, formed as the assembly forms it: the topmost layer, the map cell
+ * (i0, j0) and the weights (a, b), eps and w = 1 / eps (ncomp = 2) or eps (ncomp = 1) as plfem_profile_tangent_grams forms
+ * them.  The point CONTRIBUTES when it lies in the closed extent of the map and no layer holds it.  It then adds
+ * c = |det J| w_q dw, dw = -(w w) (ncomp = 2) or 1 (ncomp = 1), times a density of the field, times the corner weight
+ * a1 b1, a b1, a1 b, a b (a1 = 1 - a, b1 = 1 - b) to the nodes (j0, i0), (j0, i0 + 1), (j0 + 1, i0), (j0 + 1, i0 + 1); the
+ * clamped cell of the last column (i0 = nx - 2, a = 1) feeds column nx - 1.  Densities and outputs:
+ *   ncomp = 2: m_r = hx_r^2 + hy_r^2 and kk_r = the form of K_r of plfem_mode_grams at m = n, (dy hx)^2 + (dx hy)^2 -
+ *     2 dx hx dy hy; out_host[r][0] = M_px[r] = d(v_r^T B v_r) / dE and out_host[r][1] = K_px[r] = d(v_r^T A v_r) / dE;
+ *   ncomp = 1: m_r = u_r^2; out_host[r][0] = M_px[r] = d(M_w)_rr / dE, so d(v_r^T A v_r) / dE = -k0^2 M_px[r].
+ * So for any tangent map D on the grid sum_ji D[j][i] M_px[r][j][i] = M_d[r][r] of plfem_profile_tangent_grams for the
+ * tangent (0, 0.., map D), K likewise.  support_host[j][i] (may be null) = the number of contributing points in the up
+ * to four cells the node is a corner of; a node with support 0 carries an exact 0 in every plane (the mesh does not see
+ * the pixel, or layers cover it).
+ * Kernels: one lane per point writes the point's cell as a key (one past the last cell where it does not contribute)
+ * with (a, b, c); a stable radix sort of (key, point) on 25 bits makes every cell's points contiguous in ascending point
+ * order; per chunk of 16 fields one lane per contributing point writes the densities, and one wavefront per node with a
+ * non-empty list walks the node's cells in ascending order, lane l taking every 64th point from the l-th, and sums the
+ * lanes by a fixed butterfly.  No floating-point atomics: the same bits on every run, for a field whatever other fields
+ * share the call and in whatever order, and whatever the work buffer held.  Every entry of out_host and support_host is
+ * written.  Synchronises the locator's stream.
+ * work_dev: device scratch of plfem_index_map_gradient_work_bytes(loc, ncomp, k) bytes (it depends on the mesh and on the
+ * map, hence the locator), 256-byte aligned, every part rounded up to 256 bytes: k nout nx ny doubles of result (nout = 2
+ * or 1); nx ny int32; 4 x 6 ne uint32 and 3 x 6 ne doubles of keys and point data; 16 nout x 6 ne doubles of densities;
+ * 2 (nx - 1)(ny - 1) int32 of cell ranges; the sort's temporary storage (about 2 x 6 ne uint32 plus its histograms).
+ * Argument errors (ncomp not 1 or 2, k outside [1, 256], no map on the locator, k nout nx ny > 2^27 -- 1 GiB of result:
+ * call with fewer fields --, a table plfem_set_index_profile rejects, a null modes_dev, work_dev or out_host, work_bytes
+ * too small) return PLFEM_EINVAL with the locator's last error set and nothing written.
+ * plfem_index_map_gradient_work_bytes rejects a null loc or bytes (left alone) and the first four of these; the sort's
+ * storage is sized by rocPRIM for the device at hand, so without a device it returns PLFEM_EHIP. */
+int plfem_index_map_gradient_work_bytes(const plfem_locator* loc, int32_t ncomp, int32_t k, int64_t* bytes);
+int plfem_index_map_gradients(plfem_locator* loc, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                              const double* layers_host, int32_t nlayer, double eps_bg,
+                              void* work_dev, int64_t work_bytes,
+                              double* out_host /* [k][nout][ny][nx], nout = 2 (M_px, K_px) or 1 */,
+                              int32_t* support_host /* [ny][nx] or NULL */);
+
 /* Quartic mode-overlap tensor of k staged modes over the locator's mesh (the input of multimode nonlinear propagation:
  * f_ijkl, A_eff, gamma), on the 16-point degree-8 rule (products of four P2 fields are of degree 8).  Pairs i <= j are
  * numbered p(i,j) = i k - i (i - 1) / 2 + (j - i), np = k (k + 1) / 2.

@@ -10,6 +10,7 @@ from .bend import bend_propagate, bend_quantities_from_grams, bend_response  # n
 from .profile import IndexProfile, ProfileTangent, ProfiledGeometry  # noqa: F401
 from .profile_response import (profile_bend_from_grams, profile_bend_response, profile_dispersion,  # noqa: F401
                                profile_dispersion_from_grams, profile_sensitivity, profile_sensitivity_from_grams)
+from .map_gradient import index_map_gradient, index_map_gradient_from_densities  # noqa: F401
 from .adapt import adaptive_solve, mark_elements, mode_error_indicators, refine_marked  # noqa: F401
 from .splice import (flux_transfer_from_grams, splice_map, splice_power_map, splice_quantities_from_overlaps,  # noqa: F401
                      taper_from_interfaces, taper_transfer, taper_transfer_vectorial)
@@ -24,4 +25,5 @@ __all__ = ["MCFGeometry", "PhotonicLanternGeometry", "mcf_positions", "TriMesh",
            "mode_power", "power_quantities_from_grams", "Z0_OHM", "flux_overlap_poses", "flux_transfer_from_grams",
            "splice_power_map", "taper_transfer_vectorial", "ProfileTangent", "profile_dispersion", "profile_dispersion_from_grams",
            "profile_sensitivity", "profile_sensitivity_from_grams", "profile_bend_response", "profile_bend_from_grams",
-           "core_velocities", "shape_response", "shape_response_from_grams", "disorder_statistics"]
+           "core_velocities", "shape_response", "shape_response_from_grams", "disorder_statistics", "index_map_gradient",
+           "index_map_gradient_from_densities"]

@@ -50,6 +50,7 @@ EXPORTS = (
     "plfem_flux_overlap_posed_work_bytes", "plfem_flux_overlap_posed",
     "plfem_profile_tangent_gram_work_bytes", "plfem_profile_tangent_grams",
     "plfem_velocity_gram_work_bytes", "plfem_velocity_grams",
+    "plfem_index_map_gradient_work_bytes", "plfem_index_map_gradients",
 )
 SOLVE_STATS = ("nconv", "n_opinv", "restarts", "max_rel_res", "n_block_solves", "true_residual_first", "true_residual", "refined",
                "pivot_perturbations", "assemble_us", "factor_us", "lanczos_us", "post_us", "upload_us", "residual_us", "call_us")
@@ -274,6 +275,8 @@ def load_library() -> ctypes.CDLL:
     lib.plfem_flux_overlap_posed.argtypes = ([vp, vp, i32, i32] + material) * 2 + [i32, vp] + tail
     lib.plfem_velocity_gram_work_bytes.argtypes = [vp, i32, i32, i32] + size
     lib.plfem_velocity_grams.argtypes = head + material + [vp, i32] + tail + [vp]
+    lib.plfem_index_map_gradient_work_bytes.argtypes = [vp, i32, i32] + size
+    lib.plfem_index_map_gradients.argtypes = head + [vp, i32, f64] + tail + [vp]
     lib.plfem_mesh_refine_marked_count.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_int32]

@@ -14,7 +14,9 @@
 // at points (k_sample_efields) with the Grams their cross powers are built from (k_flux_grams + k_overlap_reduce), and the
 // E x H cross flux of two vectorial mode sets on two meshes under a table of poses (k_flux_overlap_posed + k_overlap_reduce),
 // and the first-order change of the Grams when the mesh moves with a vertex velocity field and carries its material along
-// (k_velocity_flag, k_velocity_count + k_velocity_fill, k_velocity_grams + k_overlap_reduce + k_velocity_symmetrise).
+// (k_velocity_flag, k_velocity_count + k_velocity_fill, k_velocity_grams + k_overlap_reduce + k_velocity_symmetrise),
+// and the derivative of the profile Grams' diagonal in every pixel of a sampled map (k_map_point_keys, the sort of
+// sort_pairs.h, k_map_cell_ranges, k_point_densities, k_map_gather).
 //
 // Replaces, on the user's side, scikit-fem's Basis.probes / Basis.interpolate on the reference's P2 basis
 // (reference solver_fem.py:126): the reference itself turns no mode vector back into a field, so the Grams, the
@@ -28,6 +30,7 @@
 
 #include "device.h"
 #include "p2_element.h"
+#include "sort_pairs.h"
 
 struct plfem_locator {
   const plfem::Symbolic* S = nullptr;
@@ -1599,6 +1602,169 @@ __global__ __launch_bounds__(256) void k_weighted_grams(LocArgs L, int k, int64_
     }
 }
 #undef WG_ACC
+
+// Pixel densities of a sampled map (plfem_index_map_gradients): the derivative of the diagonal of M_w (and K_w) of
+// k_profile_grams in the value of every pixel of the locator's map -- the adjoint of the bilinear interpolant of
+// profile_eps, one pass over the quadrature points whatever the number of pixels.  A point CONTRIBUTES when it lies in
+// the closed extent of the map and no layer holds it; it then adds c = |det J| w_q dw, dw = -(w w) (NCOMP = 2) or 1
+// (NCOMP = 1), times a density of the field -- m = hx^2 + hy^2 (u^2), kk = the form of K_r at m = n -- times a corner
+// weight to the four nodes of its cell.  No floating-point atomics: the points are sorted by cell and every node sums
+// its own lists in a fixed order.
+//
+// k_map_point_keys: one lane per quadrature point, the walk of k_profile_point_weights.  key = j0 (nx - 1) + i0 of a
+// contributing point, (nx - 1)(ny - 1) -- past every cell, so it sorts last -- of any other; val = the point; (a, b) the
+// weights of sampled_cell and c as above (0 where the point does not contribute).
+template <int NCOMP>
+__global__ __launch_bounds__(256) void k_map_point_keys(LocArgs L, const double* __restrict__ layers, int nlayer,
+                                                        uint32_t* __restrict__ key, uint32_t* __restrict__ val,
+                                                        double* __restrict__ pa, double* __restrict__ pb,
+                                                        double* __restrict__ pc, EpsMap em) {
+  const int64_t nq = (int64_t)6 * L.ne;
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= nq) return;
+  const int e = (int)(g / 6), q = (int)(g % 6);
+  const P2Map M(L.edof, L.ne, L.pxy, L.pxy + L.nv, e);
+  double X, Y, tg;
+  M.point(c_qx[q], c_qy[q], X, Y);
+  const int top = profile_top_layer(X, Y, layers, nlayer, tg);
+  const SampledGrid G = em.grid();
+  int i0 = 0, j0 = 0;
+  double a = 0.0, b = 0.0, c = 0.0;
+  uint32_t kk = (uint32_t)(G.nx - 1) * (uint32_t)(G.ny - 1);
+  if (sampled_cell(G, X, Y, i0, j0, a, b) && top < 0) {
+    const double eps = map_bilinear(em.eps(), G.nx, i0, j0, a, b);
+    const double w = NCOMP == 2 ? 1.0 / eps : eps;
+    const double dw = NCOMP == 2 ? -mul_rn(w, w) : 1.0;
+    c = mul_rn(mul_rn(fabs(M.det()), c_qw[q]), dw);
+    kk = (uint32_t)j0 * (uint32_t)(G.nx - 1) + (uint32_t)i0;
+  } else {
+    a = b = 0.0;
+  }
+  key[g] = kk;
+  val[g] = (uint32_t)g;
+  pa[g] = a;
+  pb[g] = b;
+  pc[g] = c;
+}
+
+// k_map_cell_ranges: one lane per place p of the sorted keys; where a cell's run begins (ends) it writes first[cell]
+// (last[cell], one past).  The arrays are zeroed before: a cell no point lies in keeps the empty range [0, 0).
+__global__ __launch_bounds__(256) void k_map_cell_ranges(int64_t nq, uint32_t ncell, const uint32_t* __restrict__ skey,
+                                                         int32_t* __restrict__ first, int32_t* __restrict__ last) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= nq) return;
+  const uint32_t kk = skey[p];
+  if (kk >= ncell) return;
+  if (p == 0 || skey[p - 1] != kk) first[kk] = (int32_t)p;
+  if (p == nq - 1 || skey[p + 1] != kk) last[kk] = (int32_t)(p + 1);
+}
+
+// k_point_densities: one lane per quadrature point, element-major, for the fields f0 .. f0 + nf - 1 of the call: the
+// features of the Gram kernels at the point (P2Map, p2_grad, p2_phi; the staged rows of dev_row) and from them
+// dens[f][0][g] = m, dens[f][1][g] = kk (NCOMP = 2).  Every sum is a chain of explicit fused multiply-adds in one written
+// order, and the fields are walked by a loop that is not unrolled: a field's bits do not depend on its place in the call.
+// A point that does not contribute (key = ncell) is skipped: no list holds it, so its slots are never read.
+constexpr int MAPG_FC = 16;     // fields per chunk: 32 accumulators per lane of k_map_gather
+
+template <int NCOMP>
+__global__ __launch_bounds__(256) void k_point_densities(LocArgs L, int k, int64_t nrows, const double* __restrict__ V, int f0,
+                                                         int nf, uint32_t ncell, const uint32_t* __restrict__ key,
+                                                         double* __restrict__ dens) {
+  constexpr int NOUT = NCOMP == 2 ? 2 : 1;
+  const int64_t nq = (int64_t)6 * L.ne;
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= nq || key[g] >= ncell) return;
+  const int e = (int)(g / 6), q = (int)(g % 6);
+  const P2Map M(L.edof, L.ne, L.pxy, L.pxy + L.nv, e);
+  const double xi = c_qx[q], eta = c_qy[q];
+  double inv[4], gx[6], gy[6], phi[6];
+  M.inverse(M.det(), inv);
+  p2_grad(inv, xi, eta, gx, gy);
+  p2_phi(xi, eta, phi);
+  int64_t row[6];
+  dev_row_offsets(L, e, k, row);
+#pragma unroll 1
+  for (int f = 0; f < nf; ++f) {
+    const int m = f0 + f;
+    double u[NCOMP], ux[NCOMP], uy[NCOMP];
+#pragma unroll
+    for (int c = 0; c < NCOMP; ++c) {
+      u[c] = ux[c] = uy[c] = 0.0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const double v = row[a] < 0 ? 0.0 : V[(int64_t)c * nrows * k + row[a] + m];
+        u[c] = fma(phi[a], v, u[c]);
+        ux[c] = fma(gx[a], v, ux[c]);
+        uy[c] = fma(gy[a], v, uy[c]);
+      }
+    }
+    double mm = mul_rn(u[0], u[0]);
+    if constexpr (NCOMP == 2) {
+      mm = fma(u[1], u[1], mm);
+      // dy hx dy hx + dx hy dx hy - dx hx dy hy - dy hy dx hx at m = n
+      double kk = mul_rn(uy[0], uy[0]);
+      kk = fma(ux[1], ux[1], kk);
+      kk = fma(-ux[0], uy[1], kk);
+      kk = fma(-uy[1], ux[0], kk);
+      dens[((int64_t)f * NOUT + 1) * nq + g] = kk;
+    }
+    dens[((int64_t)f * NOUT) * nq + g] = mm;
+  }
+}
+
+// k_map_gather: one wavefront per map node (four per workgroup) for the nf fields of the chunk.  The node (j, i) is a
+// corner of up to four cells, walked in ascending key: (j - 1, i - 1) with the corner weight a b, (j - 1, i) with a1 b,
+// (j, i - 1) with a b1, (j, i) with a1 b1 (a1 = 1 - a, b1 = 1 - b, every product rounded on its own).  Lane l takes the
+// places first + l, first + l + 64, .. of each cell's run of the sorted points -- ascending point order -- and adds
+// (c beta) dens by fused multiply-adds; the fixed butterfly of multi_reduce sums the lanes.  A field's sum depends on
+// the node's lists alone: the same bits whatever other fields share the chunk, in any place of it.  A node whose four
+// runs are empty writes nothing: the result and the support are zeroed before the launch.  support = the runs' lengths.
+template <int NCOMP>
+__global__ __launch_bounds__(256) void k_map_gather(int nx, int ny, int64_t nq, int nf, const int32_t* __restrict__ first,
+                                                    const int32_t* __restrict__ last, const uint32_t* __restrict__ sval,
+                                                    const double* __restrict__ pa, const double* __restrict__ pb,
+                                                    const double* __restrict__ pc, const double* __restrict__ dens,
+                                                    double* __restrict__ out, int32_t* __restrict__ support) {
+  constexpr int NOUT = NCOMP == 2 ? 2 : 1;
+  constexpr int NV = MAPG_FC * NOUT;
+  const int lane = threadIdx.x & 63;
+  const int64_t npix = (int64_t)nx * ny;
+  const int64_t node = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (node >= npix) return;                   // (the whole wavefront)
+  const int j = (int)(node / nx), i = (int)(node % nx);
+  int lo[4], hi[4], total = 0;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int cj = j - 1 + (s >> 1), ci = i - 1 + (s & 1);
+    lo[s] = hi[s] = 0;
+    if (cj >= 0 && cj < ny - 1 && ci >= 0 && ci < nx - 1) {
+      const int64_t cell = (int64_t)cj * (nx - 1) + ci;
+      lo[s] = first[cell];
+      hi[s] = last[cell];
+    }
+    total += hi[s] - lo[s];
+  }
+  if (total == 0) return;
+  double acc[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    for (int p = lo[s] + lane; p < hi[s]; p += 64) {
+      const int64_t g = sval[p];
+      const double a = pa[g], b = pb[g];
+      const double wa = (s & 1) ? 1.0 - a : a, wb = (s >> 1) ? 1.0 - b : b;
+      const double cb = mul_rn(pc[g], mul_rn(wa, wb));
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        if (v < nf * NOUT) acc[v] = fma(cb, dens[(int64_t)v * nq + g], acc[v]);
+    }
+  }
+  multi_reduce<NV>(acc, lane);
+  const int v = multi_reduce_index<NV>(lane);
+  if (lane < NV && v < nf * NOUT) out[(int64_t)v * npix + node] = acc[0];
+  if (support && lane == 0) support[node] = total;
+}
 
 // Quartic mode-overlap tensor (plfem_mode_quartic): Q[p(i,j)][p(l,m)] = sum over the points of the 16-point degree-8 rule
 // of |det J| w_q wt(x) (u_i . u_j)(u_l . u_m), i.e. Q = R^T diag(w) R with R[point][pair] = u_i . u_j.  R never reaches
@@ -3223,6 +3389,107 @@ extern "C" int plfem_profile_tangent_grams(plfem_locator* L, int32_t ncomp, int3
     TRY(check_launch(L, "k_overlap_reduce"));
   }
   return result_to_host(L, call.O, (size_t)ncol * nout * k * k, out_host);
+} catch (...) { return host_failure(L); }
+
+namespace {
+constexpr int MAPG_KMAX = 256;                 // most fields per call
+constexpr int MAPG_KEY_BITS = 25;              // a key is at most (nx - 1)(ny - 1) < nx ny <= 2^24 (MAP_SAMPLES)
+constexpr int64_t MAPG_MAX_RESULT = (int64_t)1 << 27;   // most doubles of one call's result (1 GiB)
+int map_gradient_outputs(int ncomp) { return ncomp == 2 ? 2 : 1; }
+// Work buffer of plfem_index_map_gradients: the result [k][nout][ny][nx]; the support [ny][nx]; keys and points before
+// and after the sort, 4 x [6 ne] uint32; (a, b, c) of every point, 3 x [6 ne]; the densities of ONE chunk of fields
+// [16][nout][6 ne]; first and last place of every cell, 2 x [(nx - 1)(ny - 1)] int32; the sort's temporary storage; every
+// part 256-byte aligned.
+struct MapGradientLayout { size_t off_support, off_keys, off_abc, off_dens, off_cells, off_temp, temp_bytes, total; };
+MapGradientLayout map_gradient_layout(const plfem_locator* L, int ncomp, int k) {
+  const size_t nout = map_gradient_outputs(ncomp), npix = (size_t)L->map.nx * L->map.ny;
+  const size_t ncell = (size_t)(L->map.nx - 1) * (L->map.ny - 1), nq = std::max<size_t>(1, (size_t)6 * L->ne);
+  MapGradientLayout l;
+  size_t o = align256((size_t)k * nout * npix * sizeof(double));
+  l.off_support = o; o += align256(npix * sizeof(int32_t));
+  l.off_keys = o;    o += 4 * align256(nq * sizeof(uint32_t));
+  l.off_abc = o;     o += 3 * align256(nq * sizeof(double));
+  l.off_dens = o;    o += align256((size_t)MAPG_FC * nout * nq * sizeof(double));
+  l.off_cells = o;   o += 2 * align256(ncell * sizeof(int32_t));
+  l.temp_bytes = sort_pairs_temp_bytes(nq, MAPG_KEY_BITS);
+  l.off_temp = o;    o += align256(std::max<size_t>(1, l.temp_bytes));
+  l.total = o;
+  return l;
+}
+const char* map_gradient_args(const plfem_locator* L, int ncomp, int k) {
+  if (!modes_ok(ncomp, k, MAPG_KMAX)) return "ncomp must be 1 or 2 and 1 <= k <= 256";
+  if (!L->map.set()) return "no map on the locator (plfem_locator_set_index_map)";
+  if ((int64_t)k * map_gradient_outputs(ncomp) * L->map.nx * L->map.ny > MAPG_MAX_RESULT)
+    return "k nout nx ny must be <= 2^27: call with fewer fields";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int plfem_index_map_gradient_work_bytes(const plfem_locator* L, int32_t ncomp, int32_t k, int64_t* bytes) try {
+  if (!L || !bytes || map_gradient_args(L, ncomp, k)) return PLFEM_EINVAL;
+  const MapGradientLayout lay = map_gradient_layout(L, ncomp, k);
+  if (lay.temp_bytes == 0) return PLFEM_EHIP;       // (the sort could not be sized: no device)
+  *bytes = (int64_t)lay.total;
+  return PLFEM_OK;
+} catch (...) { return host_failure(nullptr, 0); }
+
+extern "C" int plfem_index_map_gradients(plfem_locator* L, int32_t ncomp, int32_t k, const double* modes_dev, int32_t indexed,
+                                         const double* layers_host, int32_t nlayer, double eps_bg, void* work_dev,
+                                         int64_t work_bytes, double* out_host, int32_t* support_host) try {
+  if (!L) return PLFEM_EINVAL;
+  FieldCall call{L, "plfem_index_map_gradients"};
+  if (const char* bad = map_gradient_args(L, ncomp, k)) return call.reject(bad);
+  if (const char* bad = profile_table_error(layers_host, nlayer, eps_bg)) return call.reject(bad);
+  if (!modes_dev || !work_dev || !out_host) return call.reject("null array");
+  const MapGradientLayout lay = map_gradient_layout(L, ncomp, k);
+  TRY(call.enter(indexed, "plfem_index_map_gradient_work_bytes", work_dev, work_bytes, lay.total, lay.off_support));
+  const int nx = L->map.nx, ny = L->map.ny, nout = map_gradient_outputs(ncomp);
+  const size_t npix = (size_t)nx * ny;
+  const uint32_t ncell = (uint32_t)(nx - 1) * (uint32_t)(ny - 1);
+  const int64_t nq = (int64_t)6 * L->ne;
+  const size_t qs = align256(std::max<size_t>(1, (size_t)nq) * sizeof(uint32_t)), ds = align256(std::max<size_t>(1, (size_t)nq) * sizeof(double));
+  char* base = (char*)work_dev;
+  int32_t* d_support = (int32_t*)(base + lay.off_support);
+  uint32_t *key = (uint32_t*)(base + lay.off_keys), *val = (uint32_t*)(base + lay.off_keys + qs);
+  uint32_t *skey = (uint32_t*)(base + lay.off_keys + 2 * qs), *sval = (uint32_t*)(base + lay.off_keys + 3 * qs);
+  double *pa = (double*)(base + lay.off_abc), *pb = (double*)(base + lay.off_abc + ds), *pc = (double*)(base + lay.off_abc + 2 * ds);
+  double* dens = (double*)(base + lay.off_dens);
+  const size_t cs = align256((size_t)ncell * sizeof(int32_t));
+  int32_t *first = (int32_t*)(base + lay.off_cells), *last = (int32_t*)(base + lay.off_cells + cs);
+  // (every call of a locator that reads the table ends with a stream synchronisation: nothing in flight reads the old one)
+  if (nlayer > 0)
+    HIP_TRY(L, hipMemcpyAsync(L->d_layers, layers_host, sizeof(double) * LAYER_DOUBLES * nlayer, hipMemcpyHostToDevice, L->stream));
+  // result, support and cell ranges: zero, whatever the buffer held; the kernels write the non-empty nodes and cells
+  HIP_TRY(L, hipMemsetAsync(call.O, 0, lay.off_support + npix * sizeof(int32_t), L->stream));
+  HIP_TRY(L, hipMemsetAsync(first, 0, 2 * cs, L->stream));
+  if (nq > 0) {
+    const dim3 qgrid((unsigned)((nq + 255) / 256));
+    with_constant<2, 1>(ncomp, [&](auto nco) {
+      hipLaunchKernelGGL(k_map_point_keys<decltype(nco)::value>, qgrid, dim3(256), 0, L->stream, call.loc, L->d_layers,
+                         (int)nlayer, key, val, pa, pb, pc, eps_map(L->map));
+    });
+    TRY(check_launch(L, "k_map_point_keys"));
+    HIP_TRY(L, sort_pairs(base + lay.off_temp, lay.temp_bytes, key, skey, val, sval, (size_t)nq, MAPG_KEY_BITS, L->stream));
+    hipLaunchKernelGGL(k_map_cell_ranges, qgrid, dim3(256), 0, L->stream, nq, ncell, skey, first, last);
+    TRY(check_launch(L, "k_map_cell_ranges"));
+    const dim3 ngrid((unsigned)((npix + 3) / 4));
+    for (int f0 = 0; f0 < k; f0 += MAPG_FC) {
+      const int nf = std::min(MAPG_FC, k - f0);
+      with_constant<2, 1>(ncomp, [&](auto nco) {
+        hipLaunchKernelGGL(k_point_densities<decltype(nco)::value>, qgrid, dim3(256), 0, L->stream, call.loc, (int)k, call.nrows,
+                           modes_dev, f0, nf, ncell, key, dens);
+      });
+      TRY(check_launch(L, "k_point_densities"));
+      with_constant<2, 1>(ncomp, [&](auto nco) {
+        hipLaunchKernelGGL(k_map_gather<decltype(nco)::value>, ngrid, dim3(256), 0, L->stream, nx, ny, nq, nf, first, last, sval,
+                           pa, pb, pc, dens, call.O + (size_t)f0 * nout * npix, f0 == 0 ? d_support : (int32_t*)nullptr);
+      });
+      TRY(check_launch(L, "k_map_gather"));
+    }
+  }
+  if (support_host)
+    HIP_TRY(L, hipMemcpyAsync(support_host, d_support, sizeof(int32_t) * npix, hipMemcpyDeviceToHost, L->stream));
+  return result_to_host(L, call.O, (size_t)k * nout * npix, out_host);
 } catch (...) { return host_failure(L); }
 
 namespace {

@@ -1,7 +1,8 @@
 // The P2 element on the device: the quadrature rule, the basis, the element map and the core test that every kernel
 // integrating or evaluating on the mesh shares (k_element_matrices, k_count_core_qp, k_core_mask, k_sample_fields,
 // k_field_overlap, k_mode_grams, k_profile_grams, k_mode_quartic, k_mode_project, k_mode_project_sampled, k_core_owner,
-// k_mode_indicators, k_flux_grams, k_sample_efields, k_flux_overlap_posed, k_profile_point_weights, k_weighted_grams).  One definition, so that a quadrature point lands in the same region, and det J rounds
+// k_mode_indicators, k_flux_grams, k_sample_efields, k_flux_overlap_posed, k_profile_point_weights, k_weighted_grams, k_map_point_keys,
+// k_point_densities).  One definition, so that a quadrature point lands in the same region, and det J rounds
 // the same way, in the assembly and in every kernel that must reproduce it.
 #pragma once
 #include <hip/hip_runtime.h>

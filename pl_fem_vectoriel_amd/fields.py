@@ -33,7 +33,10 @@ is done by ``libplfem_hip.so`` (``include/plfem.h``, "Mode fields at arbitrary p
   x and y, on the same rule (``plfem_mode_project``): what :mod:`.launch` builds far fields and launch maps from;
 * :meth:`ModeFields.project_sampled` -- the projection of the modes on a batch of complex images on a pixel grid (PSF
   frames, speckle, measured near fields, beam-propagation output), interpolated bilinearly at the points of the same
-  rule (``plfem_mode_project_sampled``): what :func:`.launch.field_coupling` builds response maps from.
+  rule (``plfem_mode_project_sampled``): what :func:`.launch.field_coupling` builds response maps from;
+* :meth:`ModeFields.index_map_densities` -- the derivative of the modes' weighted Grams in every pixel of a profile's
+  sampled map, one pass over the quadrature points (``plfem_index_map_gradients``): what :mod:`.map_gradient` builds the
+  gradient of every n_eff in every pixel from.
 
 Containment (``PLFEM_LOC_TOL``): a point is inside an element when every barycentric coordinate is >= -1e-10 (minus
 that coordinate's floating-point rounding bound, which matters on sliver elements only); when
@@ -66,6 +69,8 @@ POSE_MAX_CHUNK_PAIRS = 256         # POSE_MAX_PAIRS of csrc/kernels_fields.hip: 
 FLUX_POSE_MAX_CHUNK_PAIRS = 64     # FLUX_POSE_MAX_PAIRS: the same per posed flux call
 TANGENT_MAX = 256                  # TAN_MAX of csrc/kernels_fields.hip: tangents per call of plfem_profile_tangent_grams
 TANGENT_MAPS = 8                   # TAN_MAPS: tangent maps per call
+MAP_GRADIENT_MAX = 256             # MAPG_KMAX: fields per call of plfem_index_map_gradients
+MAP_GRADIENT_RESULT = 1 << 27      # MAPG_MAX_RESULT: doubles of one call's result
 PROJECT_TILE = (8, 8)             # PJ_X, PJ_Y of csrc/kernels_fields.hip: x- and y-factors per workgroup tile
 PROJECT_MAX_FACTORS = 4096         # PJ_LMAX
 PROJECT_SAMPLED_TILE = 32          # PS_F: frames per workgroup tile of the sampled projection
@@ -522,6 +527,68 @@ class ModeFields:
             if mom:
                 out[ntan:] = part[len(idx):]
         return self._tangent_result(kind, out, ntan, moments)
+
+    def index_map_densities(self, modes: Sequence[Dict], geometry, basis=None) -> Dict[str, np.ndarray]:
+        """Pixel densities of the sampled map of a profile solve (``plfem_index_map_gradients``): the derivative of the
+        diagonal of ``M_w`` (and ``K_w``) of :meth:`profile_grams` in the permittivity of EVERY pixel of the map, in one pass
+        over the quadrature points whatever the size of the map.  ``M_px`` (k', ny, nx) is ``d (v_r^T B v_r) / d E`` for
+        vectorial records and ``d (M_w)_rr / d E`` for scalar ones (so ``d (v_r^T A v_r) / d E = -k0^2 M_px``); ``K_px``
+        (vectorial only) is ``d (v_r^T A v_r) / d E``; ``support`` (ny, nx) int32 counts the quadrature points that see the
+        pixel -- inside the map's extent, under no layer, in a cell the pixel is a corner of: where it is 0 every plane is
+        exactly 0.  For a tangent map D, ``(D * M_px[r]).sum()`` is ``M_d[0][r, r]`` of :meth:`profile_tangent_grams`.
+
+        ``basis``: an optional (k', k) matrix; the fields are then ``v_r = sum_m basis[r, m] mode_m``, formed on the host
+        before staging (default: the modes themselves, k' = k).  Off-diagonal densities of a pair of modes follow by
+        polarisation: ``basis`` rows ``h_m + h_n`` and ``h_m - h_n`` give ``4 d (h_m^T B h_n) / d E`` as their difference.
+        The fields go in calls of at most 256 that keep a call's result under 2^27 doubles."""
+        profile = index_profile_of(geometry)
+        if profile is None:
+            raise ValueError("index_map_densities needs a geometry that carries an index profile (ProfiledGeometry)")
+        if profile.index_map is None:
+            raise ValueError("index_map_densities needs a profile with a sampled map (IndexProfile.sampled)")
+        kind, vals, _, k = self._checked(modes)
+        ny, nx = profile.index_map[0].shape
+        if basis is not None:
+            try:
+                Bm = np.asarray(basis, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"basis must be a matrix of shape (k', {k}) of finite numbers") from None
+            if Bm.ndim != 2 or Bm.shape[1] != k or not np.all(np.isfinite(Bm)):
+                raise ValueError(f"basis must be a matrix of shape (k', {k}) of finite numbers")
+            if k:
+                vals = np.ascontiguousarray(np.einsum("pm,cmn->cpn", Bm, vals))
+            k = Bm.shape[0] if k else 0
+        if k == 0:
+            res = {"M_px": np.zeros((0, ny, nx))}
+            if kind != "scalar":
+                res["K_px"] = np.zeros((0, ny, nx))
+            res["support"] = np.zeros((ny, nx), dtype=np.int32)
+            return res
+        return self._index_map_densities_staged(kind, self._staged(vals), profile)
+
+    def _index_map_densities_staged(self, kind, staged, profile, work=None) -> Dict[str, np.ndarray]:
+        """``plfem_index_map_gradients`` on fields already staged (ncomp, n, k) on the device, in calls of at most
+        ``MAP_GRADIENT_MAX`` fields whose result stays under ``MAP_GRADIENT_RESULT`` doubles; ``work`` as for
+        :meth:`_profile_grams_staged`."""
+        self._set_index_map(profile.index_map)
+        ncomp, n, k = staged.shape
+        nout = 2 if ncomp == 2 else 1
+        ny, nx = profile.index_map[0].shape
+        table = profile.table()
+        per = max(1, min(MAP_GRADIENT_MAX, MAP_GRADIENT_RESULT // (nout * nx * ny)))
+        out = np.empty((k, nout, ny, nx), dtype=np.float64)
+        support = np.empty((ny, nx), dtype=np.int32)
+        for f0 in range(0, k, per):
+            f1 = min(k, f0 + per)
+            part = staged if (f0, f1) == (0, k) else staged[:, :, f0:f1].contiguous()
+            self._mode_call("plfem_index_map_gradient_work_bytes", {"ncomp": ncomp, "k": f1 - f0}, "plfem_index_map_gradients",
+                            kind, part, (_native._ptr(table), table.shape[0], float(profile.eps_background)),
+                            (out[f0:f1], support), work=work, loc=self._loc)
+        res = {"M_px": np.ascontiguousarray(out[:, 0])}
+        if nout == 2:
+            res["K_px"] = np.ascontiguousarray(out[:, 1])
+        res["support"] = support
+        return res
 
     def indicators(self, modes: Sequence[Dict], geometry, alpha_p: float = 1.0) -> Dict[str, np.ndarray]:
         """A-posteriori error indicators of the modes on this mesh (``plfem_mode_indicators``): ``{"eta2": (k, ne),
