@@ -25,7 +25,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "flu
 PAIRS = ((1, 65), (33, 70), (32, 33))
 KMAX = 70
 POSES = (IDENTITY, COVERING, OUTSIDE)
-MATERIALS = ("discs/discs", "profile/profile", "discs/profile")
+MATERIALS = ("discs/discs", "profile/profile", "discs/profile", "profile/discs")      # all four kernel instances
 EMU_TOL = 1e-12          # of each output's largest entry
 SENTINEL = -7.0
 NAN, INF = float("nan"), float("inf")
@@ -48,7 +48,8 @@ def geometries(em_b):
     discs_b, rim_point = rim_disc_geometry(em_b)
     discs_a = power_cases.discs([[0.3, -0.2], [-0.6, 0.5], [0.1, 0.1]], [0.45, 0.3, 0.12], n_core=1.535, n_clad=1.0)
     prof_a, prof_b = profiled(wide_profile(), discs_a), profiled(centred_profile(), discs_b)
-    return {"discs/discs": (discs_a, discs_b), "profile/profile": (prof_a, prof_b), "discs/profile": (discs_a, prof_b)}, rim_point
+    return {"discs/discs": (discs_a, discs_b), "profile/profile": (prof_a, prof_b), "discs/profile": (discs_a, prof_b),
+            "profile/discs": (prof_a, discs_b)}, rim_point
 
 
 @pytest.fixture(scope="module")
@@ -119,6 +120,30 @@ def test_identity_pose_of_a_set_on_itself_is_flux_grams(pair, mname):
         errs = {"MA": rel(G["MA"][0], M), "MB": rel(G["MB"][0], M), "GA": rel(G["GA"][0], Gw), "GB": rel(G["GB"][0], Gw.T)}
         print(mname, k, {nm: f"{e:.2e}" for nm, e in errs.items()})
         assert max(errs.values()) <= 1e-13, (mname, k, errs)
+
+
+def test_a_profile_reaches_the_side_it_is_given_to(pair):
+    """The same locator and modes on both sides at the identity pose, a profile on one side and discs on the other: with
+    the profile on A, MA and GA carry 1 / eps of the profile and MB and GB that of the discs; with the sides exchanged the
+    outputs exchange their roles, MA <-> MB^T and GA <-> GB^T.  A kernel instance that took the other side's material, or
+    evaluated it at the other side's point, differs from that by what the profile differs from the discs."""
+    from pl_fem_vectoriel_amd import flux_overlap_poses
+    discs, prof = pair.geoms["discs/discs"][1], pair.geoms["profile/profile"][1]
+    for k in (1, 33, 70):
+        modes = pair.rb[:k]
+        call = lambda ga, gb: {nm: v[0] for nm, v in flux_overlap_poses(modes, pair.fb, ga, modes, pair.fb, gb, [IDENTITY]).items()}
+        PD, DP, DD = call(prof, discs), call(discs, prof), call(discs, discs)
+        errs = {"MA": rel(PD["MA"], DP["MB"].T), "MB": rel(PD["MB"], DP["MA"].T), "GA": rel(PD["GA"], DP["GB"].T),
+                "GB": rel(PD["GB"], DP["GA"].T)}
+        moved = {"MA of profile/discs": rel(PD["MA"], DD["MA"]), "GA of profile/discs": rel(PD["GA"], DD["GA"]),
+                 "MB of discs/profile": rel(DP["MB"], DD["MB"]), "GB of discs/profile": rel(DP["GB"], DD["GB"])}
+        kept = {"MB of profile/discs": rel(PD["MB"], DD["MB"]), "GB of profile/discs": rel(PD["GB"], DD["GB"]),
+                "MA of discs/profile": rel(DP["MA"], DD["MA"]), "GA of discs/profile": rel(DP["GA"], DD["GA"])}
+        print(k, {nm: f"{e:.2e}" for nm, e in errs.items()}, {nm: f"{e:.2e}" for nm, e in moved.items()},
+              {nm: f"{e:.2e}" for nm, e in kept.items()})
+        assert max(errs.values()) <= 1e-13, (k, errs)
+        assert min(moved.values()) > 1e-3, (k, moved)                  # the profile changes its own side's outputs
+        assert max(kept.values()) <= 1e-13, (k, kept)                  # and leaves the discs' side as discs / discs has it
 
 
 @pytest.mark.parametrize("mname", MATERIALS)

@@ -16,6 +16,10 @@ from pl_fem_vectoriel_amd.solver_fem import ScalarHelmholtzSolver, TrueVectorial
 
 pytestmark = pytest.mark.gpu
 
+# the bound of every comparison with the emulation or the exact integral below, as a share of max |Q| (also imported by
+# tests/test_gpu_field_instances.py)
+QUARTIC_TOL = 1e-12
+
 
 @pytest.fixture(scope="module")
 def c1(c1_geometry, gpu_device, built_library):

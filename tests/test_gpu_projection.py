@@ -2,7 +2,10 @@
 emulation (tests/projection_emulation.py), every entry within ``tol_m = 1.2e-16 (Q + 64 + 8 Phi) S_m``: random P2 fields
 on a 512-element mesh and its shifted copy at k = 1, 33, 64 over factor counts on both sides of the kernel's tile;
 bit-identical repeats; ``far_field`` and ``gaussian_coupling`` on solver output at C1 L = 0 with the Hermitian and shift
-identities; the norm of a projection against the beam's norm; and the argument errors of the C ABI."""
+identities; the norm of a projection against the beam's norm; and the argument errors of the C ABI.  These mode counts run
+5 of the 12 instances of ``k_mode_project`` and at most 9 tiles on a mesh with more elements than slices: every instance at
+both ends of its range, the bits of a mode across instances, the tile regimes (one slice, more than 1024 tiles, thin tile
+grids) and meshes with fewer elements than slices are in tests/test_gpu_field_instances.py."""
 import ctypes
 from types import SimpleNamespace
 

@@ -3,7 +3,10 @@ emulation (tests/sampled_projection_emulation.py), every entry within ``tol = 1.
 fields on a 512-element mesh and its shifted copy at k = 1, 33, 64 over frame counts on both sides of the kernel's frame
 tile, three image sizes and three extents; bit-identical repeats and chunks; the all-ones frame against ``project``;
 ``field_coupling`` of sampled Gaussian spots against ``gaussian_coupling`` on solver output at C1 L = 0; and the argument
-errors of the C ABI."""
+errors of the C ABI.  These mode counts run 5 of the 6 instances of ``k_mode_project_sampled``, and at most 67 frames are
+one launch of the entry's loop over groups of 16 frame tiles: every instance at both ends of its range, the bits of a mode
+across instances, 512 to 4096 frames in one call (two to eight groups) and meshes with fewer elements than slices are in
+tests/test_gpu_field_instances.py."""
 import ctypes
 from types import SimpleNamespace
 
