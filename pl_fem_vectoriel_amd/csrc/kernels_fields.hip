@@ -599,6 +599,107 @@ __device__ __forceinline__ void gram_features(int tid, int k, int64_t nrows, con
       acc[o][0][0] = fma((s) * a[p].x, b[q].x, acc[o][0][0]); acc[o][0][1] = fma((s) * a[p].x, b[q].y, acc[o][0][1]); \
       acc[o][1][0] = fma((s) * a[p].y, b[q].x, acc[o][1][0]); acc[o][1][1] = fma((s) * a[p].y, b[q].y, acc[o][1][1]);
 
+// acc[o] += wgt x p on a lane's 2 x 2 block, p the block's unweighted products (gram_m_block, gram_k_block) and wgt the
+// same for every lane: the accumulate of k_moment_grams and k_weighted_grams.
+#define GRAM_WACC(o, wgt, p)                                                                        \
+      acc[o][0][0] = fma(wgt, p[0][0], acc[o][0][0]); acc[o][0][1] = fma(wgt, p[0][1], acc[o][0][1]); \
+      acc[o][1][0] = fma(wgt, p[1][0], acc[o][1][0]); acc[o][1][1] = fma(wgt, p[1][1], acc[o][1][1]);
+
+// p = a[0] (x) b[0] (+ a[1] (x) b[1] when NCOMP = 2) on a lane's block: u u', or hx hx' + hy hy'.  One multiply, then one
+// fused multiply-add, in this order for the four entries.
+template <int NCOMP, int NF>
+__device__ __forceinline__ void gram_m_block(const double2 (&a)[NF], const double2 (&b)[NF], double (&p)[2][2]) {
+  p[0][0] = a[0].x * b[0].x; p[0][1] = a[0].x * b[0].y; p[1][0] = a[0].y * b[0].x; p[1][1] = a[0].y * b[0].y;
+  if constexpr (NCOMP == 2) {
+    p[0][0] = fma(a[1].x, b[1].x, p[0][0]); p[0][1] = fma(a[1].x, b[1].y, p[0][1]);
+    p[1][0] = fma(a[1].y, b[1].x, p[1][0]); p[1][1] = fma(a[1].y, b[1].y, p[1][1]);
+  }
+}
+
+// p = the form of K_r on a lane's block: dy hx dy hx' + dx hy dx hy' - dx hx dy hy' - dy hy dx hx' (features 2 dx hx,
+// 3 dy hx, 4 dx hy, 5 dy hy).  One multiply, then three fused multiply-adds, in this order for the four entries.
+#define GRAM_K_ENTRY(r_, s_, ar, bs)                                                                \
+  p[r_][s_] = a[3].ar * b[3].bs; p[r_][s_] = fma(a[4].ar, b[4].bs, p[r_][s_]);                       \
+  p[r_][s_] = fma(-a[2].ar, b[5].bs, p[r_][s_]); p[r_][s_] = fma(-a[5].ar, b[2].bs, p[r_][s_]);
+__device__ __forceinline__ void gram_k_block(const double2 (&a)[6], const double2 (&b)[6], double (&p)[2][2]) {
+  GRAM_K_ENTRY(0, 0, x, x) GRAM_K_ENTRY(0, 1, x, y) GRAM_K_ENTRY(1, 0, y, x) GRAM_K_ENTRY(1, 1, y, y)
+}
+#undef GRAM_K_ENTRY
+
+// The LDS of a tile: what gram_stage_point stages and gram_features fills.  A kernel's own per-point values (region,
+// material weight, coordinates, velocity gradient) stay in arrays of its own.  alignas(16): the loads of the t loop are
+// double2; a struct of doubles is 8-aligned, and then each becomes a pair of 64-bit LDS reads (a fifth slower, measured).
+template <int NCOMP>
+struct alignas(16) GramTile {
+  double f[2][3 * NCOMP][GT][OC];             // [0]: row chunk, plain; [1]: column chunk, times the weight
+  double gx[6][GT], gy[6][GT];
+  int r[6][GT];
+  double w[GT];                               // |det J| w_q
+  int q[GT];
+};
+
+template <int NCOMP, typename AtPoint>
+__device__ __forceinline__ void gram_stage_point(const LocArgs& L, int64_t g, bool live, int lane, GramTile<NCOMP>& S,
+                                                 AtPoint&& at_point) {
+  gram_stage_point(L, g, live, lane, S.gx, S.gy, S.r, S.w, S.q, at_point);
+}
+
+// What the same-mesh Gram kernels after k_mode_grams share besides the tile, as a local object of the kernel: the lane's
+// place in the workgroup's (row chunk, column chunk) pair = blockIdx.y, its zeroed 2 x 2 block of each of NOUT outputs,
+// the feature pass, the loads of the t loop and the store of the partials.  The tile walk, the staging and every
+// accumulate stay in the kernel, on `acc` through a local reference: the accumulators must never be seen through a
+// pointer that a branch could index (they would go to scratch).  k_mode_grams itself stays written out: its scalar
+// instance measured 0.4 % slower on the frame.
+template <int NCOMP, int NOUT>
+struct GramFrame {
+  static constexpr int NF = 3 * NCOMP;        // features per (point, mode)
+  const int tid, i0, j0, ti, tj;
+  double acc[NOUT][2][2];
+
+  __device__ __forceinline__ explicit GramFrame(int nchunk)
+      : tid(threadIdx.x), i0((int)(blockIdx.y / nchunk) * OC), j0((int)(blockIdx.y % nchunk) * OC), ti(tid >> 4), tj(tid & 15) {
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
+  }
+
+  // gram_features between its two barriers: after the staging lanes, before the t loop.  settle = false leaves the
+  // second barrier to a caller that first rewrites features in place, every lane those it wrote itself.
+  __device__ __forceinline__ void features(GramTile<NCOMP>& S, int k, int64_t nrows, const double* __restrict__ V,
+                                           bool settle = true) const {
+    __syncthreads();
+    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, S.gx, S.gy, S.r, S.w, S.q, S.f);
+    if (settle) __syncthreads();
+  }
+
+  // features C0 .. C1 - 1 of point t: the lane's two row modes and two column modes
+  template <int C0 = 0, int C1 = NF>
+  __device__ __forceinline__ void load(const GramTile<NCOMP>& S, int t, double2 (&a)[NF], double2 (&b)[NF]) const {
+#pragma unroll
+    for (int c = C0; c < C1; ++c) {
+      a[c] = *reinterpret_cast<const double2*>(&S.f[0][c][t][2 * ti]);
+      b[c] = *reinterpret_cast<const double2*>(&S.f[1][c][t][2 * tj]);
+    }
+  }
+
+  // The partial slots: [output][chunk pair][slice = blockIdx.x][OC * OC], output o of the kernel at first_out + place(o)
+  // of the launch's list, every slot written.  This is one half of a contract: k_overlap_reduce sums the slices of
+  // (output, chunk pair) in slice order, and gram_layout, CoreGramLayout, VelocityGramLayout and TangentGramLayout size
+  // the buffer and count the outputs (first_out = core x NOUT, velocity x NOUT for the listed calls).
+  template <typename Place>
+  __device__ __forceinline__ void store(double* __restrict__ partial, int64_t first_out, Place place) const {
+    const int64_t npair = (int64_t)gridDim.y;
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) {
+      double* out = partial + (((first_out + place(o)) * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
+      for (int r = 0; r < 2; ++r)
+        for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
+    }
+  }
+  __device__ __forceinline__ void store(double* __restrict__ partial, int64_t first_out) const {
+    store(partial, first_out, [](int o) { return o; });
+  }
+};
+
 template <int NCOMP>
 __global__ __launch_bounds__(256) void k_mode_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
                                                     CoreTable cores, int ncore, int nchunk, double* __restrict__ partial) {
@@ -736,38 +837,24 @@ __global__ __launch_bounds__(256) void k_core_grams(LocArgs L, int k, int64_t nr
                                                     int nchunk, double* __restrict__ partial) {
   constexpr int NF = 3 * NCOMP;
   constexpr int NOUT = NCOMP == 2 ? 3 : 1;
-  __shared__ double s_f[2][NF][GT][OC];
-  __shared__ double s_gx[6][GT], s_gy[6][GT];
-  __shared__ int s_r[6][GT];
-  __shared__ double s_w[GT];
-  __shared__ int s_q[GT];
-  const int tid = threadIdx.x, core = blockIdx.z;
-  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
-  const int i0 = ci * OC, j0 = cj * OC;
+  __shared__ GramTile<NCOMP> S;
+  GramFrame<NCOMP, NOUT> F(nchunk);
+  double (&acc)[NOUT][2][2] = F.acc;
+  const int tid = F.tid, core = blockIdx.z;
   const int count = meta[core];
   const int32_t* mine = list + meta[MAX_CORES + core];
   const int ntiles = (count + GT - 1) / GT;
-  const int ti = tid >> 4, tj = tid & 15;
-  double acc[NOUT][2][2];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (tid < GT) {
       const int p = tile * GT + tid;
       const bool live = p < count;
-      gram_stage_point(L, live ? (int64_t)mine[p] : 0, live, tid, s_gx, s_gy, s_r, s_w, s_q, [](double, double) {});
+      gram_stage_point(L, live ? (int64_t)mine[p] : 0, live, tid, S, [](double, double) {});
     }
-    __syncthreads();
-    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
-    __syncthreads();
+    F.features(S, k, nrows, V);
 #pragma unroll 1
     for (int t = 0; t < GT; ++t) {
       double2 a[NF], b[NF];
-#pragma unroll
-      for (int c = 0; c < NF; ++c) {
-        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
-        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
-      }
+      F.load(S, t, a, b);
       GRAM_ACC(0, 0, 0, 1.0)                    // Mx (M when ncomp = 1)
       if constexpr (NCOMP == 2) {
         GRAM_ACC(1, 1, 1, 1.0)
@@ -776,13 +863,7 @@ __global__ __launch_bounds__(256) void k_core_grams(LocArgs L, int k, int64_t nr
     }
     __syncthreads();
   }
-  const int64_t npair = (int64_t)gridDim.y;
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    double* out = partial + ((((int64_t)core * NOUT + o) * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
-    for (int r = 0; r < 2; ++r)
-      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
-  }
+  F.store(partial, (int64_t)core * NOUT);
 }
 
 // Grams of a profile solve (plfem_profile_grams): the forms of k_mode_grams with the permittivity of an index profile in
@@ -801,41 +882,28 @@ __global__ __launch_bounds__(256) void k_profile_grams(LocArgs L, int k, int64_t
                                                        double* __restrict__ partial, Map... map) {
   constexpr int NF = 3 * NCOMP;
   constexpr int NOUT = NCOMP == 2 ? 4 : 3;
-  __shared__ double s_f[2][NF][GT][OC];
-  __shared__ double s_gx[6][GT], s_gy[6][GT];
-  __shared__ int s_r[6][GT];
-  __shared__ double s_w[GT], s_wt[GT];        // |det J| w_q, and the material weight of the point
-  __shared__ int s_q[GT];
-  const int tid = threadIdx.x;
-  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
-  const int i0 = ci * OC, j0 = cj * OC;
+  __shared__ GramTile<NCOMP> S;
+  __shared__ double s_wt[GT];                 // the material weight of the point
+  GramFrame<NCOMP, NOUT> F(nchunk);
+  double (&acc)[NOUT][2][2] = F.acc;
+  const int tid = F.tid;
   const int64_t nq = (int64_t)6 * L.ne;
   const int64_t ntiles = (nq + GT - 1) / GT;
-  const int ti = tid >> 4, tj = tid & 15;
-  double acc[NOUT][2][2];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (tid < GT) {
       const int64_t g = tile * GT + tid;
       double wt = 1.0;
-      gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q, [&](double X, double Y) {
+      gram_stage_point(L, g, g < nq, tid, S, [&](double X, double Y) {
         const double eps = profile_eps(X, Y, layers, nlayer, eps_bg, map...);
         wt = NCOMP == 2 ? 1.0 / eps : eps;
       });
       s_wt[tid] = wt;
     }
-    __syncthreads();
-    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
-    __syncthreads();
+    F.features(S, k, nrows, V);
 #pragma unroll 1
     for (int t = 0; t < GT; ++t) {
       double2 a[NF], b[NF];
-#pragma unroll
-      for (int c = 0; c < NF; ++c) {
-        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
-        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
-      }
+      F.load(S, t, a, b);
       const double w = s_wt[t];                 // the same for every lane
       if constexpr (NCOMP == 2) {
         // features 0 hx, 1 hy, 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy
@@ -852,13 +920,7 @@ __global__ __launch_bounds__(256) void k_profile_grams(LocArgs L, int k, int64_t
     }
     __syncthreads();
   }
-  const int64_t npair = (int64_t)gridDim.y;
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    double* out = partial + (((int64_t)o * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
-    for (int r = 0; r < 2; ++r)
-      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
-  }
+  F.store(partial, 0);
 }
 
 // Power Grams of vectorial modes (plfem_flux_grams): with e = E / Z0 from curl H = j w eps0 eps E, the cross power of
@@ -882,16 +944,12 @@ __global__ __launch_bounds__(256) void k_flux_grams(LocArgs L, int k, int64_t nr
   __shared__ int s_r[6][GT];
   __shared__ double s_w[GT], s_wt[GT];        // |det J| w_q, and 1 / eps of the point
   __shared__ int s_q[GT], s_core[GT];
-  const int tid = threadIdx.x;
-  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
-  const int i0 = ci * OC, j0 = cj * OC;
+  GramFrame<2, NOUT> F(nchunk);               // the frame's indices, accumulators and store; the tile is this kernel's own
+  double (&acc)[NOUT][2][2] = F.acc;
+  const int tid = F.tid, i0 = F.i0, j0 = F.j0, ti = F.ti, tj = F.tj;
   const int64_t nq = (int64_t)6 * L.ne;
   const int64_t ntiles = (nq + GT - 1) / GT;
-  const int ti = tid >> 4, tj = tid & 15;
   const double* V1 = V + nrows * k;
-  double acc[NOUT][2][2];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (tid < GT) {
       const int64_t g = tile * GT + tid;
@@ -963,13 +1021,7 @@ __global__ __launch_bounds__(256) void k_flux_grams(LocArgs L, int k, int64_t nr
     }
     __syncthreads();
   }
-  const int64_t npair = (int64_t)gridDim.y;
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    double* out = partial + (((int64_t)o * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
-    for (int r = 0; r < 2; ++r)
-      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
-  }
+  F.store(partial, 0);
 }
 
 // Velocity Grams (plfem_velocity_grams): the first-order change of the forms of k_profile_grams when the mesh moves by
@@ -1064,30 +1116,23 @@ __global__ __launch_bounds__(256) void k_velocity_grams(LocArgs L, int k, int64_
                                                         double* __restrict__ partial, Map... map) {
   constexpr int NF = 3 * NCOMP;
   constexpr int NOUT = NCOMP == 2 ? 4 : 3;
-  __shared__ double s_f[2][NF][GT][OC];
-  __shared__ double s_gx[6][GT], s_gy[6][GT];
-  __shared__ int s_r[6][GT];
-  __shared__ double s_w[GT], s_wt[GT], s_G[4][GT];
-  __shared__ int s_q[GT];
-  const int tid = threadIdx.x, v = blockIdx.z;
-  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
-  const int i0 = ci * OC, j0 = cj * OC;
+  __shared__ GramTile<NCOMP> S;
+  __shared__ double s_wt[GT], s_G[4][GT];
+  GramFrame<NCOMP, NOUT> F(nchunk);
+  double (&acc)[NOUT][2][2] = F.acc;
+  double (&s_f)[2][NF][GT][OC] = S.f;
+  const int tid = F.tid, v = blockIdx.z;
   const int64_t npts = (int64_t)6 * meta[v];
   const int32_t* mine = list + meta[VG_GROUP + v];
   const double* myvel = vel + (int64_t)v * 2 * L.nv;
   const int64_t ntiles = (npts + GT - 1) / GT;
-  const int ti = tid >> 4, tj = tid & 15;
-  double acc[NOUT][2][2];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (tid < GT) {
       const int64_t p = tile * GT + tid;
       const bool live = p < npts;
       const int e = live ? mine[p / 6] : 0;
       double wt = 1.0, G[4] = {0.0, 0.0, 0.0, 0.0};
-      gram_stage_point(L, (int64_t)6 * e + p % 6, live, tid, s_gx, s_gy, s_r, s_w, s_q,
-                       [&](double X, double Y) {
+      gram_stage_point(L, (int64_t)6 * e + p % 6, live, tid, S, [&](double X, double Y) {
         bool in = false;
         if constexpr (!PROFILE) in = in_any_core(X, Y, mat.cores.c, mat.ncore);
         const double eps = material_eps<PROFILE>(mat, X, Y, in, map...);
@@ -1098,8 +1143,7 @@ __global__ __launch_bounds__(256) void k_velocity_grams(LocArgs L, int k, int64_
       s_wt[tid] = wt;
       for (int c = 0; c < 4; ++c) s_G[c][tid] = G[c];
     }
-    __syncthreads();
-    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
+    F.features(S, k, nrows, V, false);          // no barrier yet: it follows the transform
     // the row chunk (side 0 of gram_features: the same idx -> (mode, point) map, so every lane reads what it wrote)
     for (int idx = tid; idx < GT * OC; idx += 256) {
       const int i = idx % OC, t = idx / OC;
@@ -1117,11 +1161,7 @@ __global__ __launch_bounds__(256) void k_velocity_grams(LocArgs L, int k, int64_
 #pragma unroll 1
     for (int t = 0; t < GT; ++t) {
       double2 a[NF], b[NF];
-#pragma unroll
-      for (int c = 0; c < NF; ++c) {
-        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
-        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
-      }
+      F.load(S, t, a, b);
       const double w = s_wt[t];                 // the same for every lane
       if constexpr (NCOMP == 2) {
         // features 0 hx, 1 hy, 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy (row chunk: transformed)
@@ -1138,13 +1178,7 @@ __global__ __launch_bounds__(256) void k_velocity_grams(LocArgs L, int k, int64_
     }
     __syncthreads();
   }
-  const int64_t npair = (int64_t)gridDim.y;
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    double* out = partial + ((((int64_t)v * NOUT + o) * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
-    for (int r = 0; r < 2; ++r)
-      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
-  }
+  F.store(partial, (int64_t)v * NOUT);
 }
 
 // Pass 4, after k_overlap_reduce: O[m] <- O[m] + O[m]^T in place, blockIdx.y = matrix.  One lane per pair i <= j reads both
@@ -1159,7 +1193,6 @@ __global__ __launch_bounds__(256) void k_velocity_symmetrise(int k, double* __re
     O[(int64_t)j * k + i] = s;
   }
 }
-#undef GRAM_ACC
 
 // Posed flux overlap (plfem_flux_overlap_posed): the cross flux int (E_a x H_b + E_b x H_a) . z of two vectorial mode sets
 // on two meshes under a pose, as the four sums the host needs, free of beta, k0 and m.  Pose, location and the turn of A's
@@ -1343,10 +1376,6 @@ __global__ __launch_bounds__(256) void k_flux_overlap_posed(LocArgs A, LocArgs B
 // scalar call); KPART = true (NCOMP = 2): the four made of kk (K_core_X, K_core_Y, K_clad_X, K_clad_Y).  The vectorial
 // call runs both instances: 11 outputs x 4 accumulators do not fit 128 VGPRs beside the features.  Partials
 // [output][chunk pair][workgroup][OC * OC] at the outputs' places in the call's list, every slot written.
-#define MOM_ACC(o, wgt, p)                                                                          \
-      acc[o][0][0] = fma(wgt, p[0][0], acc[o][0][0]); acc[o][0][1] = fma(wgt, p[0][1], acc[o][0][1]); \
-      acc[o][1][0] = fma(wgt, p[1][0], acc[o][1][0]); acc[o][1][1] = fma(wgt, p[1][1], acc[o][1][1]);
-
 template <int NCOMP, bool KPART>
 __global__ __launch_bounds__(256) void k_moment_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
                                                       CoreTable cores, int ncore, double ox, double oy, int nchunk,
@@ -1354,27 +1383,20 @@ __global__ __launch_bounds__(256) void k_moment_grams(LocArgs L, int k, int64_t 
   static_assert(NCOMP == 2 || !KPART, "the scalar call has no K");
   constexpr int NF = 3 * NCOMP;
   constexpr int NOUT = KPART ? 4 : 7;
-  __shared__ double s_f[2][NF][GT][OC];
-  __shared__ double s_gx[6][GT], s_gy[6][GT];
-  __shared__ int s_r[6][GT];
-  __shared__ double s_w[GT];
+  __shared__ GramTile<NCOMP> S;
   __shared__ double s_mx[5][GT];              // X, Y, X^2, XY, Y^2 of the tile's points
-  __shared__ int s_q[GT], s_core[GT];
-  const int tid = threadIdx.x;
-  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
-  const int i0 = ci * OC, j0 = cj * OC;
+  __shared__ int s_core[GT];
+  GramFrame<NCOMP, NOUT> F(nchunk);
+  double (&acc)[NOUT][2][2] = F.acc;
+  const int tid = F.tid;
   const int64_t nq = (int64_t)6 * L.ne;
   const int64_t ntiles = (nq + GT - 1) / GT;
-  const int ti = tid >> 4, tj = tid & 15;
-  double acc[NOUT][2][2];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) acc[o][0][0] = acc[o][0][1] = acc[o][1][0] = acc[o][1][1] = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (tid < GT) {
       const int64_t g = tile * GT + tid;
       int core = 0;
       double X = 0.0, Y = 0.0;
-      gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q, [&](double x, double y) {
+      gram_stage_point(L, g, g < nq, tid, S, [&](double x, double y) {
         core = in_any_core(x, y, cores.c, ncore) ? 1 : 0;
         X = x - ox;
         Y = y - oy;
@@ -1386,53 +1408,28 @@ __global__ __launch_bounds__(256) void k_moment_grams(LocArgs L, int k, int64_t 
       s_mx[3][tid] = mul_rn(X, Y);
       s_mx[4][tid] = mul_rn(Y, Y);
     }
-    __syncthreads();
-    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
-    __syncthreads();
+    F.features(S, k, nrows, V);
 #pragma unroll 1
     for (int t = 0; t < GT; ++t) {
       constexpr int C0 = KPART ? 2 : 0, C1 = KPART ? NF : NCOMP;   // the features this instance reads
       double2 a[NF], b[NF];
-#pragma unroll
-      for (int c = C0; c < C1; ++c) {
-        a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
-        b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
-      }
+      F.template load<C0, C1>(S, t, a, b);
       const double X = s_mx[0][t], Y = s_mx[1][t];
       const bool core = s_core[t] != 0;         // the same for every lane
       double p[2][2];
-      if constexpr (KPART) {
-        // dy hx dy hx' + dx hy dx hy' - dx hx dy hy' - dy hy dx hx'  (features 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy)
-#define MOM_K(r_, s_, ar, bs)                                                                       \
-        p[r_][s_] = a[3].ar * b[3].bs; p[r_][s_] = fma(a[4].ar, b[4].bs, p[r_][s_]);                  \
-        p[r_][s_] = fma(-a[2].ar, b[5].bs, p[r_][s_]); p[r_][s_] = fma(-a[5].ar, b[2].bs, p[r_][s_]);
-        MOM_K(0, 0, x, x) MOM_K(0, 1, x, y) MOM_K(1, 0, y, x) MOM_K(1, 1, y, y)
-#undef MOM_K
-      } else {
-        p[0][0] = a[0].x * b[0].x; p[0][1] = a[0].x * b[0].y; p[1][0] = a[0].y * b[0].x; p[1][1] = a[0].y * b[0].y;
-        if constexpr (NCOMP == 2) {
-          p[0][0] = fma(a[1].x, b[1].x, p[0][0]); p[0][1] = fma(a[1].x, b[1].y, p[0][1]);
-          p[1][0] = fma(a[1].y, b[1].x, p[1][0]); p[1][1] = fma(a[1].y, b[1].y, p[1][1]);
-        }
-      }
-      if (core) { MOM_ACC(0, X, p) MOM_ACC(1, Y, p) } else { MOM_ACC(2, X, p) MOM_ACC(3, Y, p) }
+      if constexpr (KPART) gram_k_block(a, b, p);
+      else gram_m_block<NCOMP>(a, b, p);
+      if (core) { GRAM_WACC(0, X, p) GRAM_WACC(1, Y, p) } else { GRAM_WACC(2, X, p) GRAM_WACC(3, Y, p) }
       if constexpr (!KPART) {
         const double XX = s_mx[2][t], XY = s_mx[3][t], YY = s_mx[4][t];
-        MOM_ACC(4, XX, p) MOM_ACC(5, XY, p) MOM_ACC(6, YY, p)
+        GRAM_WACC(4, XX, p) GRAM_WACC(5, XY, p) GRAM_WACC(6, YY, p)
       }
     }
     __syncthreads();
   }
-  const int64_t npair = (int64_t)gridDim.y;
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    const int og = KPART ? 4 + o : (o < 4 ? o : 4 * NCOMP + (o - 4));   // the output's place in the call's list
-    double* out = partial + (((int64_t)og * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
-    for (int r = 0; r < 2; ++r)
-      for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[o][r][s];
-  }
+  // the output's place in the call's list
+  F.store(partial, 0, [](int o) { return KPART ? 4 + o : (o < 4 ? o : 4 * NCOMP + (o - 4)); });
 }
-#undef MOM_ACC
 
 // Tangent Grams of a profile solve (plfem_profile_tangent_grams): the M_w (and K_w) of k_profile_grams under a batch of
 // point weights ("columns") in place of w -- the first-order change dw of w along a tangent of the profile's values, or
@@ -1509,10 +1506,6 @@ __global__ __launch_bounds__(256) void k_profile_point_weights(LocArgs L, const 
 // written order, the same for the four entries of the block and for every column, so an entry's bits depend neither on
 // its place in the block nor on the column's place in the group.  Partials [column of the group][output][chunk pair]
 // [workgroup][OC * OC], every slot written.
-#define WG_ACC(c, o, p)                                                                             \
-      acc[c][o][0][0] = fma(wt, p[0][0], acc[c][o][0][0]); acc[c][o][0][1] = fma(wt, p[0][1], acc[c][o][0][1]); \
-      acc[c][o][1][0] = fma(wt, p[1][0], acc[c][o][1][0]); acc[c][o][1][1] = fma(wt, p[1][1], acc[c][o][1][1]);
-
 template <int NCOMP, int NW>
 __global__ __launch_bounds__(256) void k_weighted_grams(LocArgs L, int k, int64_t nrows, const double* __restrict__ V,
                                                         const double* __restrict__ wbuf, int nchunk,
@@ -1520,88 +1513,53 @@ __global__ __launch_bounds__(256) void k_weighted_grams(LocArgs L, int k, int64_
   static_assert(NW * GT <= 192, "the weights are loaded by lanes GT .. of one pass");
   constexpr int NF = 3 * NCOMP;
   constexpr int NOUT = NCOMP == 2 ? 2 : 1;
-  __shared__ double s_f[2][NF][GT][OC];
-  __shared__ double s_gx[6][GT], s_gy[6][GT];
-  __shared__ int s_r[6][GT];
-  __shared__ double s_w[GT], s_wt[NW][GT];    // |det J| w_q, and the columns' weights of the point
-  __shared__ int s_q[GT];
-  const int tid = threadIdx.x;
-  const int ci = blockIdx.y / nchunk, cj = blockIdx.y % nchunk;
-  const int i0 = ci * OC, j0 = cj * OC;
+  __shared__ GramTile<NCOMP> S;
+  __shared__ double s_wt[NW][GT];             // the columns' weights of the point
+  GramFrame<NCOMP, NW * NOUT> F(nchunk);      // output o of column c at c NOUT + o: the slot order
+  double (&acc)[NW * NOUT][2][2] = F.acc;
+  const int tid = F.tid;
   const int64_t nq = (int64_t)6 * L.ne;
   const int64_t ntiles = (nq + GT - 1) / GT;
-  const int ti = tid >> 4, tj = tid & 15;
-  double acc[NW][NOUT][2][2];
-#pragma unroll
-  for (int c = 0; c < NW; ++c)
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) acc[c][o][0][0] = acc[c][o][0][1] = acc[c][o][1][0] = acc[c][o][1][1] = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     if (tid < GT) {
       const int64_t g = tile * GT + tid;
-      gram_stage_point(L, g, g < nq, tid, s_gx, s_gy, s_r, s_w, s_q, [](double, double) {});
+      gram_stage_point(L, g, g < nq, tid, S, [](double, double) {});
     } else if (tid >= 64 && tid < 64 + NW * GT) {
       const int c = (tid - 64) / GT, t = (tid - 64) % GT;
       const int64_t g = tile * GT + t;
       s_wt[c][t] = g < nq ? wbuf[(int64_t)c * nq + g] : 0.0;
     }
-    __syncthreads();
-    gram_features<NCOMP>(tid, k, nrows, V, i0, j0, s_gx, s_gy, s_r, s_w, s_q, s_f);
-    __syncthreads();
+    F.features(S, k, nrows, V);
 #pragma unroll 1
     for (int t = 0; t < GT; ++t) {
       double p[2][2];
       {
-        double2 a[NCOMP], b[NCOMP];
-#pragma unroll
-        for (int c = 0; c < NCOMP; ++c) {
-          a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
-          b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
-        }
-        p[0][0] = a[0].x * b[0].x; p[0][1] = a[0].x * b[0].y; p[1][0] = a[0].y * b[0].x; p[1][1] = a[0].y * b[0].y;
-        if constexpr (NCOMP == 2) {
-          p[0][0] = fma(a[1].x, b[1].x, p[0][0]); p[0][1] = fma(a[1].x, b[1].y, p[0][1]);
-          p[1][0] = fma(a[1].y, b[1].x, p[1][0]); p[1][1] = fma(a[1].y, b[1].y, p[1][1]);
-        }
+        double2 a[NF], b[NF];
+        F.template load<0, NCOMP>(S, t, a, b);
+        gram_m_block<NCOMP>(a, b, p);
       }
 #pragma unroll
       for (int c = 0; c < NW; ++c) {
         const double wt = s_wt[c][t];           // the same for every lane
-        WG_ACC(c, 0, p)
+        GRAM_WACC(c * NOUT, wt, p)
       }
       if constexpr (NCOMP == 2) {
-        // dy hx dy hx' + dx hy dx hy' - dx hx dy hy' - dy hy dx hx'  (features 2 dx hx, 3 dy hx, 4 dx hy, 5 dy hy)
         double2 a[NF], b[NF];
-#pragma unroll
-        for (int c = 2; c < NF; ++c) {
-          a[c] = *reinterpret_cast<const double2*>(&s_f[0][c][t][2 * ti]);
-          b[c] = *reinterpret_cast<const double2*>(&s_f[1][c][t][2 * tj]);
-        }
-#define WG_K(r_, s_, ar, bs)                                                                        \
-        p[r_][s_] = a[3].ar * b[3].bs; p[r_][s_] = fma(a[4].ar, b[4].bs, p[r_][s_]);                  \
-        p[r_][s_] = fma(-a[2].ar, b[5].bs, p[r_][s_]); p[r_][s_] = fma(-a[5].ar, b[2].bs, p[r_][s_]);
-        WG_K(0, 0, x, x) WG_K(0, 1, x, y) WG_K(1, 0, y, x) WG_K(1, 1, y, y)
-#undef WG_K
+        F.template load<2, NF>(S, t, a, b);
+        gram_k_block(a, b, p);
 #pragma unroll
         for (int c = 0; c < NW; ++c) {
           const double wt = s_wt[c][t];
-          WG_ACC(c, NOUT - 1, p)
+          GRAM_WACC(c * NOUT + NOUT - 1, wt, p)
         }
       }
     }
     __syncthreads();
   }
-  const int64_t npair = (int64_t)gridDim.y;
-#pragma unroll
-  for (int c = 0; c < NW; ++c)
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-      double* out = partial + ((((int64_t)c * NOUT + o) * npair + blockIdx.y) * gridDim.x + blockIdx.x) * (OC * OC);
-      for (int r = 0; r < 2; ++r)
-        for (int s = 0; s < 2; ++s) out[(2 * ti + r) * OC + 2 * tj + s] = acc[c][o][r][s];
-    }
+  F.store(partial, 0);
 }
-#undef WG_ACC
+#undef GRAM_ACC
+#undef GRAM_WACC
 
 // Pixel densities of a sampled map (plfem_index_map_gradients): the derivative of the diagonal of M_w (and K_w) of
 // k_profile_grams in the value of every pixel of the locator's map -- the adjoint of the bilinear interpolant of
